@@ -105,6 +105,56 @@ def make_reads(n_reads, genome, seed, first, torch, threads, L=None):
     return t
 
 
+DUMP_SAMPLE = 1 << 20         # --dump-outputs: keys drawn from the final table
+DUMP_SEED = 20251015
+DUMP_MAX_BYTES = 64 << 20
+
+
+def table_outputs(data, tot):
+    """--dump-outputs: the table a step hands its caller, from its .yak bytes (htab.c:373-394: a 16-byte header {magic, k, pre, counter bits},
+    then per sub-table {capacity, size} and its keys in slot order), as float64 arrays that hold every value exactly: h->tot, each sub-table's
+    capacity and size, the histogram of the counts over all keys, and a seeded sample of the keys (position in file order, upper and lower
+    32 bits; the lower ones end in the count)"""
+    import struct
+    import numpy as np
+    _, pre, cbits = struct.unpack_from("<3I", data, 4)
+    w = np.frombuffer(data, dtype="<u8")
+    mask = np.uint64((1 << cbits) - 1)
+    caps, sizes, starts = [], [], []
+    hist = np.zeros(1 << cbits, dtype=np.int64)
+    off = 16
+    for _ in range(1 << pre):
+        cap, n = struct.unpack_from("<2I", data, off)
+        caps.append(cap); sizes.append(n); starts.append((off + 8) // 8)
+        hist += np.bincount((w[starts[-1]:starts[-1] + n] & mask).astype(np.int64), minlength=1 << cbits)
+        off += 8 + 8 * n
+    sizes, starts = np.array(sizes, dtype=np.int64), np.array(starts, dtype=np.int64)
+    n_keys = int(sizes.sum())
+    if n_keys <= DUMP_SAMPLE:
+        pos = np.arange(n_keys, dtype=np.int64)
+    else:
+        pos = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n_keys, size=DUMP_SAMPLE))
+    first = np.concatenate(([0], np.cumsum(sizes)))
+    sub = np.searchsorted(first, pos, side="right") - 1
+    keys = w[starts[sub] + (pos - first[sub])]
+    return {"tot": np.array([tot], dtype=np.float64),
+            "subtable_capacity": np.array(caps, dtype=np.float64), "subtable_size": sizes.astype(np.float64),
+            "count_histogram": hist.astype(np.float64),
+            "sample_position": pos.astype(np.float64),
+            "sample_key_hi32": (keys >> np.uint64(32)).astype(np.float64), "sample_key_lo32": (keys & np.uint64(0xffffffff)).astype(np.float64)}
+
+
+def write_outputs(out_dir, arrays):
+    """DIR/<name>.npy for every array (float32 / float64 only, 64 MB at most in all)"""
+    import numpy as np
+    total = sum(x.nbytes for x in arrays.values())
+    if total > DUMP_MAX_BYTES or any(x.dtype not in (np.float32, np.float64) for x in arrays.values()):
+        raise SystemExit(f"--dump-outputs: {total} bytes or a dtype other than float32 / float64")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+
+
 def _ref_count(fq, bits, threads, k=K):
     from oracle import pyoracle
     t0 = time.time()
@@ -490,7 +540,13 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend: nccl (= RCCL, default); gloo lets several ranks share one GPU for testing")
     ap.add_argument("--driver", default="c", choices=["c", "torch"], help="N > 1: c = the library's own multi-GPU driver (yakamd_count_multi_dev: one process, RCCL inside the library; default); "
                                                                           "torch = one process per GPU, yak_amd/shard.py + torch.distributed all-to-all")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the table the last one computed as DIR/<name>.npy (float64: sub-table sizes, count histogram, a seeded sample of the keys)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and (a.gpus > 1 or a.force_exchange or a.config in ("cfg3shard", "cfg4", "cfg5")):
+        ap.error("--dump-outputs is implemented for the one-GPU cfg2 and nofilter runs only")
     a.reads_given = any(x == "--reads" or x.startswith("--reads=") for x in sys.argv[1:])
     a.warmup_given = any(x == "--warmup" or x.startswith("--warmup=") for x in sys.argv[1:])
     a.batch_reads_given = any(x == "--batch-reads" or x.startswith("--batch-reads=") for x in sys.argv[1:])
@@ -655,7 +711,10 @@ def main():
     wall = {}
     last_stats = [None]
 
-    def step(keep=False):
+    capture_s = [0.0]     # --dump-outputs: seconds spent copying the last timed step's table out (taken off the timed region)
+    outputs = {}
+
+    def step(keep=False, capture=False):
         def tick(name, t0):
             dev_sync()
             t1 = time.perf_counter()
@@ -685,6 +744,11 @@ def main():
         tot = t.tot
         if keep:
             return t, tot, s1, s2
+        if capture:                                 # the device is idle here (the last tick synchronised it)
+            tc = time.perf_counter()
+            outputs.update(table_outputs(t.dump_bytes(), tot))
+            tp = time.perf_counter()
+            capture_s[0] = tp - tc
         t.close()
         tick("close", tp)
         return None, tot, s1, s2
@@ -698,11 +762,13 @@ def main():
         step()
     barrier()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        _, tot, s1, s2 = step()
+    for i_ in range(a.steps):
+        _, tot, s1, s2 = step(capture=bool(a.dump_outputs) and i_ == a.steps - 1)
     barrier()
-    dt = time.perf_counter() - t0
+    dt = time.perf_counter() - t0 - capture_s[0]
     wall_timed = dict(wall)
+    if a.dump_outputs:
+        write_outputs(a.dump_outputs, outputs)
     if sharded:
         v = torch.tensor([dt, float(tot), float(s1["n_instances"] + (s2["n_instances"] if s2 else 0))],
                          dtype=torch.float64, device=dev)

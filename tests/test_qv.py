@@ -1,6 +1,6 @@
 """The lookup-only path (`yak qv`, reference qv.c:34-135).
 CPU: the oracle's restatement against the reference-produced golden vectors (tests/golden/qv.json)
-and, where the prebuilt reference binary exists, against `yak qv` itself.
+and against the output of `yak qv` itself (tests/golden/ref_cli.json).
 GPU: the library (yak_ch_restore + yak_qv through the C ABI, the `yak-amd qv` caller, and the two
 device entry points on their own) against the oracle and the golden vectors."""
 import ctypes as C
@@ -13,11 +13,15 @@ import pytest
 
 from conftest import GOLD, ROOT
 
-REF = os.path.join(ROOT, "oracle", "_ref", "yak")
 YKO = os.path.join(ROOT, "oracle", "yko")
 YAM = os.path.join(ROOT, "yak_amd", "yak-amd")
 SYN = os.path.join(ROOT, "tools", "yaksynth")
 QV = json.load(open(os.path.join(GOLD, "qv.json")))
+REF_GOLD = os.path.join(GOLD, "ref_cli.json")       # what the reference printed (tests/gen_golden_ref.py)
+
+
+def ref_gold(key):
+    return json.load(open(REF_GOLD))[key]
 
 
 def query_file(desc, tmp_path):
@@ -45,16 +49,39 @@ def test_oracle_qv_matches_reference_golden(name, oracle, tmp_path):
     check_against_golden(out, desc, oracle)
 
 
-@pytest.mark.skipif(not os.path.exists(REF), reason="prebuilt reference binary not present")
-@pytest.mark.parametrize("args", [["-p", "-E"], ["-p", "-l", "2500"], ["-f", "0.88", "-p"], ["-K", "10k", "-p"]], ids=lambda a: "".join(a))
-def test_oracle_qv_cli_equals_reference_cli(args, oracle, tmp_path):
-    fq, fa, tab = str(tmp_path / "r.fq"), str(tmp_path / "a.fa"), str(tmp_path / "t.yak")
+QV_CLI_ARGS = [["-p", "-E"], ["-p", "-l", "2500"], ["-f", "0.88", "-p"], ["-K", "10k", "-p"]]
+
+
+def qv_cli_inputs(tmp_path):
+    fq, fa = str(tmp_path / "r.fq"), str(tmp_path / "a.fa")
     subprocess.check_call([SYN, "-n", "5000", "-l", "150", "-g", "30000", "-s", "11", "-o", fq])
     subprocess.check_call([SYN, "-a", "-n", "25", "-l", "3000", "-g", "30000", "-s", "11", "-e", "0.004", "-N", "0.0005", "-o", fa])
-    subprocess.run([REF, "count", "-k27", "-b24", "-o", tab, fq], check=True, stderr=subprocess.DEVNULL)
-    a = oracle.parse_qv_output(subprocess.run([REF, "qv"] + args + [tab, fa], check=True, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode())
+    return fq, fa
+
+
+def qv_digest(parsed):
+    """md5 over what oracle.parse_qv_output makes of a qv run's stdout: the CT columns, the sorted SQ and EK lines"""
+    ct, sq, ek = parsed
+    return hashlib.md5(json.dumps([sorted(ct.items()), sq, ek]).encode()).hexdigest()
+
+
+def counted_table(tmp_path, reads, args, want):
+    """the oracle CLI's `count` of the reads: its bytes must be the ones the reference wrote for them"""
+    tab = str(tmp_path / "t.yak")
+    subprocess.run([YKO, "count"] + args + ["-o", tab, reads], check=True, stderr=subprocess.DEVNULL)
+    data = open(tab, "rb").read()
+    assert [hashlib.md5(data).hexdigest(), len(data)] == want
+    return tab
+
+
+@pytest.mark.parametrize("args", QV_CLI_ARGS, ids=lambda a: "".join(a))
+def test_oracle_qv_cli_equals_reference_cli(args, oracle, tmp_path):
+    """`yko qv` against the output of `yak qv` (tests/golden/ref_cli.json, tests/gen_golden_ref.py) on the same table and sequences"""
+    g = ref_gold("qv_cli")
+    fq, fa = qv_cli_inputs(tmp_path)
+    tab = counted_table(tmp_path, fq, ["-k27", "-b24"], g["table"])
     b = oracle.parse_qv_output(subprocess.run([YKO, "qv"] + args + [tab, fa], check=True, stdout=subprocess.PIPE).stdout.decode())
-    assert a == b and sum(v[1] for v in a[0].values()) > 0
+    assert qv_digest(b) == g["output_md5"]["".join(args)] and sum(v[1] for v in b[0].values()) > 0
 
 
 # ------------------------------------------------------------------------------------------ GPU
@@ -194,44 +221,63 @@ def test_lookup_and_reduce_entry_points(ya, oracle, synth, tmp_path):
 
 
 # ------------------------------------------------------------------------------------------ host statistics
-@pytest.mark.skipif(not os.path.exists(REF), reason="prebuilt reference binary not present")
-@pytest.mark.parametrize("cov,e_asm", [(40, 0.002), (25, 0.0005), (60, 0.01), (3, 0.002)], ids=["40x", "25x_clean", "60x_noisy", "3x_low"])
-def test_qv_solve_prints_what_the_reference_prints(cov, e_asm, tmp_path):
-    """yak_qv_solve (qv.c:146-244) is host arithmetic: fed with the very histograms the reference
-    printed (CT columns 3 and 4), it must reproduce the reference's CT / FR / ER / CV / QV lines"""
-    import yak_amd
-    L = yak_amd.lib()
+QV_SOLVE_CASES = [(40, 0.002), (25, 0.0005), (60, 0.01), (3, 0.002)]
+
+
+def qv_solve_inputs(tmp_path, cov, e_asm):
     G = 200000
-    fq, fa, tab = str(tmp_path / "r.fq"), str(tmp_path / "a.fa"), str(tmp_path / "t.yak")
+    fq, fa = str(tmp_path / "r.fq"), str(tmp_path / "a.fa")
     subprocess.check_call([SYN, "-n", str(G * cov // 150), "-l", "150", "-g", str(G), "-s", "23", "-o", fq])
     subprocess.check_call([SYN, "-a", "-n", "40", "-l", "10000", "-g", str(G), "-s", "23", "-e", str(e_asm), "-N", "0.0001", "-o", fa])
-    subprocess.run([REF, "count", "-k21", "-b28", "-o", tab, fq], check=True, stderr=subprocess.DEVNULL)
-    out = subprocess.run([REF, "qv", tab, fa], check=True, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode().splitlines()
-    ct = {int(f[1]): f for f in (l.split("\t") for l in out if l.startswith("CT\t"))}
-    hist = (C.c_int64 * 1024)(*[int(ct[i][2]) for i in range(1024)])
-    cnt = (C.c_int64 * 1024)(*[int(ct[i][3]) for i in range(1024)])
+    return fq, fa
+
+
+def qv_solve_id(cov, e_asm):
+    return f"{cov}x_{e_asm:g}"
+
+
+@pytest.mark.parametrize("cov,e_asm", QV_SOLVE_CASES, ids=["40x", "25x_clean", "60x_noisy", "3x_low"])
+def test_qv_solve_prints_what_the_reference_prints(cov, e_asm):
+    """yak_qv_solve (qv.c:146-244) is host arithmetic: fed with the very histograms the reference printed (CT columns 3 and 4)
+    for `yak qv` of an assembly against its reads' table, it must reproduce the reference's CT / FR / ER / CV / QV lines
+    (tests/golden/ref_cli.json: the histograms, the FR / ER / CV / QV lines and the md5 of the CT lines)"""
+    import yak_amd
+    L = yak_amd.lib()
+    g = ref_gold("qv_solve")[qv_solve_id(cov, e_asm)]
+    hist = (C.c_int64 * 1024)(*[g["hist"].get(str(i), 0) for i in range(1024)])
+    cnt = (C.c_int64 * 1024)(*[g["cnt"].get(str(i), 0) for i in range(1024)])
     qs = yak_amd.QstatT()
     L.yak_qv_solve(hist, cnt, 21, 0.00004, C.byref(qs))
     import math
 
     def f3(x):                                                # C's printf keeps the sign of a NaN, Python's % does not
         return ("-nan" if math.copysign(1.0, x) < 0 else "nan") if math.isnan(x) else "%.3f" % x
-    mine = ["CT\t%d\t%d\t%d\t%s" % (i, hist[i], cnt[i], f3(qs.adj_cnt[i])) for i in range(1023, -1, -1)]
-    mine += ["FR\t%.3g\t%.3g" % (qs.fpr_lower, qs.fpr_upper), "ER\t%d\t%s" % (qs.tot, f3(qs.err)), "CV\t%s" % f3(qs.cov),
-             "QV\t%s\t%s" % (f3(qs.qv_raw), f3(qs.qv))]
-    assert mine == [l for l in out if l[:2] in ("CT", "FR", "ER", "CV", "QV")]
+    ct = ["CT\t%d\t%d\t%d\t%s" % (i, hist[i], cnt[i], f3(qs.adj_cnt[i])) for i in range(1023, -1, -1)]
+    rest = ["FR\t%.3g\t%.3g" % (qs.fpr_lower, qs.fpr_upper), "ER\t%d\t%s" % (qs.tot, f3(qs.err)), "CV\t%s" % f3(qs.cov),
+            "QV\t%s\t%s" % (f3(qs.qv_raw), f3(qs.qv))]
+    assert rest == g["rest"]
+    assert hashlib.md5("\n".join(ct).encode()).hexdigest() == g["ct_md5"]
+
+
+def qv_full_inputs(tmp_path):
+    G = 150000
+    fq, fa = str(tmp_path / "r.fq"), str(tmp_path / "a.fa")
+    subprocess.check_call([SYN, "-n", str(G * 35 // 150), "-l", "150", "-g", str(G), "-s", "29", "-o", fq])
+    subprocess.check_call([SYN, "-a", "-n", "30", "-l", "8000", "-g", str(G), "-s", "29", "-e", "0.003", "-N", "0.0001", "-o", fa])
+    return fq, fa
+
+
+def qv_full_digest(lines):
+    """md5 of the SQ lines as a sorted set and md5 of every other line in order"""
+    return [hashlib.md5("\n".join(sorted(l for l in lines if l.startswith("SQ"))).encode()).hexdigest(),
+            hashlib.md5("\n".join(l for l in lines if not l.startswith("SQ")).encode()).hexdigest()]
 
 
 @pytest.mark.gpu
-@pytest.mark.skipif(not os.path.exists(REF), reason="prebuilt reference binary not present")
 def test_yak_amd_qv_full_output_equals_reference(ya, tmp_path):
-    """`yak-amd qv -p` against `yak qv -p`: every line, SQ lines as a sorted set"""
-    G = 150000
-    fq, fa, tab = str(tmp_path / "r.fq"), str(tmp_path / "a.fa"), str(tmp_path / "t.yak")
-    subprocess.check_call([SYN, "-n", str(G * 35 // 150), "-l", "150", "-g", str(G), "-s", "29", "-o", fq])
-    subprocess.check_call([SYN, "-a", "-n", "30", "-l", "8000", "-g", str(G), "-s", "29", "-e", "0.003", "-N", "0.0001", "-o", fa])
-    subprocess.run([REF, "count", "-k21", "-b28", "-o", tab, fq], check=True, stderr=subprocess.DEVNULL)
-    a = subprocess.run([REF, "qv", "-p", tab, fa], check=True, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode().splitlines()
+    """`yak-amd qv -p` against `yak qv -p` (tests/golden/ref_cli.json): every line, SQ lines as a sorted set"""
+    g = ref_gold("qv_full")
+    fq, fa = qv_full_inputs(tmp_path)
+    tab = counted_table(tmp_path, fq, ["-k21", "-b28"], g["table"])
     b = subprocess.run([YAM, "qv", "-p", tab, fa], check=True, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode().splitlines()
-    assert sorted(l for l in a if l.startswith("SQ")) == sorted(l for l in b if l.startswith("SQ"))
-    assert [l for l in a if not l.startswith("SQ")] == [l for l in b if not l.startswith("SQ")] and any(l.startswith("QV") for l in a)
+    assert qv_full_digest(b) == g["output_md5"] and any(l.startswith("QV") for l in b)
