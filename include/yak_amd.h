@@ -208,6 +208,8 @@ typedef struct {
 	int64_t n_bloom_candidates;     /* keys that needed exact in-batch bloom resolution */
 	double ms_part2;                /* level-2 partition (part of ms_extract) */
 	double ms_shrink;               /* last yak_ch_shrink on this table: compaction + layout replay */
+	int64_t pass2_path;             /* how yakamd_count_retained counted this pass: 0 it did not, 1 the counts the pass before found (k_cnt2_apply
+	                                 * alone), 2 a recount of the retained sub-bucket records (k_cnt2), 3 a recount of the retained level-1 records */
 } yakamd_stats_t;
 int yakamd_get_stats(yak_ch_t *h, yakamd_stats_t *st);
 

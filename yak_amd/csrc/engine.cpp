@@ -173,7 +173,7 @@ static void retained_drop(yakamd_ctx *c)
 	bloom_undefer(c);
 	for (auto &r : c->retained) dfree(r.d_rec);
 	c->retained.clear(); c->retained_bytes = 0; c->src_set = false;
-	dfree(c->ret2.d_r2); dfree(c->ret2.d_sbstart); dfree(c->ret2.d_koff); dfree(c->ret2.d_kkc); dfree(c->ret2.d_segbase);
+	dfree(c->ret2.d_r2); dfree(c->ret2.d_sbstart); dfree(c->ret2.d_koff); dfree(c->ret2.d_kkc); dfree(c->ret2.d_segbase); dfree(c->ret2.d_kc2);
 	c->ret2.valid = false; c->ret2.n_total = 0;
 }
 
@@ -973,6 +973,19 @@ extern "C" int yakamd_count_retained(yak_ch_t *h)
 	yakamd_ctx *c = ctx_of(h);
 	if (!c || !c->in_pass || c->create_new) return fail("yakamd_count_retained needs an open create_new = 0 pass");
 	HIPCK(hipSetDevice(c->dev));
+	if (c->ret2.valid && !c->retain_broken && c->ret2.d_kc2) {
+		/* k_lc2 counted every instance of every key it selected while it owned the sub-bucket: all that is left is to add those counts */
+		EvTimer tm(c->st);
+		yk_launch_cnt2_apply(c->ret2.fp, c->ret2.d_kkc, c->ret2.d_kc2, c->ret2.d_segbase, img_view(c), c->st);
+		const double ms = tm.stop();
+		const bool bad = hipGetLastError() != hipSuccess;
+		c->st_cur.n_instances += (int64_t)c->ret2.n_total;
+		c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1;
+		c->st_cur.pass2_path = 1;
+		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] count pass: the counts of the pass before applied (%llu keys, %.2f ms)\n", (unsigned long long)c->ret2.n_keys, ms);
+		retained_drop(c);
+		return bad ? fail("applying the counts of the pass before failed") : 0;
+	}
 	if (c->ret2.valid && !c->retain_broken) {
 		u32 *d_kcnt = 0;
 		if (dmalloc(&d_kcnt, c->ret2.n_keys)) return -1;
@@ -987,6 +1000,8 @@ extern "C" int yakamd_count_retained(yak_ch_t *h)
 		const bool bad = hipGetLastError() != hipSuccess;
 		c->st_cur.n_instances += (int64_t)c->ret2.n_total;
 		c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1;
+		c->st_cur.pass2_path = 2;
+		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] count pass: k_cnt2 over the retained sub-bucket records (%llu keys, %.2f ms)\n", (unsigned long long)c->ret2.n_keys, ms);
 		retained_drop(c);
 		return bad ? fail("the count over the retained sub-bucket records failed") : 0;
 	}
@@ -1008,6 +1023,7 @@ extern "C" int yakamd_count_retained(yak_ch_t *h)
 	}
 	c->d_rec = keep;
 	retained_drop(c);
+	if (!r) c->st_cur.pass2_path = 3;
 	return r ? -1 : 0;
 }
 
@@ -1186,13 +1202,14 @@ static int fast_finish(yakamd_ctx *c, bool last)
 
 	Chunk2 *d_chunks = 0; u32 *d_cf = 0, *d_rows2 = 0, *d_segcur = 0, *d_ovf2 = 0, *d_ndist = 0; u64 *d_bbase = 0, *d_sbstart = 0, *d_segbase = 0, *d_sba = 0, *d_koff = 0; Rec *d_r2 = 0, *d_ra = 0;
 	u64 *kc[2] = { 0, 0 }, *tt[2] = { 0, 0 };
-	LcOut lo; lo.kc = 0; lo.T = 0; lo.nsel = 0; lo.lp = 0; lo.nd = 0;
+	LcOut lo; lo.kc = 0; lo.T = 0; lo.nsel = 0; lo.lp = 0; lo.nd = 0; lo.c2 = 0;
 	u64 *d_scr = 0, *d_scroff = 0;
+	u32 *d_kc2 = 0;
 	/* every device buffer of this function is released here, whichever way it is left */
 	struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ [&]() {
 		dfree(d_chunks); dfree(d_cf); dfree(d_rows2); dfree(d_segcur); dfree(d_ovf2); dfree(d_ndist); dfree(d_bbase); dfree(d_sbstart);
 		dfree(d_segbase); dfree(d_r2); dfree(kc[0]); dfree(kc[1]); dfree(tt[0]); dfree(tt[1]); dfree(lo.kc); dfree(lo.T); dfree(lo.nsel); dfree(lo.lp); dfree(lo.nd);
-		dfree(d_scr); dfree(d_scroff); dfree(d_sba); dfree(d_ra); dfree(d_koff);
+		dfree(lo.c2); dfree(d_kc2); dfree(d_scr); dfree(d_scroff); dfree(d_sba); dfree(d_ra); dfree(d_koff);
 	} };
 	if (dmalloc(&d_chunks, chunks.size()) || dmalloc(&d_cf, P + 1) || dmalloc(&d_bbase, P + 1) || dmalloc(&d_rows2, chunks.size() * S2F) ||
 	    dmalloc(&d_sbstart, n_sb + 1) || dmalloc(&d_segcur, P) || dmalloc(&d_ovf2, n_sb)) return -1;
@@ -1277,6 +1294,10 @@ static int fast_finish(yakamd_ctx *c, bool last)
 	else if (dmalloc(&lo.kc, n_total)) return -1;
 	if (dmalloc(&lo.T, n_total) || dmalloc(&lo.nsel, n_sb) || dmalloc(&lo.lp, n_sb) || dmalloc(&lo.nd, n_sb) || dmalloc(&d_ndist, P)) return -1;
 	const Rec *lc_rec_in = kc_inplace ? (const Rec*)lo.kc : d_r2;
+	/* the count pass over these same records (keep2) gets its counts from the counting kernels, next to the keys they select: every instance of a
+	 * key lies in its sub-bucket, which they own outright (k_cnt2 would read all the records again to count what they had in LDS).  Without the
+	 * room for them the count pass recounts (k_cnt2) */
+	if (keep2 && env_i64("YAKAMD_CNT2_FUSED", 1) != 0) lo.c2 = (unsigned short*)pool_alloc(n_total * 2);
 	if (c->plo > 0 || c->phi < P) {                              /* sub-buckets outside the shard are never visited */
 		HIPCK(hipMemsetAsync(lo.nsel, 0, n_sb * 4, c->st)); HIPCK(hipMemsetAsync(lo.lp, 0, n_sb * 4, c->st)); HIPCK(hipMemsetAsync(lo.nd, 0, n_sb * 4, c->st));
 	}
@@ -1379,13 +1400,14 @@ static int fast_finish(yakamd_ctx *c, bool last)
 	if (dmalloc(&kc[0], n_sel) || dmalloc(&tt[0], n_sel) || dmalloc(&d_segbase, P + 1)) return -1;
 	if (tsort && (dmalloc(&d_kt, n_sel) || dmalloc(&d_tsfail, 1))) return -1;
 	HIPCK(hipMemcpyAsync(d_segbase, ro.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
+	if (lo.c2) d_kc2 = (u32*)pool_alloc(std::max<u64>(n_sel, 1) * 4);   /* the count pass's counts, in the order of the gathered list (ret2.d_kkc) */
 	{
 		EvTimer tm(c->st);
 		if (flat) {
 			if (dmalloc(&d_koff, n_sb + 1)) return -1;
 			yk_launch_nsel_scan(lo.nsel, s2, c->plo, c->phi, P, d_segbase, d_koff, c->st);
-			yk_launch_lc_gather(lo, d_sbstart, d_koff, s2, c->plo, c->phi, kc[0], tt[0], d_kt, c->st);
-		} else yk_launch_lc_compact(lo, d_sbstart, s2, c->plo, c->phi, fp.t_pass0, d_segbase, kc[0], tt[0], c->d_lastput, d_ndist, d_kt, c->st);
+			yk_launch_lc_gather(lo, d_sbstart, d_koff, s2, c->plo, c->phi, kc[0], tt[0], d_kt, d_kc2, c->st);
+		} else yk_launch_lc_compact(lo, d_sbstart, s2, c->plo, c->phi, fp.t_pass0, d_segbase, kc[0], tt[0], c->d_lastput, d_ndist, d_kt, d_kc2, c->st);
 		c->st_cur.ms_select += tm.stop();
 	}
 	{
@@ -1414,12 +1436,13 @@ static int fast_finish(yakamd_ctx *c, bool last)
 			else HIPCK(hipMemcpyAsync(c->ret2.d_kkc, kc[0], n_sel * 8, hipMemcpyDeviceToDevice, c->st));
 			c->ret2.d_sbstart = d_sbstart; d_sbstart = 0;
 			HIPCK(hipMemcpyAsync(c->ret2.d_segbase, d_segbase, (P + 1) * 8, hipMemcpyDeviceToDevice, c->st));
+			c->ret2.d_kc2 = d_kc2; d_kc2 = 0;
 			c->ret2.n_keys = n_sel;
 			c->ret2.valid = true;
 			c->bf_deferred = fp.bf_nowb != 0;
 		}
 	}
-	dfree(lo.kc); dfree(lo.T); dfree(lo.nsel); dfree(lo.lp); dfree(lo.nd); dfree(d_sbstart); dfree(d_ndist); dfree(d_koff);
+	dfree(lo.kc); dfree(lo.T); dfree(lo.nsel); dfree(lo.lp); dfree(lo.nd); dfree(lo.c2); dfree(d_kc2); dfree(d_sbstart); dfree(d_ndist); dfree(d_koff);
 	lap("gather of the selected keys");
 	int cur = 0;
 	bool sorted = false;

@@ -89,8 +89,9 @@ struct yakamd_ctx {
 	struct Retained { u64 *d_rec; u64 n; std::vector<u64> bstart; };
 	std::vector<Retained> retained; bool retain_on, retain_broken; u64 retained_bytes;
 	/* ... or, when the whole pass was one slice into an empty table, its level-2 records (grouped by sub-bucket) + the keys every sub-bucket put
-	 * into the table: the count pass then owns each key's counter in LDS (k_cnt2) */
-	struct Ret2 { Rec *d_r2; u64 *d_sbstart, *d_koff, *d_kkc, *d_segbase; FastParams fp; u64 n_total, n_keys; bool valid; } ret2;
+	 * into the table: the count pass then owns each key's counter in LDS (k_cnt2) -- or, with d_kc2, takes every key's count as k_lc2 found it
+	 * (the same records: min(instances, 1023) per key, in d_kkc's order) and only applies them */
+	struct Ret2 { Rec *d_r2; u64 *d_sbstart, *d_koff, *d_kkc, *d_segbase; u32 *d_kc2; FastParams fp; u64 n_total, n_keys; bool valid; } ret2;
 	int n_slices;                      /* slices of the running pass counted so far (fast_flush_slice) */
 	u64 src_id[5]; bool src_set;       /* identity of the file the retained records came from + its sequence count (yak_count) */
 

@@ -502,6 +502,7 @@ __device__ void lc_body(const FastParams &fp, const LcTab &T, u32 sb, const u64 
 		if (fp.or_mode) c = T.T1[s] & (fp.or_mode == 1 ? 15u : 1023u);   /* a key seen once per load: its flag / saved count travels in the time's low bits */
 		const u32 r = atomicAdd(s_run, 1u);
 		O.kc[lo + r] = (T.K[s] >> fp.pre) << 10 | c; O.T[lo + r] = fp.t_pass0 + Tt;
+		if (O.c2) { const u32 n = T.CN[s] & LC_CMASK; O.c2[lo + r] = (unsigned short)(n > 1023 ? 1023 : n); }   /* every instance: the count pass's share */
 	}
 	lc_sync();
 	if (tid == 0) { O.nsel[sb] = *s_run; O.lp[sb] = *s_lp; O.nd[sb] = *s_ndist; }
@@ -815,6 +816,7 @@ void k_lc2(FastParams fp, const u64 *__restrict__ sbstart, const Rec *__restrict
 					if (fp.or_mode) c = t1x & (fp.or_mode == 1 ? 15u : 1023u);      /* a key seen once per load: its flag / saved count travels in the time's low bits */
 					const u32 r = atomicAdd(s_run, 1u);
 					O.kc[lo + r] = kx << 10 | c; O.T[lo + r] = fp.t_pass0 + Tt;
+					if (O.c2) { const u32 n = cn & LC2_CMASK; O.c2[lo + r] = (unsigned short)(n > 1023 ? 1023 : n); }   /* clamped at >= 0x800, exact below */
 				}
 				if (best) atomicMax(s_lp, best);
 				if (prof) tp2 = __builtin_readcyclecounter();
@@ -912,6 +914,7 @@ void k_lc2(FastParams fp, const u64 *__restrict__ sbstart, const Rec *__restrict
 				if (fp.or_mode) c = s_T1[s] & (fp.or_mode == 1 ? 15u : 1023u);       /* a key seen once per load: its flag / saved count travels in the time's low bits */
 				const u32 r = atomicAdd(s_run, 1u);
 				O.kc[lo + r] = kx << 10 | c; O.T[lo + r] = fp.t_pass0 + Tt;
+				if (O.c2) { const u32 n = cn & LC2_CMASK; O.c2[lo + r] = (unsigned short)(n > 1023 ? 1023 : n); }
 			}
 			if (best) atomicMax(s_lp, best);
 			}
@@ -990,6 +993,8 @@ void k_bf_rebuild(FastParams fp, const u64 *__restrict__ sbstart, const Rec *__r
  * probe per KEY instead of one per instance; exclusive owner: a plain read-modify-write).  Persistent workgroups with the next sub-bucket's
  * first records in flight, as in k_lc2.  A sub-bucket with more keys than the LDS set takes (other tiers of the insert kernel) looks every
  * instance up in the image with device atomics.  k_img_fold saturates the counts afterwards.
+ * k_lc2 owned the same sub-buckets of the same records and had these counts in LDS already: it hands them out (LcOut.c2), and the count pass
+ * is then k_cnt2_apply alone.  k_cnt2 stays for a pass 1 that did not keep them (engine.cpp: YAKAMD_CNT2_FUSED=0).
  * ------------------------------------------------------------------------------------------ */
 /* C2_CAP slots for up to C2_FULL keys: 2048 / 1280 hold whatever k_lc2 lets through (28 KB of LDS, six workgroups per CU); reads with
  * coverage put a few dozen keys into a sub-bucket, and 512 / 320 (7 KB) lets the CU's wave slots, eight workgroups, be the limit */
@@ -1169,7 +1174,8 @@ void k_lc_sum3(LcOut O, int s2_bits, int plo, u64 t_pass0, u32 *seg_cnt, u64 *la
 }
 
 __global__ __launch_bounds__(256)
-void k_lc_gather(LcOut O, const u64 *__restrict__ sbstart, const u64 *__restrict__ key_off, u32 sb_lo, u32 n_sb, u64 *__restrict__ out_kc, u64 *__restrict__ out_T, Rec *__restrict__ out_kt)
+void k_lc_gather(LcOut O, const u64 *__restrict__ sbstart, const u64 *__restrict__ key_off, u32 sb_lo, u32 n_sb, u64 *__restrict__ out_kc, u64 *__restrict__ out_T, Rec *__restrict__ out_kt,
+                 u32 *__restrict__ out_c2)
 {
 	const u32 lane = threadIdx.x & 63, n_waves = gridDim.x * 4;
 	/* 64 sub-buckets per step: lane l looks up where sub-bucket j0 + l lies, then the wave copies them one after the other */
@@ -1185,6 +1191,7 @@ void k_lc_gather(LcOut O, const u64 *__restrict__ sbstart, const u64 *__restrict
 			const u64 a = __shfl(src, l), d = __shfl(dst, l);
 			if (out_kt) for (u32 i = lane; i < n; i += 64) out_kt[d + i] = make_ulonglong2(O.kc[a + i], O.T[a + i]);     /* {key, time} pairs for the sort */
 			else for (u32 i = lane; i < n; i += 64) { out_kc[d + i] = O.kc[a + i]; out_T[d + i] = O.T[a + i]; }
+			if (out_c2) for (u32 i = lane; i < n; i += 64) out_c2[d + i] = O.c2[a + i];                                 /* the count pass's counts, same order */
 		}
 	}
 }
@@ -1315,7 +1322,7 @@ void k_ts_rank(const u64 *__restrict__ binstart, const Rec *__restrict__ in, int
  * follows); last put-call and distinct k-mers of the sub-table */
 __global__ __launch_bounds__(256)
 void k_lc_compact(LcOut O, const u64 *__restrict__ sbstart, int s2_bits, int plo, u64 t_pass0, const u64 *__restrict__ seg_base,
-                  u64 *__restrict__ out_kc, u64 *__restrict__ out_T, u64 *lastput, u32 *ndist_p, Rec *__restrict__ out_kt)
+                  u64 *__restrict__ out_kc, u64 *__restrict__ out_T, u64 *lastput, u32 *ndist_p, Rec *__restrict__ out_kt, u32 *__restrict__ out_c2)
 {
 	__shared__ u32 s_off[256], s_red[2];
 	const u32 p = (u32)plo + blockIdx.x, S2 = 1u << s2_bits, tid = threadIdx.x, lane = tid & 63;
@@ -1345,6 +1352,7 @@ void k_lc_compact(LcOut O, const u64 *__restrict__ sbstart, int s2_bits, int plo
 			const u64 src = sbstart[b0 + j0 + q], dst = run + s_off[q];
 			if (out_kt) for (u32 i = lane; i < cnt; i += 64) out_kt[dst + i] = make_ulonglong2(O.kc[src + i], O.T[src + i]);
 			else for (u32 i = lane; i < cnt; i += 64) { out_kc[dst + i] = O.kc[src + i]; out_T[dst + i] = O.T[src + i]; }
+			if (out_c2) for (u32 i = lane; i < cnt; i += 64) out_c2[dst + i] = O.c2[src + i];
 		}
 		run += s_red[1];
 	}

@@ -594,16 +594,16 @@ void yk_launch_lc_sum3(LcOut O, int s2_bits, int plo, int phi, u64 t_pass0, u32 
 {
 	hipLaunchKernelGGL(k_lc_sum3, dim3(phi - plo), dim3(256), 0, st, O, s2_bits, plo, t_pass0, seg_cnt, lastput, ndist_p);
 }
-void yk_launch_lc_gather(LcOut O, const u64 *sbstart, const u64 *key_off, int s2_bits, int plo, int phi, u64 *out_kc, u64 *out_T, Rec *out_kt, hipStream_t st)
+void yk_launch_lc_gather(LcOut O, const u64 *sbstart, const u64 *key_off, int s2_bits, int plo, int phi, u64 *out_kc, u64 *out_T, Rec *out_kt, u32 *out_c2, hipStream_t st)
 {
 	const u32 n_sb = (u32)(phi - plo) << s2_bits;
 	const u32 grid = (u32)std::min<u64>(((u64)n_sb + 255) / 256, 256 * 8 * 16);
-	if (grid) hipLaunchKernelGGL(k_lc_gather, dim3(grid), dim3(256), 0, st, O, sbstart, key_off, (u32)plo << s2_bits, n_sb, out_kc, out_T, out_kt);
+	if (grid) hipLaunchKernelGGL(k_lc_gather, dim3(grid), dim3(256), 0, st, O, sbstart, key_off, (u32)plo << s2_bits, n_sb, out_kc, out_T, out_kt, out_c2);
 }
 void yk_launch_lc_compact(LcOut O, const u64 *sbstart, int s2_bits, int plo, int phi, u64 t_pass0, const u64 *seg_base,
-                          u64 *out_kc, u64 *out_T, u64 *lastput, u32 *ndist_p, Rec *out_kt, hipStream_t st)
+                          u64 *out_kc, u64 *out_T, u64 *lastput, u32 *ndist_p, Rec *out_kt, u32 *out_c2, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_lc_compact, dim3(phi - plo), dim3(256), 0, st, O, sbstart, s2_bits, plo, t_pass0, seg_base, out_kc, out_T, lastput, ndist_p, out_kt);
+	hipLaunchKernelGGL(k_lc_compact, dim3(phi - plo), dim3(256), 0, st, O, sbstart, s2_bits, plo, t_pass0, seg_base, out_kc, out_T, lastput, ndist_p, out_kt, out_c2);
 }
 
 void yk_launch_seg_sort_pass2(const u64 *seg_base, const u32 *seg_cnt, int P, const u64 *src_kc, const u64 *src_t,
@@ -623,9 +623,13 @@ void yk_launch_cnt2(FastParams fp, const u64 *sbstart, const Rec *rec, const u64
 	const dim3 grid(std::min<u32>(n_sb, (u32)std::max(1, wgs)));
 	if (n_sb && small_max >= 0 && n_keys / n_sb <= (u64)small_max) hipLaunchKernelGGL((k_cnt2<512, 320>), grid, dim3(256), 0, st, fp, sbstart, rec, key_off, key_kc, img, n_sb, key_cnt, used_delta);
 	else hipLaunchKernelGGL((k_cnt2<2048, 1280>), grid, dim3(256), 0, st, fp, sbstart, rec, key_off, key_kc, img, n_sb, key_cnt, used_delta);
+	yk_launch_cnt2_apply(fp, key_kc, key_cnt, seg_base, img, st);
+}
+void yk_launch_cnt2_apply(FastParams fp, const u64 *key_kc, const u32 *key_cnt, const u64 *seg_base, ImgView img, hipStream_t st)
+{
 	const int n_p = fp.phi - fp.plo;
 	const int per = std::max(1, 8192 / std::max(1, n_p));                  /* ~8 K workgroups in all */
-	hipLaunchKernelGGL(k_cnt2_apply, dim3(per, n_p), dim3(256), 0, st, key_kc, (const u32*)key_cnt, seg_base, fp.plo, fp.pre, img);
+	hipLaunchKernelGGL(k_cnt2_apply, dim3(per, n_p), dim3(256), 0, st, key_kc, key_cnt, seg_base, fp.plo, fp.pre, img);
 }
 void yk_launch_nsel_scan(const u32 *nsel, int s2_bits, int plo, int phi, int P, const u64 *seg_base, u64 *key_off, hipStream_t st)
 {

@@ -179,8 +179,10 @@ struct FastParams {
 
 /* outputs of the exclusive-ownership counting kernels: the keys a sub-bucket adds to its sub-table go to the
  * front of the sub-bucket's own record range in kc / T (fragments, gathered by k_lc_compact); per sub-bucket
- * their number, the time (relative to the slice, + 1; 0 = none) of its last put-call, its distinct k-mers */
-struct LcOut { u64 *kc, *T; u32 *nsel, *lp, *nd; };
+ * their number, the time (relative to the slice, + 1; 0 = none) of its last put-call, its distinct k-mers.
+ * c2 (0 = not wanted): next to every selected key, min(instances of the key in the sub-bucket's records, 1023) -- what a count pass over the
+ * same records adds to it (engine.cpp keep2: that pass then only applies these, k_cnt2_apply) */
+struct LcOut { u64 *kc, *T; u32 *nsel, *lp, *nd; unsigned short *c2; };
 
 #ifdef __cplusplus
 extern "C" {
@@ -220,14 +222,15 @@ int yk_lc2_per_sb(int bloom_mode);
 void yk_launch_lc2(FastParams fp, const u64 *sbstart, const Rec *rec, u32 *bloom32, ImgView img, LcOut O, u64 *counters, u32 *ovf_list, hipStream_t st);
 void yk_launch_lc_sum(const u32 *nsel, int s2_bits, int plo, int phi, u32 *seg_cnt, hipStream_t st);
 void yk_launch_lc_compact(LcOut O, const u64 *sbstart, int s2_bits, int plo, int phi, u64 t_pass0, const u64 *seg_base,
-                          u64 *out_kc, u64 *out_T, u64 *lastput, u32 *ndist_p, Rec *out_kt, hipStream_t st);
+                          u64 *out_kc, u64 *out_T, u64 *lastput, u32 *ndist_p, Rec *out_kt, u32 *out_c2, hipStream_t st);
 void yk_launch_part2_ts(const Chunk2 *chunks, int n_chunks, const u32 *chunk_first, const u64 *bbase, FastParams fp, int P, u32 *rows2, u64 *sbstart, Rec *out, hipStream_t st);
 int yk_launch_ts_rank(const u64 *binstart, const Rec *in, int w, int j, u32 bin_lo, u32 n_bins, u64 *out_kc, u64 *out_t, u32 *fail, hipStream_t st);
 void yk_launch_kt_split(const Rec *in, u64 n, u64 *out_kc, u64 *out_t, hipStream_t st);
 void yk_launch_bf_rebuild(FastParams fp, const u64 *sbstart, const Rec *rec, u32 *bloom32, hipStream_t st);
 void yk_launch_lc_sum3(LcOut O, int s2_bits, int plo, int phi, u64 t_pass0, u32 *seg_cnt, u64 *lastput, u32 *ndist_p, hipStream_t st);
-void yk_launch_lc_gather(LcOut O, const u64 *sbstart, const u64 *key_off, int s2_bits, int plo, int phi, u64 *out_kc, u64 *out_T, Rec *out_kt, hipStream_t st);
+void yk_launch_lc_gather(LcOut O, const u64 *sbstart, const u64 *key_off, int s2_bits, int plo, int phi, u64 *out_kc, u64 *out_T, Rec *out_kt, u32 *out_c2, hipStream_t st);
 void yk_launch_cnt2(FastParams fp, const u64 *sbstart, const Rec *rec, const u64 *key_off, const u64 *key_kc, const u64 *seg_base, u32 *key_cnt, ImgView img, u64 n_keys, u32 *used_delta, hipStream_t st);
+void yk_launch_cnt2_apply(FastParams fp, const u64 *key_kc, const u32 *key_cnt, const u64 *seg_base, ImgView img, hipStream_t st);
 void yk_launch_nsel_scan(const u32 *nsel, int s2_bits, int plo, int phi, int P, const u64 *seg_base, u64 *key_off, hipStream_t st);
 void yk_launch_seg_sort_pass2(const u64 *seg_base, const u32 *seg_cnt, int P, const u64 *src_kc, const u64 *src_t,
                               u64 *dst_kc, u64 *dst_t, int shift, hipStream_t st, int big);
