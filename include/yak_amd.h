@@ -130,6 +130,29 @@ int yakamd_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, void *d
 int yakamd_qv_reduce_dev(yak_ch_t *h, const void *d_t_u16, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
                          int min_len, double min_frac, uint32_t *d_tot, uint32_t *d_non0, uint64_t *d_hist1024);
 
+/* Lookup-only path of `yak triobin` (reference triobin.c:41-101, k in [1, 63]) on a table loaded with yak_ch_restore_core(...,
+ * YAK_LOAD_TRIOBIN1, ...) and then (..., YAK_LOAD_TRIOBIN2, ...).  yakamd_triobin_lookup_dev(): d_flag_u8[i] = max(0, yak_ch_get())
+ * of the canonical k-mer ENDING at byte i of the base image -- the flag pat class | mat class << 2 --, 0xff where no k-mer ends;
+ * fails with a message (and no flag trusted) if a probed count field exceeds 15, i.e. the table was not made by those loads.  Not
+ * inside an open pass, not on a table sharded over prefix ranges.  yakamd_triobin_reduce_dev(): sequence j = bytes
+ * [d_seq_off[j], d_seq_off[j] + d_seq_len[j]) of that flag array; d_cnt_i32x19[19 j ..] receives c[16] (histogram of the flags of
+ * its k-mers), sc[2] (the paternal / maternal solid-run sums of triobin.c:94-100) and nk (its number of k-mers).  `stream` = a
+ * hipStream_t or 0; both calls return when the device is done. */
+int yakamd_triobin_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, void *d_flag_u8);
+int yakamd_triobin_reduce_dev(int k, const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
+                              int32_t *d_cnt_i32x19, void *stream);
+/* `yak triobin` as a library call: every read of `fn` (FASTA/FASTQ, .gz, "-" = stdin) classified against `ch` (the two TRIOBIN loads),
+ * output byte-equal to the reference's with -t1 (per chunk of chunk_size bases: the D lines of print_diff, then one line per read)
+ * written to out_fn (NULL = stdout).  0 on success, -1 after a message on stderr. */
+typedef struct {
+	double ratio_thres;       /* -r, 0.33 */
+	int print_diff;           /* -p, 0 */
+	int n_threads;            /* -t, 8: the reference's worker threads; here the reads are looked up on the device and a second thread reads ahead */
+	int64_t chunk_size;       /* bases per chunk, 200000000 (triobin.c:13) */
+} yakamd_tbopt_t;
+void yakamd_tbopt_init(yakamd_tbopt_t *opt);
+int yakamd_triobin(const yakamd_tbopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn);
+
 /* Host-only test hook (no device needed): the base image yak_count() hands to the device for a
  * FASTA/FASTQ(.gz) file -- sequences of >= min_len bases, each followed by '\n'.  use_fast_path = 0
  * forces the general record reader for every record.  *out is malloc()ed; returns its length or -1. */

@@ -34,6 +34,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_lookup_dev", "yakamd_qv_reduce_dev", "yakamd_host_image", "yakamd_host_image_packed", "yakamd_gz_tune", "yakamd_gz_inflate", "yakamd_test_set", "yakamd_test_reset",
     "yakamd_retain_input", "yakamd_count_retained", "yakamd_retained_instances", "yakamd_count_multi_dev",
     "yakamd_host_alloc", "yakamd_host_free", "yakamd_device_sync", "yakamd_mem_info", "yakamd_last_sweeps", "yakamd_pool_report",
+    "yakamd_triobin_lookup_dev", "yakamd_triobin_reduce_dev", "yakamd_tbopt_init", "yakamd_triobin",
 ]
 
 
@@ -55,6 +56,10 @@ class QoptT(C.Structure):                      # yak_qopt_t (reference yak.h:33-
 class QstatT(C.Structure):                     # yak_qstat_t (reference yak.h:42-47)
     _fields_ = [("tot", C.c_int64), ("qv_raw", C.c_double), ("qv", C.c_double), ("cov", C.c_double), ("err", C.c_double),
                 ("fpr_lower", C.c_double), ("fpr_upper", C.c_double), ("adj_cnt", C.c_double * 1024)]
+
+
+class TboptT(C.Structure):                     # yakamd_tbopt_t, include/yak_amd.h
+    _fields_ = [("ratio_thres", C.c_double), ("print_diff", C.c_int32), ("n_threads", C.c_int32), ("chunk_size", C.c_int64)]
 
 
 class StatsT(C.Structure):                     # yakamd_stats_t
@@ -191,6 +196,12 @@ def lib():
     L.yakamd_dev_free.argtypes = [C.c_void_p]
     L.yakamd_memcpy_h2d.restype = C.c_int; L.yakamd_memcpy_h2d.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     L.yakamd_memcpy_d2h.restype = C.c_int; L.yakamd_memcpy_d2h.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.yakamd_triobin_lookup_dev.restype = C.c_int
+    L.yakamd_triobin_lookup_dev.argtypes = [P(ChT), C.c_void_p, C.c_int64, C.c_void_p]
+    L.yakamd_triobin_reduce_dev.restype = C.c_int
+    L.yakamd_triobin_reduce_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.yakamd_tbopt_init.restype = None; L.yakamd_tbopt_init.argtypes = [P(TboptT)]
+    L.yakamd_triobin.restype = C.c_int; L.yakamd_triobin.argtypes = [P(TboptT), P(ChT), C.c_char_p, C.c_char_p]
     _lib = L
     return L
 
@@ -383,6 +394,37 @@ def qv_counts(table_fn, seq_fn, min_len=0, min_frac=0.5, chunk=1000000000):
     L.yak_qv(C.byref(o), seq_fn.encode(), h, cnt)
     L.yak_ch_destroy(h)
     return list(cnt)
+
+
+def triobin_table(pat_yak, mat_yak, min_cnt=2, mid_cnt=5):
+    """the table of `yak triobin` (reference triobin.c:187-188): both parents' classes in one table"""
+    L = lib()
+    h = L.yak_ch_restore_core(None, pat_yak.encode(), 2, C.c_int(min_cnt), C.c_int(mid_cnt))       # YAK_LOAD_TRIOBIN1
+    if h:
+        h = L.yak_ch_restore_core(h, mat_yak.encode(), 3, C.c_int(min_cnt), C.c_int(mid_cnt))     # YAK_LOAD_TRIOBIN2
+    if not h:
+        raise RuntimeError("yak_ch_restore_core (TRIOBIN) failed: " + _err())
+    return h
+
+
+def triobin(pat_yak, mat_yak, seq_fn, min_cnt=2, mid_cnt=5, ratio=0.33, print_diff=False, chunk=None):
+    """`yak triobin` through the C ABI (two TRIOBIN loads + yakamd_triobin): the bytes the reference writes with -t1"""
+    import tempfile
+    L = lib()
+    h = triobin_table(pat_yak, mat_yak, min_cnt, mid_cnt)
+    try:
+        o = TboptT()
+        L.yakamd_tbopt_init(C.byref(o))
+        o.ratio_thres, o.print_diff = ratio, int(bool(print_diff))
+        if chunk is not None:
+            o.chunk_size = chunk
+        with tempfile.TemporaryDirectory() as d:
+            out = os.path.join(d, "triobin.txt")
+            if L.yakamd_triobin(C.byref(o), h, seq_fn.encode(), out.encode()) != 0:
+                raise RuntimeError("yakamd_triobin failed: " + _err())
+            return open(out, "rb").read()
+    finally:
+        L.yak_ch_destroy(h)
 
 
 def pack_bases_host(buf):

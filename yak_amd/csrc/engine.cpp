@@ -1064,6 +1064,34 @@ extern "C" int yakamd_qv_reduce_dev(yak_ch_t *h, const void *d_t_u16, const uint
 	return 0;
 }
 
+/* ---- lookup-only path (yak triobin) ---- */
+extern "C" int yakamd_triobin_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, void *d_flag_u8)
+{
+	yakamd_ctx *c = ctx_of(h);
+	if (!c) return fail("not an engine table");
+	if (((const yak_ch_ext*)h)->n_sub > 1 || c->plo != 0 || c->phi != c->P) return fail("triobin lookup: not available on a table sharded over prefix ranges");
+	if (c->in_pass) return fail("lookup during an open pass");
+	if (c->k < 1 || c->k >= 64) return fail("triobin lookup: k must be in [1, 63]");
+	if (((uintptr_t)d_bases & 15) != 0) return fail("device base image must be 16-byte aligned");
+	HIPCK(hipSetDevice(c->dev));
+	yk_launch_tb_lookup((const uint8_t*)d_bases, n_bytes, c->k, img_view(c), (uint8_t*)d_flag_u8, c->st);
+	HIPCK(hipGetLastError());
+	HIPCK(hipStreamSynchronize(c->st));
+	if (n_bytes > 0 && yk_tb_over_seen(c->st))
+		return fail("triobin lookup: a count above 15 in the table -- it was not loaded with yak_ch_restore_core(..., YAK_LOAD_TRIOBIN1 / 2, ...)");
+	return 0;
+}
+
+extern "C" int yakamd_triobin_reduce_dev(int k, const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
+                                         int32_t *d_cnt_i32x19, void *stream)
+{
+	if (k < 1 || k >= 64) return fail("triobin reduce: k must be in [1, 63]");
+	yk_launch_tb_reduce((const uint8_t*)d_flag_u8, (const u64*)d_seq_off, d_seq_len, n_seq, k, (int*)d_cnt_i32x19, (hipStream_t)stream);
+	HIPCK(hipGetLastError());
+	HIPCK(hipStreamSynchronize((hipStream_t)stream));
+	return 0;
+}
+
 extern "C" int64_t yakamd_extract_dev(int k, const void *d_bases, int64_t n_bytes, void *d_hash, void *d_t,
                                       int pre, int plo, int phi, void *stream)
 {

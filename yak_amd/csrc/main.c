@@ -1,11 +1,12 @@
 /*
  * main.c -- `yak-amd`: the repo's own small command-line driver of libyak_amd.so, plain C against
- * include/yak.h only.  It is a test and benchmark vehicle (tests/, bench.py's e2e_cli figure), not a
+ * include/yak.h (and include/yak_amd.h for triobin and -X).  It is a test and benchmark vehicle (tests/, bench.py's e2e_cli figure), not a
  * re-creation of the reference's CLI: that one runs unmodified on the library (INTEGRATION.md section 2,
- * oracle/_ref/yak_on_amd).  Two sub-commands drive the two call sequences the library serves:
- *     count   the counting protocol behind reference main.c:53-61 (one pass, or two passes + shrink
- *             when a bloom filter is asked for)
- *     qv      the lookup protocol behind reference main.c:163-215 (restore, histogram, yak_qv, solve)
+ * oracle/_ref/yak_on_amd).  Three sub-commands drive the call sequences the library serves:
+ *     count    the counting protocol behind reference main.c:53-61 (one pass, or two passes + shrink
+ *              when a bloom filter is asked for)
+ *     qv       the lookup protocol behind reference main.c:163-215 (restore, histogram, yak_qv, solve)
+ *     triobin  the read binning of reference triobin.c:153-197 (two TRIOBIN loads, yakamd_triobin)
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
  */
@@ -14,7 +15,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "yak.h"
-void yakamd_test_set(const char *name, int64_t value);        /* include/yak_amd.h: the one entry point beyond yak.h this driver knows, for -X */
+#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X) and yakamd_triobin */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
 enum arg_kind { ARG_FLAG, ARG_I32, ARG_SIZE, ARG_I64SIZE, ARG_F64, ARG_TEXT };
@@ -152,11 +153,37 @@ static int cmd_qv(int argc, char **argv)
 	return 0;
 }
 
+/* ---- triobin ---- */
+static int cmd_triobin(int argc, char **argv)
+{
+	yakamd_tbopt_t o;
+	int min_cnt = 2, mid_cnt = 5;                            /* reference triobin.c:156 */
+	yakamd_tbopt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'c', ARG_I32, &min_cnt, "min occurrence in a parent" },
+		{ 'd', ARG_I32, &mid_cnt, "mid occurrence in a parent (solid)" },
+		{ 'r', ARG_F64, &o.ratio_thres, "ratio threshold" },
+		{ 't', ARG_I32, &o.n_threads, "host threads (accepted for the reference's command line)" },
+		{ 'p', ARG_FLAG, &o.print_diff, "print the positions where the parents differ (D lines)" },
+		{ 'K', ARG_I64SIZE, &o.chunk_size, "bases per chunk" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 2 >= argc) { arg_help("triobin [options] <pat.yak> <mat.yak> <seq.fa>", defs, nd); return 1; }
+	yak_ch_t *tab = yak_ch_restore_core(0, argv[first], YAK_LOAD_TRIOBIN1, min_cnt, mid_cnt);
+	if (tab) tab = yak_ch_restore_core(tab, argv[first + 1], YAK_LOAD_TRIOBIN2, min_cnt, mid_cnt);
+	if (!tab) { fprintf(stderr, "yak-amd triobin: cannot load %s and %s (or no MI355X)\n", argv[first], argv[first + 1]); return 2; }
+	const int rc = yakamd_triobin(&o, tab, argv[first + 2], 0) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 int main(int argc, char **argv)
 {
 	static const struct { const char *name; int (*run)(int, char**); const char *what; } cmds[] = {
 		{ "count", cmd_count, "count k-mers on the GPU, write a .yak table" },
 		{ "qv", cmd_qv, "look the k-mers of sequences up in a .yak table" },
+		{ "triobin", cmd_triobin, "bin reads by the k-mers of the two parents' .yak tables" },
 	};
 	/* -X name=value (anywhere on the line, any number of times): a test switch of the library (yakamd_test_set) -- tests force code paths with it */
 	for (int i = 1; i + 1 < argc; ) {
@@ -171,6 +198,6 @@ int main(int argc, char **argv)
 		for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i)
 			if (strcmp(argv[1], cmds[i].name) == 0) return cmds[i].run(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
-	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-6s %s\n", cmds[i].name, cmds[i].what);
+	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-7s %s\n", cmds[i].name, cmds[i].what);
 	return 1;
 }
