@@ -1,4 +1,4 @@
-"""`yak triobin` on the device (k_tb_lookup + k_tb_reduce + yakamd_triobin): byte-equal to the reference's
+"""`yak triobin` on the device (k_lookup + k_tb_reduce + yakamd_triobin): byte-equal to the reference's
 `triobin -t1` on the stored fixtures, per-position flags equal to the host mirror's yak_ch_get(), and the
 per-read reduction equal to a numpy restatement of triobin.c:74-100."""
 import ctypes as C

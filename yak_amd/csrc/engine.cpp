@@ -1039,18 +1039,25 @@ bool yk_ctx_same_source(yakamd_ctx *c, const uint64_t id[4], int64_t *n_seq)
 	return true;
 }
 
-/* ---- lookup-only path (yak qv) ---- */
+/* ---- lookup-only paths (yak qv, yak triobin) ---- */
+/* what the two lookup exports share, after their own checks: the kernel writes `width` bytes per position (yk_launch_lookup) */
+static int lookup_dev(yakamd_ctx *c, const void *d_bases, int64_t n_bytes, void *d_out, int width)
+{
+	if (((uintptr_t)d_bases & 15) != 0) return fail("device base image must be 16-byte aligned");
+	HIPCK(hipSetDevice(c->dev));
+	yk_launch_lookup((const uint8_t*)d_bases, n_bytes, c->k, img_view(c), d_out, width, c->st);
+	if (width == 1) HIPCK(hipGetLastError());          /* triobin's export reports a failed launch here; qv's leaves it to the synchronise */
+	HIPCK(hipStreamSynchronize(c->st));
+	return 0;
+}
+
 extern "C" int yakamd_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, void *d_out_u16)
 {
 	yakamd_ctx *c = ctx_of(h);
 	if (!c) return fail("not an engine table");
 	if (c->in_pass) return fail("lookup during an open pass");
 	if (c->k < 1 || c->k >= 32) return fail("lookup: k must be below 32 (reference qv.c:44)");
-	if (((uintptr_t)d_bases & 15) != 0) return fail("device base image must be 16-byte aligned");
-	HIPCK(hipSetDevice(c->dev));
-	yk_launch_lookup((const uint8_t*)d_bases, n_bytes, c->k, img_view(c), (unsigned short*)d_out_u16, c->st);
-	HIPCK(hipStreamSynchronize(c->st));
-	return 0;
+	return lookup_dev(c, d_bases, n_bytes, d_out_u16, 2);
 }
 
 extern "C" int yakamd_qv_reduce_dev(yak_ch_t *h, const void *d_t_u16, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
@@ -1064,7 +1071,6 @@ extern "C" int yakamd_qv_reduce_dev(yak_ch_t *h, const void *d_t_u16, const uint
 	return 0;
 }
 
-/* ---- lookup-only path (yak triobin) ---- */
 extern "C" int yakamd_triobin_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, void *d_flag_u8)
 {
 	yakamd_ctx *c = ctx_of(h);
@@ -1072,11 +1078,7 @@ extern "C" int yakamd_triobin_lookup_dev(yak_ch_t *h, const void *d_bases, int64
 	if (((const yak_ch_ext*)h)->n_sub > 1 || c->plo != 0 || c->phi != c->P) return fail("triobin lookup: not available on a table sharded over prefix ranges");
 	if (c->in_pass) return fail("lookup during an open pass");
 	if (c->k < 1 || c->k >= 64) return fail("triobin lookup: k must be in [1, 63]");
-	if (((uintptr_t)d_bases & 15) != 0) return fail("device base image must be 16-byte aligned");
-	HIPCK(hipSetDevice(c->dev));
-	yk_launch_tb_lookup((const uint8_t*)d_bases, n_bytes, c->k, img_view(c), (uint8_t*)d_flag_u8, c->st);
-	HIPCK(hipGetLastError());
-	HIPCK(hipStreamSynchronize(c->st));
+	if (lookup_dev(c, d_bases, n_bytes, d_flag_u8, 1)) return -1;
 	if (n_bytes > 0 && yk_tb_over_seen(c->st))
 		return fail("triobin lookup: a count above 15 in the table -- it was not loaded with yak_ch_restore_core(..., YAK_LOAD_TRIOBIN1 / 2, ...)");
 	return 0;

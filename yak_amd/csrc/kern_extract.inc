@@ -670,50 +670,39 @@ __device__ __forceinline__ int64_t img_find(const ImgView &img, u64 key)
 }
 
 /* ------------------------------------------------------------------------------------------
- * lookup-only path (`yak qv`, reference qv.c:34-86): t = max(0, yak_ch_get()) of the k-mer ENDING
- * at every position of a base image (QV_NOKMER where none ends: window shorter than k or holding a
- * non-ACGT byte); then per sequence tot = k-mers, non0 = present ones, and the sequences with
- * non0 >= tot * min_frac add all their t values to the 1024-bin histogram.
+ * lookup-only paths: t = max(0, yak_ch_get()) of the k-mer ENDING at every position of a base image, all ones of the output element where
+ * none ends (window shorter than k or holding a non-ACGT byte); then a reduction per sequence.
+ *   `yak qv` (reference qv.c:34-86): u16 t (QV_NOKMER); per sequence tot = k-mers, non0 = present ones, and the sequences with
+ *   non0 >= tot * min_frac add all their t values to the 1024-bin histogram.
+ *   `yak triobin` (reference triobin.c:41-101): u8 t (TB_NOKMER), a flag.  The table comes from the two YAK_LOAD_TRIOBIN loads, which OR a
+ *   2-bit class per parent into the count field, so a flag is 4 bits.
  * ------------------------------------------------------------------------------------------ */
 #define QV_NOKMER 0xffffu
-/* yak_ch_get() clamped at 0 (qv.c:59-60), read-only and on the key array alone: the image keeps every
- * unused slot at YK_EMPTY (k_replay publishes it so), which no 2k < 64-bit key can equal, so the
- * `used` bitmap -- a second random 64-byte read per probe -- is not needed here */
-__device__ __forceinline__ u32 img_get_count(const ImgView &img, u64 key)
-{
-	const u32 p = (u32)key & ((1u << img.pre) - 1);
-	const u32 bits = img.bits[p];
-	if (bits == YK_NOCAP) return 0;
-	const u64 kid = key >> img.pre;
-	const u64 *keys = img.keys + img.off[p];
-	const u32 nmask = (1u << bits) - 1;
-	u32 i = yk_h2b((u32)kid, bits);
-	const u32 first = i;
-	for (;;) {
-		const u64 kc = keys[i];
-		if (kc == YK_EMPTY) return 0;
-		if (kc >> 10 == kid) return (u32)(kc & 1023u);
-		i = (i + 1) & nmask;
-		if (i == first) return 0;
-	}
-}
-/* plo / phi: one sweep of several over prefix ranges -- a table image beyond the 256 MB of the Infinity Cache is probed range by range, each range
- * small enough to stay there while all the queries go by (the queries are extracted once per sweep: that is the cheap part).  A position is written
- * by the sweep that owns its k-mer's prefix; positions without a k-mer by the sweep that starts at prefix 0 */
-/* the sub-tables' {offset, log2 capacity} sit in LDS (dynamic: 8 bytes per sub-table while pre <= 12): a probe is then one dependent global read,
+#define TB_NOKMER 0xffu
+__device__ u32 d_tb_over;          /* triobin: a probed count field above 15 was met */
+/* yak_ch_get() clamped at 0 (qv.c:59-60, triobin.c:62-84), read-only and on the key array alone: the image keeps every unused slot at YK_EMPTY
+ * (k_replay publishes it so), and no stored key equals it, so the `used` bitmap -- a second random 64-byte read per probe -- is not needed.  At
+ * k < 32 no 2k < 64-bit key can equal it.  At k >= 32 a 64-bit hash can make (hash >> pre) << 10 all ones, but a TRIOBIN load stores a count
+ * field of at most 15, never 1023.  A count field above 15 means the table did not come from those loads (the reference would index past its
+ * c[16]): the one-byte lookup raises d_tb_over and its caller fails.
+ * The sub-tables' {offset, log2 capacity} sit in LDS (dynamic: 8 bytes per sub-table while pre <= 12): a probe is then one dependent global read,
  * not three; LK_U positions of a lane are hashed first and their home slots requested together (the probe of one position used to wait for the
  * one before it) */
-template <int LK_U>                         /* probes a lane keeps in flight */
+#define LK_U 2                             /* probes a lane keeps in flight */
+template <typename T, bool LONG>           /* T: unsigned short (qv) or uint8_t (triobin's flag); LONG: k in [32, 63], yak_hash_long (triobin.c:78-81) */
 __global__ __launch_bounds__(XT_THREADS)
-void k_lookup(const uint8_t *__restrict__ bases, int64_t n, int k, ImgView img, unsigned short *__restrict__ out, u32 plo, u32 phi, int tab)
+void k_lookup(const uint8_t *__restrict__ bases, int64_t n, int k, ImgView img, T *__restrict__ out, int tab)
 {
+	constexpr u32 NOKMER = (T)~0u;
+	constexpr bool FLAG = sizeof(T) == 1;  /* a flag holds 4 bits */
 	__shared__ XtTile S;
 	extern __shared__ __attribute__((aligned(16))) u64 s_tab[];
 	const u32 pmask = (1u << img.pre) - 1;
 	if (tab) for (u32 p = threadIdx.x; p <= pmask; p += XT_THREADS) { const u32 b = img.bits[p]; s_tab[p] = img.off[p] | (u64)(b == YK_NOCAP ? 63u : b) << 58; }
 	xt_init(S);
-	const u64 mask = (1ull << (2 * k)) - 1, kones = (1ull << k) - 1;
+	const u64 mask = LONG ? 0 : (1ull << (2 * k)) - 1, kones = LONG ? 0 : (1ull << k) - 1;
 	const u64 YK_GLOBAL *karena = yk_global(u64, img.keys);
+	u32 over = 0;
 	for (int t = 0; t < XP_T; ++t) {
 		const int64_t tile0 = ((int64_t)blockIdx.x * XP_T + t) * XT_TILE;
 		if (tile0 >= n) break;
@@ -722,17 +711,17 @@ void k_lookup(const uint8_t *__restrict__ bases, int64_t n, int k, ImgView img, 
 			u64 kid[LK_U], kc[LK_U];
 			const u64 YK_GLOBAL *keys[LK_U];
 			u32 idx[LK_U], nmask[LK_U], v[LK_U];
-			bool live[LK_U], mine[LK_U];
+			bool live[LK_U];
 #pragma unroll
 			for (int u = 0; u < LK_U; ++u) {
 				const int q = (r0 + u) * XT_THREADS + (int)threadIdx.x;
 				u64 h;
-				const bool ok = xt_kmer(S, q, k, mask, kones, tile0, n, &h);
+				const bool ok = LONG ? xt_kmer_long(S, q, k, img.pre, tile0, n, &h) : xt_kmer(S, q, k, mask, kones, tile0, n, &h);
 				const u32 p = (u32)h & pmask;
-				mine[u] = tile0 + q < n && (ok ? (p >= plo && p < phi) : plo == 0);
-				v[u] = ok ? 0u : QV_NOKMER;
-				live[u] = false; kid[u] = h >> img.pre; keys[u] = karena; idx[u] = 0; nmask[u] = 0;
-				if (mine[u] && ok) {
+				v[u] = ok ? 0u : NOKMER;
+				/* htab.c:93-100 compares (hash >> pre) << 10 >> 10: the stored key keeps 54 bits of it, all of them at k < 32 (pre >= 10) */
+				live[u] = false; kid[u] = LONG ? (h >> img.pre) & (~0ull >> 10) : h >> img.pre; keys[u] = karena; idx[u] = 0; nmask[u] = 0;
+				if (ok) {
 					u64 off; u32 bits;
 					if (tab) { const u64 e = s_tab[p]; off = e & ((1ull << 58) - 1); bits = (u32)(e >> 58); bits = bits == 63u ? YK_NOCAP : bits; }
 					else { bits = img.bits[p]; off = img.off[p]; }
@@ -743,7 +732,6 @@ void k_lookup(const uint8_t *__restrict__ bases, int64_t n, int k, ImgView img, 
 			for (int u = 0; u < LK_U; ++u) kc[u] = live[u] ? keys[u][idx[u]] : YK_EMPTY;
 #pragma unroll
 			for (int u = 0; u < LK_U; ++u) {
-				/* htab.c:93-100 on the image: the key array alone is probed (every unused slot holds YK_EMPTY, which no 2k < 64-bit key equals) */
 				const u32 first = idx[u];
 				while (kc[u] != YK_EMPTY) {
 					if (kc[u] >> 10 == kid[u]) { v[u] = (u32)(kc[u] & 1023u); break; }
@@ -751,11 +739,14 @@ void k_lookup(const uint8_t *__restrict__ bases, int64_t n, int k, ImgView img, 
 					if (idx[u] == first) break;
 					kc[u] = keys[u][idx[u]];
 				}
-				if (mine[u]) out[tile0 + (r0 + u) * XT_THREADS + (int)threadIdx.x] = (unsigned short)v[u];
+				if (FLAG && v[u] != NOKMER && v[u] > 15u) { over = 1; v[u] &= 15u; }
+				const int64_t pos = tile0 + (r0 + u) * XT_THREADS + (int)threadIdx.x;
+				if (pos < n) out[pos] = (T)v[u];
 			}
 		}
 		__syncthreads();
 	}
+	if (FLAG && over) d_tb_over = 1;
 }
 
 /* one wave per sequence; tot = 0xffffffff marks a sequence below min_len (qv.c:45) */
@@ -782,15 +773,85 @@ void k_qv_reduce(const unsigned short *__restrict__ t, const u64 *__restrict__ r
 	for (u32 i = threadIdx.x; i < 1024; i += 256) if (s_hist[i]) atomicAdd(&hist[i], (unsigned long long)s_hist[i]);
 }
 
-void yk_launch_lookup(const uint8_t *bases, int64_t n, int k, ImgView img, unsigned short *out, hipStream_t st)
+/* triobin's per-read reduction (triobin.c:74-100): one wave per read, 64 positions per step.
+ *   c[16]  histogram of the flags over the positions that have a k-mer; nk = their number
+ *   sc[2]  a position's type is 1 where flag == 2 (pat solid, mat absent), 2 where flag == 8, 0
+ *          elsewhere (also where no k-mer ends); every maximal run of one type t > 0 and length
+ *          >= k - 4 adds its length to sc[t - 1]
+ * The run open at a step's start is carried as (start, type); the step's run starts are a ballot,
+ * walked bit by bit with scalar ops.  A run of type 0 "opens" at position 0: it adds nothing, and a
+ * read that starts with a typed position closes it at once.
+ * Output per read: 19 int32 = c[0..15], sc[0], sc[1], nk. */
+__global__ __launch_bounds__(256)
+void k_tb_reduce(const uint8_t *__restrict__ flag, const u64 *__restrict__ roff, const u32 *__restrict__ rlen, int64_t n_reads, int k,
+                 int *__restrict__ cnt)
+{
+	const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const int64_t min_run = (int64_t)k - 4;
+	for (int64_t r = (int64_t)blockIdx.x * 4 + wave; r < n_reads; r += (int64_t)gridDim.x * 4) {
+		const uint8_t *f = flag + roff[r];
+		const u32 len = rlen[r];
+		u32 mine = 0;                                 /* lane j < 16: c[j] */
+		int64_t run0 = 0, sc0 = 0, sc1 = 0;
+		u32 rtype = 0;
+		u32 nxt = lane < len ? f[lane] : TB_NOKMER;
+		for (u32 base = 0; base < len; base += 64) {
+			const u32 i = base + lane;
+			const u32 v = nxt;
+			nxt = i + 64 < len ? f[i + 64] : TB_NOKMER;              /* the next step's load in flight during this one */
+			const u32 ty = v == 2u ? 1u : v == 8u ? 2u : 0u;
+			const u64 in = __ballot(i < len);
+			const u64 t1 = __ballot(ty == 1u), t2 = __ballot(ty == 2u);
+#pragma unroll
+			for (u32 j = 0; j < 16; ++j) { const u32 c = (u32)__popcll(__ballot(v == j)); mine += lane == j ? c : 0u; }
+			/* run starts: positions whose type differs from the one before (lane 0: from the run carried in) */
+			const u32 prev = __shfl_up(ty, 1);
+			const u64 starts = __ballot(lane == 0 ? ty != rtype : ty != prev) & in;
+			for (u64 m = starts; m; m &= m - 1) {
+				const u32 j = (u32)__ffsll((unsigned long long)m) - 1;
+				const int64_t p = (int64_t)base + j, l = p - run0;
+				if (rtype && l >= min_run) { if (rtype == 1) sc0 += l; else sc1 += l; }
+				run0 = p;
+				rtype = (t1 >> j & 1) ? 1u : (t2 >> j & 1) ? 2u : 0u;
+			}
+		}
+		{
+			const int64_t l = (int64_t)len - run0;
+			if (rtype && l >= min_run) { if (rtype == 1) sc0 += l; else sc1 += l; }
+		}
+		int *o = cnt + r * 19;
+		if (lane < 16) o[lane] = (int)mine;
+		u32 nk = 0;
+		for (int j = 0; j < 16; ++j) nk += __shfl(mine, j);
+		if (lane == 16) o[16] = (int)sc0;
+		if (lane == 17) o[17] = (int)sc1;
+		if (lane == 18) o[18] = (int)nk;
+	}
+}
+
+/* width 2: qv's counts (k < 32); width 1: triobin's flags, after clearing the flag yk_tb_over_seen() reads */
+void yk_launch_lookup(const uint8_t *bases, int64_t n, int k, ImgView img, void *out, int width, hipStream_t st)
 {
 	if (n <= 0) return;
 	/* one sweep over the whole image.  (Probing one prefix range of the image at a time -- each small enough for the 256 MB Infinity Cache, the queries
 	 * extracted once per sweep -- was measured on the benchmark's 512 MB image: 2 sweeps 38 ms against 36, 4 sweeps 52; more probes of a lane in flight,
-	 * 2 / 4 / 8: 34.3 / 35.2 / 40.8 ms against 34.7.  ~48 G probes/s is the rate at which DRAM rows can be opened: the kernel's arguments keep the range
-	 * for a caller that wants it) */
+	 * 2 / 4 / 8: 34.3 / 35.2 / 40.8 ms against 34.7.  ~48 G probes/s is the rate at which DRAM rows can be opened) */
 	const int tab = img.pre <= 12;
-	hipLaunchKernelGGL((k_lookup<2>), dim3(yk_xpart_blocks(n)), dim3(XT_THREADS), tab ? (size_t)8 << img.pre : 0, st, bases, n, k, img, out, 0u, 1u << img.pre, tab);
+	const size_t lds = tab ? (size_t)8 << img.pre : 0;
+	const dim3 grid(yk_xpart_blocks(n)), block(XT_THREADS);
+	if (width == 2) { hipLaunchKernelGGL((k_lookup<unsigned short, false>), grid, block, lds, st, bases, n, k, img, (unsigned short*)out, tab); return; }
+	void *over = 0;
+	if (hipGetSymbolAddress(&over, HIP_SYMBOL(d_tb_over)) == hipSuccess) (void)hipMemsetAsync(over, 0, 4, st);
+	if (k < 32) hipLaunchKernelGGL((k_lookup<uint8_t, false>), grid, block, lds, st, bases, n, k, img, (uint8_t*)out, tab);
+	else hipLaunchKernelGGL((k_lookup<uint8_t, true>), grid, block, lds, st, bases, n, k, img, (uint8_t*)out, tab);
+}
+
+int yk_tb_over_seen(hipStream_t st)
+{
+	u32 v = 0;
+	(void)hipStreamSynchronize(st);
+	(void)hipMemcpyFromSymbol(&v, HIP_SYMBOL(d_tb_over), 4);
+	return (int)v;
 }
 
 void yk_launch_qv_reduce(const unsigned short *t, const u64 *roff, const u32 *rlen, int64_t n_reads, int min_len, double min_frac,
@@ -802,3 +863,9 @@ void yk_launch_qv_reduce(const unsigned short *t, const u64 *roff, const u32 *rl
 	                   tot_out, non0_out, (unsigned long long*)hist);
 }
 
+void yk_launch_tb_reduce(const uint8_t *flag, const u64 *roff, const u32 *rlen, int64_t n_reads, int k, int *cnt, hipStream_t st)
+{
+	if (n_reads <= 0) return;
+	const int64_t want = (n_reads + 3) / 4;
+	hipLaunchKernelGGL(k_tb_reduce, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, st, flag, roff, rlen, n_reads, k, cnt);
+}

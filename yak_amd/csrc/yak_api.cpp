@@ -104,7 +104,7 @@ yak_ch_t *yak_ch_init(int k, int pre, int n_hash, int n_shift)
 	return h;
 }
 
-static int multi_refuse(const yak_ch_t *h, const char *what)
+int multi_refuse(const yak_ch_t *h, const char *what)
 {
 	if (!YK_MULTI((const yak_ch_ext*)h)) return 0;
 	fprintf(stderr, "[E::%s] not available on a table sharded over prefix ranges (several GPUs, or a large unfiltered count taken in sweeps: YAKAMD_GPUS / YAKAMD_AUTO_SWEEP_GB)\n", what);
@@ -942,117 +942,6 @@ int64_t yakamd_gz_inflate(const char *fn, int n_threads, char **out)
 	*out = (char*)malloc(all.size() + 1);
 	memcpy(*out, all.data(), all.size());
 	return (int64_t)all.size();
-}
-
-/* reference qv.c:137-144 */
-void yak_qopt_init(yak_qopt_t *opt)
-{
-	memset(opt, 0, sizeof(yak_qopt_t));
-	opt->chunk_size = 1000000000;
-	opt->n_threads = 4;
-	opt->min_frac = 0.5;
-	opt->fpr = 0.00004;
-}
-
-/* reference qv.c:34-135.  The table is already resident on the device; every chunk of sequences is
- * looked up there (k_lookup), reduced per sequence and binned (k_qv_reduce).  The EK / SQ lines of
- * -E / -p are printed from the values copied back, in input order (the reference prints them in a
- * thread-dependent order).  On a device error the function prints a message and leaves cnt zeroed. */
-void yak_qv(const yak_qopt_t *opt, const char *fn, const yak_ch_t *ch, int64_t *cnt)
-{
-	const int n_cnt = 1 << YAK_COUNTER_BITS;
-	memset(cnt, 0, n_cnt * sizeof(int64_t));
-	yak_ch_t *h = (yak_ch_t*)ch;
-	if (ch->k >= 32) { fprintf(stderr, "[E::yak_qv] k must be below 32\n"); return; }   /* qv.c:44 asserts */
-	if (multi_refuse(ch, __func__)) return;                      /* the lookup kernel reads one table image: restore the .yak file for qv */
-	FxReader fx;
-	if (!fx.open_file(fn)) return;
-	uint64_t *d_hist = (uint64_t*)yakamd_dev_alloc(n_cnt * 8);
-	std::vector<uint64_t> zero(n_cnt, 0), h_off;
-	std::vector<uint32_t> h_len, h_tot, h_non0;
-	std::vector<std::string> names;
-	std::vector<char> chunk;
-	std::vector<unsigned short> h_t;
-	bool ok = d_hist && yakamd_memcpy_h2d(d_hist, zero.data(), n_cnt * 8) == 0;
-	int64_t l, sum_len = 0;
-	auto flush = [&]() {
-		const size_t nb = chunk.size(), ns = h_len.size();
-		if (ns == 0) return;
-		chunk.resize((nb + 15) & ~(size_t)15, '\n');
-		void *d_b = yakamd_dev_alloc(chunk.size()), *d_t = yakamd_dev_alloc(chunk.size() * 2);
-		uint64_t *d_off = (uint64_t*)yakamd_dev_alloc(ns * 8);
-		uint32_t *d_len = (uint32_t*)yakamd_dev_alloc(ns * 4), *d_tot = (uint32_t*)yakamd_dev_alloc(ns * 4), *d_non0 = (uint32_t*)yakamd_dev_alloc(ns * 4);
-		ok = ok && d_b && d_t && d_off && d_len && d_tot && d_non0
-		     && yakamd_memcpy_h2d(d_b, chunk.data(), chunk.size()) == 0 && yakamd_memcpy_h2d(d_off, h_off.data(), ns * 8) == 0
-		     && yakamd_memcpy_h2d(d_len, h_len.data(), ns * 4) == 0
-		     && yakamd_lookup_dev(h, d_b, (int64_t)nb, d_t) == 0
-		     && yakamd_qv_reduce_dev(h, d_t, d_off, d_len, (int64_t)ns, opt->min_len, opt->min_frac, d_tot, d_non0, d_hist) == 0;
-		if (ok && (opt->print_each || opt->print_err_kmer)) {
-			h_tot.resize(ns); h_non0.resize(ns);
-			ok = yakamd_memcpy_d2h(h_tot.data(), d_tot, ns * 4) == 0 && yakamd_memcpy_d2h(h_non0.data(), d_non0, ns * 4) == 0;
-			if (ok && opt->print_err_kmer) { h_t.resize(chunk.size()); ok = yakamd_memcpy_d2h(h_t.data(), d_t, chunk.size() * 2) == 0; }
-			for (size_t j = 0; ok && j < ns; ++j) {
-				if (h_tot[j] == 0xffffffffu) continue;                          /* below min_len: qv.c:45 */
-				if (opt->print_err_kmer)
-					for (uint32_t i = 0; i < h_len[j]; ++i)
-						if (h_t[h_off[j] + i] == 0) printf("EK\t%s\t%d\n", names[j].c_str(), (int)(i + 1 - ch->k));
-				if (opt->print_each) {
-					const int tot = (int)h_tot[j], non0 = (int)h_non0[j];
-					double qv = -1.0;
-					if (tot > 0) {
-						if (non0 > 0) {
-							if (tot > non0) { qv = log((double)tot / non0) / ch->k; qv = -4.3429448190325175 * log(qv); }
-							else qv = 99.0;
-						} else qv = 0.0;
-					}
-					printf("SQ\t%s\t%d\t%d\t%d\t%.2f\n", names[j].c_str(), (int)h_len[j], tot, non0, qv);
-				}
-			}
-		}
-		yakamd_dev_free(d_b); yakamd_dev_free(d_t); yakamd_dev_free(d_off); yakamd_dev_free(d_len); yakamd_dev_free(d_tot); yakamd_dev_free(d_non0);
-		fprintf(stderr, "[M::%s] processed %ld sequences\n", "yak_qv", (long)ns);
-		chunk.clear(); h_off.clear(); h_len.clear(); names.clear(); sum_len = 0;
-	};
-	/* without -p / -E nothing of a record but its bases is needed: a plain, block-gzipped or gzip file then goes through the parallel reader
-	 * (every record's sequence + '\n', in order: bseq.c:40 keeps records of any length, qv.c:45 skips the short ones later) */
-	const int n_thr = parse_threads(opt->n_threads);
-	ByteSource psrc; int psrc_fd = -1;
-	pgz::Reader *gz_p = new pgz::Reader;
-	struct GzDrop { pgz::Reader *p; ~GzDrop() { pgz::Reader *q = p; yk_reap_later([q]() { delete q; }); } } gz_drop{ gz_p };
-	bool parallel = false;
-	if (ok && !opt->print_each && !opt->print_err_kmer) {
-		const ImgSink sink = [&](const char *img, size_t n, int64_t, const WinPack*) {
-			const size_t base = chunk.size();
-			for (const char *p = img, *e = img + n; p < e; ) {
-				const char *q = (const char*)memchr(p, '\n', (size_t)(e - p));
-				if (!q) q = e;
-				h_off.push_back(base + (size_t)(p - img)); h_len.push_back((uint32_t)(q - p));
-				sum_len += q - p;
-				p = q + 1;
-			}
-			chunk.insert(chunk.end(), img, img + n);
-			if (sum_len >= opt->chunk_size || chunk.size() > ((size_t)1 << 31)) flush();   /* bseq.c:54 */
-			return ok;
-		};
-		if (parallel_source(fn, fx, n_thr, 1 << 20, &psrc, &psrc_fd)) { parallel = true; ok = parse_parallel(&psrc, 0, n_thr, sink) && ok; }
-		else if (gz_source(fn, fx, n_thr, gz_p)) { parallel = true; ok = parse_gz(gz_p, 0, n_thr, sink) && ok; }
-		if (psrc_fd >= 0) ::close(psrc_fd);
-	}
-	while (ok && !parallel && (l = fx.next()) >= 0) {         /* bseq.c:40 */
-		h_off.push_back(chunk.size()); h_len.push_back((uint32_t)l);
-		if (opt->print_each || opt->print_err_kmer) names.emplace_back(fx.name.begin(), fx.name.end());
-		chunk.insert(chunk.end(), fx.seq.begin(), fx.seq.end());
-		chunk.push_back('\n');
-		sum_len += l;
-		if (sum_len >= opt->chunk_size || chunk.size() > ((size_t)1 << 31)) flush();   /* bseq.c:54 */
-	}
-	if (ok) flush();
-	std::vector<uint64_t> hh(n_cnt, 0);
-	ok = ok && yakamd_memcpy_d2h(hh.data(), d_hist, n_cnt * 8) == 0;
-	if (ok) for (int i = 0; i < n_cnt; ++i) cnt[i] = (int64_t)hh[i];
-	else fprintf(stderr, "[E::yak_qv] %s\n", yakamd_last_error());
-	yakamd_dev_free(d_hist);
-	fx.close_file();
 }
 
 /* n x n linear system a x = b by Gauss-Jordan elimination with full pivoting (the solver the

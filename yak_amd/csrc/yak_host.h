@@ -1,6 +1,7 @@
 /*
- * yak_host.h -- internal: what the three host translation units of the library share (yak_api.cpp: the yak.h surface, dump / restore, qv;
- * yak_reader.cpp: the FASTA / FASTQ reader, its parallel parser and packer, the gzip hooks; yak_multi.cpp: several GPUs behind yak_count()).
+ * yak_host.h -- internal: what the host translation units of the library share (yak_api.cpp: the yak.h surface, dump / restore, qv's solver;
+ * yak_reader.cpp: the FASTA / FASTQ reader, its parallel parser and packer, the gzip hooks; yak_multi.cpp: several GPUs behind yak_count();
+ * yak_lookup.cpp: the lookup-only commands qv and triobin).
  */
 #ifndef YAK_HOST_H
 #define YAK_HOST_H
@@ -438,6 +439,9 @@ bool parallel_source(const char *fn, const FxReader &fx, int n_thr, int64_t min_
 bool parse_parallel(const ByteSource *fd, int min_len, int n_thr, const ImgSink &sink, int64_t *stopped_at = 0, bool *stream_ended = 0);
 bool gz_source(const char *fn, const FxReader &fx, int n_thr, pgz::Reader *z);
 bool parse_gz(pgz::Reader *z, int min_len, int n_thr, const ImgSink &sink, bool pack = false);
+
+/* 1 (and a message naming `what`) on a table sharded over prefix ranges (yak_api.cpp) */
+extern "C" int multi_refuse(const yak_ch_t *h, const char *what);
 
 /* ---- several GPUs behind yak_count() (yak_multi.cpp) ---- */
 bool env_fast_default();
