@@ -121,7 +121,8 @@ int64_t yakamd_retained_instances(yak_ch_t *h);
 
 /* Lookup-only path (`yak qv`, reference qv.c:34-86, k < 32).  yakamd_lookup_dev(): d_out_u16[i] =
  * max(0, yak_ch_get()) of the canonical k-mer ENDING at byte i of the base image, 0xffff where no
- * k-mer ends (window shorter than k or holding a non-ACGT byte).  yakamd_qv_reduce_dev(): sequence j
+ * k-mer ends (window shorter than k or holding a non-ACGT byte); not inside an open pass, not on a table
+ * sharded over prefix ranges.  yakamd_qv_reduce_dev(): sequence j
  * is bytes [d_seq_off[j], d_seq_off[j] + d_seq_len[j]) of that image; d_tot / d_non0 receive its
  * number of k-mers / of k-mers present in the table (d_tot = 0xffffffff for a sequence shorter than
  * min_len), and every sequence with non0 >= tot * min_frac adds its values to d_hist1024 (uint64

@@ -75,6 +75,15 @@ def lib():
         L.yko_read_image.restype = C.c_int64; L.yko_read_image.argtypes = [C.c_char_p, C.c_int, P(C.c_void_p)]
         L.yko_ch_hist.argtypes = [P(Ch), P(C.c_int64)]
         L.yko_ch_setcnt.argtypes = [P(Ch), C.c_int]
+        L.yko_ch_inc.restype = C.c_int; L.yko_ch_inc.argtypes = [P(Ch), C.c_uint64]
+        L.yko_ch_tighten.argtypes = [P(Ch)]
+        L.yko_ch_merge.argtypes = [P(Ch), P(Ch), C.c_int, C.c_int, C.c_int]
+        L.yko_ch_subtract.argtypes = [P(Ch), P(Ch)]
+        L.yko_ch_isec.argtypes = [P(Ch), P(Ch)]
+        L.yko_ch_restore_core.restype = P(Ch)
+        L.yko_ch_restore_core.argtypes = [P(Ch), C.c_char_p, C.c_int, C.c_int, C.c_int]
+        L.yko_lookup_image.restype = None
+        L.yko_lookup_image.argtypes = [P(Ch), C.c_char_p, C.c_int64, C.c_void_p, C.c_int]
         L.yko_qopt_init.argtypes = [P(Qopt)]
         L.yko_qv.restype = C.c_int; L.yko_qv.argtypes = [P(Qopt), C.c_char_p, P(Ch), P(C.c_int64), C.c_void_p]
         L.yko_count_file.restype = P(Ch); L.yko_count_file.argtypes = [C.c_char_p, P(Copt), P(Ch)]
@@ -148,6 +157,15 @@ def parse_qv_output(text):
         elif f[0] == "EK":
             ek.append(l)
     return ct, sorted(sq), sorted(ek)
+
+
+def lookup_image(h, img, width):
+    """yko_lookup_image: max(0, yko_ch_get()) of the k-mer ending at every byte of img, all ones where none ends -> numpy array
+    (uint16 for width 2, uint8 for width 1)"""
+    import numpy as np
+    out = np.empty(len(img), np.uint16 if width == 2 else np.uint8)
+    lib().yko_lookup_image(h, bytes(img), len(img), out.ctypes.data, width)
+    return out
 
 
 def read_image(fn, min_len=0):

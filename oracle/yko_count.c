@@ -91,6 +91,38 @@ int64_t yko_extract_pos(int k, const uint8_t *bases, int64_t n, uint64_t *out_ha
 	return m;
 }
 
+/* the lookup-only commands' per-position values (qv.c:50-62, triobin.c:62-84): for every byte i < n, max(0, yko_ch_get()) of the canonical
+ * k-mer ENDING at i, all ones of the element where none ends (window shorter than k or holding a byte yko_nt4 maps to 4).  k < 32 hashes the
+ * 2k-bit canonical k-mer (count.c:28-43); k >= 32 the four 1-bit planes (count.c:45-60).  width 2: uint16_t, the 10-bit count; width 1:
+ * uint8_t, the value as a byte (for tables whose values are <= 15, as the triobin loads make them) */
+void yko_lookup_image(const yko_ch_t *h, const uint8_t *bases, int64_t n, void *out, int width)
+{
+	const int k = h->k;
+	const uint64_t mask = k < 32 ? (1ULL << 2 * k) - 1 : (1ULL << k) - 1;
+	const int shift = k < 32 ? 2 * (k - 1) : k - 1;
+	uint64_t x[4] = { 0, 0, 0, 0 };
+	int64_t i;
+	int run = 0;
+	for (i = 0; i < n; ++i) {
+		int c = yko_nt4[bases[i]], v = -1;
+		if (c >= 4) { run = 0; x[0] = x[1] = x[2] = x[3] = 0; }
+		else if (k < 32) {
+			x[0] = (x[0] << 2 | (uint64_t)c) & mask;
+			x[1] = x[1] >> 2 | (uint64_t)(3 - c) << shift;
+			if (++run >= k) v = yko_ch_get(h, yko_hash64(x[0] < x[1] ? x[0] : x[1], mask));
+		} else {
+			x[0] = (x[0] << 1 | (uint64_t)(c & 1)) & mask;
+			x[1] = (x[1] << 1 | (uint64_t)(c >> 1)) & mask;
+			x[2] = x[2] >> 1 | (uint64_t)(1 - (c & 1)) << shift;
+			x[3] = x[3] >> 1 | (uint64_t)(1 - (c >> 1)) << shift;
+			if (++run >= k) v = yko_ch_get(h, yko_hash_long(x));
+		}
+		if (run >= k && v < 0) v = 0;
+		if (width == 2) ((uint16_t*)out)[i] = v < 0 ? 0xffff : (uint16_t)v;
+		else ((uint8_t*)out)[i] = v < 0 ? 0xff : (uint8_t)v;
+	}
+}
+
 /* ------------------------------------------------------------------ FASTA/FASTQ reader
  * Record grammar followed (kseq.h:192-232): skip to a line starting with '>' or '@'; name = up
  * to the first white space, rest of the line ignored; sequence = concatenation of the following

@@ -1,5 +1,5 @@
 """`yak triobin` on the device (k_lookup + k_tb_reduce + yakamd_triobin): byte-equal to the reference's
-`triobin -t1` on the stored fixtures, per-position flags equal to the host mirror's yak_ch_get(), and the
+`triobin -t1` on the stored fixtures and at -p13, per-position flags equal to the oracle's restatement (yko_lookup_image), and the
 per-read reduction equal to a numpy restatement of triobin.c:74-100."""
 import ctypes as C
 import json
@@ -144,53 +144,22 @@ class Dev:
             self.L.yakamd_dev_free(p)
 
 
-NT4 = np.full(256, 4, np.uint8)
-for i, ch in enumerate(b"ACGT"):
-    NT4[ch] = NT4[ch + 32] = i
-NT4[ord("U")] = NT4[ord("u")] = 3
-
-
-def host_flags(L, h, k, img, oracle_lib):
-    """triobin.c:62-84 on the host: max(0, yak_ch_get()) of the k-mer ending at each byte, NOKMER where none"""
-    out = np.full(len(img), NOKMER, np.uint8)
-    mask = (1 << (2 * k if k < 32 else k)) - 1
-    shift = 2 * (k - 1) if k < 32 else k - 1
-    x = [0, 0, 0, 0]
-    l = 0
-    xl = (C.c_uint64 * 4)()
-    for i, b in enumerate(img):
-        c = int(NT4[b])
-        if c >= 4:
-            l, x = 0, [0, 0, 0, 0]
-            continue
-        if k < 32:
-            x[0] = (x[0] << 2 | c) & mask
-            x[1] = x[1] >> 2 | (3 - c) << shift
-        else:
-            x[0] = (x[0] << 1 | (c & 1)) & mask
-            x[1] = (x[1] << 1 | (c >> 1)) & mask
-            x[2] = x[2] >> 1 | (1 - (c & 1)) << shift
-            x[3] = x[3] >> 1 | (1 - (c >> 1)) << shift
-        l += 1
-        if l >= k:
-            if k < 32:
-                y = oracle_lib.yko_hash64(min(x[0], x[1]), mask)
-            else:
-                for j in range(4):
-                    xl[j] = x[j]
-                y = oracle_lib.yko_hash_long(xl)
-            out[i] = max(0, L.yak_ch_get(h, y))
-    return out
-
-
 @pytest.mark.parametrize("k", [21, 31, 32, 41])
 def test_lookup_equals_host_mirror(trio, oracle, k):
+    """per-position flags against the oracle's restatement (yko_lookup_image) on the oracle's own two TRIOBIN loads of the same files, and
+    the library's table bytes against the oracle's"""
     import yak_amd
-    L = yak_amd.lib()
+    L, O = yak_amd.lib(), oracle.lib()
     p, table = trio
     h = yak_amd.triobin_table(table(k, "pat"), table(k, "mat"), 1, 2)
+    o = O.yko_ch_restore_core(None, table(k, "pat").encode(), 2, 1, 2)
+    o = O.yko_ch_restore_core(o, table(k, "mat").encode(), 3, 1, 2)
     dev = Dev(L)
     try:
+        out = C.POINTER(C.c_uint8)()
+        n = L.yakamd_dump_mem(h, C.byref(out))
+        assert n > 0 and C.string_at(out, n) == oracle.dump_bytes(o)
+        C.CDLL(None).free(out)
         recs = _records(p["child.fa"])
         img = b"".join(s[:6000] + b"\n" for _, s in recs)           # every record, the long ones cut to 6 kb
         img += b"\n" * (-len(img) % 16)
@@ -198,13 +167,35 @@ def test_lookup_equals_host_mirror(trio, oracle, k):
         d_flag = dev.empty(len(img))
         assert L.yakamd_triobin_lookup_dev(h, d_img, len(img), d_flag) == 0, yak_amd._err()
         got = dev.get(d_flag, len(img), np.uint8)
-        want = host_flags(L, h, k, img, oracle.lib())
+        want = oracle.lookup_image(o, img, 1)
         assert (got <= 15).sum() > 1000 and (got[got <= 15] > 0).sum() > 1000
         bad = np.flatnonzero(got != want)
         assert bad.size == 0, (bad[:10], got[bad[:10]], want[bad[:10]])
     finally:
         dev.free()
         L.yak_ch_destroy(h)
+        O.yko_ch_destroy(o)
+
+
+@pytest.mark.skipif(not os.path.exists(G.REF_YAK), reason="reference binary not built")
+@pytest.mark.parametrize("k", [21, 41])
+def test_live_reference_on_parents_counted_at_p13(gold, trio, oracle, k, tmp_path):
+    """-p13: the parents' tables have 8192 sub-tables and the lookup reads its directory from global memory (pre >= 13).  (13 is the largest
+    prefix length the library's flag-mode loads take)"""
+    p, _ = trio
+    tabs = []
+    for who in ("pat", "mat"):
+        fn, want = str(tmp_path / (who + ".yak")), str(tmp_path / (who + "_oracle.yak"))
+        for exe, out in ((CLI, fn), (os.path.join(ROOT, "oracle", "yko"), want)):
+            subprocess.run([exe, "count", "-k%d" % k, "-p13"] + gold["count_args"] + ["-o", out, p[who + ".fa"]], check=True,
+                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
+        data = open(fn, "rb").read()
+        assert data == open(want, "rb").read() and data[8:12] == (13).to_bytes(4, "little")
+        tabs.append(fn)
+    for opts in (["-p"], ["-c1", "-d2"], []):
+        mine = subprocess.run([CLI, "triobin"] + opts + tabs + [p["child.fa"]], check=True, stdout=subprocess.PIPE,
+                              stderr=subprocess.DEVNULL, timeout=600).stdout
+        assert G.ref_triobin(G.REF_YAK, tabs[0], tabs[1], p["child.fa"], opts) == mine and len(mine) > 500
 
 
 def reduce_ref(f, k):

@@ -98,9 +98,6 @@ def test_cntasm_sequence_on_the_oracle_equals_reference_cli(pre_resize, tmp_path
     (main.c:90-161): three assemblies, unique k-mers per sample, merged, shrunk, tightened, dumped"""
     import ctypes as C
     O = oracle.lib()
-    O.yko_ch_merge.argtypes = [C.POINTER(oracle.Ch), C.POINTER(oracle.Ch), C.c_int, C.c_int, C.c_int]
-    O.yko_ch_shrink.argtypes = [C.POINTER(oracle.Ch), C.c_int, C.c_int]
-    O.yko_ch_tighten.argtypes = [C.POINTER(oracle.Ch)]
     fas = cntasm_assemblies(tmp_path)
     K = 21
     oo = oracle.copt(k=K, chunk=1900000000)
@@ -122,10 +119,7 @@ def test_cntasm_sequence_on_the_oracle_equals_reference_cli(pre_resize, tmp_path
 @pytest.mark.parametrize("cmd", ["subtract", "isec"])
 def test_subtract_isec_sequence_on_the_oracle_equals_reference_cli(cmd, tmp_path, oracle):
     """`yak subtract` / `yak isec` (main.c:217-284) against the oracle's restore + set operation + tighten"""
-    import ctypes as C
     O = oracle.lib()
-    O.yko_ch_subtract.argtypes = [C.POINTER(oracle.Ch)] * 2; O.yko_ch_isec.argtypes = [C.POINTER(oracle.Ch)] * 2
-    O.yko_ch_tighten.argtypes = [C.POINTER(oracle.Ch)]
     g = gold()
     tabs = k25_tables(tmp_path, SET_OP_READS, g["set_op_tables"])
     o0, o1 = O.yko_ch_restore(tabs[0].encode()), O.yko_ch_restore(tabs[1].encode())
@@ -143,10 +137,7 @@ def restore_core_steps(family, tabs):
 def test_restore_core_flag_modes_equal_reference_library(family, tmp_path, oracle):
     """yak_ch_restore_core modes 2-6 (htab.c:396-476) as the reference's own shared library (oracle/_ref/libyakref.so)
     computed them against the oracle's restatement: flag sets ORed into one table"""
-    import ctypes as C
     O = oracle.lib()
-    O.yko_ch_restore_core.restype = C.POINTER(oracle.Ch)
-    O.yko_ch_restore_core.argtypes = [C.POINTER(oracle.Ch), C.c_char_p, C.c_int, C.c_int, C.c_int]
     g = gold()
     tabs = k25_tables(tmp_path, CORE_READS, g["restore_core_tables"])
     ho = None

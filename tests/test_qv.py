@@ -117,6 +117,21 @@ def test_yak_qv_through_the_c_abi(opt, k, bf, ya, oracle, tmp_path):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("pre", [12, 14])
+@pytest.mark.parametrize("k,bf", [(21, 0), (27, 24)])
+def test_yak_qv_through_the_c_abi_at_other_prefix_lengths(pre, k, bf, ya, oracle, tmp_path):
+    """-p12 stages a 32 KB sub-table directory in LDS, -p14 makes the lookup read it from global memory (pre >= 13)"""
+    fq, fa, tab = str(tmp_path / "r.fq"), str(tmp_path / "a.fa"), str(tmp_path / "t.yak")
+    subprocess.check_call([SYN, "-n", "20000", "-l", "150", "-g", "100000", "-s", "13", "-o", fq])
+    subprocess.check_call([SYN, "-a", "-n", "60", "-l", "4000", "-g", "100000", "-s", "13", "-e", "0.004", "-N", "0.0005", "-o", fa])
+    subprocess.run([YKO, "count", f"-k{k}", f"-b{bf}", f"-p{pre}", "-o", tab, fq], check=True, stderr=subprocess.DEVNULL)
+    assert open(tab, "rb").read()[8:12] == pre.to_bytes(4, "little")
+    for opt in (dict(), dict(min_frac=0.0)):
+        want = oracle.qv_counts(tab, fa, **opt)
+        assert ya.qv_counts(tab, fa, **opt) == want and sum(want) > 0 and sum(want[2:]) > 0
+
+
+@pytest.mark.gpu
 def test_yak_qv_reads_large_files_through_the_parallel_reader(ya, oracle, tmp_path, monkeypatch):
     """without -p / -E yak_qv needs nothing of a record but its bases: a file of more than 1 MB -- plain, ordinary gzip, wrapped FASTA with short
     and empty records among the long ones -- goes through the parallel reader (threads x windows), and the histogram is the one-thread reader's

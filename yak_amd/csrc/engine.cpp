@@ -1051,9 +1051,17 @@ static int lookup_dev(yakamd_ctx *c, const void *d_bases, int64_t n_bytes, void 
 	return 0;
 }
 
+/* the kernel reads one whole table image: refused are several GPUs' tables (which have no context of their own) and a yakamd_set_shard range */
+static bool lookup_sharded(const yak_ch_t *h, const yakamd_ctx *c)
+{
+	const yak_ch_ext *e = (const yak_ch_ext*)h;
+	return (h && e->magic == EXT_MAGIC && e->n_sub > 1) || (c && (c->plo != 0 || c->phi != c->P));
+}
+
 extern "C" int yakamd_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, void *d_out_u16)
 {
 	yakamd_ctx *c = ctx_of(h);
+	if (lookup_sharded(h, c)) return fail("lookup: not available on a table sharded over prefix ranges");
 	if (!c) return fail("not an engine table");
 	if (c->in_pass) return fail("lookup during an open pass");
 	if (c->k < 1 || c->k >= 32) return fail("lookup: k must be below 32 (reference qv.c:44)");
@@ -1074,8 +1082,8 @@ extern "C" int yakamd_qv_reduce_dev(yak_ch_t *h, const void *d_t_u16, const uint
 extern "C" int yakamd_triobin_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, void *d_flag_u8)
 {
 	yakamd_ctx *c = ctx_of(h);
+	if (lookup_sharded(h, c)) return fail("triobin lookup: not available on a table sharded over prefix ranges");
 	if (!c) return fail("not an engine table");
-	if (((const yak_ch_ext*)h)->n_sub > 1 || c->plo != 0 || c->phi != c->P) return fail("triobin lookup: not available on a table sharded over prefix ranges");
 	if (c->in_pass) return fail("lookup during an open pass");
 	if (c->k < 1 || c->k >= 64) return fail("triobin lookup: k must be in [1, 63]");
 	if (lookup_dev(c, d_bases, n_bytes, d_flag_u8, 1)) return -1;
