@@ -154,6 +154,31 @@ typedef struct {
 void yakamd_tbopt_init(yakamd_tbopt_t *opt);
 int yakamd_triobin(const yakamd_tbopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn);
 
+/* Streak reduction of `yak trioeval` (reference trioeval.c:89-116, k in [1, 63]) over the flags yakamd_triobin_lookup_dev() wrote:
+ * a position's type is 1 where its flag is 2, 2 where it is 8, 0 elsewhere; a streak is a maximal run [st, en) of one type > 0 with
+ * en - st >= min_n.  The array is bytes [0, n_bytes) of d_flag_u8; sequence j starts at d_seq_off[j] (ascending), and the byte after every
+ * sequence must not be 2 or 8 (an image's '\n' is 0xff), so that no run crosses two sequences.  d_cnt_i32x6[6 j ..] receives d[0], d[1],
+ * c[0..3] of sequence j (trioeval.c:92-99, int32).  With d_streaks != NULL, *d_streaks receives a device buffer (the caller frees it
+ * with yakamd_dev_free; NULL when there is no streak) of *n_streaks yakamd_streak_t in sequence and position order, st and en relative
+ * to the sequence.  `stream` = a hipStream_t or 0; returns when the device is done. */
+typedef struct {
+	uint32_t seq, st, en, type;
+} yakamd_streak_t;
+int yakamd_trioeval_reduce_dev(int k, int min_n, const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
+                               int64_t n_bytes, int32_t *d_cnt_i32x6, void **d_streaks, int64_t *n_streaks, void *stream);
+/* `yak trioeval` as a library call: the phasing of every sequence of `fn` (FASTA/FASTQ, .gz, "-" = stdin) against `ch` (the two
+ * TRIOBIN loads), output byte-equal to the reference's with -t1 (the C header; per chunk of chunk_size bases the F / E lines, then
+ * one S line per sequence; then the W, H and N lines) written to out_fn (NULL = stdout).  0 on success, -1 after a message on stderr. */
+typedef struct {
+	int min_n;                /* -n, 2: the shortest streak */
+	int print_err;            /* -e, 0: E lines at the switches */
+	int print_frag;           /* 1 (-F sets 0): F lines of the fragments */
+	int n_threads;            /* -t, 8: the reference's worker threads; here the sequences are reduced on the device and a second thread reads ahead */
+	int64_t chunk_size;       /* bases per chunk, 1000000000 (trioeval.c:12) */
+} yakamd_teopt_t;
+void yakamd_teopt_init(yakamd_teopt_t *opt);
+int yakamd_trioeval(const yakamd_teopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn);
+
 /* Host-only test hook (no device needed): the base image yak_count() hands to the device for a
  * FASTA/FASTQ(.gz) file -- sequences of >= min_len bases, each followed by '\n'.  use_fast_path = 0
  * forces the general record reader for every record.  *out is malloc()ed; returns its length or -1. */

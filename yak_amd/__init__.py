@@ -35,6 +35,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_retain_input", "yakamd_count_retained", "yakamd_retained_instances", "yakamd_count_multi_dev",
     "yakamd_host_alloc", "yakamd_host_free", "yakamd_device_sync", "yakamd_mem_info", "yakamd_last_sweeps", "yakamd_pool_report",
     "yakamd_triobin_lookup_dev", "yakamd_triobin_reduce_dev", "yakamd_tbopt_init", "yakamd_triobin",
+    "yakamd_trioeval_reduce_dev", "yakamd_teopt_init", "yakamd_trioeval",
 ]
 
 
@@ -60,6 +61,15 @@ class QstatT(C.Structure):                     # yak_qstat_t (reference yak.h:42
 
 class TboptT(C.Structure):                     # yakamd_tbopt_t, include/yak_amd.h
     _fields_ = [("ratio_thres", C.c_double), ("print_diff", C.c_int32), ("n_threads", C.c_int32), ("chunk_size", C.c_int64)]
+
+
+class TeoptT(C.Structure):                     # yakamd_teopt_t, include/yak_amd.h
+    _fields_ = [("min_n", C.c_int32), ("print_err", C.c_int32), ("print_frag", C.c_int32), ("n_threads", C.c_int32),
+                ("chunk_size", C.c_int64)]
+
+
+class StreakT(C.Structure):                    # yakamd_streak_t, include/yak_amd.h
+    _fields_ = [("seq", C.c_uint32), ("st", C.c_uint32), ("en", C.c_uint32), ("type", C.c_uint32)]
 
 
 class StatsT(C.Structure):                     # yakamd_stats_t
@@ -202,6 +212,11 @@ def lib():
     L.yakamd_triobin_reduce_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.yakamd_tbopt_init.restype = None; L.yakamd_tbopt_init.argtypes = [P(TboptT)]
     L.yakamd_triobin.restype = C.c_int; L.yakamd_triobin.argtypes = [P(TboptT), P(ChT), C.c_char_p, C.c_char_p]
+    L.yakamd_trioeval_reduce_dev.restype = C.c_int
+    L.yakamd_trioeval_reduce_dev.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
+                                             P(C.c_void_p), P(C.c_int64), C.c_void_p]
+    L.yakamd_teopt_init.restype = None; L.yakamd_teopt_init.argtypes = [P(TeoptT)]
+    L.yakamd_trioeval.restype = C.c_int; L.yakamd_trioeval.argtypes = [P(TeoptT), P(ChT), C.c_char_p, C.c_char_p]
     _lib = L
     return L
 
@@ -422,6 +437,26 @@ def triobin(pat_yak, mat_yak, seq_fn, min_cnt=2, mid_cnt=5, ratio=0.33, print_di
             out = os.path.join(d, "triobin.txt")
             if L.yakamd_triobin(C.byref(o), h, seq_fn.encode(), out.encode()) != 0:
                 raise RuntimeError("yakamd_triobin failed: " + _err())
+            return open(out, "rb").read()
+    finally:
+        L.yak_ch_destroy(h)
+
+
+def trioeval(pat_yak, mat_yak, seq_fn, min_cnt=2, mid_cnt=5, min_n=2, print_err=False, print_frag=True, chunk=None):
+    """`yak trioeval` through the C ABI (two TRIOBIN loads + yakamd_trioeval): the bytes the reference writes to stdout with -t1"""
+    import tempfile
+    L = lib()
+    h = triobin_table(pat_yak, mat_yak, min_cnt, mid_cnt)
+    try:
+        o = TeoptT()
+        L.yakamd_teopt_init(C.byref(o))
+        o.min_n, o.print_err, o.print_frag = min_n, int(bool(print_err)), int(bool(print_frag))
+        if chunk is not None:
+            o.chunk_size = chunk
+        with tempfile.TemporaryDirectory() as d:
+            out = os.path.join(d, "trioeval.txt")
+            if L.yakamd_trioeval(C.byref(o), h, seq_fn.encode(), out.encode()) != 0:
+                raise RuntimeError("yakamd_trioeval failed: " + _err())
             return open(out, "rb").read()
     finally:
         L.yak_ch_destroy(h)

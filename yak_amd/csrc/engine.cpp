@@ -1102,6 +1102,78 @@ extern "C" int yakamd_triobin_reduce_dev(int k, const void *d_flag_u8, const uin
 	return 0;
 }
 
+/* trioeval's scratch (kern_trioeval.inc): kept from one call to the next, grown when a call needs more, on the device of the last call */
+namespace {
+struct TeBuf {
+	void *p = 0;
+	size_t cap = 0;
+	bool fit(size_t n) { if (n <= cap) return true; (void)hipFree(p); p = 0; cap = n + n / 8; if (hipMalloc(&p, cap) != hipSuccess) { p = 0; cap = 0; } return p != 0; }
+};
+struct TeScratch {
+	std::mutex mu;
+	int dev = -1;
+	TeBuf tcnt, toff, st, en, kcnt, koff, list;
+	u64 *host = 0;                                     /* pinned: the two totals read back */
+	void on(int d) { if (d == dev) return; for (TeBuf *b : { &tcnt, &toff, &st, &en, &kcnt, &koff, &list }) { (void)hipFree(b->p); *b = TeBuf(); } dev = d; }
+};
+TeScratch g_te;
+}
+
+extern "C" int yakamd_trioeval_reduce_dev(int k, int min_n, const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
+                                          int64_t n_bytes, int32_t *d_cnt_i32x6, void **d_streaks, int64_t *n_streaks, void *stream)
+{
+	(void)d_seq_len;                                   /* the records are told apart by their separators; off[] places a streak */
+	if (d_streaks) *d_streaks = 0;
+	if (n_streaks) *n_streaks = 0;
+	if (k < 1 || k >= 64) return fail("trioeval reduce: k must be in [1, 63]");
+	if (n_seq < 0 || n_seq > (int64_t)0xfffffffe || n_bytes < 0) return fail("trioeval reduce: bad n_seq or n_bytes");
+	const hipStream_t st = (hipStream_t)stream;
+	if (n_seq > 0) HIPCK(hipMemsetAsync(d_cnt_i32x6, 0, (size_t)n_seq * 24, st));
+	if (n_seq == 0 || n_bytes == 0) { HIPCK(hipStreamSynchronize(st)); return 0; }
+	const uint8_t *flag = (const uint8_t*)d_flag_u8;
+	std::lock_guard<std::mutex> lk(g_te.mu);
+	int dev = 0;
+	HIPCK(hipGetDevice(&dev));
+	g_te.on(dev);
+	TeScratch &s = g_te;
+	const int64_t nt = yk_te_tiles(n_bytes);
+	if (!s.tcnt.fit((size_t)nt * 8) || !s.toff.fit((size_t)(nt + 1) * 16)) return fail("trioeval reduce: out of device memory");
+	if (!s.host) HIPCK(hipHostMalloc((void**)&s.host, 16));
+	yk_launch_te_runs(flag, n_bytes, (u32*)s.tcnt.p, 0, 0, 0, 0, st);
+	yk_launch_te_scan((const u32*)s.tcnt.p, nt, 2, (u64*)s.toff.p, st);
+	HIPCK(hipGetLastError());
+	HIPCK(hipMemcpyAsync(s.host, (const u64*)s.toff.p + nt, 8, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
+	const u64 n_runs = s.host[0];
+	void *list = 0;
+	s.host[1] = 0;
+	if (n_runs > 0) {                                  /* the list is sized by the runs: the number kept stays on the device until the end */
+		if (!s.st.fit(n_runs * 8) || !s.en.fit(n_runs * 8)) return fail("trioeval reduce: out of device memory for %llu runs", (unsigned long long)n_runs);
+		const int64_t nb = yk_te_keep_blocks((int64_t)n_runs);
+		if (!s.kcnt.fit((size_t)nb * 4) || !s.koff.fit((size_t)(nb + 1) * 8)) return fail("trioeval reduce: out of device memory");
+		if (d_streaks) { if (hipMalloc(&list, n_runs * 16) != hipSuccess) return fail("trioeval reduce: out of device memory for %llu runs", (unsigned long long)n_runs); }
+		else if (!s.list.fit(n_runs * 16)) return fail("trioeval reduce: out of device memory");
+		else list = s.list.p;
+		yk_launch_te_runs(flag, n_bytes, 0, (const u64*)s.toff.p, (u64*)s.st.p, (u64*)s.en.p, 1, st);
+		yk_launch_te_keep((const u64*)s.st.p, (const u64*)s.en.p, flag, (int64_t)n_runs, min_n, (u32*)s.kcnt.p, 0, (const u64*)d_seq_off, n_seq, 0, 0, st);
+		yk_launch_te_scan((const u32*)s.kcnt.p, nb, 1, (u64*)s.koff.p, st);
+		yk_launch_te_keep((const u64*)s.st.p, (const u64*)s.en.p, flag, (int64_t)n_runs, min_n, 0, (const u64*)s.koff.p, (const u64*)d_seq_off, n_seq, list, 1, st);
+		yk_launch_te_seq(list, (const u64*)s.koff.p + nb, (int64_t)n_runs, k, (int*)d_cnt_i32x6, st);
+		const hipError_t e = hipGetLastError();
+		if (e == hipSuccess) (void)hipMemcpyAsync(s.host + 1, (const u64*)s.koff.p + nb, 8, hipMemcpyDeviceToHost, st);
+	}
+	const hipError_t e = hipGetLastError(), e2 = hipStreamSynchronize(st);
+	const u64 n_keep = s.host[1];
+	if (e != hipSuccess || e2 != hipSuccess) {
+		if (d_streaks) (void)hipFree(list);
+		return fail("trioeval reduce: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+	}
+	if (d_streaks && n_keep == 0) { (void)hipFree(list); list = 0; }
+	if (d_streaks) *d_streaks = list;
+	if (n_streaks) *n_streaks = (int64_t)n_keep;
+	return 0;
+}
+
 extern "C" int64_t yakamd_extract_dev(int k, const void *d_bases, int64_t n_bytes, void *d_hash, void *d_t,
                                       int pre, int plo, int phi, void *stream)
 {

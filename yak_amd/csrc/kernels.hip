@@ -89,6 +89,7 @@ __device__ const unsigned char d_nt4[256] = {
 };
 
 #include "kern_extract.inc"
+#include "kern_trioeval.inc"
 #include "kern_general.inc"
 #include "kern_layout.inc"
 #include "kern_replay2.inc"

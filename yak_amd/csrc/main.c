@@ -2,11 +2,12 @@
  * main.c -- `yak-amd`: the repo's own small command-line driver of libyak_amd.so, plain C against
  * include/yak.h (and include/yak_amd.h for triobin and -X).  It is a test and benchmark vehicle (tests/, bench.py's e2e_cli figure), not a
  * re-creation of the reference's CLI: that one runs unmodified on the library (INTEGRATION.md section 2,
- * oracle/_ref/yak_on_amd).  Three sub-commands drive the call sequences the library serves:
+ * oracle/_ref/yak_on_amd).  Four sub-commands drive the call sequences the library serves:
  *     count    the counting protocol behind reference main.c:53-61 (one pass, or two passes + shrink
  *              when a bloom filter is asked for)
  *     qv       the lookup protocol behind reference main.c:163-215 (restore, histogram, yak_qv, solve)
  *     triobin  the read binning of reference triobin.c:153-197 (two TRIOBIN loads, yakamd_triobin)
+ *     trioeval the phasing evaluation of reference trioeval.c:153-212 (two TRIOBIN loads, yakamd_trioeval)
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
  */
@@ -15,7 +16,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "yak.h"
-#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X) and yakamd_triobin */
+#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin and yakamd_trioeval */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
 enum arg_kind { ARG_FLAG, ARG_I32, ARG_SIZE, ARG_I64SIZE, ARG_F64, ARG_TEXT };
@@ -178,12 +179,43 @@ static int cmd_triobin(int argc, char **argv)
 	return rc;
 }
 
+/* ---- trioeval ---- */
+static int cmd_trioeval(int argc, char **argv)
+{
+	yakamd_teopt_t o;
+	int min_cnt = 2, mid_cnt = 5, no_frag = 0;               /* reference trioeval.c:158 */
+	yakamd_teopt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'c', ARG_I32, &min_cnt, "min occurrence in a parent" },
+		{ 'd', ARG_I32, &mid_cnt, "mid occurrence in a parent (solid)" },
+		{ 'n', ARG_I32, &o.min_n, "min streak" },
+		{ 't', ARG_I32, &o.n_threads, "host threads (accepted for the reference's command line)" },
+		{ 'e', ARG_FLAG, &o.print_err, "print the switch positions (E lines)" },
+		{ 'F', ARG_FLAG, &no_frag, "do not print the fragments (F lines)" },
+		{ 'K', ARG_I64SIZE, &o.chunk_size, "bases per chunk" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 2 >= argc) { arg_help("trioeval [options] <pat.yak> <mat.yak> <seq.fa>", defs, nd); return 1; }
+	if (no_frag) o.print_frag = 0;
+	yak_ch_t *tab = yak_ch_restore_core(0, argv[first], YAK_LOAD_TRIOBIN1, min_cnt, mid_cnt);
+	if (tab) tab = yak_ch_restore_core(tab, argv[first + 1], YAK_LOAD_TRIOBIN2, min_cnt, mid_cnt);
+	if (!tab) { fprintf(stderr, "yak-amd trioeval: cannot load %s and %s (or no MI355X)\n", argv[first], argv[first + 1]); return 2; }
+	static int64_t cnt[YAK_N_COUNTS];
+	yak_ch_hist(tab, cnt, o.n_threads);
+	fprintf(stderr, "[M::%s] %ld file1-specific k-mers and %ld file2-specific k-mers\n", "main_trioeval", (long)cnt[0<<2|2], (long)cnt[2<<2|0]);
+	const int rc = yakamd_trioeval(&o, tab, argv[first + 2], 0) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 int main(int argc, char **argv)
 {
 	static const struct { const char *name; int (*run)(int, char**); const char *what; } cmds[] = {
 		{ "count", cmd_count, "count k-mers on the GPU, write a .yak table" },
 		{ "qv", cmd_qv, "look the k-mers of sequences up in a .yak table" },
 		{ "triobin", cmd_triobin, "bin reads by the k-mers of the two parents' .yak tables" },
+		{ "trioeval", cmd_trioeval, "evaluate the phasing of an assembly by the k-mers of the two parents' .yak tables" },
 	};
 	/* -X name=value (anywhere on the line, any number of times): a test switch of the library (yakamd_test_set) -- tests force code paths with it */
 	for (int i = 1; i + 1 < argc; ) {

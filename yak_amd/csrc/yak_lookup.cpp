@@ -1,7 +1,8 @@
 /*
- * yak_lookup.cpp -- the lookup-only commands on the device: `yak qv` (reference qv.c) and `yak triobin` (reference triobin.c).  The table
- * is resident on the device; every chunk of records is uploaded, its k-mers are looked up there (k_lookup) and reduced per record
- * (k_qv_reduce, k_tb_reduce), and what the command prints comes from the values copied back.
+ * yak_lookup.cpp -- the lookup-only commands on the device: `yak qv` (reference qv.c), `yak triobin` (reference triobin.c) and
+ * `yak trioeval` (reference trioeval.c).  The table is resident on the device; every chunk of records is uploaded, its k-mers are looked
+ * up there (k_lookup) and reduced per record (k_qv_reduce, k_tb_reduce, the k_te_* streak kernels), and what the command prints comes
+ * from the values copied back.
  */
 #include "yak_host.h"
 #include "yak_amd.h"
@@ -245,6 +246,121 @@ int yakamd_triobin(const yakamd_tbopt_t *opt, const yak_ch_t *ch, const char *fn
 		}
 		reader.join();
 		std::swap(cur, nxt);
+	}
+	if (!ok) fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error());
+	if (out_fn) { if (fclose(out) != 0) ok = false; }
+	else fflush(out);
+	fx.close_file();
+	return ok ? 0 : -1;
+}
+
+/* reference trioeval.c:146-147 */
+void yakamd_teopt_init(yakamd_teopt_t *opt)
+{
+	memset(opt, 0, sizeof(yakamd_teopt_t));
+	opt->min_n = 2;
+	opt->print_err = 0;
+	opt->print_frag = 1;
+	opt->n_threads = 8;
+	opt->chunk_size = 1000000000;
+}
+
+/* reference trioeval.c:119-212 with one device and -t1's output order: the C header, then per chunk the F / E lines of every sequence in
+ * input order (trioeval.c:101-116, from the ordered streak list) and one S line per sequence (trioeval.c:136-145), then the W / H / N
+ * lines.  A chunk closes where bseq_read(fp, 1000000000) closes it.  The next chunk is read on a second thread while the device and the
+ * writer work on this one (the reference's two-step kt_pipeline). */
+int yakamd_trioeval(const yakamd_teopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn)
+{
+	yak_ch_t *h = (yak_ch_t*)ch;
+	const int k = ch->k;
+	FxReader fx;
+	if (!fx.open_file(fn)) { fprintf(stderr, "[E::%s] cannot open '%s'\n", __func__, fn ? fn : "-"); return -1; }
+	FILE *out = out_fn ? fopen(out_fn, "wb") : stdout;
+	if (!out) { fprintf(stderr, "[E::%s] cannot write '%s'\n", __func__, out_fn); fx.close_file(); return -1; }
+	const int64_t chunk_size = opt->chunk_size > 0 ? opt->chunk_size : 1;
+	const bool want_list = opt->print_err || opt->print_frag;
+	std::string line =
+		"C\tS  seqName     #patKmer  #matKmer  #pat-pat  #pat-mat  #mat-pat  #mat-mat  seqLen\n"
+		"C\tF  seqName     type      startPos  endPos    count\n"
+		"C\tW  #switchErr  denominator  switchErrRate\n"
+		"C\tH  #hammingErr denominator  hammingErrRate\n"
+		"C\tN  #totPatKmer #totMatKmer  errRate\n"
+		"C\n";
+	int64_t n_pair = 0, n_site = 0, n_switch = 0, n_err = 0, n_par[2] = { 0, 0 };
+	DevChunk d;
+	DevBuf d_flag, d_cnt;
+	std::vector<int32_t> cnt;
+	std::vector<yakamd_streak_t> sk;
+	Chunk cur, nxt;
+	read_chunk(fx, chunk_size, SIZE_MAX, true, &cur);
+	bool ok = true;
+	auto drain = [&]() { if (line.size() >= (1u << 20)) { ok = ok && fwrite(line.data(), 1, line.size(), out) == line.size(); line.clear(); } };
+	while (ok && !cur.len.empty()) {
+		std::thread reader([&]() { read_chunk(fx, chunk_size, SIZE_MAX, true, &nxt); });
+		const size_t ns = cur.len.size();
+		fprintf(stderr, "[M::%s] read %ld sequences\n", __func__, (long)ns);
+		const size_t nb = cur.pad();
+		cnt.resize(ns * 6);
+		void *d_sk = 0;
+		int64_t n_sk = 0;
+		ok = d.put(cur) && d_flag.fit(nb) && d_cnt.fit(ns * 6 * 4)
+		     && yakamd_triobin_lookup_dev(h, d.img.p, (int64_t)nb, d_flag.p) == 0
+		     && yakamd_trioeval_reduce_dev(k, opt->min_n, d_flag.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, (int64_t)nb,
+		                                   (int32_t*)d_cnt.p, want_list ? &d_sk : 0, &n_sk, 0) == 0
+		     && yakamd_memcpy_d2h(cnt.data(), d_cnt.p, ns * 6 * 4) == 0;
+		sk.resize(want_list ? (size_t)n_sk : 0);
+		if (ok && want_list && n_sk > 0) ok = yakamd_memcpy_d2h(sk.data(), d_sk, (size_t)n_sk * sizeof(yakamd_streak_t)) == 0;
+		yakamd_dev_free(d_sk);
+		if (ok && want_list) {                                    /* trioeval.c:101-116 per sequence, in input order */
+			char buf[96];
+			uint32_t seq = UINT32_MAX, last = 0, f_type = 0;
+			int f_st = 0, f_en = 0, f_cnt = 0;
+			auto frag = [&]() {
+				if (f_type > 0 && opt->print_frag) {
+					line += "F\t"; line += cur.names[seq];
+					line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%d\n", (int)f_type, f_st, f_en, f_cnt));
+				}
+			};
+			for (int64_t i = 0; ok && i < n_sk; ++i) {
+				const yakamd_streak_t &s = sk[i];
+				if (s.seq != seq) { if (seq != UINT32_MAX) frag(); seq = s.seq; last = 0; f_type = 0; drain(); }
+				if (last > 0 && opt->print_err && last != s.type) {
+					line += "E\t"; line += cur.names[seq];
+					line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%d\t%d\t%d\n", (int)s.en, (int)last, (int)s.type));
+				}
+				if (f_type != s.type) { frag(); f_type = s.type; f_st = (int)s.st + 1 - k; f_cnt = 0; }
+				++f_cnt; f_en = (int)s.en + 1;
+				last = s.type;
+			}
+			if (seq != UINT32_MAX) frag();
+		}
+		if (ok) {
+			char buf[160];
+			for (size_t j = 0; j < ns; ++j) {                      /* trioeval.c:136-145 */
+				const int32_t *dd = cnt.data() + j * 6, *c = dd + 2;
+				n_par[0] += dd[0]; n_par[1] += dd[1];
+				if (dd[0] + dd[1] >= 2) {
+					n_pair += c[0] + c[1] + c[2] + c[3];
+					n_switch += c[1] + c[2];
+					n_site += dd[0] + dd[1];
+					n_err += dd[0] < dd[1] ? dd[0] : dd[1];
+				}
+				line += "S\t"; line += cur.names[j];
+				line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", dd[0], dd[1], c[0], c[1], c[2], c[3], (int)cur.len[j]));
+				drain();
+				if (!ok) break;
+			}
+		}
+		reader.join();
+		std::swap(cur, nxt);
+	}
+	if (ok) {                                                     /* trioeval.c:207-209: the operands' order and types as there */
+		char buf[256];
+		line.append(buf, (size_t)snprintf(buf, sizeof buf, "W\t%ld\t%ld\t%.6f\n", (long)n_switch, (long)n_pair, (double)n_switch / n_pair));
+		line.append(buf, (size_t)snprintf(buf, sizeof buf, "H\t%ld\t%ld\t%.6f\n", (long)n_err, (long)n_site, (double)n_err / n_site));
+		line.append(buf, (size_t)snprintf(buf, sizeof buf, "N\t%ld\t%ld\t%.6f\n", (long)n_par[0], (long)n_par[1],
+		                                  (double)(n_par[0] < n_par[1] ? n_par[0] : n_par[1]) / (n_par[0] + n_par[1])));
+		ok = fwrite(line.data(), 1, line.size(), out) == line.size();
 	}
 	if (!ok) fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error());
 	if (out_fn) { if (fclose(out) != 0) ok = false; }

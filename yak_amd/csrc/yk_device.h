@@ -93,6 +93,13 @@ void yk_launch_qv_reduce(const unsigned short *t, const u64 *roff, const u32 *rl
                          u32 *tot_out, u32 *non0_out, u64 *hist, hipStream_t st);
 int yk_tb_over_seen(hipStream_t st);
 void yk_launch_tb_reduce(const uint8_t *flag, const u64 *roff, const u32 *rlen, int64_t n_reads, int k, int *cnt, hipStream_t st);
+int64_t yk_te_tiles(int64_t n);                               /* trioeval's streak reduction (kern_trioeval.inc) */
+int64_t yk_te_keep_blocks(int64_t n_runs);
+void yk_launch_te_runs(const uint8_t *flag, int64_t n, u32 *tcnt, const u64 *toff, u64 *st, u64 *en, int scatter, hipStream_t s);
+void yk_launch_te_scan(const u32 *cnt, int64_t m, int n_arrays, u64 *off, hipStream_t s);
+void yk_launch_te_keep(const u64 *st, const u64 *en, const uint8_t *flag, int64_t n_runs, int min_n, u32 *kcnt, const u64 *koff,
+                       const u64 *seq_off, int64_t n_seq, void *list, int scatter, hipStream_t s);
+void yk_launch_te_seq(const void *list, const u64 *n_list, int64_t n_max, int k, int *cnt6, hipStream_t s);
 int yk_launch_img_count_lds(const void *rec, int hash_only, const u64 *bstart, ImgView img, int plo, int phi, size_t lds, u64 *compact, u32 stride, hipStream_t st);
 void yk_launch_img_count_h(const u64 *hash, int64_t n, ImgView img, hipStream_t st);
 void yk_launch_img_inc(ImgView img, u64 hash, u64 *out2, hipStream_t st);
