@@ -20,6 +20,14 @@ instance over the step's wall-clock time; `roofline.traffic` the rocprofv3 count
 `roofline.dominant_kernel` is the single kernel with the largest time, timed with HIP events on the engine's own
 stream inside the library (to be compared with profiles/*_kernel_stats.csv); `cpu_baseline` is the reference
 (oracle/_ref) or the oracle port timed on this host on a bounded sample.
+
+A plain run of the counting workload (cfg2 / nofilter, any N) does only what `value` needs: it makes the
+reads, warms up, times the steps, writes --dump-outputs and prints the line.  `--full` adds everything else
+it measures or checks, each behind its own --no-* switch as before: the .yak against the reference's and
+the batch-independence check (`verify`, with smoke()), the packed-image, lookup, unfiltered and PCIe / CLI
+side runs, `cpu_baseline`, and at N > 1 `weak_base` and the whole job's .yak against one table's.  A plain
+run leaves their fields null or out.  `--config cfg3shard|cfg4|cfg5` are configurations of their own and run
+their checks either way.
 """
 import argparse
 import ctypes as C
@@ -345,7 +353,7 @@ def run_multi_c(a):
     inst = sum(sizes) // rec_len * (READ_LEN - K + 1) * (2 if bf else 1)
     verify = None
     gfn = os.path.join(ROOT, "tests", "golden", "cfg3_full.json")
-    if bf == 0 and not a.no_verify and os.path.exists(gfn) and P % N == 0:
+    if a.full and bf == 0 and not a.no_verify and os.path.exists(gfn) and P % N == 0:
         # BASELINE configs[2] itself (600 M reads, any N that divides the pinned ranges): the oracle counted the whole stream for all eight ranges of 128
         # sub-tables (tests/gen_golden_cfg3.py: the whole table, 41 GB of .yak bytes); the job's bytes at every one of them must be the oracle's
         g = json.load(open(gfn))
@@ -360,7 +368,7 @@ def run_multi_c(a):
             tm.close()
             if not all(v for k_, v in verify.items() if k_.startswith("subtables_")):
                 raise SystemExit(f"FAILED: the job's sub-tables differ from the oracle's: {verify}")
-    if a.job_md5 or per_gpu * N <= 4_000_000:
+    if a.job_md5 or (a.full and per_gpu * N <= 4_000_000):
         # the sharded table's .yak bytes against ONE unsharded table fed the same stream, chunk after chunk
         h, _ = step(keep=True)
         tm = yak_amd.Table(K, PRE, N_HASH, bf, ptr=h)
@@ -387,7 +395,7 @@ def run_multi_c(a):
     # ---- the same per-GPU workload on ONE device in this process: per_gpu reads (G = 5 x reads: 30x as the job), all 1024 sub-tables, the same
     # driver with one rank -- the N = 1 point of THIS curve (the `--gpus 1` line of the driver's sweep is configs[1], a different job)
     weak_base = None
-    if not a.no_weak_base:
+    if a.full and not a.no_weak_base:
         del d_chunk
         bufs.clear()                                         # the job's chunks go before the base's are made (a one-GPU box holds N ranks' input)
         torch.cuda.empty_cache()
@@ -431,7 +439,7 @@ def run_multi_c(a):
         del b1
     barrier()
     cpu_base = None
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         # the reference itself on a bounded sample of the per-GPU workload (same generator, same error rate, 30x), all host cores of this box
         n_cpu = min(per_gpu, 4_000_000)
         cpu_base = cpu_baseline(n_cpu, 5 * n_cpu, bf, min(os.cpu_count() or 8, 32), t1_reads=0, err=err)
@@ -480,18 +488,19 @@ def run_multi_c(a):
         dist.destroy_process_group()
 
 
-def _device_or_retry():
+def _device_or_retry(with_torch):
     """A process that starts within seconds of the exit of another one that used the device (seen in round 5 right behind 1 Gb-assembly runs, and once right
     behind a 15 s pytest run) can find NO device: `No HIP GPUs are available` from torch, an empty device list from the HIP runtime -- and the runtime keeps
     that answer for the life of the process.  So the question is asked in a CHILD process first (torch, then libyak_amd.so: the import order INTEGRATION.md
-    asks for), again every 5 s for up to a minute while the answer is no or the child fails; if the device stays away, the configuration's own check fails
-    loudly as before."""
+    asks for; libyak_amd.so alone where the run never imports torch), again every 5 s for up to a minute while the answer is no or the child fails; if the
+    device stays away, the configuration's own check fails loudly as before."""
     probe = ("import sys; sys.path.insert(0, %r)\n"
-             "import torch\n"
-             "ok = torch.cuda.is_available() and torch.cuda.device_count() >= 1\n"
-             "if ok: torch.cuda.init()\n"
+             "ok = True\n" +
+             ("import torch\n"
+              "ok = torch.cuda.is_available() and torch.cuda.device_count() >= 1\n"
+              "if ok: torch.cuda.init()\n" if with_torch else "") +
              "import yak_amd\n"
-             "sys.exit(0 if ok and yak_amd.lib().yakamd_device_count() >= 1 else 3)\n" % ROOT)
+             "sys.exit(0 if ok and yak_amd.lib().yakamd_device_count() >= 1 else 3)\n") % ROOT
     for attempt in range(12):
         try:
             rc = subprocess.run([sys.executable, "-c", probe], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=180).returncode
@@ -504,8 +513,6 @@ def _device_or_retry():
 
 
 def main():
-    if int(os.environ.get("RANK", "0")) == 0 or "--driver" in sys.argv:   # (under torch.distributed.run only rank 0 drives the devices, the others wait at its barrier -- unless `--driver torch` gives every rank its own)
-        _device_or_retry()
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -542,6 +549,9 @@ def main():
                                                                           "torch = one process per GPU, yak_amd/shard.py + torch.distributed all-to-all")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write the table the last one computed as DIR/<name>.npy (float64: sub-table sizes, count histogram, a seeded sample of the keys)")
+    ap.add_argument("--full", action="store_true",
+                    help="cfg2 / nofilter: after the timed steps also run the checks and side measurements (verify, packed, qv, nofilter, PCIe / CLI, cpu_baseline; "
+                         "N > 1: weak_base, the job's .yak against one table's); a plain run skips them")
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
@@ -551,6 +561,8 @@ def main():
     a.warmup_given = any(x == "--warmup" or x.startswith("--warmup=") for x in sys.argv[1:])
     a.batch_reads_given = any(x == "--batch-reads" or x.startswith("--batch-reads=") for x in sys.argv[1:])
     a.bf_shift_given = any(x == "--bf-shift" or x.startswith("--bf-shift=") for x in sys.argv[1:])
+    if int(os.environ.get("RANK", "0")) == 0 or "--driver" in sys.argv:   # (under torch.distributed.run only rank 0 drives the devices, the others wait at its barrier -- unless `--driver torch` gives every rank its own)
+        _device_or_retry(a.gpus > 1 or a.force_exchange or a.config in ("cfg3shard", "cfg4", "cfg5"))     # (one GPU, cfg2 / nofilter: the library alone, no torch)
     maybe_spawn(a)
     if a.knob:                                                    # the library is loaded once per process: one place serves every mode below
         if a.config in ("cfg3shard", "cfg4", "cfg5") or a.gpus > 1:
@@ -801,7 +813,7 @@ def main():
         job_md5 = hashlib.md5(data[:16] + blob).hexdigest()
 
     verify = None
-    if not a.no_verify and not sharded:
+    if a.full and not a.no_verify and not sharded:
         # full-size property: the .yak bytes do not depend on how the stream is cut into device
         # batches (the reference's independence of -K / -t)
         t_a, _, _, _ = step(keep=True)
@@ -831,7 +843,7 @@ def main():
     # the same protocol from the PACKED image (2-bit codes + validity bits, 0.375 B per base; north_star: "packed reads"): a side
     # measurement with its own md5 check -- the default line reads the ASCII image the reference's parser hands over
     packed_probe = None
-    if not a.no_packed and not sharded:
+    if a.full and not a.no_packed and not sharded:
         nw = (n_bytes + 31) // 32
         d_codes = dev_empty(4 * (2 * nw + 4))
         d_valid = dev_empty(4 * (nw + 4))
@@ -861,7 +873,7 @@ def main():
     # second kernel family (BASELINE configs[4]): the lookup-only kernel of `yak qv`
     # on the table just built, over the same resident reads -- a side measurement, never `value`
     qv_probe = None
-    if not a.no_qv and not sharded:
+    if a.full and not a.no_qv and not sharded:
         t_q, _, _, _ = step(keep=True)
         d_t16 = dev_empty(2 * n_bytes)
         L.yakamd_lookup_dev(t_q.h, d_reads.data_ptr(), n_bytes, d_t16.data_ptr())       # warm-up
@@ -888,7 +900,7 @@ def main():
     # the unfiltered protocol on the same resident reads (main.c:53, one pass, singletons kept): its roofline fraction at SURVEY 8(d)'s
     # 32 B per instance carries no bloom-block credit -- printed beside the default line, never `value`
     nb_probe = None
-    if not a.no_nofilter and not sharded and a.bf_shift > 0:
+    if a.full and not a.no_nofilter and not sharded and a.bf_shift > 0:
         def nofilter_step():
             t_ = yak_amd.Table(K, PRE, N_HASH, 0)
             t_.count_pass(1, [(d_reads.data_ptr(), n_bytes, 0)])
@@ -911,7 +923,7 @@ def main():
     # yak_count() does after parsing) and the whole `yak-amd count` command on the same reads as a FASTQ file
     # (process start, parsing, PCIe, counting, writing the .yak) -- side figures, never `value`
     pcie_ms = e2e = host_pack = None
-    if not a.no_pcie and not sharded:
+    if a.full and not a.no_pcie and not sharded:
         # the parser's share, outside the timed region like the parsing itself: the image packed to 0.375 B per base (yakamd_pack_bases_host,
         # what yak_count()'s parser threads do with what they parsed) in page-locked memory
         h_packed = HostBuf(L, L.yakamd_packed_bytes(n_bytes))
@@ -1118,7 +1130,7 @@ def main():
         "e2e_cli": e2e,
         "replay_doublings_parallel_vs_serial_fallback": list(dbgc),
     }
-    if not a.no_cpu_baseline and world == 1:                      # rank 0 at N = 1 only
+    if a.full and not a.no_cpu_baseline and world == 1:           # rank 0 at N = 1 only
         out["cpu_baseline"] = cpu_baseline(a.reads, genome, a.bf_shift, min(os.cpu_count() or 8, 32))
     print(json.dumps(out))
     if os.environ.get("YAKAMD_VERBOSE"):

@@ -26,7 +26,7 @@ def bench_line(*args):
     import yak_amd
     if yak_amd.lib().yakamd_device_count() < 1:
         pytest.skip("no MI355X visible")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-qv", "--no-pcie", "--no-packed", "--no-nofilter"] + list(args),
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline", "--no-qv", "--no-pcie", "--no-packed", "--no-nofilter"] + list(args),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     return json.loads([l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1])

@@ -66,9 +66,9 @@ def test_bench_n_gpus_runs_the_librarys_own_driver(n, bf, extra):
 def test_bench_n_gpus_with_a_slot_per_rank_runs_the_exchange(knobs, exchange):
     """the device-resident driver with every rank a slot of its own on device 0 (YAKAMD_MGPU_SLOT_PER_RANK): rounds of two chunks, the partition of round
     b + 1 overlapped with the exchange and feed of round b, records crossing between the slots' send and receive buffers -- and the sharded table's bytes
-    still equal ONE table's (bench.py --job-md5 fails loudly otherwise).  The line carries weak_base, cpu_baseline and (null without a counter pass of
-    this very command) roofline.traffic with its source."""
-    args = ["--gpus", "2", "--reads", "150000", "--batch-reads", "40000", "--steps", "1", "--warmup", "0", "--job-md5", "--knob", "YAKAMD_MGPU_SLOT_PER_RANK=1"]
+    still equal ONE table's (bench.py --job-md5 fails loudly otherwise).  Under --full the line carries weak_base, cpu_baseline and (null without a
+    counter pass of this very command) roofline.traffic with its source."""
+    args = ["--gpus", "2", "--reads", "150000", "--batch-reads", "40000", "--steps", "1", "--warmup", "0", "--full", "--job-md5", "--knob", "YAKAMD_MGPU_SLOT_PER_RANK=1"]
     for kv in knobs:
         args += ["--knob", kv]
     r = run_bench(args, nproc=2, port=29611 + len(knobs) + len(exchange))

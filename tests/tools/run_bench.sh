@@ -2,7 +2,7 @@
 # a short verified bench line of the default workload -> gpurun_out/$1/b.json
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-chk}; mkdir -p $O; shift
-YAKAMD_VERBOSE=1 timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline "$@" 2>$O/b.err | grep '^{' > $O/b.json
+YAKAMD_VERBOSE=1 timeout 600 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline "$@" 2>$O/b.err | grep '^{' > $O/b.json
 grep -E "key-owning|k_lc2" $O/b.err | tail -2
 python - $O <<'PY'
 import json,sys

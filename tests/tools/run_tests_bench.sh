@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-chk}; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -25
-YAKAMD_VERBOSE=1 timeout 600 python bench.py --steps 3 --warmup 1 --no-cpu-baseline 2>$O/b.err | grep '^{' > $O/b.json
+YAKAMD_VERBOSE=1 timeout 600 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline 2>$O/b.err | grep '^{' > $O/b.json
 grep -E "key-owning|k_lc2" $O/b.err | tail -2
 python - $O <<'PY'
 import json,sys
