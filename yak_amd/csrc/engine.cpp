@@ -23,7 +23,6 @@
 #include <mutex>
 #include <algorithm>
 #include <chrono>
-#include <functional>
 #include "engine_int.h"
 
 static thread_local char g_err[512] = "";
@@ -315,6 +314,8 @@ struct EvTimer {
 	double stop() { float ms = 0; hipEventRecord(b, st); hipEventSynchronize(b); hipEventElapsedTime(&ms, a, b); return ms; }
 	~EvTimer() { ev_put(a); ev_put(b); }
 };
+/* the time of an insert kernel (timed by tm) into the pass's statistics */
+static double insert_ms(yakamd_ctx *c, EvTimer &tm) { const double ms = tm.stop(); c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1; return ms; }
 
 /* bloom gate over the keys first seen in the batch just inserted (kernels.hip K2) */
 static int bloom_phases(yakamd_ctx *c, u64 n_new)
@@ -335,13 +336,12 @@ static int bloom_phases(yakamd_ctx *c, u64 n_new)
 		const u64 n_cand = h_cnt[YKC_NCAND], n_marked = h_cnt[YKC_NMARKED];
 		if (n_cand) {
 			const int map_bits = std::max(10, ceil_log2_u64(2 * n_marked + 2));
-			u64 *d_map = 0;
-			if (dmalloc(&d_map, (size_t)2 << map_bits)) return -1;
+			DevBuf<u64> d_map;
+			if (d_map.alloc((size_t)2 << map_bits)) return -1;
 			HIPCK(hipMemsetAsync(d_map, 0, (size_t)16 << map_bits, c->st));
 			yk_launch_bf_mapfill(c->acc, c->d_newlist, n_new, bf, c->d_miss, c->d_multi, c->multi_bits, d_map, map_bits, c->st);
 			yk_launch_bf_resolve(c->acc, c->d_newlist, c->d_cand, n_cand, bf, c->d_miss, d_map, map_bits, c->st);
 			HIPCK(hipStreamSynchronize(c->st));
-			dfree(d_map);
 			c->st_cur.n_bloom_candidates += (int64_t)n_cand;
 		}
 		HIPCK(hipMemsetAsync(c->d_multi, 0, (size_t)1 << (c->multi_bits - 3), c->st));
@@ -412,6 +412,39 @@ static size_t count_lds_bytes(yakamd_ctx *c)
 	return lds > 150 * 1024 ? 0 : lds;
 }
 
+/* a chunk table of the level-2 partition kernels: work items of at most a given number of records, each inside one bucket, grouped by bucket
+ * (first[q]: bucket q's first item, first[n_buckets]: their number); the last item of a bucket has spare = 1 */
+struct ChunkTable {
+	std::vector<Chunk2> h;
+	std::vector<u32> first;
+	DevBuf<Chunk2> d; DevBuf<u32> d_first;
+	int upload(hipStream_t st)                                   /* (the host tables must outlive the copies: the caller synchronises) */
+	{
+		if (d.alloc(h.size()) || d_first.alloc(first.size())) return -1;
+		HIPCK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(Chunk2), hipMemcpyHostToDevice, st));
+		HIPCK(hipMemcpyAsync(d_first, first.data(), first.size() * 4, hipMemcpyHostToDevice, st));
+		return 0;
+	}
+	void reset() { d.reset(); d_first.reset(); }
+};
+
+/* the runs [start[q], start[q + 1]) of buckets q < n_buckets, records of `stride` bytes from `base`, cut into items of at most `len` records */
+static void chunk_runs(ChunkTable &t, const void *base, size_t stride, const u64 *start, size_t n_buckets, u64 len)
+{
+	t.h.clear();
+	t.first.assign(n_buckets + 1, 0);
+	for (size_t q = 0; q < n_buckets; ++q) {
+		t.first[q] = (u32)t.h.size();
+		for (u64 o = start[q]; o < start[q + 1]; o += len) {
+			Chunk2 ch = {};
+			ch.rec = (const Rec*)((const char*)base + o * stride); ch.n = (u32)std::min<u64>(len, start[q + 1] - o); ch.bucket = (u32)q;
+			t.h.push_back(ch);
+		}
+		if (t.h.size() > t.first[q]) t.h.back().spare = 1;
+	}
+	t.first[n_buckets] = (u32)t.h.size();
+}
+
 /* count-existing pass, records = 8-byte hashes grouped by prefix (d_bstart), tables beyond the LDS
  * kernel: level-2 partition by home-slot range (k_hpart2) + one workgroup per range (k_img_count_rng).
  * Returns 0 done, -1 error, 1 not applicable (caller falls back to the device-atomics kernel). */
@@ -426,34 +459,18 @@ static int count_by_ranges(yakamd_ctx *c, int64_t n_rec, const u64 *d_bstart)
 	std::vector<u64> bst(NB + 1);
 	HIPCK(hipMemcpyAsync(bst.data(), d_bstart, (NB + 1) * 8, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
-	const u64 ch = (u64)yk_hpart2_chunk();
-	std::vector<Chunk2> chunks;
-	std::vector<u32> chunk_first(P + 1, 0);
+	ChunkTable t;
+	chunk_runs(t, c->d_rec, 8, bst.data(), P, (u64)yk_hpart2_chunk());
 	std::vector<u64> bbase(P + 1, 0);
-	for (int p = 0; p < P; ++p) {
-		chunk_first[p] = (u32)chunks.size();
-		const u64 a = bst[p], b = bst[p + 1];
-		for (u64 o = a; o < b; o += ch) {
-			Chunk2 k;
-			k.rec = (const Rec*)((const u64*)c->d_rec + o); k.spare = 0;
-			k.n = (u32)std::min<u64>(ch, b - o); k.bucket = (u32)p; k.tbase = 0; k.pad = 0;
-			chunks.push_back(k);
-		}
-		if (chunks.size() > chunk_first[p]) chunks.back().spare = 1;
-		bbase[p + 1] = bbase[p] + (b - a);
-	}
-	chunk_first[P] = (u32)chunks.size();
-	Chunk2 *d_chunks = 0; u32 *d_cf = 0, *d_rows2 = 0, *d_ln = 0; u64 *d_bbase = 0, *d_sbstart = 0, *d_h2 = 0, *d_list = 0;
-	struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ [&]() { dfree(d_chunks); dfree(d_cf); dfree(d_bbase); dfree(d_rows2); dfree(d_sbstart); dfree(d_h2); dfree(d_list); dfree(d_ln); } };
+	for (int p = 0; p < P; ++p) bbase[p + 1] = bbase[p] + (bst[p + 1] - bst[p]);
+	DevBuf<u64> d_bbase, d_sbstart, d_h2, d_list; DevBuf<u32> d_rows2, d_ln;
 	const u32 list_cap = (u32)std::min<int64_t>(env_i64("YAKAMD_XLIST_CAP", 1 << 22), 1 << 22);   /* the knob is for tests */
-	if (dmalloc(&d_chunks, chunks.size()) || dmalloc(&d_cf, P + 1) || dmalloc(&d_bbase, P + 1) || dmalloc(&d_rows2, (chunks.size() + 1) * S2) ||
-	    dmalloc(&d_sbstart, n_sb + 1) || dmalloc(&d_h2, (size_t)n_rec) || dmalloc(&d_list, (size_t)1 << 22) || dmalloc(&d_ln, 2)) return -1;
-	HIPCK(hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(Chunk2), hipMemcpyHostToDevice, c->st));
-	HIPCK(hipMemcpyAsync(d_cf, chunk_first.data(), (P + 1) * 4, hipMemcpyHostToDevice, c->st));
+	if (t.upload(c->st) || d_bbase.alloc(P + 1) || d_rows2.alloc((t.h.size() + 1) * S2) ||
+	    d_sbstart.alloc(n_sb + 1) || d_h2.alloc((size_t)n_rec) || d_list.alloc((size_t)1 << 22) || d_ln.alloc(2)) return -1;
 	HIPCK(hipMemcpyAsync(d_bbase, bbase.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
 	HIPCK(hipMemsetAsync(d_ln, 0, 8, c->st));
 	const ImgView img = img_view(c);
-	yk_launch_hpart2(d_chunks, (int)chunks.size(), d_cf, d_bbase, img, rb, P, d_rows2, d_sbstart, d_h2, c->st);
+	yk_launch_hpart2(t.d, (int)t.h.size(), t.d_first, d_bbase, img, rb, P, d_rows2, d_sbstart, d_h2, c->st);
 	const u32 max_len = bmax > (u32)yk_rng_log() ? 1u << yk_rng_log() : 1u << bmax;
 	int r = 0;
 	if (yk_launch_img_count_rng(d_h2, 0, d_sbstart, img, c->plo, c->phi, rb, max_len, d_list, d_ln, list_cap, c->st)) r = fail("range count kernel could not be configured");
@@ -504,9 +521,9 @@ static int count_own(yakamd_ctx *c, int64_t n_rec, const u64 *d_bstart, int hash
 	const int pl = count_own_plan(c, &rng_log, &rb, &kmax);
 	if (pl) return ytag ? fail("the table changed between the extraction and the count of a pass") : 1;
 	if (rb < 0) return 0;
-	u64 *d_list = 0; u32 *d_ln = 0;
+	DevBuf<u32> d_ln; DevBuf<u64> d_list;
 	const u32 list_cap = (u32)std::min<int64_t>(env_i64("YAKAMD_XLIST_CAP", 1 << 22), 1 << 22);   /* the knob is for tests */
-	if (dmalloc(&d_list, (size_t)1 << 22) || dmalloc(&d_ln, 2)) { dfree(d_list); return -1; }
+	if (d_list.alloc((size_t)1 << 22) || d_ln.alloc(2)) return -1;
 	int r = 0;
 	const ImgView img = img_view(c);
 	const size_t lds = yk_count_own_lds(1u << rng_log, kmax);
@@ -522,7 +539,6 @@ static int count_own(yakamd_ctx *c, int64_t n_rec, const u64 *d_bstart, int hash
 		if (hipStreamSynchronize(c->st) != hipSuccess) r = fail("count sweep failed");
 	}
 	(void)n_rec;
-	dfree(d_list); dfree(d_ln);
 	return r;
 }
 
@@ -540,8 +556,7 @@ static int consume_records(yakamd_ctx *c, int64_t n_rec, u64 t0, u64 batch_lo, u
 		if (d_bstart) {
 			const int r = count_own(c, n_rec, d_bstart, hash_only, ytag);
 			if (r <= 0 || ytag) {
-				const double ms = tm.stop();
-				c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1;
+				insert_ms(c, tm);
 				return r;
 			}
 		}
@@ -550,8 +565,7 @@ static int consume_records(yakamd_ctx *c, int64_t n_rec, u64 t0, u64 batch_lo, u
 			/* sub-tables too large for one workgroup's LDS: split each one's hashes by home-slot range first */
 			const int r = count_by_ranges(c, n_rec, d_bstart);
 			if (r <= 0) {                                        /* done (0) or failed (-1); 1 = not applicable */
-				const double ms = tm.stop();
-				c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1;
+				insert_ms(c, tm);
 				return r;
 			}
 		}
@@ -566,8 +580,7 @@ static int consume_records(yakamd_ctx *c, int64_t n_rec, u64 t0, u64 batch_lo, u
 			if (hash_only) yk_launch_img_count_h((const u64*)c->d_rec, n_rec, img, c->st);
 			else yk_launch_img_count(c->d_rec, n_rec, img, c->st);
 		}
-		const double ms = tm.stop();
-		c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1;
+		insert_ms(c, tm);
 		return 0;
 	}
 	const int img_nonempty = c->img_keys_total > 0;
@@ -579,8 +592,7 @@ static int consume_records(yakamd_ctx *c, int64_t n_rec, u64 t0, u64 batch_lo, u
 		EvTimer tm(c->st);
 		yk_launch_acc_insert(c->d_rec, n_rec, t0, c->acc, img, img_nonempty, c->bloom_mode,
 		                     c->bloom_mode ? c->d_newlist : 0, c->d_counters, c->st);
-		const double ms = tm.stop();
-		c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1;
+		insert_ms(c, tm);
 	}
 	HIPCK(hipMemcpyAsync(h_cnt, c->d_counters, sizeof(h_cnt), hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
@@ -744,16 +756,22 @@ static int feed_image(yak_ch_t *h, const void *d_bases, const u32 *d_valid, int6
 	return 0;
 }
 
+/* the staging buffer of the host feeds: room for n bytes */
+static int stage_reserve(yakamd_ctx *c, int64_t n)
+{
+	if (n <= c->stage_cap) return 0;
+	dfree(c->d_stage);
+	c->stage_cap = n + (n >> 3) + 4096;
+	if (dmalloc(&c->d_stage, (size_t)c->stage_cap)) { c->stage_cap = 0; return -1; }
+	return 0;
+}
+
 extern "C" int yakamd_feed_bases_host(yak_ch_t *h, const void *h_bases, int64_t n_bytes, uint64_t t0)
 {
 	yakamd_ctx *c = ctx_of(h);
 	if (!c || !c->in_pass) return fail("feed outside a pass");
 	HIPCK(hipSetDevice(c->dev));
-	if (n_bytes > c->stage_cap) {
-		dfree(c->d_stage);
-		c->stage_cap = n_bytes + (n_bytes >> 3) + 4096;
-		if (dmalloc(&c->d_stage, (size_t)c->stage_cap)) { c->stage_cap = 0; return -1; }
-	}
+	if (stage_reserve(c, n_bytes)) return -1;
 	HIPCK(hipMemcpyAsync(c->d_stage, h_bases, (size_t)n_bytes, hipMemcpyHostToDevice, c->st));
 	return yakamd_feed_bases_dev(h, c->d_stage, n_bytes, t0);
 }
@@ -768,11 +786,7 @@ extern "C" int yakamd_feed_packed_host(yak_ch_t *h, const void *h_packed, int64_
 	if (n_bases <= 0) return 0;
 	HIPCK(hipSetDevice(c->dev));
 	const int64_t need = yakamd_packed_bytes(n_bases), valid_at = need - (n_bases + 31) / 32 * 4;
-	if (need > c->stage_cap) {
-		dfree(c->d_stage);
-		c->stage_cap = need + (need >> 3) + 4096;
-		if (dmalloc(&c->d_stage, (size_t)c->stage_cap)) { c->stage_cap = 0; return -1; }
-	}
+	if (stage_reserve(c, need)) return -1;
 	HIPCK(hipMemcpyAsync(c->d_stage, h_packed, (size_t)need, hipMemcpyHostToDevice, c->st));
 	return yakamd_feed_packed_dev(h, c->d_stage, c->d_stage + valid_at, n_bases, t0);
 }
@@ -788,11 +802,7 @@ extern "C" int yakamd_feed_packed_pieces_host(yak_ch_t *h, int n_pieces, const v
 	if (nw == 0) return 0;
 	HIPCK(hipSetDevice(c->dev));
 	const int64_t n_bases = nw * 32, need = yakamd_packed_bytes(n_bases), valid_at = need - nw * 4;
-	if (need > c->stage_cap) {
-		dfree(c->d_stage);
-		c->stage_cap = need + (need >> 3) + 4096;
-		if (dmalloc(&c->d_stage, (size_t)c->stage_cap)) { c->stage_cap = 0; return -1; }
-	}
+	if (stage_reserve(c, need)) return -1;
 	int64_t w = 0;
 	for (int i = 0; i < n_pieces; ++i) {
 		if (n_words[i] == 0) continue;
@@ -828,8 +838,8 @@ static int64_t partition_dev(int k, int pre, const void *d_bases, int64_t n_byte
 	if (((uintptr_t)d_bases & 15) != 0 || n_bytes >= ((int64_t)1 << 32)) { fail("partition: base image must be 16-byte aligned and < 4 GiB"); return -1; }
 	const size_t NB = (size_t)1 << pre;
 	const int n_blk = yk_xpart_blocks(n_bytes);
-	u32 *d_rows = 0; u64 *d_partial = 0, *d_bstart = 0;
-	if (dmalloc(&d_rows, NB * (size_t)n_blk) || dmalloc(&d_partial, NB * yk_part_groups()) || dmalloc(&d_bstart, NB + 1)) return -1;
+	DevBuf<u64> d_bstart, d_partial; DevBuf<u32> d_rows;
+	if (d_rows.alloc(NB * (size_t)n_blk) || d_partial.alloc(NB * yk_part_groups()) || d_bstart.alloc(NB + 1)) return -1;
 	/* on a stream of its own, not the null stream (which waits for, and holds up, every other stream of the device): a multi-GPU job partitions the
 	 * chunks of its next round while the owners' streams take in the round before */
 	int dev = 0;
@@ -839,7 +849,6 @@ static int64_t partition_dev(int k, int pre, const void *d_bases, int64_t n_byte
 	hipError_t e = hipMemcpyAsync(h_bstart, d_bstart, (NB + 1) * 8, hipMemcpyDeviceToHost, ps);
 	if (e == hipSuccess) e = hipStreamSynchronize(ps);
 	stream_put(dev, ps);
-	dfree(d_rows); dfree(d_partial); dfree(d_bstart);
 	if (e != hipSuccess) { fail("partition: %s", hipGetErrorString(e)); return -1; }
 	return (int64_t)h_bstart[NB];
 }
@@ -939,9 +948,8 @@ extern "C" int yakamd_count_hashes_dev(yak_ch_t *h, const void *d_hash_u64, int6
 	c->delta_dirty = true;
 	EvTimer tm(c->st);
 	yk_launch_img_count_h((const u64*)d_hash_u64, n, img_view(c), c->st);
-	const double ms = tm.stop();
+	insert_ms(c, tm);
 	c->st_cur.n_instances += n;
-	c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1;
 	return 0;
 }
 
@@ -977,10 +985,9 @@ extern "C" int yakamd_count_retained(yak_ch_t *h)
 		/* k_lc2 counted every instance of every key it selected while it owned the sub-bucket: all that is left is to add those counts */
 		EvTimer tm(c->st);
 		yk_launch_cnt2_apply(c->ret2.fp, c->ret2.d_kkc, c->ret2.d_kc2, c->ret2.d_segbase, img_view(c), c->st);
-		const double ms = tm.stop();
+		const double ms = insert_ms(c, tm);
 		const bool bad = hipGetLastError() != hipSuccess;
 		c->st_cur.n_instances += (int64_t)c->ret2.n_total;
-		c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1;
 		c->st_cur.pass2_path = 1;
 		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] count pass: the counts of the pass before applied (%llu keys, %.2f ms)\n", (unsigned long long)c->ret2.n_keys, ms);
 		retained_drop(c);
@@ -994,12 +1001,11 @@ extern "C" int yakamd_count_retained(yak_ch_t *h)
 		yk_launch_cnt2(c->ret2.fp, c->ret2.d_sbstart, c->ret2.d_r2, c->ret2.d_koff, c->ret2.d_kkc, c->ret2.d_segbase, d_kcnt, img_view(c), c->ret2.n_keys, c->d_nmissing, c->st);
 		u32 used = 1;
 		(void)hipMemcpyAsync(&used, c->d_nmissing, 4, hipMemcpyDeviceToHost, c->st);
-		const double ms = tm.stop();
+		const double ms = insert_ms(c, tm);
 		if (used) c->delta_dirty = true;
 		dfree(d_kcnt);
 		const bool bad = hipGetLastError() != hipSuccess;
 		c->st_cur.n_instances += (int64_t)c->ret2.n_total;
-		c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1;
 		c->st_cur.pass2_path = 2;
 		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] count pass: k_cnt2 over the retained sub-bucket records (%llu keys, %.2f ms)\n", (unsigned long long)c->ret2.n_keys, ms);
 		retained_drop(c);
@@ -1189,25 +1195,31 @@ extern "C" int64_t yakamd_extract_dev(int k, const void *d_bases, int64_t n_byte
 	return (int64_t)n;
 }
 
-/* pass_end of the fast path: level-2 partition -> exclusive LDS counting (+ bloom gate) ->
- * per sub-table sort by insertion time -> exact layout replay */
-static int fast_finish(yakamd_ctx *c, bool last)
-{
-	const int P = c->P;
-	u64 n_total = 0;
-	for (auto &k : c->kept) n_total += k.n;
-	const int fmt_in = c->kept.empty() ? 0 : c->kept.front().fmt;
-	u64 sort_tmax = c->t_end;
+/* ---- pass_end of the fast path (fast_finish): plan -> level-2 partition (the retain decision between its sweeps) -> exclusive LDS counting
+ * (+ bloom gate) -> gather of the selected keys -> per sub-table sort by insertion time -> exact layout replay ---- */
+
+/* what the stages of fast_finish hand each other: every device buffer stays here until a stage frees it or hands it to the context */
+struct Slice {
 	FastParams fp;
-	fp.pre = c->pre; fp.k = c->k; fp.bloom_mode = c->bloom_mode; fp.nb = c->nb; fp.n_hash = c->n_hash;
-	fp.img_nonempty = c->img_keys_total > 0; fp.plo = c->plo; fp.phi = c->phi; fp.t_pass0 = c->t_pass0;
-	fp.dbg = (int)env_i64("YAKAMD_DBG", 0);
-	fp.or_mode = c->or_mode;
-	fp.bf_nowb = 0;
-	/* YAKAMD_VERBOSE > 1: wall-clock laps of the stages (each behind a stream synchronise: allocation stalls show up where they happen) */
-	const bool laps = env_i64("YAKAMD_VERBOSE", 0) > 1;
-	double lap_t = now_ms();
-	auto lap = [&](const char *what) {
+	u64 n_total = 0, sort_tmax = 0, budget = 0;
+	int fmt_in = 0, s2 = 0, s2a = 0, s2b = 0;
+	bool three = false, nowb_plan = false, keep2 = false;
+	size_t n_sb = 0;
+	DevBuf<u64> sbstart; DevBuf<u32> segcur, ovf2; DevBuf<Rec> r2;   /* the level-2 partition: the sub-buckets' starts and records */
+	DevBuf<u64> lo_kc, lo_T; DevBuf<u32> lo_nsel, lo_lp, lo_nd; DevBuf<unsigned short> lo_c2;   /* k_lc2's output (LcOut) */
+	DevBuf<u32> ndist;
+	std::vector<u32> m; std::vector<u64> ro; u64 n_sel = 0;        /* the gather: keys per sub-table (m), their offsets (ro) */
+	DevBuf<u64> segbase, koff; DevBuf<u32> kc2;
+	/* the sort: {key, time} pairs as gathered (kt), keys and times in two buffer pairs, the current one cur */
+	int tbits = 0, ts_b = 0, ts_w = 0, ts_j = 0; bool tsort = false;
+	DevBuf<u64> kc[2], tt[2]; int cur = 0;
+	DevBuf<Rec> kt; DevBuf<u32> tsfail;
+	bool laps; double lap_t;   /* YAKAMD_VERBOSE > 1: wall-clock laps of the stages (each behind a stream synchronise: allocation stalls show up where they happen) */
+
+	Slice() : laps(env_i64("YAKAMD_VERBOSE", 0) > 1), lap_t(now_ms()) {}
+	LcOut lo() const { LcOut o; o.kc = lo_kc; o.T = lo_T; o.nsel = lo_nsel; o.lp = lo_lp; o.nd = lo_nd; o.c2 = lo_c2; return o; }
+	void lap(yakamd_ctx *c, const char *what)
+	{
 		if (!laps) return;
 		(void)hipStreamSynchronize(c->st);
 		const double t = now_ms();
@@ -1215,7 +1227,23 @@ static int fast_finish(yakamd_ctx *c, bool last)
 		(void)hipMemGetInfo(&fr, &tt_);
 		fprintf(stderr, "[yak_amd] slice stage %-28s %9.2f ms   (device memory in use %.1f GB, of it idle in the pool %.1f GB)\n", what, t - lap_t, (double)(tt_ - fr) / 1e9, (double)yk_pool_cached_bytes() / 1e9);
 		lap_t = now_ms();
-	};
+	}
+};
+
+/* the plan of the slice: sub-buckets per sub-table (s2, in one or two sweeps), the filter-less plan (nowb_plan), the FastParams they imply */
+static int slice_plan(yakamd_ctx *c, Slice &s, bool last)
+{
+	const int P = c->P;
+	for (auto &k : c->kept) s.n_total += k.n;
+	s.fmt_in = c->kept.empty() ? 0 : c->kept.front().fmt;
+	s.sort_tmax = c->t_end;
+	FastParams &fp = s.fp;
+	fp.pre = c->pre; fp.k = c->k; fp.bloom_mode = c->bloom_mode; fp.nb = c->nb; fp.n_hash = c->n_hash;
+	fp.img_nonempty = c->img_keys_total > 0; fp.plo = c->plo; fp.phi = c->phi; fp.t_pass0 = c->t_pass0;
+	fp.dbg = (int)env_i64("YAKAMD_DBG", 0);
+	fp.or_mode = c->or_mode;
+	fp.bf_nowb = 0;
+	const u64 n_total = s.n_total;
 	/* mean sub-bucket <= ~600 instances: even if all are distinct the 1024-slot LDS table holds them.  With a filter the input is reads with
 	 * coverage (a filtered count of all-distinct k-mers keeps nothing): three times as many instances per sub-bucket still leave the distinct
 	 * k-mers far below the table's 624 (30 x coverage: ~100 distinct per 560 instances), and 2048 sub-buckets per sub-table are what the
@@ -1228,23 +1256,20 @@ static int fast_finish(yakamd_ctx *c, bool last)
 	/* Known before the partition: will every record of this pass stay on the device for the count pass over the same input (keep2 below) while
 	 * the filter is still untouched?  Then nobody reads the filter's bits before the records can rebuild them (bf_nowb), k_lc2 needs no stage of
 	 * the filter in LDS, and a sub-bucket may own 256 blocks instead of 128: half as many, twice as large */
-	bool nowb_plan = false;
-	{
-		size_t fr = 0, tot = 0;
-		const int64_t cap_gb = env_i64("YAKAMD_RETAIN_GB", -1);
-		u64 budget = cap_gb >= 0 ? (u64)cap_gb << 30 : 0;
-		if (cap_gb < 0 && hipMemGetInfo(&fr, &tot) == hipSuccess) budget = tot / 8;
-		nowb_plan = c->bloom_mode && c->bf_virgin && last && c->n_slices == 0 && c->img_keys_total == 0 && c->retain_on && !c->retain_broken && fmt_in == 1 &&
-		            !c->or_mode && c->retained.empty() && c->retained_bytes + n_total * 8 <= budget && c->n_hash <= 32 &&
-		            env_i64("YAKAMD_RETAIN2", 1) != 0 && env_i64("YAKAMD_BF_DEFER", 1) != 0 && env_i64("YAKAMD_LC2", 1) != 0 && env_i64("YAKAMD_LC2_NOSTAGE", 1) != 0;
-		for (auto &k : c->kept) nowb_plan = nowb_plan && k.owned;
-	}
+	const int64_t cap_gb = env_i64("YAKAMD_RETAIN_GB", -1);   /* the budget of the records kept for that pass (slice_retain): else an eighth of the device */
+	size_t fr = 0, tot = 0;
+	s.budget = cap_gb >= 0 ? (u64)cap_gb << 30 : hipMemGetInfo(&fr, &tot) == hipSuccess ? tot / 8 : 0;
+	bool &nowb_plan = s.nowb_plan;
+	nowb_plan = c->bloom_mode && c->bf_virgin && last && c->n_slices == 0 && c->img_keys_total == 0 && c->retain_on && !c->retain_broken && s.fmt_in == 1 &&
+	            !c->or_mode && c->retained.empty() && c->retained_bytes + n_total * 8 <= s.budget && c->n_hash <= 32 &&
+	            env_i64("YAKAMD_RETAIN2", 1) != 0 && env_i64("YAKAMD_BF_DEFER", 1) != 0 && env_i64("YAKAMD_LC2", 1) != 0 && env_i64("YAKAMD_LC2_NOSTAGE", 1) != 0;
+	for (auto &k : c->kept) nowb_plan = nowb_plan && k.owned;
 	/* one sweep of the level-2 scatter takes up to 2^11 sub-buckets (2^13 in sweeps over the chunk); beyond that -- the share of an N-GPU job's rank:
 	 * 128 sub-tables of 69 M instances each -- the partition takes two sweeps (p3): the high bits first into {hash, rank} records, then 2^p3_low
 	 * sub-buckets inside every group.  2^18 sub-buckets per sub-table bound the per-sub-bucket arrays */
 	const int p3_min = (int)env_i64("YAKAMD_P3_MIN", 13), p3_low = (int)std::min<int64_t>(11, std::max<int64_t>(1, env_i64("YAKAMD_P3_LOW", 11)));
-	int s2 = 0, s2a = 0, s2b = 0;
-	bool three = false;
+	int &s2 = s.s2, &s2a = s.s2a, &s2b = s.s2b;
+	bool &three = s.three;
 	for (int attempt = 0; attempt < 2; ++attempt) {
 		const int lb_max = nowb_plan ? 8 : 7;                      /* log2 blocks a sub-bucket may own: k_lc2 stages at most 128; without a stage its table gives every block >= 4 home slots */
 		s2 = n_total ? ceil_log2_u64((n_total / (u64)(c->phi - c->plo) + per_sb - 1) / per_sb) : 0;
@@ -1269,7 +1294,7 @@ static int fast_finish(yakamd_ctx *c, bool last)
 	fp.s2_bits = s2; fp.s2_tot = s2;
 	fp.sw = c->bloom_mode ? c->nb - 9 : s2; fp.ssh = fp.sw - s2;
 	fp.bf_virgin = 0;
-	fp.rec8_in = fmt_in; fp.tb = YK_R8_TAG_BITS + s2;
+	fp.rec8_in = s.fmt_in; fp.tb = YK_R8_TAG_BITS + s2;
 	fp.rec8_out = 0;                                         /* set below, once the largest sub-table stream is known */
 	if (c->bloom_mode) {
 		const bool lc2_runs = env_i64("YAKAMD_LC2", 1) != 0 && c->n_hash <= 32;   /* (with the block range below: yk_lc2_ok) -- the tier behind k_lc2 works on the filter in memory and needs real zeros */
@@ -1277,148 +1302,136 @@ static int fast_finish(yakamd_ctx *c, bool last)
 		else if (bloom_materialise(c)) return -1;
 		c->bf_virgin = false;
 	}
-	const int s2_first = three ? s2a : s2;                       /* bits of the sweep that reads the level-1 records */
+	s.n_sb = (size_t)P << s2;
+	if (s.fmt_in) {
+		if (np_max >= (1ull << 32)) return fail("more than 2^32 k-mer instances of one sub-table in one slice");
+		fp.rec8_out = np_max < (1ull << fp.tb) && env_i64("YAKAMD_REC8_OUT", 1) != 0;   /* the rank must fit below the hash bits; else 16-byte records {hash, rank} */
+		fp.t_pass0 = 0;                                       /* times are ranks inside the sub-table's stream of this slice */
+		s.sort_tmax = np_max;
+	}
+	return 0;
+}
+
+/* the level-1 records stay for the count pass over the same input when the caller asked for that and they fit the budget: all of the pass's
+ * records, or none.  The kept batches are released or handed to c->retained */
+static void slice_retain(yakamd_ctx *c, Slice &s, bool last)
+{
+	bool keep = c->retain_on && !c->retain_broken && s.fmt_in == 1 && c->bloom_mode && !c->or_mode && c->retained_bytes + s.n_total * 8 <= s.budget;
+	for (auto &k : c->kept) keep = keep && k.owned;
+	/* the whole pass in this one slice, into an empty table: the level-2 records and the sub-buckets' key lists serve the count pass better (k_cnt2) */
+	s.keep2 = keep && last && c->n_slices == 0 && c->img_keys_total == 0 && s.fp.rec8_out && c->retained.empty() && env_i64("YAKAMD_RETAIN2", 1) != 0;
+	if (s.keep2) keep = false;
+	if (c->retain_on && !keep && !s.keep2 && !c->kept.empty()) { c->retain_broken = true; retained_drop(c); }
+	for (auto &k : c->kept) {
+		if (keep && k.n) { yakamd_ctx::Retained r; r.d_rec = (u64*)k.d_rec; r.n = k.n; r.bstart.swap(k.bstart); c->retained.push_back(std::move(r)); c->retained_bytes += k.n * 8; }
+		else if (k.owned) dfree(k.d_rec);
+	}
+	c->kept.clear(); c->kept_bytes = 0;
+}
+
+/* the level-2 partition in one or two sweeps; the retain decision runs behind the first, which reads the level-1 records */
+static int slice_partition(yakamd_ctx *c, Slice &s, bool last)
+{
+	const int P = c->P;
+	const FastParams &fp = s.fp;
+	const int s2_first = s.three ? s.s2a : s.s2;                 /* bits of the sweep that reads the level-1 records */
 	const u64 ch2 = std::max<u64>((u64)env_i64("YAKAMD_CH2", YK_CH2), (u64)32 << s2_first);    /* keep >= 32 records per sub-bucket run */
-	/* chunk table: runs of one sub-table's records, grouped by sub-table */
-	std::vector<Chunk2> chunks;
-	std::vector<u32> chunk_first(P + 1, 0);
+	/* chunk table: runs of one sub-table's records, grouped by sub-table; each batch's runs cut on their own */
+	ChunkTable t;
+	t.first.assign(P + 1, 0);
 	std::vector<u64> bbase(P + 1, 0);
 	for (int p = 0; p < P; ++p) {
-		chunk_first[p] = (u32)chunks.size();
+		t.first[p] = (u32)t.h.size();
 		u64 np = 0;
 		for (auto &k : c->kept) {
 			const u64 a = k.bstart[p], b = k.bstart[p + 1];
 			for (u64 o = a; o < b; o += ch2) {
 				Chunk2 ch;
-				ch.rec = fmt_in ? (const Rec*)((const u64*)k.d_rec + o) : k.d_rec + o; ch.spare = 0;
+				ch.rec = s.fmt_in ? (const Rec*)((const u64*)k.d_rec + o) : k.d_rec + o; ch.spare = 0;
 				ch.n = (u32)std::min<u64>(ch2, b - o); ch.bucket = (u32)p;
-				ch.tbase = fmt_in ? (u32)np : (u32)(k.t0 - c->t_pass0); ch.pad = (u32)fmt_in;   /* tagged: ranks continue from the earlier batches of this sub-table */
+				ch.tbase = s.fmt_in ? (u32)np : (u32)(k.t0 - c->t_pass0); ch.pad = (u32)s.fmt_in;   /* tagged: ranks continue from the earlier batches of this sub-table */
 				ch.before = (u32)(o - a); ch.after = (u32)(b - (o + ch.n));
-				chunks.push_back(ch);
+				t.h.push_back(ch);
 			}
 			np += b - a;
 		}
 		bbase[p + 1] = bbase[p] + np;
-		if (chunks.size() > chunk_first[p]) chunks.back().spare = 1;   /* last chunk of its sub-table */
+		if (t.h.size() > t.first[p]) t.h.back().spare = 1;          /* last chunk of its sub-table */
 	}
-	chunk_first[P] = (u32)chunks.size();
-	const size_t n_sb = (size_t)P << s2, S2F = (size_t)1 << s2_first;
-	if (fmt_in) {
-		if (np_max >= (1ull << 32)) return fail("more than 2^32 k-mer instances of one sub-table in one slice");
-		fp.rec8_out = np_max < (1ull << fp.tb) && env_i64("YAKAMD_REC8_OUT", 1) != 0;   /* the rank must fit below the hash bits; else 16-byte records {hash, rank} */
-		fp.t_pass0 = 0;                                       /* times are ranks inside the sub-table's stream of this slice */
-		sort_tmax = np_max;
-	}
-
-	Chunk2 *d_chunks = 0; u32 *d_cf = 0, *d_rows2 = 0, *d_segcur = 0, *d_ovf2 = 0, *d_ndist = 0; u64 *d_bbase = 0, *d_sbstart = 0, *d_segbase = 0, *d_sba = 0, *d_koff = 0; Rec *d_r2 = 0, *d_ra = 0;
-	u64 *kc[2] = { 0, 0 }, *tt[2] = { 0, 0 };
-	LcOut lo; lo.kc = 0; lo.T = 0; lo.nsel = 0; lo.lp = 0; lo.nd = 0; lo.c2 = 0;
-	u64 *d_scr = 0, *d_scroff = 0;
-	u32 *d_kc2 = 0;
-	/* every device buffer of this function is released here, whichever way it is left */
-	struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ [&]() {
-		dfree(d_chunks); dfree(d_cf); dfree(d_rows2); dfree(d_segcur); dfree(d_ovf2); dfree(d_ndist); dfree(d_bbase); dfree(d_sbstart);
-		dfree(d_segbase); dfree(d_r2); dfree(kc[0]); dfree(kc[1]); dfree(tt[0]); dfree(tt[1]); dfree(lo.kc); dfree(lo.T); dfree(lo.nsel); dfree(lo.lp); dfree(lo.nd);
-		dfree(lo.c2); dfree(d_kc2); dfree(d_scr); dfree(d_scroff); dfree(d_sba); dfree(d_ra); dfree(d_koff);
-	} };
-	if (dmalloc(&d_chunks, chunks.size()) || dmalloc(&d_cf, P + 1) || dmalloc(&d_bbase, P + 1) || dmalloc(&d_rows2, chunks.size() * S2F) ||
-	    dmalloc(&d_sbstart, n_sb + 1) || dmalloc(&d_segcur, P) || dmalloc(&d_ovf2, n_sb)) return -1;
-	if (three ? (dmalloc(&d_ra, n_total) || dmalloc(&d_sba, ((size_t)P << s2a) + 1)) : dmalloc(&d_r2, fp.rec8_out ? (n_total + 1) / 2 : n_total)) return -1;
-	HIPCK(hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * sizeof(Chunk2), hipMemcpyHostToDevice, c->st));
-	HIPCK(hipMemcpyAsync(d_cf, chunk_first.data(), (P + 1) * 4, hipMemcpyHostToDevice, c->st));
+	t.first[P] = (u32)t.h.size();
+	DevBuf<u64> d_bbase, d_sba; DevBuf<u32> d_rows2; DevBuf<Rec> d_ra;
+	if (t.upload(c->st) || d_bbase.alloc(P + 1) || d_rows2.alloc(t.h.size() << s2_first) || s.sbstart.alloc(s.n_sb + 1) || s.segcur.alloc(P) || s.ovf2.alloc(s.n_sb)) return -1;
+	if (s.three ? (d_ra.alloc(s.n_total) || d_sba.alloc(((size_t)P << s.s2a) + 1)) : s.r2.alloc(fp.rec8_out ? (s.n_total + 1) / 2 : s.n_total)) return -1;
 	HIPCK(hipMemcpyAsync(d_bbase, bbase.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
 	HIPCK(hipMemsetAsync(c->d_counters + YKC_NOVF2, 0, 8, c->st));
 	std::vector<u64> h_sba;
 	{
 		EvTimer tm(c->st);
-		if (!three) yk_launch_part2(d_chunks, (int)chunks.size(), d_cf, d_bbase, fp, P, d_rows2, d_sbstart, d_r2, c->st);
+		if (!s.three) yk_launch_part2(t.d, (int)t.h.size(), t.d_first, d_bbase, fp, P, d_rows2, s.sbstart, s.r2, c->st);
 		else {
 			/* first sweep: the high s2a bits of the sub-bucket, {hash, rank} records out (the rank no longer fits beside the hash while only
 			 * s2a of its bits are implied by the place) */
 			FastParams fa = fp;
-			fa.s2_bits = s2a; fa.ssh = fp.sw - s2a; fa.rec8_out = 0;
-			yk_launch_part2(d_chunks, (int)chunks.size(), d_cf, d_bbase, fa, P, d_rows2, d_sba, d_ra, c->st);
-			h_sba.resize(((size_t)P << s2a) + 1);
+			fa.s2_bits = s.s2a; fa.ssh = fp.sw - s.s2a; fa.rec8_out = 0;
+			yk_launch_part2(t.d, (int)t.h.size(), t.d_first, d_bbase, fa, P, d_rows2, d_sba, d_ra, c->st);
+			h_sba.resize(((size_t)P << s.s2a) + 1);
 			HIPCK(hipMemcpyAsync(h_sba.data(), d_sba, h_sba.size() * 8, hipMemcpyDeviceToHost, c->st));
 		}
 		c->ms_part2 = tm.stop();
 		c->st_cur.ms_extract += c->ms_part2; c->st_cur.ms_part2 += c->ms_part2;
 	}
-	lap("level-2 partition (first sweep)");
-	bool keep2 = false;
-	{
-		/* the level-1 records stay for the count pass over the same input when the caller asked for that and they fit the budget
-		 * (an eighth of the device memory unless YAKAMD_RETAIN_GB says otherwise): all of the pass's records, or none */
-		size_t fr = 0, tot = 0;
-		const int64_t cap_gb = env_i64("YAKAMD_RETAIN_GB", -1);
-		u64 budget = cap_gb >= 0 ? (u64)cap_gb << 30 : 0;
-		if (cap_gb < 0 && hipMemGetInfo(&fr, &tot) == hipSuccess) budget = tot / 8;
-		bool keep = c->retain_on && !c->retain_broken && fmt_in == 1 && c->bloom_mode && !c->or_mode && c->retained_bytes + n_total * 8 <= budget;
-		for (auto &k : c->kept) keep = keep && k.owned;
-		/* the whole pass in this one slice, into an empty table: the level-2 records and the sub-buckets' key lists serve the count pass better (k_cnt2) */
-		keep2 = keep && last && c->n_slices == 0 && c->img_keys_total == 0 && fp.rec8_out && c->retained.empty() && env_i64("YAKAMD_RETAIN2", 1) != 0;
-		if (keep2) keep = false;
-		if (c->retain_on && !keep && !keep2 && !c->kept.empty()) { c->retain_broken = true; retained_drop(c); }
-		for (auto &k : c->kept) {
-			if (keep && k.n) { yakamd_ctx::Retained r; r.d_rec = (u64*)k.d_rec; r.n = k.n; r.bstart.swap(k.bstart); c->retained.push_back(std::move(r)); c->retained_bytes += k.n * 8; }
-			else if (k.owned) dfree(k.d_rec);
-		}
-	}
-	c->kept.clear(); c->kept_bytes = 0;
-	dfree(d_chunks); dfree(d_cf); dfree(d_rows2); dfree(d_bbase);
-	if (three) {
+	s.lap(c, "level-2 partition (first sweep)");
+	slice_retain(c, s, last);
+	t.reset(); d_rows2.reset(); d_bbase.reset();
+	if (s.three) {
 		/* second sweep: every group of the first is a bucket of its own (sub-table << s2a | group); its 2^s2b sub-buckets take the group's place in
 		 * the final numbering sub-table << s2 | sub-bucket, so the offsets of the first sweep are the bucket bases of the second */
-		const size_t PB = (size_t)P << s2a, S2B = (size_t)1 << s2b;
-		const u64 chb = std::max<u64>((u64)env_i64("YAKAMD_CH2", YK_CH2), (u64)32 << s2b);
-		std::vector<Chunk2> cb;
-		std::vector<u32> cfb(PB + 1, 0);
-		for (size_t q = 0; q < PB; ++q) {
-			cfb[q] = (u32)cb.size();
-			for (u64 o = h_sba[q]; o < h_sba[q + 1]; o += chb) {
-				Chunk2 ch;
-				ch.rec = d_ra + o; ch.spare = 0; ch.n = (u32)std::min<u64>(chb, h_sba[q + 1] - o); ch.bucket = (u32)q; ch.tbase = 0; ch.pad = 0; ch.before = 0; ch.after = 0;
-				cb.push_back(ch);
-			}
-			if (cb.size() > cfb[q]) cb.back().spare = 1;
-		}
-		cfb[PB] = (u32)cb.size();
+		const size_t PB = (size_t)P << s.s2a, S2B = (size_t)1 << s.s2b;
+		chunk_runs(t, d_ra, sizeof(Rec), h_sba.data(), PB, std::max<u64>((u64)env_i64("YAKAMD_CH2", YK_CH2), (u64)32 << s.s2b));
 		FastParams fb = fp;
-		fb.s2_bits = s2b; fb.rec8_in = 0;                          /* routes by the low s2b bits, packs with all of them (s2_tot) */
-		if (dmalloc(&d_chunks, cb.size()) || dmalloc(&d_cf, PB + 1) || dmalloc(&d_rows2, cb.size() * S2B) || dmalloc(&d_r2, fp.rec8_out ? (n_total + 1) / 2 : n_total)) return -1;
-		HIPCK(hipMemcpyAsync(d_chunks, cb.data(), cb.size() * sizeof(Chunk2), hipMemcpyHostToDevice, c->st));
-		HIPCK(hipMemcpyAsync(d_cf, cfb.data(), (PB + 1) * 4, hipMemcpyHostToDevice, c->st));
+		fb.s2_bits = s.s2b; fb.rec8_in = 0;                          /* routes by the low s2b bits, packs with all of them (s2_tot) */
+		if (t.upload(c->st) || d_rows2.alloc(t.h.size() * S2B) || s.r2.alloc(fp.rec8_out ? (s.n_total + 1) / 2 : s.n_total)) return -1;
 		EvTimer tm(c->st);
-		yk_launch_part2(d_chunks, (int)cb.size(), d_cf, d_sba, fb, (int)PB, d_rows2, d_sbstart, d_r2, c->st);
+		yk_launch_part2(t.d, (int)t.h.size(), t.d_first, d_sba, fb, (int)PB, d_rows2, s.sbstart, s.r2, c->st);
 		const double ms = tm.stop();                                /* (the host vectors above outlive the copies) */
 		c->ms_part2 += ms; c->st_cur.ms_extract += ms; c->st_cur.ms_part2 += ms;
-		dfree(d_chunks); dfree(d_cf); dfree(d_rows2); dfree(d_ra); dfree(d_sba);
-		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] level-2 partition in two sweeps: 2^%d groups, then 2^%d sub-buckets each (%llu records, %.2f ms)\n", s2a, s2b, (unsigned long long)n_total, c->ms_part2);
+		t.reset(); d_rows2.reset(); d_ra.reset(); d_sba.reset();
+		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] level-2 partition in two sweeps: 2^%d groups, then 2^%d sub-buckets each (%llu records, %.2f ms)\n", s.s2a, s.s2b, (unsigned long long)s.n_total, c->ms_part2);
 	}
-	lap("release / second sweep");
+	s.lap(c, "release / second sweep");
+	return 0;
+}
+
+/* the count: k_lc2 owns every sub-bucket in LDS and selects its new keys; the sub-buckets it passes on go to the same algorithm on tables in
+ * global scratch, a group of them at a time */
+static int slice_count(yakamd_ctx *c, Slice &s)
+{
+	const int P = c->P;
+	FastParams &fp = s.fp;
+	const size_t n_sb = s.n_sb;
 	/* the keys a sub-bucket selects are written over the front of its own record range in lo.kc / lo.T */
 	/* 8-byte level-2 records that nobody keeps: the keys go over the records themselves (a workgroup has read all of its sub-bucket's records
 	 * before it writes its first key, and nobody else reads them) -- 8 bytes per record less at the peak of a slice (a cfg3 rank: 71 GB) */
-	const bool kc_inplace = fp.rec8_out && !keep2 && env_i64("YAKAMD_KC_INPLACE", 1) != 0;
-	if (kc_inplace) { lo.kc = (u64*)d_r2; d_r2 = 0; }
-	else if (dmalloc(&lo.kc, n_total)) return -1;
-	if (dmalloc(&lo.T, n_total) || dmalloc(&lo.nsel, n_sb) || dmalloc(&lo.lp, n_sb) || dmalloc(&lo.nd, n_sb) || dmalloc(&d_ndist, P)) return -1;
-	const Rec *lc_rec_in = kc_inplace ? (const Rec*)lo.kc : d_r2;
+	const bool kc_inplace = fp.rec8_out && !s.keep2;
+	if (kc_inplace) s.lo_kc = DevBuf<u64>((u64*)s.r2.release());
+	else if (s.lo_kc.alloc(s.n_total)) return -1;
+	if (s.lo_T.alloc(s.n_total) || s.lo_nsel.alloc(n_sb) || s.lo_lp.alloc(n_sb) || s.lo_nd.alloc(n_sb) || s.ndist.alloc(P)) return -1;
+	const Rec *lc_rec_in = kc_inplace ? (const Rec*)s.lo_kc.get() : s.r2.get();
 	/* the count pass over these same records (keep2) gets its counts from the counting kernels, next to the keys they select: every instance of a
 	 * key lies in its sub-bucket, which they own outright (k_cnt2 would read all the records again to count what they had in LDS).  Without the
 	 * room for them the count pass recounts (k_cnt2) */
-	if (keep2 && env_i64("YAKAMD_CNT2_FUSED", 1) != 0) lo.c2 = (unsigned short*)pool_alloc(n_total * 2);
+	if (s.keep2 && env_i64("YAKAMD_CNT2_FUSED", 1) != 0) s.lo_c2 = DevBuf<unsigned short>((unsigned short*)pool_alloc(s.n_total * 2));
 	if (c->plo > 0 || c->phi < P) {                              /* sub-buckets outside the shard are never visited */
-		HIPCK(hipMemsetAsync(lo.nsel, 0, n_sb * 4, c->st)); HIPCK(hipMemsetAsync(lo.lp, 0, n_sb * 4, c->st)); HIPCK(hipMemsetAsync(lo.nd, 0, n_sb * 4, c->st));
+		HIPCK(hipMemsetAsync(s.lo_nsel, 0, n_sb * 4, c->st)); HIPCK(hipMemsetAsync(s.lo_lp, 0, n_sb * 4, c->st)); HIPCK(hipMemsetAsync(s.lo_nd, 0, n_sb * 4, c->st));
 	}
-	HIPCK(hipMemsetAsync(d_ndist, 0, P * 4, c->st));
-	HIPCK(hipMemsetAsync(d_segcur, 0, P * 4, c->st));
+	HIPCK(hipMemsetAsync(s.ndist, 0, P * 4, c->st));
+	HIPCK(hipMemsetAsync(s.segcur, 0, P * 4, c->st));
 	u64 h_cnt[YKC_N];
 	/* every record of the pass stays on the device (keep2) and the filter has never been written: the 2^bf_shift bits are not written at all --
 	 * yak_ch_destroy_bf usually comes next (main.c:55); whatever reads the filter first rebuilds it (bloom_undefer).  nowb_plan said so before the
 	 * partition (sub-buckets of up to 256 blocks, no stage in LDS); with the stage (a plan that was off) the bits are kept in LDS and dropped */
-	fp.bf_nowb = keep2 && fp.bf_virgin && env_i64("YAKAMD_BF_DEFER", 1) != 0 && env_i64("YAKAMD_LC2", 1) != 0 && c->n_hash <= 32;
-	if (nowb_plan && !fp.bf_nowb) {
+	fp.bf_nowb = s.keep2 && fp.bf_virgin && env_i64("YAKAMD_BF_DEFER", 1) != 0 && env_i64("YAKAMD_LC2", 1) != 0 && c->n_hash <= 32;
+	if (s.nowb_plan && !fp.bf_nowb) {
 		/* the two predicates (nowb_plan before the partition, keep2 behind it) disagree: the sub-buckets own up to 256 filter blocks, which only the
 		 * kernel without a stage takes.  Not a reason to fail the pass: the filter gets its real zeros and the tier behind k_lc2 counts on it in memory */
 		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] a pass planned without a filter stage does not keep its records after all: filter materialised, sub-buckets to the global-scratch tier\n");
@@ -1428,19 +1441,18 @@ static int fast_finish(yakamd_ctx *c, bool last)
 	if (!lc2) fp.bf_nowb = 0;
 	{
 		EvTimer tm(c->st);
-		if (lc2) yk_launch_lc2(fp, d_sbstart, lc_rec_in, c->d_bf, img_view(c), lo, c->d_counters, d_ovf2, c->st);
-		c->ms_lds = tm.stop();
-		c->st_cur.ms_insert += c->ms_lds; c->st_cur.ms_dominant_kernel += c->ms_lds; c->st_cur.n_dominant_launches += 1;
+		if (lc2) yk_launch_lc2(fp, s.sbstart, lc_rec_in, c->d_bf, img_view(c), s.lo(), c->d_counters, s.ovf2, c->st);
+		c->ms_lds = insert_ms(c, tm);
 	}
 	HIPCK(hipMemcpyAsync(h_cnt, c->d_counters, sizeof(h_cnt), hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
 	if (!lc2) {
 		/* k_lc2 does not run this pass (n_hash > 32, sub-buckets that own more filter blocks than it stages, YAKAMD_LC2=0): every sub-bucket of the shard
 		 * goes to the tier behind it */
-		const u32 first = (u32)c->plo << s2, n_all = (u32)(c->phi - c->plo) << s2;
+		const u32 first = (u32)c->plo << s.s2, n_all = (u32)(c->phi - c->plo) << s.s2;
 		std::vector<u32> all(n_all);
 		for (u32 i = 0; i < n_all; ++i) all[i] = first + i;
-		HIPCK(hipMemcpy(d_ovf2, all.data(), (size_t)n_all * 4, hipMemcpyHostToDevice));
+		HIPCK(hipMemcpy(s.ovf2, all.data(), (size_t)n_all * 4, hipMemcpyHostToDevice));
 		h_cnt[YKC_NOVF2] = n_all;
 	}
 	if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] %s: %.2f ms, %llu of %zu sub-buckets passed on\n", lc2 ? "k_lc2" : "k_lc2 not run", c->ms_lds, (unsigned long long)h_cnt[YKC_NOVF2], n_sb);
@@ -1448,13 +1460,14 @@ static int fast_finish(yakamd_ctx *c, bool last)
 		const u32 n_ovf = (u32)h_cnt[YKC_NOVF2];
 		std::vector<u32> ovf(n_ovf);
 		std::vector<u64> sbs(n_sb + 1), off(n_ovf);
-		HIPCK(hipMemcpy(ovf.data(), d_ovf2, n_ovf * 4, hipMemcpyDeviceToHost));
-		HIPCK(hipMemcpy(sbs.data(), d_sbstart, (n_sb + 1) * 8, hipMemcpyDeviceToHost));
+		HIPCK(hipMemcpy(ovf.data(), s.ovf2, n_ovf * 4, hipMemcpyDeviceToHost));
+		HIPCK(hipMemcpy(sbs.data(), s.sbstart, (n_sb + 1) * 8, hipMemcpyDeviceToHost));
 		/* scratch tables of 40 B per slot (5 u64), in groups of sub-buckets that stay within a quarter of the free memory */
 		size_t fr = 0, tot = 0;
 		if (hipMemGetInfo(&fr, &tot) != hipSuccess) return fail("hipMemGetInfo failed");
 		const u64 max_words = (u64)env_i64("YAKAMD_OVF_SCRATCH_WORDS", (int64_t)(std::max<u64>(fr / 4, (u64)1 << 28) / 8));
-		if (dmalloc(&d_scroff, n_ovf)) return -1;
+		DevBuf<u64> scroff;
+		if (scroff.alloc(n_ovf)) return -1;
 		for (u32 i0 = 0; i0 < n_ovf;) {
 			u64 words = 0;
 			u32 i1 = i0;
@@ -1464,162 +1477,171 @@ static int fast_finish(yakamd_ctx *c, bool last)
 				if (i1 > i0 && words + 5 * cap > max_words) break;
 				off[i1] = words; words += 5 * cap;
 			}
-			if (dmalloc(&d_scr, words)) return -1;
-			HIPCK(hipMemcpyAsync(d_scroff + i0, off.data() + i0, (size_t)(i1 - i0) * 8, hipMemcpyHostToDevice, c->st));
+			DevBuf<u64> scr;
+			if (scr.alloc(words)) return -1;
+			HIPCK(hipMemcpyAsync(scroff + i0, off.data() + i0, (size_t)(i1 - i0) * 8, hipMemcpyHostToDevice, c->st));
 			EvTimer tm(c->st);
-			yk_launch_lds_count_ovf(fp, d_sbstart, lc_rec_in, c->d_bf, img_view(c), lo, d_ovf2 + i0, i1 - i0, d_scroff + i0, d_scr, c->st);
+			yk_launch_lds_count_ovf(fp, s.sbstart, lc_rec_in, c->d_bf, img_view(c), s.lo(), s.ovf2 + i0, i1 - i0, scroff + i0, scr, c->st);
 			c->st_cur.ms_insert += tm.stop();
 			HIPCK(hipStreamSynchronize(c->st));
-			dfree(d_scr); d_scr = 0;
+			scr.reset();
 			i0 = i1;
 		}
-		dfree(d_scroff); d_scroff = 0;
 	}
-	lap("insert (k_lc2 + tiers)");
-	if (keep2) { c->ret2.d_r2 = d_r2; d_r2 = 0; c->ret2.n_total = n_total; c->ret2.fp = fp; c->ret2.fp.bf_nowb = 0; }
-	dfree(d_r2); dfree(d_ovf2);
-	/* gather the fragments: keys per sub-table, then one contiguous list each */
-	std::vector<u32> m(P, 0);
-	std::vector<u64> ro(P + 1, 0);
+	return 0;
+}
+
+/* gather the fragments: keys per sub-table, then one contiguous list each, and the plan of the sort by insertion time; with keep2 the list and its
+ * sub-bucket offsets go to c->ret2 */
+static int slice_gather(yakamd_ctx *c, Slice &s)
+{
+	const int P = c->P;
+	const FastParams &fp = s.fp;
+	const int s2 = s.s2;
+	const LcOut lo = s.lo();
+	s.m.assign(P, 0);
+	s.ro.assign(P + 1, 0);
 	/* many sub-buckets per sub-table, or few sub-tables: the gather spread over the whole chip (k_lc_sum3 / k_nsel_scan / k_lc_gather) */
 	const bool flat = env_i64("YAKAMD_LC_FLAT", (s2 > 11 || c->phi - c->plo < 512) ? 1 : 0) != 0;
-	if (flat) yk_launch_lc_sum3(lo, s2, c->plo, c->phi, fp.t_pass0, d_segcur, c->d_lastput, d_ndist, c->st);
-	else yk_launch_lc_sum(lo.nsel, s2, c->plo, c->phi, d_segcur, c->st);
-	HIPCK(hipMemcpyAsync(m.data(), d_segcur, P * 4, hipMemcpyDeviceToHost, c->st));
+	if (flat) yk_launch_lc_sum3(lo, s2, c->plo, c->phi, fp.t_pass0, s.segcur, c->d_lastput, s.ndist, c->st);
+	else yk_launch_lc_sum(lo.nsel, s2, c->plo, c->phi, s.segcur, c->st);
+	HIPCK(hipMemcpyAsync(s.m.data(), s.segcur, P * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
-	for (int p = 0; p < P; ++p) ro[p + 1] = ro[p] + m[p];
-	const u64 n_sel = ro[P];
+	for (int p = 0; p < P; ++p) s.ro[p + 1] = s.ro[p] + s.m[p];
+	const u64 n_sel = s.n_sel = s.ro[P];
 	/* The sort by insertion time T.  Times are unique inside a sub-table and < 2^tbits, so the order needs no comparisons: one partition sweep by
 	 * the top ts_b bits of T (the level-2 partition's kernels on {key, T} pairs), then every bin ranks its keys with a bitmap of its 2^ts_w possible
 	 * times (k_ts_rank).  ts_w = 11 wherever that leaves at most 2^13 bins: a bin then never holds more keys than the ranking kernel's registers and
 	 * stage (the times of first occurrences are dense at the start of a stream of reads and sparse later), and the kernel takes 2^ts_j sparse
 	 * neighbours in one step (~1000 keys).  Times beyond 32 bits or bins wider than 2^18 times take the stable 8-bit passes as before */
-	const int tbits = std::max(1, ceil_log2_u64(sort_tmax + 1));
+	s.tbits = std::max(1, ceil_log2_u64(s.sort_tmax + 1));
 	u32 m_max = 0;
-	for (int p = 0; p < P; ++p) m_max = std::max(m_max, m[p]);
-	int ts_b = std::min(13, std::max(0, tbits - 11));
-	ts_b = (int)std::min<int64_t>(13, std::max<int64_t>(0, env_i64("YAKAMD_TS_BITS", ts_b)));
-	const int ts_w = std::max(5, tbits - ts_b);
-	int ts_j = 0;
-	while (ts_j < ts_b && ts_w + ts_j < 15 && ((u64)m_max >> (ts_b - ts_j - 1)) <= 256) ++ts_j;   /* a mean of 256: the head of a stream of reads is several times denser */
-	ts_j = (int)std::min<int64_t>(ts_b, std::max<int64_t>(0, env_i64("YAKAMD_TS_JOIN", ts_j)));
+	for (int p = 0; p < P; ++p) m_max = std::max(m_max, s.m[p]);
+	s.ts_b = std::min(13, std::max(0, s.tbits - 11));
+	s.ts_b = (int)std::min<int64_t>(13, std::max<int64_t>(0, env_i64("YAKAMD_TS_BITS", s.ts_b)));
+	s.ts_w = std::max(5, s.tbits - s.ts_b);
+	while (s.ts_j < s.ts_b && s.ts_w + s.ts_j < 15 && ((u64)m_max >> (s.ts_b - s.ts_j - 1)) <= 256) ++s.ts_j;   /* a mean of 256: the head of a stream of reads is several times denser */
+	s.ts_j = (int)std::min<int64_t>(s.ts_b, std::max<int64_t>(0, env_i64("YAKAMD_TS_JOIN", s.ts_j)));
 	/* short lists in many sub-tables (a filtered count of reads: ~50 K keys per sub-table) are done sooner by three launches of the stable pass */
-	const bool tsort = env_i64("YAKAMD_TSORT", (m_max >= 100000 || c->phi - c->plo < 512) ? 1 : 0) != 0 && tbits <= 32 && ts_w + ts_j <= 18 && n_sel > 0;
-	Rec *d_kt = 0, *d_kt2 = 0; u32 *d_tsfail = 0; u64 *d_binstart = 0;
-	struct Guard2 { std::function<void()> f; ~Guard2() { f(); } } guard2{ [&]() { dfree(d_kt); dfree(d_kt2); dfree(d_tsfail); dfree(d_binstart); } };
-	if (dmalloc(&kc[0], n_sel) || dmalloc(&tt[0], n_sel) || dmalloc(&d_segbase, P + 1)) return -1;
-	if (tsort && (dmalloc(&d_kt, n_sel) || dmalloc(&d_tsfail, 1))) return -1;
-	HIPCK(hipMemcpyAsync(d_segbase, ro.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
-	if (lo.c2) d_kc2 = (u32*)pool_alloc(std::max<u64>(n_sel, 1) * 4);   /* the count pass's counts, in the order of the gathered list (ret2.d_kkc) */
+	s.tsort = env_i64("YAKAMD_TSORT", (m_max >= 100000 || c->phi - c->plo < 512) ? 1 : 0) != 0 && s.tbits <= 32 && s.ts_w + s.ts_j <= 18 && n_sel > 0;
+	if (s.kc[0].alloc(n_sel) || s.tt[0].alloc(n_sel) || s.segbase.alloc(P + 1)) return -1;
+	if (s.tsort && (s.kt.alloc(n_sel) || s.tsfail.alloc(1))) return -1;
+	HIPCK(hipMemcpyAsync(s.segbase, s.ro.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
+	if (lo.c2) s.kc2 = DevBuf<u32>((u32*)pool_alloc(std::max<u64>(n_sel, 1) * 4));   /* the count pass's counts, in the order of the gathered list (ret2.d_kkc) */
 	{
 		EvTimer tm(c->st);
 		if (flat) {
-			if (dmalloc(&d_koff, n_sb + 1)) return -1;
-			yk_launch_nsel_scan(lo.nsel, s2, c->plo, c->phi, P, d_segbase, d_koff, c->st);
-			yk_launch_lc_gather(lo, d_sbstart, d_koff, s2, c->plo, c->phi, kc[0], tt[0], d_kt, d_kc2, c->st);
-		} else yk_launch_lc_compact(lo, d_sbstart, s2, c->plo, c->phi, fp.t_pass0, d_segbase, kc[0], tt[0], c->d_lastput, d_ndist, d_kt, d_kc2, c->st);
+			if (s.koff.alloc(s.n_sb + 1)) return -1;
+			yk_launch_nsel_scan(lo.nsel, s2, c->plo, c->phi, P, s.segbase, s.koff, c->st);
+			yk_launch_lc_gather(lo, s.sbstart, s.koff, s2, c->plo, c->phi, s.kc[0], s.tt[0], s.kt, s.kc2, c->st);
+		} else yk_launch_lc_compact(lo, s.sbstart, s2, c->plo, c->phi, fp.t_pass0, s.segbase, s.kc[0], s.tt[0], c->d_lastput, s.ndist, s.kt, s.kc2, c->st);
 		c->st_cur.ms_select += tm.stop();
 	}
 	{
 		std::vector<u32> nd(P);
-		HIPCK(hipMemcpy(nd.data(), d_ndist, P * 4, hipMemcpyDeviceToHost));
+		HIPCK(hipMemcpy(nd.data(), s.ndist, P * 4, hipMemcpyDeviceToHost));
 		u64 tot_d = 0;
 		for (int p = 0; p < P; ++p) tot_d += nd[p];
 		c->st_cur.n_distinct_seen += (int64_t)tot_d;
 	}
-	if (keep2) {
-		/* the gathered list is grouped by sub-bucket (k_lc_compact walks them in order): a copy of it + the first key of every sub-bucket */
-		if ((!d_koff && dmalloc(&c->ret2.d_koff, n_sb + 1)) || dmalloc(&c->ret2.d_kkc, n_sel) || dmalloc(&c->ret2.d_segbase, P + 1)) {
-			if (fp.bf_nowb) {                                         /* the records go after all: the filter they stood for is written now */
-				FastParams fr = fp;
-				fr.bf_nowb = 0;
-				HIPCK(hipMemsetAsync(c->d_bf, 0, c->bf_words * 4, c->st));
-				yk_launch_bf_rebuild(fr, d_sbstart, c->ret2.d_r2, c->d_bf, c->st);
-				HIPCK(hipStreamSynchronize(c->st));
-			}
-			retained_drop(c); c->retain_broken = true; keep2 = false;
+	if (!s.keep2) return 0;
+	/* the gathered list is grouped by sub-bucket (k_lc_compact walks them in order): a copy of it + the first key of every sub-bucket */
+	if ((!s.koff && dmalloc(&c->ret2.d_koff, s.n_sb + 1)) || dmalloc(&c->ret2.d_kkc, n_sel) || dmalloc(&c->ret2.d_segbase, P + 1)) {
+		if (fp.bf_nowb) {                                         /* the records go after all: the filter they stood for is written now */
+			FastParams fr = fp;
+			fr.bf_nowb = 0;
+			HIPCK(hipMemsetAsync(c->d_bf, 0, c->bf_words * 4, c->st));
+			yk_launch_bf_rebuild(fr, s.sbstart, c->ret2.d_r2, c->d_bf, c->st);
+			HIPCK(hipStreamSynchronize(c->st));
 		}
-		else {
-			if (d_koff) { c->ret2.d_koff = d_koff; d_koff = 0; }        /* the flat gather has them already */
-			else yk_launch_nsel_scan(lo.nsel, s2, c->plo, c->phi, P, d_segbase, c->ret2.d_koff, c->st);
-			if (d_kt) yk_launch_kt_split(d_kt, n_sel, c->ret2.d_kkc, 0, c->st);
-			else HIPCK(hipMemcpyAsync(c->ret2.d_kkc, kc[0], n_sel * 8, hipMemcpyDeviceToDevice, c->st));
-			c->ret2.d_sbstart = d_sbstart; d_sbstart = 0;
-			HIPCK(hipMemcpyAsync(c->ret2.d_segbase, d_segbase, (P + 1) * 8, hipMemcpyDeviceToDevice, c->st));
-			c->ret2.d_kc2 = d_kc2; d_kc2 = 0;
-			c->ret2.n_keys = n_sel;
-			c->ret2.valid = true;
-			c->bf_deferred = fp.bf_nowb != 0;
-		}
+		retained_drop(c); c->retain_broken = true; s.keep2 = false;
+		return 0;
 	}
-	dfree(lo.kc); dfree(lo.T); dfree(lo.nsel); dfree(lo.lp); dfree(lo.nd); dfree(lo.c2); dfree(d_kc2); dfree(d_sbstart); dfree(d_ndist); dfree(d_koff);
-	lap("gather of the selected keys");
-	int cur = 0;
+	if (s.koff) c->ret2.d_koff = s.koff.release();               /* the flat gather has them already */
+	else yk_launch_nsel_scan(lo.nsel, s2, c->plo, c->phi, P, s.segbase, c->ret2.d_koff, c->st);
+	if (s.kt) yk_launch_kt_split(s.kt, n_sel, c->ret2.d_kkc, 0, c->st);
+	else HIPCK(hipMemcpyAsync(c->ret2.d_kkc, s.kc[0], n_sel * 8, hipMemcpyDeviceToDevice, c->st));
+	c->ret2.d_sbstart = s.sbstart.release();
+	HIPCK(hipMemcpyAsync(c->ret2.d_segbase, s.segbase, (P + 1) * 8, hipMemcpyDeviceToDevice, c->st));
+	c->ret2.d_kc2 = s.kc2.release();
+	c->ret2.n_keys = n_sel;
+	c->ret2.valid = true;
+	c->bf_deferred = fp.bf_nowb != 0;
+	return 0;
+}
+
+/* the sort by insertion time: bitmap ranks, or the stable radix passes where they are refused; the result is kc[cur] / tt[cur] */
+static int slice_sort(yakamd_ctx *c, Slice &s)
+{
+	const int P = c->P;
+	const u64 n_sel = s.n_sel;
 	bool sorted = false;
-	if (tsort) {
+	if (s.tsort) {
 		EvTimer tm(c->st);
-		HIPCK(hipMemsetAsync(d_tsfail, 0, 4, c->st));
-		const Rec *rank_in = d_kt;
-		const u64 *rank_start = d_segbase;                        /* ts_b == 0: a sub-table is its one bin */
-		if (ts_b > 0) {
-			const u64 chs = std::max<u64>((u64)env_i64("YAKAMD_CH2", YK_CH2), (u64)32 << ts_b);
-			std::vector<Chunk2> cs;
-			std::vector<u32> cfs(P + 1, 0);
-			for (int p = 0; p < P; ++p) {
-				cfs[p] = (u32)cs.size();
-				for (u64 o = ro[p]; o < ro[p + 1]; o += chs) {
-					Chunk2 ch;
-					ch.rec = d_kt + o; ch.spare = 0; ch.n = (u32)std::min<u64>(chs, ro[p + 1] - o); ch.bucket = (u32)p; ch.tbase = 0; ch.pad = 0; ch.before = 0; ch.after = 0;
-					cs.push_back(ch);
-				}
-				if (cs.size() > cfs[p]) cs.back().spare = 1;
-			}
-			cfs[P] = (u32)cs.size();
-			Chunk2 *d_cs = 0; u32 *d_cfs = 0, *d_rows = 0;
-			struct Guard3 { std::function<void()> f; ~Guard3() { f(); } } guard3{ [&]() { dfree(d_cs); dfree(d_cfs); dfree(d_rows); } };
-			if (dmalloc(&d_cs, cs.size()) || dmalloc(&d_cfs, P + 1) || dmalloc(&d_rows, cs.size() << ts_b) || dmalloc(&d_binstart, ((size_t)P << ts_b) + 1) || dmalloc(&d_kt2, n_sel)) return -1;
-			HIPCK(hipMemcpyAsync(d_cs, cs.data(), cs.size() * sizeof(Chunk2), hipMemcpyHostToDevice, c->st));
-			HIPCK(hipMemcpyAsync(d_cfs, cfs.data(), (P + 1) * 4, hipMemcpyHostToDevice, c->st));
-			FastParams ft = fp;
-			ft.s2_bits = ts_b; ft.ssh = ts_w; ft.rec8_in = 0; ft.rec8_out = 0;
-			yk_launch_part2_ts(d_cs, (int)cs.size(), d_cfs, d_segbase, ft, P, d_rows, d_binstart, d_kt2, c->st);
+		HIPCK(hipMemsetAsync(s.tsfail, 0, 4, c->st));
+		const Rec *rank_in = s.kt;
+		const u64 *rank_start = s.segbase;                        /* ts_b == 0: a sub-table is its one bin */
+		DevBuf<Rec> kt2; DevBuf<u64> binstart;
+		if (s.ts_b > 0) {
+			ChunkTable t;
+			chunk_runs(t, s.kt, sizeof(Rec), s.ro.data(), P, std::max<u64>((u64)env_i64("YAKAMD_CH2", YK_CH2), (u64)32 << s.ts_b));
+			DevBuf<u32> rows;
+			if (t.upload(c->st) || rows.alloc(t.h.size() << s.ts_b) || binstart.alloc(((size_t)P << s.ts_b) + 1) || kt2.alloc(n_sel)) return -1;
+			FastParams ft = s.fp;
+			ft.s2_bits = s.ts_b; ft.ssh = s.ts_w; ft.rec8_in = 0; ft.rec8_out = 0;
+			yk_launch_part2_ts(t.d, (int)t.h.size(), t.d_first, s.segbase, ft, P, rows, binstart, kt2, c->st);
 			HIPCK(hipStreamSynchronize(c->st));                  /* the host tables above go out of scope */
-			rank_in = d_kt2; rank_start = d_binstart;
-			dfree(d_kt);                                            /* the pairs as gathered: no longer needed (a refused ranking re-splits the partitioned ones: same keys per sub-table) */
+			rank_in = kt2; rank_start = binstart;
+			s.kt.reset();                                           /* the pairs as gathered: no longer needed (a refused ranking re-splits the partitioned ones: same keys per sub-table) */
 		}
 		u32 h_fail = 1;
-		if (yk_launch_ts_rank(rank_start, rank_in, ts_w, ts_j, (u32)c->plo << ts_b, (u32)(c->phi - c->plo) << ts_b, kc[0], tt[0], d_tsfail, c->st) == 0) {
-			HIPCK(hipMemcpyAsync(&h_fail, d_tsfail, 4, hipMemcpyDeviceToHost, c->st));
+		if (yk_launch_ts_rank(rank_start, rank_in, s.ts_w, s.ts_j, (u32)c->plo << s.ts_b, (u32)(c->phi - c->plo) << s.ts_b, s.kc[0], s.tt[0], s.tsfail, c->st) == 0) {
+			HIPCK(hipMemcpyAsync(&h_fail, s.tsfail, 4, hipMemcpyDeviceToHost, c->st));
 			HIPCK(hipStreamSynchronize(c->st));
 		}
 		sorted = h_fail == 0;
 		if (!sorted) {                                            /* a time seen twice, or the kernel could not be configured: the stable passes on the gathered pairs */
 			if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] sort by bitmap ranks refused: stable radix passes instead\n");
-			yk_launch_kt_split(rank_in, n_sel, kc[0], tt[0], c->st);
+			yk_launch_kt_split(rank_in, n_sel, s.kc[0], s.tt[0], c->st);
 		}
-		dfree(d_kt2); dfree(d_binstart);
+		kt2.reset(); binstart.reset();
 		c->st_cur.ms_sort += tm.stop();
 	}
-	dfree(d_kt);
+	s.kt.reset();
 	if (!sorted) {
-		if (dmalloc(&kc[1], n_sel) || dmalloc(&tt[1], n_sel)) return -1;
+		if (s.kc[1].alloc(n_sel) || s.tt[1].alloc(n_sel)) return -1;
 		EvTimer tm(c->st);
 		const int sort_big = n_sel / (u64)std::max(1, c->phi - c->plo) >= 30000;
-		for (int shift = 0; shift < tbits; shift += 8) {
-			yk_launch_seg_sort_pass2(d_segbase, d_segcur, P, kc[cur], tt[cur], kc[cur ^ 1], tt[cur ^ 1], shift, c->st, sort_big);
-			cur ^= 1;
+		for (int shift = 0; shift < s.tbits; shift += 8) {
+			yk_launch_seg_sort_pass2(s.segbase, s.segcur, P, s.kc[s.cur], s.tt[s.cur], s.kc[s.cur ^ 1], s.tt[s.cur ^ 1], shift, c->st, sort_big);
+			s.cur ^= 1;
 		}
 		c->st_cur.ms_sort += tm.stop();
 	}
-	dfree(kc[cur ^ 1]); dfree(tt[cur ^ 1]);                     /* the sort's other buffer pair: 16 bytes per key the layout stage can use */
-	lap("sort by insertion time");
+	return 0;
+}
+
+static int fast_finish(yakamd_ctx *c, bool last)
+{
+	Slice s;
+	if (slice_plan(c, s, last) || slice_partition(c, s, last) || slice_count(c, s)) return -1;
+	s.lap(c, "insert (k_lc2 + tiers)");
+	if (s.keep2) { c->ret2.d_r2 = s.r2.release(); c->ret2.n_total = s.n_total; c->ret2.fp = s.fp; c->ret2.fp.bf_nowb = 0; }
+	s.r2.reset(); s.ovf2.reset();
+	if (slice_gather(c, s)) return -1;
+	s.lo_kc.reset(); s.lo_T.reset(); s.lo_nsel.reset(); s.lo_lp.reset(); s.lo_nd.reset(); s.lo_c2.reset();
+	s.kc2.reset(); s.sbstart.reset(); s.ndist.reset(); s.koff.reset();
+	s.lap(c, "gather of the selected keys");
+	if (slice_sort(c, s)) return -1;
+	s.kc[s.cur ^ 1].reset(); s.tt[s.cur ^ 1].reset();           /* the sort's other buffer pair: 16 bytes per key the layout stage can use */
+	s.lap(c, "sort by insertion time");
 	{
 		EvTimer tm(c->st);
-		ro.resize(P);
-		if (yk_run_replay(c, m, 0, kc[cur], tt[cur], c->d_lastput, 0, false, &ro)) return -1;
+		s.ro.resize(c->P);
+		if (yk_run_replay(c, s.m, 0, s.kc[s.cur], s.tt[s.cur], c->d_lastput, 0, false, &s.ro)) return -1;
 		c->st_cur.ms_replay += tm.stop();
 	}
-	lap("exact layout");
+	s.lap(c, "exact layout");
 	return 0;
 }
 
@@ -1663,9 +1685,8 @@ static int64_t pass_end_body(yakamd_ctx *c)
 		if (c->img_keys_total && c->d_delta) yk_launch_img_fold(img_view(c), c->n_slots, c->st);   /* put-calls that hit existing keys */
 		std::vector<u32> m(P, 0);
 		std::vector<u64> seg_off(P + 1, 0);
-		u32 *d_segcnt = 0, *d_segcur = 0; u64 *d_segoff = 0, *kc[2] = { 0, 0 }, *tt[2] = { 0, 0 };
-		struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ [&]() { dfree(d_segcnt); dfree(d_segcur); dfree(d_segoff); dfree(kc[0]); dfree(kc[1]); dfree(tt[0]); dfree(tt[1]); } };
-		if (dmalloc(&d_segcnt, P) || dmalloc(&d_segcur, P) || dmalloc(&d_segoff, P + 1)) return -1;
+		DevBuf<u64> kc[2], tt[2], d_segoff; DevBuf<u32> d_segcur, d_segcnt;
+		if (d_segcnt.alloc(P) || d_segcur.alloc(P) || d_segoff.alloc(P + 1)) return -1;
 		HIPCK(hipMemsetAsync(d_segcnt, 0, P * 4, c->st));
 		HIPCK(hipMemsetAsync(d_segcur, 0, P * 4, c->st));
 		int cur = 0;
@@ -1677,7 +1698,7 @@ static int64_t pass_end_body(yakamd_ctx *c)
 				HIPCK(hipStreamSynchronize(c->st));
 				for (int p = 0; p < P; ++p) seg_off[p + 1] = seg_off[p] + m[p];
 				const u64 tot = seg_off[P];
-				if (dmalloc(&kc[0], tot) || dmalloc(&kc[1], tot) || dmalloc(&tt[0], tot) || dmalloc(&tt[1], tot)) return -1;
+				if (kc[0].alloc(tot) || kc[1].alloc(tot) || tt[0].alloc(tot) || tt[1].alloc(tot)) return -1;
 				HIPCK(hipMemcpyAsync(d_segoff, seg_off.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
 				yk_launch_select_scatter(c->acc, c->bloom_mode, P, d_segoff, d_segcur, kc[0], tt[0], c->st);
 				c->st_cur.ms_select += tm.stop();
@@ -1694,7 +1715,7 @@ static int64_t pass_end_body(yakamd_ctx *c)
 			}
 		} else {
 			HIPCK(hipMemcpyAsync(d_segoff, seg_off.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
-			if (dmalloc(&kc[0], 1) || dmalloc(&tt[0], 1)) return -1;
+			if (kc[0].alloc(1) || tt[0].alloc(1)) return -1;
 		}
 		{
 			EvTimer tm(c->st);
@@ -1740,13 +1761,12 @@ extern "C" int yakamd_get_stats(yak_ch_t *h, yakamd_stats_t *st)
 int yk_ctx_hist(yakamd_ctx *c, int64_t *cnt1024)
 {
 	HIPCK(hipSetDevice(c->dev));
-	u64 *d_h = 0;
-	if (dmalloc(&d_h, 1024)) return -1;
+	DevBuf<u64> d_h;
+	if (d_h.alloc(1024)) return -1;
 	HIPCK(hipMemsetAsync(d_h, 0, 1024 * 8, c->st));
 	yk_launch_img_hist(img_view(c), c->n_slots, d_h, c->st);
 	const hipError_t e = hipMemcpyAsync(cnt1024, d_h, 1024 * 8, hipMemcpyDeviceToHost, c->st);
 	const hipError_t e2 = hipStreamSynchronize(c->st);
-	dfree(d_h);
 	return e == hipSuccess && e2 == hipSuccess ? 0 : fail("hist: %s", hipGetErrorString(e != hipSuccess ? e : e2));
 }
 
@@ -1780,11 +1800,10 @@ static int rebuild(yakamd_ctx *c, int cmin, int cmax, int which, yakamd_ctx *oth
 	const ImgView ov = other ? img_view(other) : img_view(c);
 	std::vector<u32> m(P), init(P);
 	std::vector<u64> seg_off(P + 1, 0);
-	u32 *d_segcnt = 0; u64 *d_segoff = 0, *d_kc = 0;
-	struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ [&]() { dfree(d_segcnt); dfree(d_segoff); dfree(d_kc); } };
+	DevBuf<u64> d_kc, d_segoff; DevBuf<u32> d_segcnt;
 	const int RG = yk_shrink_shares();                            /* workgroups per sub-table */
 	std::vector<u32> mr((size_t)P * RG);
-	if (dmalloc(&d_segcnt, (size_t)P * RG) || dmalloc(&d_segoff, P + 1)) return -1;
+	if (d_segcnt.alloc((size_t)P * RG) || d_segoff.alloc(P + 1)) return -1;
 	yk_launch_shrink_count(img_view(c), P, cmin, cmax, which, ov, d_segcnt, c->st, 1);
 	HIPCK(hipMemcpyAsync(mr.data(), d_segcnt, mr.size() * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
@@ -1793,7 +1812,7 @@ static int rebuild(yakamd_ctx *c, int cmin, int cmax, int which, yakamd_ctx *oth
 		for (int g = 0; g < RG; ++g) m[p] += mr[(size_t)p * RG + g];
 		seg_off[p + 1] = seg_off[p] + m[p]; init[p] = kh_bits_for(c->h_count[p]);
 	}
-	if (dmalloc(&d_kc, seg_off[P])) return -1;
+	if (d_kc.alloc(seg_off[P])) return -1;
 	HIPCK(hipMemcpyAsync(d_segoff, seg_off.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
 	yk_launch_shrink_scatter(img_view(c), P, cmin, cmax, which, ov, d_segoff, d_kc, c->st, d_segcnt);
 	EvTimer tm(c->st);
@@ -1829,22 +1848,16 @@ static int resize_tables(yakamd_ctx *c, const std::vector<u32> &new_bits)
 		t.new_off = new_off[p] = tot;
 		tot += std::max<u64>(32, std::max(n, N));
 	}
-	u64 *nk = 0; u32 *nu = 0, *su = 0; ResizeTask *d_tasks = 0;
-	if (dmalloc(&nk, tot) || dmalloc(&nu, tot / 32) || dmalloc(&su, tot / 32) || dmalloc(&d_tasks, P)) return -1;
+	DevBuf<ResizeTask> d_tasks; DevBuf<u32> su, nu; DevBuf<u64> nk;
+	if (nk.alloc(tot) || nu.alloc(tot / 32) || su.alloc(tot / 32) || d_tasks.alloc(P)) return -1;
 	HIPCK(hipMemsetAsync(nk, 0xff, tot * 8, c->st));
 	HIPCK(hipMemsetAsync(nu, 0, tot / 8, c->st));
 	HIPCK(hipMemcpyAsync(d_tasks, tasks.data(), P * sizeof(ResizeTask), hipMemcpyHostToDevice, c->st));
 	yk_launch_resize(d_tasks, P, c->d_keys, c->d_used, nk, nu, su, c->st);
 	HIPCK(hipStreamSynchronize(c->st));
-	dfree(su); dfree(d_tasks);
-	dfree(c->d_keys); dfree(c->d_used); dfree(c->d_delta);
-	c->d_keys = nk; c->d_used = nu; c->n_slots = tot;
-	c->h_off = new_off; c->h_bits = bits_after;
-	HIPCK(hipMemcpyAsync(c->d_bits, c->h_bits.data(), P * 4, hipMemcpyHostToDevice, c->st));
-	HIPCK(hipMemcpyAsync(c->d_off, c->h_off.data(), P * 8, hipMemcpyHostToDevice, c->st));
-	HIPCK(hipStreamSynchronize(c->st));
-	c->host_valid = false;
-	return 0;
+	su.reset(); d_tasks.reset();
+	c->h_bits = bits_after;
+	return yk_image_commit(c, nk.release(), nu.release(), tot, new_off);
 }
 
 /* new_bits of khashl's resize(want) on a set of (cap, count), or YK_LEAVE when it refuses (khashl.h:155-160) */
@@ -1892,22 +1905,20 @@ int yk_ctx_list_hashes(yakamd_ctx *c, int cmin, int cmax, u64 **d_hash, u32 **d_
 	const int P = c->P;
 	std::vector<u32> m(P);
 	std::vector<u64> seg_off(P + 1, 0);
-	u32 *d_segcnt = 0; u64 *d_segoff = 0, *d_kc = 0;
+	DevBuf<u32> t; DevBuf<u64> hash, d_kc, d_segoff; DevBuf<u32> d_segcnt;
 	*d_hash = 0; *d_t = 0;
-	bool done = false;
-	struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ [&]() { dfree(d_segcnt); dfree(d_segoff); dfree(d_kc); if (!done) { dfree(*d_hash); dfree(*d_t); } } };
-	if (dmalloc(&d_segcnt, P) || dmalloc(&d_segoff, P + 1)) return -1;
+	if (d_segcnt.alloc(P) || d_segoff.alloc(P + 1)) return -1;
 	yk_launch_shrink_count(img_view(c), P, cmin, cmax, 0, img_view(c), d_segcnt, c->st);
 	HIPCK(hipMemcpyAsync(m.data(), d_segcnt, P * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
 	for (int p = 0; p < P; ++p) seg_off[p + 1] = seg_off[p] + m[p];
 	*n = seg_off[P];
-	if (dmalloc(&d_kc, seg_off[P]) || dmalloc(d_hash, seg_off[P]) || dmalloc(d_t, seg_off[P])) return -1;
+	if (d_kc.alloc(seg_off[P]) || hash.alloc(seg_off[P]) || t.alloc(seg_off[P])) return -1;
 	HIPCK(hipMemcpyAsync(d_segoff, seg_off.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
 	yk_launch_shrink_scatter(img_view(c), P, cmin, cmax, 0, img_view(c), d_segoff, d_kc, c->st);
-	yk_launch_keys_to_hashes(d_kc, d_segoff, P, c->pre, *d_hash, *d_t, c->st);
+	yk_launch_keys_to_hashes(d_kc, d_segoff, P, c->pre, hash, t, c->st);
 	HIPCK(hipStreamSynchronize(c->st));
-	done = true;
+	*d_hash = hash.release(); *d_t = t.release();
 	return 0;
 }
 
@@ -1927,15 +1938,14 @@ int yk_ctx_dump_image_dev(yakamd_ctx *c, int lo, int hi, u64 **d_img, u64 *n_wor
 		seg_off[p] = ++at;
 		at += c->h_count[p];
 	}
-	u64 *d_segoff = 0, *d_head = 0, *img = 0;
-	struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ [&]() { dfree(d_segoff); dfree(d_head); } };
-	if (dmalloc(&d_segoff, P + 1) || dmalloc(&d_head, 2 * (size_t)n) || dmalloc(&img, at)) { dfree(img); return -1; }
+	DevBuf<u64> img, d_head, d_segoff;
+	if (d_segoff.alloc(P + 1) || d_head.alloc(2 * (size_t)n) || img.alloc(at)) return -1;
 	HIPCK(hipMemcpyAsync(d_segoff, seg_off.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
 	HIPCK(hipMemcpyAsync(d_head, head.data(), head.size() * 8, hipMemcpyHostToDevice, c->st));
 	yk_launch_shrink_scatter(img_view(c), P, 0, 1023, 0, img_view(c), d_segoff, img, c->st);
 	yk_launch_put_u64(d_head, d_head + n, (u32)n, img, c->st);
 	HIPCK(hipStreamSynchronize(c->st));                            /* (the two small host arrays and the offsets go away with this call) */
-	*d_img = img; *n_words = at;
+	*d_img = img.release(); *n_words = at;
 	return 0;
 }
 void yk_ctx_gate(yakamd_ctx *c, bool on) { c->gate_off = !on; }
@@ -1961,12 +1971,10 @@ int yk_ctx_load(yakamd_ctx *c, const uint32_t *caps, const uint32_t *sizes, cons
 	std::vector<u32> m(P), init(P);
 	u64 tot = 0;
 	for (int p = 0; p < P; ++p) { m[p] = sizes[p]; init[p] = kh_bits_for(caps[p]); tot += sizes[p]; }
-	u64 *d_kc = 0;
-	if (dmalloc(&d_kc, tot)) return -1;
+	DevBuf<u64> d_kc;
+	if (d_kc.alloc(tot)) return -1;
 	HIPCK(hipMemcpyAsync(d_kc, keys, tot * 8, hipMemcpyHostToDevice, c->st));
-	const int r = yk_run_replay(c, m, 0, d_kc, 0, 0, &init, true);
-	dfree(d_kc);
-	return r;
+	return yk_run_replay(c, m, 0, d_kc, 0, 0, &init, true);
 }
 
 /* ------------------------------------------------------------------------------------------

@@ -11,7 +11,6 @@
 #include <string>
 #include <mutex>
 #include <algorithm>
-#include <functional>
 #include "yk_device.h"
 #include "engine.h"
 
@@ -44,6 +43,22 @@ template <class T> static int dmalloc(T **p, size_t n)
 	return 0;
 }
 template <class T> static void dfree(T *&p) { if (p) { pool_free((void*)p); p = 0; } }
+
+/* one pool allocation owned by a scope: freed by its destructor or by reset(); release() hands the pointer to whoever frees it next */
+template <class T> class DevBuf {
+	T *p_ = 0;
+public:
+	DevBuf() = default;
+	explicit DevBuf(T *p) : p_(p) {}
+	DevBuf(DevBuf &&o) : p_(o.release()) {}
+	DevBuf &operator=(DevBuf &&o) { if (this != &o) { reset(); p_ = o.release(); } return *this; }   /* (and no copies) */
+	~DevBuf() { reset(); }
+	int alloc(size_t n) { reset(); return dmalloc(&p_, n); }
+	void reset() { dfree(p_); }
+	T *release() { T *p = p_; p_ = 0; return p; }
+	T *get() const { return p_; }
+	operator T *() const { return p_; }
+};
 
 struct yakamd_ctx {
 	int k, pre, P, n_hash, bf_shift, nb;
@@ -110,5 +125,7 @@ struct yak_ch_ext { yak_ch_t pub; yakamd_ctx *ctx; u32 magic; int n_sub; yak_ch_
 /* layout.cpp: the exact khashl slot layout (khashl.h:152-221) of `m[p]` new keys per sub-table, sorted by insertion time, on top of the table image */
 int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_seg_off, const u64 *d_rec_kc, const u64 *d_rec_t,
                   const u64 *d_lastput, const std::vector<u32> *init_bits, bool from_empty, const std::vector<u64> *rec_off = 0);
+/* layout.cpp: the new image replaces the context's -- `keys` / `used`, an arena of tot slots, sub-table p at new_off[p] with c->h_bits[p] / c->h_count[p] */
+int yk_image_commit(yakamd_ctx *c, u64 *keys, u32 *used, u64 tot, const std::vector<u64> &new_off);
 void yk_replay_counters(u32 *used, u32 *refused);            /* debug: replays done by the streaming kernels / handed back to k_replay */
 #endif

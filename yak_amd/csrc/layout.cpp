@@ -27,7 +27,8 @@ static u32 plan_cap(u32 cap, u32 cnt, u32 m, bool may_trail)
 static void legacy_replay_launch(yakamd_ctx *c, const std::vector<ReplayTask> &tasks, const ReplayTask *d_tasks, u64 *nk, u32 *nu, u32 *su, u32 *so, u64 *sp,
                                  const u64 *d_rec_kc, const u64 *d_rec_t, const u64 *d_lastput, u32 *d_ob, u32 *d_oc)
 {
-	const int P = c->P, n_active = c->phi - c->plo;
+	const int P = c->P, n_active = c->phi - c->plo;               /* few, large sub-tables (a shard of a multi-GPU job): more lanes per sub-table */
+	/* owner ranks of the placement stages in LDS: 32-bit up to lds_words slots, 16-bit up to twice that */
 	u32 cap_top = 0;
 	for (int p = 0; p < P; ++p) if (tasks[p].m) cap_top = std::max(cap_top, 1u << tasks[p].cap_max_bits);
 	u32 lds_words = std::min<u32>(cap_top, (u32)env_i64("YAKAMD_REPLAY_LDS", 16384));   /* 64 KB: two workgroups per CU (measured 18.5 ms against 20.5 with 128 KB); 0: owner ranks in global scratch */
@@ -35,6 +36,20 @@ static void legacy_replay_launch(yakamd_ctx *c, const std::vector<ReplayTask> &t
 	if (lds_words * 4 >= 96 * 1024) n_thr = 1024; else if (lds_words * 4 >= 48 * 1024) n_thr = std::max(n_thr, 512);
 	n_thr = (int)env_i64("YAKAMD_REPLAY_THREADS", n_thr);
 	yk_launch_replay(d_tasks, P, n_thr, c->d_keys, c->d_used, nk, nu, su, so, sp, d_rec_kc, d_rec_t, d_lastput, d_ob, d_oc, lds_words, c->st);
+}
+
+int yk_image_commit(yakamd_ctx *c, u64 *keys, u32 *used, u64 tot, const std::vector<u64> &new_off)
+{
+	dfree(c->d_keys); dfree(c->d_used); dfree(c->d_delta);
+	c->d_keys = keys; c->d_used = used; c->n_slots = tot;
+	c->h_off = new_off;
+	HIPCK(hipMemcpyAsync(c->d_bits, c->h_bits.data(), c->P * 4, hipMemcpyHostToDevice, c->st));
+	HIPCK(hipMemcpyAsync(c->d_off, c->h_off.data(), c->P * 8, hipMemcpyHostToDevice, c->st));
+	HIPCK(hipStreamSynchronize(c->st));
+	c->img_keys_total = 0;
+	for (int p = 0; p < c->P; ++p) c->img_keys_total += c->h_count[p];
+	c->host_valid = false;
+	return 0;
 }
 
 /* Layout replay with the large sub-tables on the streaming kernels (kernels.hip "replay2").  A sub-table whose
@@ -72,15 +87,12 @@ static int run_replay_v2(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_
 	/* trailing put-calls (device data: last put-call and the time of the last new key per sub-table) */
 	std::vector<u32> trail(P, 0);
 	std::vector<u64> lp_host(P, 0);
-	u32 *d_m = 0, *d_trail = 0; u64 *d_ro = 0, *d_lp2 = 0;
-	u64 *nk = 0, *sp = 0, *K0 = 0, *K1 = 0, *pk = 0, *spill = 0; u32 *nu = 0, *su = 0, *so = 0, *d_ob = 0, *d_oc = 0, *TAG = 0, *OCC = 0, *USED = 0, *pcnt = 0, *pr = 0, *segst = 0, *head = 0, *Fc = 0, *misc = 0;
-	ReplayTask *d_tasks = 0; R2Tab *d_tabs = 0; R2Act *d_acts = 0; R2Load *d_ld = 0; R2Pub *d_pub = 0;
-	struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ [&]() {
-		dfree(d_m); dfree(d_trail); dfree(d_ro); dfree(d_lp2); dfree(nk); dfree(sp); dfree(K0); dfree(K1); dfree(pk); dfree(spill); dfree(nu); dfree(su); dfree(so);
-		dfree(d_ob); dfree(d_oc); dfree(TAG); dfree(OCC); dfree(USED); dfree(pcnt); dfree(pr); dfree(segst); dfree(head); dfree(Fc); dfree(misc); dfree(d_tasks); dfree(d_tabs); dfree(d_acts); dfree(d_ld); dfree(d_pub);
-	} };
+	DevBuf<R2Pub> d_pub; DevBuf<R2Load> d_ld; DevBuf<R2Act> d_acts; DevBuf<R2Tab> d_tabs; DevBuf<ReplayTask> d_tasks;
+	DevBuf<u32> misc, Fc, head, segst, pr, pcnt, USED, OCC, TAG, d_oc, d_ob, so, su;
+	DevBuf<u64> spill, pk, K1, K0, sp, d_lp2, d_ro;
+	DevBuf<u32> d_trail, d_m;
 	if (d_lastput) {
-		if (dmalloc(&d_m, P) || dmalloc(&d_trail, P) || dmalloc(&d_ro, P) || dmalloc(&d_lp2, P)) return -1;
+		if (d_m.alloc(P) || d_trail.alloc(P) || d_ro.alloc(P) || d_lp2.alloc(P)) return -1;
 		HIPCK(hipMemcpyAsync(d_m, m.data(), P * 4, hipMemcpyHostToDevice, c->st));
 		HIPCK(hipMemcpyAsync(d_ro, rec_off.data(), P * 8, hipMemcpyHostToDevice, c->st));
 		yk_r2_trail(d_lastput, d_rec_t, d_ro, d_m, P, d_trail, c->st);
@@ -171,11 +183,10 @@ static int run_replay_v2(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_
 	bool inplace = only_side;
 	for (int p = 0; p < P && inplace; ++p) if (large[p] && (1ull << bitsF[p]) != std::max<u64>(32, capm[p])) inplace = false;
 	const u64 nk_lo = inplace ? tot : 0;
-	u64 *nk_al = 0; u32 *nu_al = 0, *img_u = 0;                  /* what was allocated: nk / nu below are shifted by nk_lo; img_u: the image's bitmap when a buffer becomes the image */
-	struct GuardNk { std::function<void()> f; ~GuardNk() { f(); } } guard_nk{ [&]() { dfree(nk_al); dfree(nu_al); dfree(img_u); nk = 0; nu = 0; } };
-	if ((par && dmalloc(&sp, 2 * scr_n)) || dmalloc(&nk_al, tot_ext - nk_lo) || dmalloc(&nu_al, (tot_ext - nk_lo) / 32 + 1) || dmalloc(&su, scr_n / 32 + 1) || dmalloc(&so, scr_n) ||
-	    dmalloc(&d_tasks, P) || dmalloc(&d_ob, P) || dmalloc(&d_oc, P)) return -1;
-	nk = nk_al - nk_lo; nu = nu_al - nk_lo / 32;
+	DevBuf<u32> img_u, nu_al; DevBuf<u64> nk_al;                  /* what was allocated: nk / nu below are shifted by nk_lo; img_u: the image's bitmap when a buffer becomes the image */
+	if ((par && sp.alloc(2 * scr_n)) || nk_al.alloc(tot_ext - nk_lo) || nu_al.alloc((tot_ext - nk_lo) / 32 + 1) || su.alloc(scr_n / 32 + 1) || so.alloc(scr_n) ||
+	    d_tasks.alloc(P) || d_ob.alloc(P) || d_oc.alloc(P)) return -1;
+	u64 *const nk = nk_al - nk_lo; u32 *const nu = nu_al - nk_lo / 32;
 	if (inplace) {
 		HIPCK(hipMemsetAsync(nk_al, 0xff, (tot_ext - tot) * 8, c->st));
 		HIPCK(hipMemsetAsync(nu_al, 0, ((tot_ext - tot) / 32 + 1) * 4, c->st));
@@ -204,7 +215,7 @@ static int run_replay_v2(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_
 	HIPCK(hipMemcpyAsync(ob.data(), d_ob, P * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipMemcpyAsync(oc.data(), d_oc, P * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
-	dfree(sp); dfree(su); dfree(so);
+	sp.reset(); su.reset(); so.reset();
 	/* buffers of the large sub-tables */
 	std::vector<R2Tab> tabs(P);
 	std::vector<u32> seg0(P, 0);
@@ -247,7 +258,7 @@ static int run_replay_v2(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_
 		u64 in1 = 0, in0 = 0;
 		for (int p = 0; p < P; ++p) if (large[p]) (pub[p].src ? in1 : in0) += 1ull << bitsF[p];
 		img_is1 = in1 > in0;
-		if (dmalloc(&img_u, tot / 32 + 1)) return -1;
+		if (img_u.alloc(tot / 32 + 1)) return -1;
 		for (int p = 0; p < P; ++p) {
 				if (!large[p] || sched[p].empty() || sched[p].back().kind != 1 || (pub[p].src != 0) != img_is1) continue;
 				acts[(sched[p].size() - 1) * P + p].pad0 = 1;
@@ -258,12 +269,12 @@ static int run_replay_v2(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_
 	const u32 spill_cap = (u32)std::min<u64>(1u << 28, std::max<u64>(1u << 20, tot2 / 16));   /* also the list of long runs of a doubling round */
 	u64 n_keys = 0;
 	for (int p = 0; p < P; ++p) n_keys = std::max(n_keys, rec_off[p] + m[p]);
-	if (dmalloc(&K0, tot2) || dmalloc(&K1, tot2) || dmalloc(&TAG, tot2 / 2 + 1) || dmalloc(&OCC, tot2 / 16 + (size_t)P + 64) || dmalloc(&USED, tot2 / 32 + 64) || dmalloc(&d_tabs, P) || dmalloc(&d_acts, acts.size()) || dmalloc(&d_ld, P) || dmalloc(&d_pub, P) ||
-	    dmalloc(&pk, n_keys) || dmalloc(&pr, n_keys) || dmalloc(&segst, nseg_tot + 1) || dmalloc(&head, (size_t)nseg_tot * yk_r2_head()) || dmalloc(&spill, spill_cap) || dmalloc(&Fc, 4 * (size_t)P) || dmalloc(&misc, 4)) return -1;
+	if (K0.alloc(tot2) || K1.alloc(tot2) || TAG.alloc(tot2 / 2 + 1) || OCC.alloc(tot2 / 16 + (size_t)P + 64) || USED.alloc(tot2 / 32 + 64) || d_tabs.alloc(P) || d_acts.alloc(acts.size()) || d_ld.alloc(P) || d_pub.alloc(P) ||
+	    pk.alloc(n_keys) || pr.alloc(n_keys) || segst.alloc(nseg_tot + 1) || head.alloc((size_t)nseg_tot * yk_r2_head()) || spill.alloc(spill_cap) || Fc.alloc(4 * (size_t)P) || misc.alloc(4)) return -1;
 	/* few large sub-tables (a shard): the keys of a stage are grouped by G workgroups per sub-table instead of one (YAKAMD_R2_PPART_G: tests) */
 	int ppG = (int)std::min<int64_t>(16, std::max<int64_t>(1, env_i64("YAKAMD_R2_PPART_G", n_large <= 512 ? 1024 / std::max<u32>(1, n_large) : 1)));
 	if ((size_t)P * ppG > (64u << 10)) ppG = 1;                   /* (the counters are indexed by sub-table: 4 KB per sub-table and share) */
-	if (ppG > 1 && dmalloc(&pcnt, (size_t)P * ppG * 1024)) return -1;
+	if (ppG > 1 && pcnt.alloc((size_t)P * ppG * 1024)) return -1;
 	HIPCK(hipMemcpyAsync(d_tabs, tabs.data(), P * sizeof(R2Tab), hipMemcpyHostToDevice, c->st));
 	HIPCK(hipMemcpyAsync(d_acts, acts.data(), acts.size() * sizeof(R2Act), hipMemcpyHostToDevice, c->st));
 	HIPCK(hipMemcpyAsync(d_ld, ld.data(), P * sizeof(R2Load), hipMemcpyHostToDevice, c->st));
@@ -304,9 +315,8 @@ static int run_replay_v2(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_
 		}
 		if (any_p) { yk_r2_place(d_tabs, da, P, p_lo, p_hi - p_lo, bp, K0, K1, d_rec_kc, pk, pr, segst, head, spill, d_nspill, spill_cap, d_fail, img_u, USED, pcnt, ppG, c->st); lap("place", k, bp, &tl); }
 	}
-	u64 *img_k = 0;                                               /* the new image, once it is certain */
+	DevBuf<u64> &A = img_is1 ? K1 : K0;                          /* the buffer that becomes the image (inplace) */
 	if (inplace) {
-		u64 *A = img_is1 ? K1 : K0;
 		/* the regions of the sub-tables that hold nothing: empty pattern, no bit */
 		for (int p = 0; p < P;) {
 			if (large[p]) { ++p; continue; }
@@ -320,7 +330,6 @@ static int run_replay_v2(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_
 		for (int p = 0; p < P; ++p) { pub[p].new_off = tabs[p].off; if (!pub_needed[p]) pub[p].bits = YK_NOCAP; }
 		HIPCK(hipMemcpyAsync(d_pub, pub.data(), P * sizeof(R2Pub), hipMemcpyHostToDevice, c->st));
 		yk_r2_publish(d_tabs, d_pub, P, bmaxF, K0, K1, A, img_u, c->st);   /* a table already in A only gets its bitmap */
-		img_k = A;
 	} else yk_r2_publish(d_tabs, d_pub, P, bmaxF, K0, K1, nk, nu, c->st);
 	lap("publish", n_steps, bmaxF, &tl);
 	u32 h_fail = 0;
@@ -336,20 +345,8 @@ static int run_replay_v2(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_
 		if (large[p]) { c->h_bits[p] = bitsF[p]; c->h_count[p] = cntF[p]; }
 		else { c->h_bits[p] = ob[p]; c->h_count[p] = oc[p]; }
 	}
-	dfree(c->d_keys); dfree(c->d_used); dfree(c->d_delta);
-	if (inplace) {
-		c->d_keys = img_k; c->d_used = img_u; img_u = 0;
-		if (img_k == K0) K0 = 0; else K1 = 0;                     /* the guard releases the other one */
-	} else { c->d_keys = nk_al; c->d_used = nu_al; nk_al = 0; nu_al = 0; }
-	c->n_slots = tot;
-	c->h_off = new_off;
-	HIPCK(hipMemcpyAsync(c->d_bits, c->h_bits.data(), P * 4, hipMemcpyHostToDevice, c->st));
-	HIPCK(hipMemcpyAsync(c->d_off, c->h_off.data(), P * 8, hipMemcpyHostToDevice, c->st));
-	HIPCK(hipStreamSynchronize(c->st));
-	c->img_keys_total = 0;
-	for (int p = 0; p < P; ++p) c->img_keys_total += c->h_count[p];
-	c->host_valid = false;
-	return 0;
+	if (inplace) return yk_image_commit(c, A.release(), img_u.release(), tot, new_off);
+	return yk_image_commit(c, nk_al.release(), nu_al.release(), tot, new_off);
 }
 
 int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_seg_off, const u64 *d_rec_kc, const u64 *d_rec_t,
@@ -379,27 +376,14 @@ int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_seg_off
 		tot += std::max<u64>(32, capm);
 	}
 	(void)d_seg_off;
-	u64 *nk = 0, *sp = 0; u32 *nu = 0, *su = 0, *so = 0, *d_ob = 0, *d_oc = 0;
-	ReplayTask *d_tasks = 0;
-	struct Guard { std::function<void()> f; ~Guard() { f(); } } guard{ [&]() {   /* nk / nu are handed to the context on success (set to 0 there) */
-		dfree(su); dfree(so); dfree(sp); dfree(d_tasks); dfree(d_ob); dfree(d_oc); dfree(nk); dfree(nu);
-	} };
+	DevBuf<u32> nu; DevBuf<u64> nk; DevBuf<u32> d_oc, d_ob; DevBuf<ReplayTask> d_tasks; DevBuf<u64> sp; DevBuf<u32> so, su;   /* nk / nu are handed to the context on success */
 	const bool par = env_i64("YAKAMD_PAR_REPLAY", 1) != 0;
-	if ((par && dmalloc(&sp, 2 * tot)) || dmalloc(&nk, tot) || dmalloc(&nu, tot / 32) || dmalloc(&su, tot / 32) || dmalloc(&so, tot) ||
-	    dmalloc(&d_tasks, P) || dmalloc(&d_ob, P) || dmalloc(&d_oc, P)) return -1;
+	if ((par && sp.alloc(2 * tot)) || nk.alloc(tot) || nu.alloc(tot / 32) || su.alloc(tot / 32) || so.alloc(tot) ||
+	    d_tasks.alloc(P) || d_ob.alloc(P) || d_oc.alloc(P)) return -1;
 	HIPCK(hipMemsetAsync(nk, 0xff, tot * 8, c->st));
 	HIPCK(hipMemsetAsync(nu, 0, tot / 8, c->st));
 	HIPCK(hipMemcpyAsync(d_tasks, tasks.data(), P * sizeof(ReplayTask), hipMemcpyHostToDevice, c->st));
-	/* few, large sub-tables (a shard of a multi-GPU job): more lanes per sub-table */
-	const int n_active = c->phi - c->plo;
-	/* owner ranks of the placement stages in LDS: 32-bit up to lds_words slots, 16-bit up to twice that */
-	u32 cap_top = 0;
-	for (int p = 0; p < P; ++p) if (tasks[p].m) cap_top = std::max(cap_top, 1u << tasks[p].cap_max_bits);
-	u32 lds_words = std::min<u32>(cap_top, (u32)env_i64("YAKAMD_REPLAY_LDS", 16384));   /* 64 KB: two workgroups per CU (measured 18.5 ms against 20.5 with 128 KB); 0: owner ranks in global scratch */
-	int n_thr = n_active <= 256 ? 1024 : n_active <= 512 ? 512 : 256;
-	if (lds_words * 4 >= 96 * 1024) n_thr = 1024; else if (lds_words * 4 >= 48 * 1024) n_thr = std::max(n_thr, 512);
-	n_thr = (int)env_i64("YAKAMD_REPLAY_THREADS", n_thr);
-	yk_launch_replay(d_tasks, P, n_thr, c->d_keys, c->d_used, nk, nu, su, so, sp, d_rec_kc, d_rec_t, d_lastput, d_ob, d_oc, lds_words, c->st);
+	legacy_replay_launch(c, tasks, d_tasks, nk, nu, su, so, sp, d_rec_kc, d_rec_t, d_lastput, d_ob, d_oc);
 	if (env_i64("YAKAMD_DBG", 0) & 32) {
 		HIPCK(hipStreamSynchronize(c->st));
 		u64 pr[8]; yk_replay_prof(pr);
@@ -410,17 +394,7 @@ int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_seg_off
 	HIPCK(hipMemcpyAsync(c->h_bits.data(), d_ob, P * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipMemcpyAsync(c->h_count.data(), d_oc, P * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
-	dfree(c->d_keys); dfree(c->d_used); dfree(c->d_delta);
-	c->d_keys = nk; c->d_used = nu; c->n_slots = tot;
-	nk = 0; nu = 0;
-	c->h_off = new_off;
-	HIPCK(hipMemcpyAsync(c->d_bits, c->h_bits.data(), P * 4, hipMemcpyHostToDevice, c->st));
-	HIPCK(hipMemcpyAsync(c->d_off, c->h_off.data(), P * 8, hipMemcpyHostToDevice, c->st));
-	HIPCK(hipStreamSynchronize(c->st));
-	c->img_keys_total = 0;
-	for (int p = 0; p < P; ++p) c->img_keys_total += c->h_count[p];
-	c->host_valid = false;
-	return 0;
+	return yk_image_commit(c, nk.release(), nu.release(), tot, new_off);
 }
 
 void yk_replay_counters(u32 *used, u32 *refused) { *used = g_r2_used; *refused = g_r2_refused; }
