@@ -179,6 +179,31 @@ typedef struct {
 void yakamd_teopt_init(yakamd_teopt_t *opt);
 int yakamd_trioeval(const yakamd_teopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn);
 
+/* `yak inspect` (reference inspect.c) on the device.  yakamd_inspect_dev() is its join: every stored key of table A adds one to
+ * d_joint[c0 * 1024 + c1] (uint64 bins, accumulated: zero them first), c0 = key & 1023 its count in A, c1 = max(0, yak_ch_get(b, h)) its count in
+ * b (0 when b is NULL: one table).  The keys are those of A's sub-tables [sub_lo, sub_hi) in dump order, d_sub_off[j] = keys before sub-table
+ * sub_lo + j (sub_hi - sub_lo + 1 device words, the last = n_keys); headers != 0: d_keys is the .yak body itself, each sub-table's 8-byte
+ * {capacity, size} word in front of its keys.  The probe hash h is (key >> 10) << pre_a | i for a key of sub-table i -- the k-mer's hash (all of
+ * it at k < 32; at k >= 32 its bits [0, pre + 54), so the two tables must have the same pre there) --, or with ref_probe the stored key itself,
+ * as inspect.c:58 passes it.  b may be sharded over prefix ranges of one device; not a table spread over several devices, not inside an open
+ * pass; its k must be k.  `stream` = a hipStream_t or 0; returns when the device is done. */
+int yakamd_inspect_dev(yak_ch_t *b, int k, int pre_a, int sub_lo, int sub_hi, const void *d_keys, int64_t n_keys,
+                       const uint64_t *d_sub_off, int headers, int ref_probe, uint64_t *d_joint, void *stream);
+/* `yak inspect` as a library call: the HS lines of in1 (fn2 NULL), or its SN and QV lines against fn2, printed as inspect.c prints them to
+ * out_fn (NULL = stdout); with ref_probe and two tables byte-equal to the reference's.  in1 is streamed in batches of about batch_keys keys.
+ * 0 on success, -1 after a message on stderr (and nothing written) */
+typedef struct {
+	int max_cnt;              /* -m, 20: the SN columns and QV lines, in [0, 1023] */
+	int ref_probe;            /* -R, 0: probe in2 with the stored key as inspect.c:58 does (finds few of the shared k-mers) */
+	int n_threads;            /* -t, 4: yak_ch_hist's threads; in1 is read ahead on a second thread */
+	int64_t batch_keys;       /* keys of in1 per device batch, 1 << 24 */
+} yakamd_inopt_t;
+void yakamd_inopt_init(yakamd_inopt_t *opt);
+int yakamd_inspect(const yakamd_inopt_t *opt, const char *fn1, const char *fn2, const char *out_fn);
+/* the same join on two resident tables (b NULL: one), such as yak_count()'s: joint = 1024 x 1024 int64 host bins, overwritten.  Either table
+ * may be sharded over prefix ranges of one device; both on the same device.  0, or -1 after a message */
+int yakamd_inspect_tables(const yak_ch_t *a, const yak_ch_t *b, int ref_probe, int64_t *joint);
+
 /* Host-only test hook (no device needed): the base image yak_count() hands to the device for a
  * FASTA/FASTQ(.gz) file -- sequences of >= min_len bases, each followed by '\n'.  use_fast_path = 0
  * forces the general record reader for every record.  *out is malloc()ed; returns its length or -1. */

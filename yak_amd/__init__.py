@@ -36,6 +36,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_host_alloc", "yakamd_host_free", "yakamd_device_sync", "yakamd_mem_info", "yakamd_last_sweeps", "yakamd_pool_report",
     "yakamd_triobin_lookup_dev", "yakamd_triobin_reduce_dev", "yakamd_tbopt_init", "yakamd_triobin",
     "yakamd_trioeval_reduce_dev", "yakamd_teopt_init", "yakamd_trioeval",
+    "yakamd_inspect_dev", "yakamd_inopt_init", "yakamd_inspect", "yakamd_inspect_tables",
 ]
 
 
@@ -66,6 +67,10 @@ class TboptT(C.Structure):                     # yakamd_tbopt_t, include/yak_amd
 class TeoptT(C.Structure):                     # yakamd_teopt_t, include/yak_amd.h
     _fields_ = [("min_n", C.c_int32), ("print_err", C.c_int32), ("print_frag", C.c_int32), ("n_threads", C.c_int32),
                 ("chunk_size", C.c_int64)]
+
+
+class InoptT(C.Structure):                     # yakamd_inopt_t, include/yak_amd.h
+    _fields_ = [("max_cnt", C.c_int32), ("ref_probe", C.c_int32), ("n_threads", C.c_int32), ("batch_keys", C.c_int64)]
 
 
 class StreakT(C.Structure):                    # yakamd_streak_t, include/yak_amd.h
@@ -217,6 +222,12 @@ def lib():
                                              P(C.c_void_p), P(C.c_int64), C.c_void_p]
     L.yakamd_teopt_init.restype = None; L.yakamd_teopt_init.argtypes = [P(TeoptT)]
     L.yakamd_trioeval.restype = C.c_int; L.yakamd_trioeval.argtypes = [P(TeoptT), P(ChT), C.c_char_p, C.c_char_p]
+    L.yakamd_inspect_dev.restype = C.c_int
+    L.yakamd_inspect_dev.argtypes = [P(ChT), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int,
+                                     C.c_void_p, C.c_void_p]
+    L.yakamd_inopt_init.restype = None; L.yakamd_inopt_init.argtypes = [P(InoptT)]
+    L.yakamd_inspect.restype = C.c_int; L.yakamd_inspect.argtypes = [P(InoptT), C.c_char_p, C.c_char_p, C.c_char_p]
+    L.yakamd_inspect_tables.restype = C.c_int; L.yakamd_inspect_tables.argtypes = [P(ChT), P(ChT), C.c_int, P(C.c_int64)]
     _lib = L
     return L
 
@@ -460,6 +471,34 @@ def trioeval(pat_yak, mat_yak, seq_fn, min_cnt=2, mid_cnt=5, min_n=2, print_err=
             return open(out, "rb").read()
     finally:
         L.yak_ch_destroy(h)
+
+
+def inspect(in1, in2=None, max_cnt=20, ref_probe=False, batch_keys=None):
+    """`yak inspect` through the C ABI (yakamd_inspect): the bytes the reference's inspect.c writes to stdout (ref_probe: its probe of in2)"""
+    import tempfile
+    L = lib()
+    o = InoptT()
+    L.yakamd_inopt_init(C.byref(o))
+    o.max_cnt, o.ref_probe = max_cnt, int(bool(ref_probe))
+    if batch_keys is not None:
+        o.batch_keys = batch_keys
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "inspect.txt")
+        if L.yakamd_inspect(C.byref(o), in1.encode(), in2.encode() if in2 else None, out.encode()) != 0:
+            raise RuntimeError("yakamd_inspect failed: " + _err())
+        return open(out, "rb").read()
+
+
+def inspect_tables(a, b=None, ref_probe=False):
+    """the joint spectrum of two resident tables (``yak_ch_t *`` or Table; b None: one table) as a 1024 x 1024 int64 numpy array, row = count in a"""
+    import numpy as np
+    L = lib()
+    J = np.zeros((1024, 1024), np.int64)
+    ha = a.h if isinstance(a, Table) else a
+    hb = (b.h if isinstance(b, Table) else b) if b is not None else None
+    if L.yakamd_inspect_tables(ha, hb, int(bool(ref_probe)), J.ctypes.data_as(C.POINTER(C.c_int64))) != 0:
+        raise RuntimeError("yakamd_inspect_tables failed: " + _err())
+    return J
 
 
 def pack_bases_host(buf):

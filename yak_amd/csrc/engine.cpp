@@ -1108,6 +1108,57 @@ extern "C" int yakamd_triobin_reduce_dev(int k, const void *d_flag_u8, const uin
 	return 0;
 }
 
+/* ---- yak inspect's join (kern_inspect.inc) ---- */
+/* the engines behind a table: its own, or one per rank of a table sharded over prefix ranges */
+static int engines_of(const yak_ch_t *h, std::vector<yakamd_ctx*> *out)
+{
+	const yak_ch_ext *e = (const yak_ch_ext*)h;
+	out->clear();
+	if (!h || e->magic != EXT_MAGIC) return fail("not an engine table");
+	if (e->n_sub > 1) for (int r = 0; r < e->n_sub; ++r) out->push_back(ctx_of(e->sub[r]));
+	else out->push_back(e->ctx);
+	for (yakamd_ctx *c : *out) {
+		if (!c) return fail("not an engine table");
+		if (c->dev != (*out)[0]->dev) return fail("inspect: the table is spread over several devices (device %d and %d); count it on one", (*out)[0]->dev, c->dev);
+		if (c->in_pass) return fail("inspect during an open pass");
+	}
+	return 0;
+}
+
+extern "C" int yakamd_inspect_dev(yak_ch_t *b, int k, int pre_a, int sub_lo, int sub_hi, const void *d_keys, int64_t n_keys,
+                                  const uint64_t *d_sub_off, int headers, int ref_probe, uint64_t *d_joint, void *stream)
+{
+	if (pre_a < YAK_COUNTER_BITS || pre_a > 30) return fail("inspect: pre %d of the first table is outside [10, 30]", pre_a);
+	if (sub_lo < 0 || sub_hi < sub_lo || sub_hi > 1 << pre_a) return fail("inspect: sub-tables [%d, %d) of %d", sub_lo, sub_hi, 1 << pre_a);
+	if (n_keys < 0 || (n_keys > 0 && sub_hi == sub_lo)) return fail("inspect: %ld keys in no sub-table", (long)n_keys);
+	if (k < 1 || k >= 64) return fail("inspect: k must be in [1, 63]");
+	if (((uintptr_t)d_keys & 7) != 0) return fail("inspect: the keys must be 8-byte aligned");
+	const hipStream_t st = (hipStream_t)stream;
+	if (!b) {                                                  /* one table: c1 = 0 */
+		if (yakamd_device_count() < 1) return fail("no gfx950 GPU visible: the join has no CPU fallback");
+		ImgView none;
+		memset(&none, 0, sizeof(none));
+		if (yk_launch_inspect((const u64*)d_keys, (const u64*)d_sub_off, (u64)n_keys, sub_hi - sub_lo, sub_lo, headers != 0, pre_a, 0, none, 0, 0,
+		                      0, (u64*)d_joint, st)) return fail("inspect: the join did not launch");
+		HIPCK(hipStreamSynchronize(st));
+		return 0;
+	}
+	std::vector<yakamd_ctx*> eng;
+	if (engines_of(b, &eng)) return -1;
+	if (b->k != k) return fail("inspect: the tables have different k (%d and %d)", k, b->k);
+	if (!ref_probe && k >= 32 && b->pre != pre_a)
+		return fail("inspect: at k >= 32 a stored key holds hash bits [pre, pre + 54): the tables must have the same pre (%d and %d)", pre_a, b->pre);
+	HIPCK(hipSetDevice(eng[0]->dev));
+	for (yakamd_ctx *c : eng)                                  /* every key is probed by the one rank that owns its sub-table of B */
+		if (yk_launch_inspect((const u64*)d_keys, (const u64*)d_sub_off, (u64)n_keys, sub_hi - sub_lo, sub_lo, headers != 0, pre_a, 1, img_view(c),
+		                      c->plo, c->phi, ref_probe != 0, (u64*)d_joint, st)) return fail("inspect: the join did not launch");
+	HIPCK(hipStreamSynchronize(st));
+	return 0;
+}
+
+/* the .yak body of a table's own sub-tables (one rank of a sharded table, or all), for yakamd_inspect_tables */
+int yk_inspect_engines(const yak_ch_t *h, std::vector<yakamd_ctx*> *eng) { return engines_of(h, eng); }
+
 /* trioeval's scratch (kern_trioeval.inc): kept from one call to the next, grown when a call needs more, on the device of the last call */
 namespace {
 struct TeBuf {

@@ -1,6 +1,7 @@
 /* engine.h -- internal interface between pool.cpp, engine.cpp and the yak.h surface (yak_api.cpp, yak_reader.cpp, yak_multi.cpp) */
 #ifndef YK_ENGINE_H
 #define YK_ENGINE_H
+#include <vector>
 #include "../../include/yak_amd.h"
 #include "yk_device.h"
 
@@ -39,6 +40,7 @@ int  yk_ctx_load(yakamd_ctx *c, const uint32_t *caps, const uint32_t *sizes, con
 int  yk_ctx_sync_host(yakamd_ctx *c, yak_ch_t *h);
 u64  yk_ctx_list_time(yakamd_ctx *c, u64 n);
 int  yk_ctx_device(yakamd_ctx *c);
+int  yk_inspect_engines(const yak_ch_t *h, std::vector<yakamd_ctx*> *eng);   /* the engines of a table (one per rank of a sharded one), all on one device and out of a pass */
 size_t yk_pool_cached_bytes(void);
 size_t yk_pool_held_bytes(int dev);
 void yk_pool_report(const char *what);

@@ -641,4 +641,34 @@ void yk_launch_fill_u64(u64 *p, u64 v, u64 n, hipStream_t st)
 	if (n) hipLaunchKernelGGL(k_fill_u64, dim3(grid_for(n)), dim3(256), 0, st, p, v, n);
 }
 
+/* yak inspect's join (kern_inspect.inc): one persistent grid over the n keys, as many workgroups as the LDS lets share a CU (the 64 KiB corner
+ * histogram, B's sub-table directory and A's offsets: 80 KiB at pre 10, two per CU), never fewer than n / 2^31 (a corner bin is a u32) */
+int yk_launch_inspect(const u64 *keys, const u64 *off, u64 n, int n_sub, int sub_lo, int hdr, int pre_a, int has_b, ImgView img, int blo, int bhi,
+                      int ref, u64 *J, hipStream_t st)
+{
+	if (n == 0) return 0;
+	InArgs a;
+	a.keys = keys; a.off = off; a.n = n; a.J = J; a.n_sub = n_sub; a.sub_lo = sub_lo; a.hdr = hdr; a.pre_a = pre_a;
+	a.blo = blo; a.bhi = bhi; a.ref = ref;
+	a.tab_b = has_b && img.pre <= 12;
+	a.tab_a = n_sub <= 4096;
+	const size_t lds = IN_CORNER_BYTES + (a.tab_b ? (size_t)8 << img.pre : 0) + (a.tab_a ? (size_t)8 * n_sub : 0);
+	int dev = 0, n_cu = 0;
+	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
+	const u64 per_cu = std::max<u64>(1, std::min<u64>(4, (u64)(160 * 1024) / lds));
+	const u64 steps = (n + IN_THREADS * IN_U - 1) / (IN_THREADS * IN_U);
+	const u64 grid = std::max<u64>(std::min<u64>((u64)n_cu * per_cu, steps), (n >> 31) + 1);
+	const bool lng = img.k >= 32;
+	static DevOnce attr;
+	if (!attr) {
+		for (const void *f : { (const void*)k_inspect<false, false>, (const void*)k_inspect<true, false>, (const void*)k_inspect<true, true> })
+			hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+		attr = true;
+	}
+	if (!has_b) hipLaunchKernelGGL((k_inspect<false, false>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
+	else if (lng) hipLaunchKernelGGL((k_inspect<true, true>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
+	else hipLaunchKernelGGL((k_inspect<true, false>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
+	return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 } /* extern "C" */

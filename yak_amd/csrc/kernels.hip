@@ -9,6 +9,7 @@
  *   sel k_select_*       keys that enter the table, grouped by sub-table
  *   srt k_seg_sort_pass  per sub-table LSD radix sort by insertion time
  *   K5  k_replay         exact khashl layout: staged FCFS placement + in-place doubling [khashl.h:152-221]
+ * `yak inspect` (inspect.c:47-62): k_inspect joins the stored keys of one table with another table's image into a 1024 x 1024 histogram.
  * All work is 64-bit integer arithmetic; the bound is HBM / L2-atomic traffic, never MFMA.
  *
  * One translation unit, cut by stage into the kern_*.inc files included at the end of this file (device helpers and __device__ globals are
@@ -95,4 +96,5 @@ __device__ const unsigned char d_nt4[256] = {
 #include "kern_replay2.inc"
 #include "kern_count.inc"
 #include "kern_pass2.inc"
+#include "kern_inspect.inc"
 #include "kern_launch.inc"

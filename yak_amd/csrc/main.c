@@ -2,12 +2,14 @@
  * main.c -- `yak-amd`: the repo's own small command-line driver of libyak_amd.so, plain C against
  * include/yak.h (and include/yak_amd.h for triobin and -X).  It is a test and benchmark vehicle (tests/, bench.py's e2e_cli figure), not a
  * re-creation of the reference's CLI: that one runs unmodified on the library (INTEGRATION.md section 2,
- * oracle/_ref/yak_on_amd).  Four sub-commands drive the call sequences the library serves:
+ * oracle/_ref/yak_on_amd).  Five sub-commands drive the call sequences the library serves:
  *     count    the counting protocol behind reference main.c:53-61 (one pass, or two passes + shrink
  *              when a bloom filter is asked for)
  *     qv       the lookup protocol behind reference main.c:163-215 (restore, histogram, yak_qv, solve)
  *     triobin  the read binning of reference triobin.c:153-197 (two TRIOBIN loads, yakamd_triobin)
  *     trioeval the phasing evaluation of reference trioeval.c:153-212 (two TRIOBIN loads, yakamd_trioeval)
+ *     inspect  the table statistics of reference inspect.c (yakamd_inspect: the k-mer histogram of one table, or the joint
+ *              spectrum of two; -R probes the second table as inspect.c:58 does)
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
  */
@@ -16,7 +18,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "yak.h"
-#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin and yakamd_trioeval */
+#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval and yakamd_inspect */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
 enum arg_kind { ARG_FLAG, ARG_I32, ARG_SIZE, ARG_I64SIZE, ARG_F64, ARG_TEXT };
@@ -209,6 +211,23 @@ static int cmd_trioeval(int argc, char **argv)
 	return rc;
 }
 
+/* ---- inspect ---- */
+static int cmd_inspect(int argc, char **argv)
+{
+	yakamd_inopt_t o;
+	yakamd_inopt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'm', ARG_I32, &o.max_cnt, "max count (effective with in2.yak)" },
+		{ 'R', ARG_FLAG, &o.ref_probe, "probe in2.yak with the stored key, as the reference's inspect.c:58 does" },
+		{ 't', ARG_I32, &o.n_threads, "host threads" },
+		{ 'B', ARG_I64SIZE, &o.batch_keys, "keys of in1.yak per device batch" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first >= argc || argc - first > 2) { arg_help("inspect [options] <in1.yak> [in2.yak]", defs, nd); return 1; }
+	return yakamd_inspect(&o, argv[first], first + 1 < argc ? argv[first + 1] : 0, 0) == 0 ? 0 : 2;
+}
+
 int main(int argc, char **argv)
 {
 	static const struct { const char *name; int (*run)(int, char**); const char *what; } cmds[] = {
@@ -216,6 +235,7 @@ int main(int argc, char **argv)
 		{ "qv", cmd_qv, "look the k-mers of sequences up in a .yak table" },
 		{ "triobin", cmd_triobin, "bin reads by the k-mers of the two parents' .yak tables" },
 		{ "trioeval", cmd_trioeval, "evaluate the phasing of an assembly by the k-mers of the two parents' .yak tables" },
+		{ "inspect", cmd_inspect, "the k-mer histogram of a .yak table, or the joint spectrum of two" },
 	};
 	/* -X name=value (anywhere on the line, any number of times): a test switch of the library (yakamd_test_set) -- tests force code paths with it */
 	for (int i = 1; i + 1 < argc; ) {

@@ -1,0 +1,275 @@
+/*
+ * yak_inspect.cpp -- `yak inspect` (reference inspect.c) on the device.  The stored keys of in1 are streamed to the device in batches and
+ * joined there with in2's table image (k_inspect, yakamd_inspect_dev) into the 1024 x 1024 histogram J[c0][c1] of inspect.c:56-60; the
+ * lines are printed from J copied back.  yakamd_inspect_tables() runs the same join on two resident tables.
+ */
+#include "yak_host.h"
+#include "yak_amd.h"
+
+namespace {
+
+const int NC = YAK_N_COUNTS;
+
+/* a device buffer kept from one batch to the next, grown when a batch needs more */
+struct DevBuf {
+	void *p = 0;
+	size_t cap = 0;
+	bool fit(size_t n) { if (n <= cap) return true; yakamd_dev_free(p); cap = n + n / 8; p = yakamd_dev_alloc(cap); if (!p) cap = 0; return p != 0; }
+	~DevBuf() { yakamd_dev_free(p); }
+};
+
+struct YakHead { int k, pre; };
+
+/* the 16-byte header of a .yak file (htab.c:378-380); false after a message */
+bool read_head(FILE *fp, const char *fn, YakHead *h)
+{
+	char magic[4];
+	uint32_t t[3];
+	if (fread(magic, 1, 4, fp) != 4 || fread(t, 4, 3, fp) != 3) { yk_set_error("inspect: '%s': truncated header", fn); return false; }
+	if (memcmp(magic, YAK_MAGIC, 4) != 0) { yk_set_error("inspect: '%s': wrong file magic", fn); return false; }
+	if (t[2] != YAK_COUNTER_BITS) { yk_set_error("inspect: '%s': saved counter bits %u, not %d", fn, t[2], YAK_COUNTER_BITS); return false; }
+	if (t[0] < 1 || t[0] > 63 || t[1] < YAK_COUNTER_BITS || t[1] > 30) { yk_set_error("inspect: '%s': k %u / pre %u out of range", fn, t[0], t[1]); return false; }
+	h->k = (int)t[0]; h->pre = (int)t[1];
+	return true;
+}
+
+/* one batch of in1: the keys of sub-tables [lo, lo + off.size() - 1) in file order, off[j] = keys before sub-table lo + j.  A sub-table larger
+ * than the room left is split: the batch ends with its first part and the next one starts with the rest, under the same index */
+struct Batch {
+	std::vector<uint64_t> keys, off;
+	int lo = 0;
+	void clear() { keys.clear(); off.clear(); }
+	int n_sub() const { return (int)off.size() - 1; }
+};
+
+/* the body of a .yak file, read sub-table by sub-table (inspect.c:47-62) */
+struct BodyReader {
+	FILE *fp = 0;
+	const char *fn = 0;
+	int P = 0, cur = 0;                  /* next sub-table */
+	uint64_t rest = 0;                   /* keys of sub-table cur still to read */
+	bool in_sub = false;                 /* its header was read */
+	bool bad = false;
+	bool done() const { return cur >= P; }
+	/* the next batch of about `cap` keys; false on a short read (after a message) */
+	bool next(int64_t cap, Batch *b)
+	{
+		b->clear();
+		b->lo = cur;
+		b->off.push_back(0);
+		while (cur < P) {
+			if (!in_sub) {
+				uint32_t t[2];
+				if (fread(t, 4, 2, fp) != 2) return fail();
+				rest = t[1]; in_sub = true;
+			}
+			const uint64_t room = (uint64_t)cap - b->keys.size(), take = rest < room ? rest : room;
+			if (take) {
+				const size_t at = b->keys.size();
+				b->keys.resize(at + take);
+				if (fread(b->keys.data() + at, 8, take, fp) != take) return fail();
+				rest -= take;
+			}
+			b->off.push_back(b->keys.size());
+			if (rest) break;                                      /* split: the rest of sub-table cur opens the next batch */
+			in_sub = false; ++cur;
+			if ((int64_t)b->keys.size() >= cap) break;
+		}
+		return true;
+	}
+	bool fail() { yk_set_error("inspect: '%s': truncated at sub-table %d", fn, cur); bad = true; return false; }
+};
+
+/* one batch on the device and joined into d_joint */
+bool join_batch(const Batch &b, yak_ch_t *ch, int k, int pre, int ref_probe, DevBuf &d_keys, DevBuf &d_off, uint64_t *d_joint)
+{
+	if (b.keys.empty()) return true;
+	const size_t nk = b.keys.size(), no = b.off.size();
+	return d_keys.fit(nk * 8) && d_off.fit(no * 8) && yakamd_memcpy_h2d(d_keys.p, b.keys.data(), nk * 8) == 0
+	       && yakamd_memcpy_h2d(d_off.p, b.off.data(), no * 8) == 0
+	       && yakamd_inspect_dev(ch, k, pre, b.lo, b.lo + b.n_sub(), d_keys.p, (int64_t)nk, (const uint64_t*)d_off.p, 0, ref_probe, d_joint, 0) == 0;
+}
+
+/* the lines of inspect.c:64-101 from J (row c0), hist = yak_ch_hist of in2 (two tables) */
+std::string format(const std::vector<int64_t> &J, const int64_t *hist, bool two, int max_cnt, int kmer)
+{
+	std::string out;
+	char buf[64];
+	std::vector<int64_t> tot(NC, 0);
+	for (int i = 0; i < NC; ++i) { int64_t s = 0; for (int j = 0; j < NC; ++j) s += J[(size_t)i * NC + j]; tot[i] = s; }
+	if (two) {
+		const double fpr = 0.00004;
+		int64_t acc_tot = 0, acc_cnt[NC];
+		std::vector<int64_t> acc(J);
+		for (int i = 0; i < NC; ++i) acc_cnt[i] = 0;
+		for (int j = NC - 2; j >= 1; --j)
+			for (int i = 0; i < NC; ++i) acc[(size_t)i * NC + j] += acc[(size_t)i * NC + (j + 1)];
+		for (int i = NC - 1; i >= 0; --i) {
+			acc_tot += tot[i];
+			if (acc_tot == 0) continue;
+			if (tot[i] == 0) continue;
+			out.append(buf, (size_t)snprintf(buf, sizeof buf, "SN\t%d\t%ld\t%ld", i, (long)tot[i], (long)hist[i]));
+			for (int j = 1; j <= max_cnt; ++j) {
+				acc_cnt[j] += acc[(size_t)i * NC + j];
+				out.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%.4f", (double)acc_cnt[j] / acc_tot));
+			}
+			out += '\n';
+		}
+		acc = J;
+		for (int i = NC - 2; i >= 0; --i)
+			for (int j = 0; j < NC; ++j) acc[(size_t)i * NC + j] += acc[(size_t)(i + 1) * NC + j];
+		yak_qstat_t *qs = (yak_qstat_t*)calloc(1, sizeof(yak_qstat_t));
+		for (int i = max_cnt; i >= 1; --i) {
+			if (tot[i] == 0) continue;
+			yak_qv_solve(hist, &acc[(size_t)i * NC], kmer, fpr, qs);
+			out.append(buf, (size_t)snprintf(buf, sizeof buf, "QV\t%d\t%ld\t%ld\t%.3f\t%.3f\n", i, (long)qs->tot, (long)acc[(size_t)i * NC], qs->qv_raw, qs->qv));
+		}
+		free(qs);
+	} else {
+		int64_t acc_tot = 0;
+		for (int i = NC - 1; i >= 0; --i) {
+			acc_tot += tot[i];
+			if (acc_tot == 0) continue;
+			out.append(buf, (size_t)snprintf(buf, sizeof buf, "HS\t%d\t%ld\t%ld\t%ld\n", i, (long)hist[i], (long)tot[i], (long)acc_tot));
+		}
+	}
+	return out;
+}
+
+}   // namespace
+
+void yakamd_inopt_init(yakamd_inopt_t *opt)
+{
+	memset(opt, 0, sizeof(yakamd_inopt_t));
+	opt->max_cnt = 20;                                          /* inspect.c:11 */
+	opt->ref_probe = 0;
+	opt->n_threads = 4;
+	opt->batch_keys = (int64_t)1 << 24;
+}
+
+/* reference inspect.c:8-105.  The checks of both headers come before any device call; the output is written only when everything succeeded */
+int yakamd_inspect(const yakamd_inopt_t *opt, const char *fn1, const char *fn2, const char *out_fn)
+{
+	if (opt->max_cnt < 0 || opt->max_cnt > NC - 1) { yk_set_error("inspect: -m %d is outside [0, %d]", opt->max_cnt, NC - 1); return -1; }
+	std::vector<char> fbuf((size_t)1 << 22);                    /* (outlives the stream) */
+	FILE *fp = fopen(fn1, "rb");
+	if (!fp) { yk_set_error("inspect: cannot open '%s'", fn1); return -1; }
+	struct Closer { FILE *f; ~Closer() { fclose(f); } } fp_close{ fp };
+	setvbuf(fp, fbuf.data(), _IOFBF, fbuf.size());
+	YakHead h1, h2;
+	if (!read_head(fp, fn1, &h1)) return -1;
+	if (fn2) {
+		FILE *f2 = fopen(fn2, "rb");
+		if (!f2) { yk_set_error("inspect: cannot open '%s'", fn2); return -1; }
+		const bool ok = read_head(f2, fn2, &h2);
+		fclose(f2);
+		if (!ok) return -1;
+		if (h1.k != h2.k) { yk_set_error("inspect: the tables have different k (%d and %d)", h1.k, h2.k); return -1; }
+		if (!opt->ref_probe && h1.k >= 32 && h1.pre != h2.pre) {
+			yk_set_error("inspect: at k >= 32 a stored key holds hash bits [pre, pre + 54): the tables must have the same pre (%d and %d; -R probes as the reference does)", h1.pre, h2.pre);
+			return -1;
+		}
+	}
+	if (yakamd_device_count() < 1) { yk_set_error("inspect: no gfx950 GPU visible: inspect has no CPU path"); return -1; }
+	const double t0 = yk_realtime();
+	int64_t hist[NC];
+	memset(hist, 0, sizeof hist);
+	yak_ch_t *ch = 0;
+	if (fn2) {
+		ch = yak_ch_restore(fn2);
+		if (!ch) { yk_set_error("inspect: cannot load '%s': %s", fn2, yakamd_last_error()); return -1; }
+		yak_ch_hist(ch, hist, opt->n_threads);
+	}
+	const double t1 = yk_realtime();
+	uint64_t *d_joint = (uint64_t*)yakamd_dev_alloc((size_t)NC * NC * 8);
+	std::vector<int64_t> J((size_t)NC * NC, 0);
+	bool ok = d_joint && yakamd_memcpy_h2d(d_joint, J.data(), J.size() * 8) == 0;
+	BodyReader rd;
+	rd.fp = fp; rd.fn = fn1; rd.P = 1 << h1.pre;
+	const int64_t cap = opt->batch_keys > 0 ? opt->batch_keys : 1;
+	Batch cur, nxt;
+	DevBuf d_keys, d_off;
+	double t_read = 0, t_join = 0;
+	{
+		const double a = yk_realtime();
+		ok = ok && rd.next(cap, &cur);
+		t_read += yk_realtime() - a;
+	}
+	while (ok) {
+		const bool more = !rd.done();
+		bool rok = true;
+		double t_rd = 0;
+		std::thread reader;
+		if (more) reader = std::thread([&]() { const double a = yk_realtime(); rok = rd.next(cap, &nxt); t_rd = yk_realtime() - a; });
+		const double a = yk_realtime();
+		ok = join_batch(cur, ch, h1.k, h1.pre, opt->ref_probe, d_keys, d_off, d_joint);
+		t_join += yk_realtime() - a;
+		if (more) reader.join();
+		t_read += t_rd;
+		if (!ok) { fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error()); break; }
+		if (!more) break;
+		if (!rok) { ok = false; break; }
+		std::swap(cur, nxt);
+	}
+	ok = ok && yakamd_memcpy_d2h(J.data(), d_joint, J.size() * 8) == 0;
+	yakamd_dev_free(d_joint);
+	yak_ch_destroy(ch);
+	if (!ok) return -1;
+	if (yak_verbose >= 3)
+		fprintf(stderr, "[M::%s] %s: restore %.3f s, read %.3f s, join %.3f s (read overlaps the join)\n", __func__, fn2 ? "two tables" : "one table",
+		        t1 - t0, t_read, t_join);
+	const std::string text = format(J, hist, fn2 != 0, opt->max_cnt, h1.k);
+	FILE *out = out_fn ? fopen(out_fn, "wb") : stdout;
+	if (!out) { yk_set_error("inspect: cannot write '%s'", out_fn); return -1; }
+	ok = fwrite(text.data(), 1, text.size(), out) == text.size();
+	if (out_fn) { if (fclose(out) != 0) ok = false; }
+	else fflush(out);
+	return ok ? 0 : -1;
+}
+
+/* the join of yakamd_inspect on resident tables: A's keys in dump order come from its device-side .yak body (yk_ctx_dump_image_dev), one
+ * rank's sub-tables at a time, headers left in place */
+int yakamd_inspect_tables(const yak_ch_t *a, const yak_ch_t *b, int ref_probe, int64_t *joint)
+{
+	std::vector<yakamd_ctx*> ea, eb;
+	if (yk_inspect_engines(a, &ea) || (b && yk_inspect_engines(b, &eb))) { fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error()); return -1; }
+	if (b && yk_ctx_device(ea[0]) != yk_ctx_device(eb[0])) {
+		yk_set_error("inspect: the tables are on different devices (%d and %d)", yk_ctx_device(ea[0]), yk_ctx_device(eb[0]));
+		return -1;
+	}
+	if (b && a->k != b->k) { yk_set_error("inspect: the tables have different k (%d and %d)", a->k, b->k); return -1; }
+	if (b && !ref_probe && a->k >= 32 && a->pre != b->pre) {
+		yk_set_error("inspect: at k >= 32 the tables must have the same pre (%d and %d)", a->pre, b->pre);
+		return -1;
+	}
+	if (hipSetDevice(yk_ctx_device(ea[0])) != hipSuccess) { yk_set_error("inspect: cannot select device %d", yk_ctx_device(ea[0])); return -1; }
+	const yak_ch_ext *e = (const yak_ch_ext*)a;
+	const int n_rank = YK_MULTI(e) ? e->n_sub : 1;
+	uint64_t *d_joint = (uint64_t*)yakamd_dev_alloc((size_t)NC * NC * 8);
+	std::vector<int64_t> J((size_t)NC * NC, 0);
+	bool ok = d_joint && yakamd_memcpy_h2d(d_joint, J.data(), J.size() * 8) == 0;
+	DevBuf d_off;
+	for (int r = 0; ok && r < n_rank; ++r) {
+		yak_ch_t *s = YK_MULTI(e) ? e->sub[r] : (yak_ch_t*)a;
+		yakamd_ctx *c = ea[r];
+		int lo = 0, hi = 0;
+		yk_ctx_range(c, &lo, &hi);
+		std::vector<uint64_t> off(1, 0);
+		for (int p = lo; p < hi; ++p) {
+			uint32_t cap = 0, size = 0;
+			yakamd_subtable(s, p, &cap, &size);
+			off.push_back(off.back() + size);
+		}
+		if (off.back() == 0) continue;
+		u64 *d_img = 0, n_words = 0;
+		ok = yk_ctx_dump_image_dev(c, lo, hi, &d_img, &n_words) == 0 && d_off.fit(off.size() * 8)
+		     && yakamd_memcpy_h2d(d_off.p, off.data(), off.size() * 8) == 0
+		     && yakamd_inspect_dev((yak_ch_t*)b, a->k, a->pre, lo, hi, d_img, (int64_t)off.back(), (const uint64_t*)d_off.p, 1, ref_probe, d_joint, 0) == 0;
+		yk_pool_release(d_img);
+	}
+	ok = ok && yakamd_memcpy_d2h(J.data(), d_joint, J.size() * 8) == 0;
+	yakamd_dev_free(d_joint);
+	if (!ok) { fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error()); return -1; }
+	memcpy(joint, J.data(), J.size() * 8);
+	return 0;
+}

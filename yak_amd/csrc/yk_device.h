@@ -92,6 +92,10 @@ void yk_launch_lookup(const uint8_t *bases, int64_t n, int k, ImgView img, void 
 void yk_launch_qv_reduce(const unsigned short *t, const u64 *roff, const u32 *rlen, int64_t n_reads, int min_len, double min_frac,
                          u32 *tot_out, u32 *non0_out, u64 *hist, hipStream_t st);
 int yk_tb_over_seen(hipStream_t st);
+/* yak inspect's join (kern_inspect.inc): J[c0 * 1024 + c1] += 1 per key of A's sub-tables [sub_lo, sub_lo + n_sub) (keys / off / hdr as
+ * InArgs), probed in B's image on its sub-tables [blo, bhi) (has_b = 0: c1 = 0); 0, or -1 if the launch failed */
+int yk_launch_inspect(const u64 *keys, const u64 *off, u64 n, int n_sub, int sub_lo, int hdr, int pre_a, int has_b, ImgView img, int blo, int bhi,
+                      int ref, u64 *J, hipStream_t st);
 void yk_launch_tb_reduce(const uint8_t *flag, const u64 *roff, const u32 *rlen, int64_t n_reads, int k, int *cnt, hipStream_t st);
 int64_t yk_te_tiles(int64_t n);                               /* trioeval's streak reduction (kern_trioeval.inc) */
 int64_t yk_te_keep_blocks(int64_t n_runs);
