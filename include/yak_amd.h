@@ -134,7 +134,8 @@ int yakamd_qv_reduce_dev(yak_ch_t *h, const void *d_t_u16, const uint64_t *d_seq
 /* Lookup-only path of `yak triobin` (reference triobin.c:41-101, k in [1, 63]) on a table loaded with yak_ch_restore_core(...,
  * YAK_LOAD_TRIOBIN1, ...) and then (..., YAK_LOAD_TRIOBIN2, ...).  yakamd_triobin_lookup_dev(): d_flag_u8[i] = max(0, yak_ch_get())
  * of the canonical k-mer ENDING at byte i of the base image -- the flag pat class | mat class << 2 --, 0xff where no k-mer ends;
- * fails with a message (and no flag trusted) if a probed count field exceeds 15, i.e. the table was not made by those loads.  Not
+ * fails with a message (and no flag trusted) if a probed count field exceeds 15, i.e. the table was not made by those loads.  It serves
+ * the three YAK_LOAD_SEXCHR1 / 2 / 3 loads of `yak sexchr` too, whose flags (1 | 2 | 4) are at most 7.  Not
  * inside an open pass, not on a table sharded over prefix ranges.  yakamd_triobin_reduce_dev(): sequence j = bytes
  * [d_seq_off[j], d_seq_off[j] + d_seq_len[j]) of that flag array; d_cnt_i32x19[19 j ..] receives c[16] (histogram of the flags of
  * its k-mers), sc[2] (the paternal / maternal solid-run sums of triobin.c:94-100) and nk (its number of k-mers).  `stream` = a
@@ -178,6 +179,45 @@ typedef struct {
 } yakamd_teopt_t;
 void yakamd_teopt_init(yakamd_teopt_t *opt);
 int yakamd_trioeval(const yakamd_teopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn);
+
+/* `yak chkerr` (reference chkerr.c) on the device, k in [1, 63], on a YAK_LOAD_ALL table (yak_ch_restore).  yakamd_chkerr_lookup_dev() writes
+ * one byte per position of a base image as yakamd_lookup_dev() takes it: 1 where the k-mer ending there is low, i.e. the signed
+ * yak_ch_get() < min_cnt (-1 for an absent k-mer: min_cnt 0 marks the absent ones alone), 0 where it is not, 0xff where no k-mer ends.  Refused:
+ * a table sharded over prefix ranges or spread over several devices, an open pass.  Returns when the device is done.
+ * yakamd_chkerr_streaks_dev() finds the streaks in those bytes: maximal runs [st, en) of 1 with en - st > min_streak (every run when
+ * min_streak < 0), sequence j starting at d_seq_off[j] (ascending; the byte after every sequence must not be 1, as an image's '\n' is 0xff).
+ * *d_streaks receives a device buffer (free it with yakamd_dev_free; NULL when there is no streak) of *n_streaks yakamd_streak_t in sequence and
+ * position order, st and en relative to the sequence, type 1; with d_streaks NULL only the number.  `stream` = a hipStream_t or 0. */
+int yakamd_chkerr_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, int min_cnt, void *d_low_u8);
+int yakamd_chkerr_streaks_dev(int min_streak, const void *d_low_u8, const uint64_t *d_seq_off, int64_t n_seq, int64_t n_bytes,
+                              void **d_streaks, int64_t *n_streaks, void *stream);
+/* `yak chkerr` as a library call: the streaks of low k-mers of every sequence of `fn` (FASTA/FASTQ, .gz, "-" = stdin) in `ch`, printed as the
+ * reference prints them with -t1 (`name \t start \t end \t length` per streak, input order; with min_streak < 0 also its line `name \t 1-k \t 0 \t 0`
+ * ahead of each sequence's streaks) to out_fn (NULL = stdout).  0 on success, -1 after a message on stderr. */
+typedef struct {
+	int min_cnt;              /* -c, 3: a k-mer is low when its count is below this (-1 when absent) */
+	int min_streak;           /* -s, 5: a streak is printed when longer than this */
+	int n_threads;            /* -t, 8: the reference's worker threads; here the sequences are looked up on the device and a second thread reads ahead */
+	int64_t chunk_size;       /* bases per chunk, 1000000000 (chkerr.c:103) */
+} yakamd_ceopt_t;
+void yakamd_ceopt_init(yakamd_ceopt_t *opt);
+int yakamd_chkerr(const yakamd_ceopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn);
+
+/* `yak sexchr` (reference sexchr.c) on the device.  The table is the three loads yak_ch_restore_core(0, chrY, YAK_LOAD_SEXCHR1), (ch, chrX,
+ * YAK_LOAD_SEXCHR2), (ch, PAR, YAK_LOAD_SEXCHR3); yakamd_triobin_lookup_dev() looks a chunk up in it (flags 0-7).  yakamd_sexchr_reduce_dev()
+ * tallies those flags per sequence: d_cnt_u64x4[4 j ..] = n_k (positions of sequence j where a k-mer ends), n_sexchr (flag > 0), n_sex1 (flag == 1),
+ * n_sex2 (flag == 2), overwritten; sequence j is bytes [d_seq_off[j], d_seq_off[j] + d_seq_len[j]) (ascending) of the n_bytes of d_flag_u8.
+ * `stream` = a hipStream_t or 0; returns when the device is done. */
+int yakamd_sexchr_reduce_dev(const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq, int64_t n_bytes,
+                             uint64_t *d_cnt_u64x4, void *stream);
+/* `yak sexchr` as a library call: the two header lines, then one S line per sequence of fn_hap1 (hap 1), then of fn_hap2 (hap 2), in input order,
+ * byte-equal to the reference's -t1 output, to out_fn (NULL = stdout).  0 on success, -1 after a message on stderr. */
+typedef struct {
+	int n_threads;            /* -t, 8: as yakamd_ceopt_t's */
+	int64_t chunk_size;       /* -K, bases per chunk, 1000000000 (sexchr.c:13) */
+} yakamd_scopt_t;
+void yakamd_scopt_init(yakamd_scopt_t *opt);
+int yakamd_sexchr(const yakamd_scopt_t *opt, const yak_ch_t *ch, const char *fn_hap1, const char *fn_hap2, const char *out_fn);
 
 /* `yak inspect` (reference inspect.c) on the device.  yakamd_inspect_dev() is its join: every stored key of table A adds one to
  * d_joint[c0 * 1024 + c1] (uint64 bins, accumulated: zero them first), c0 = key & 1023 its count in A, c1 = max(0, yak_ch_get(b, h)) its count in

@@ -37,6 +37,8 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_triobin_lookup_dev", "yakamd_triobin_reduce_dev", "yakamd_tbopt_init", "yakamd_triobin",
     "yakamd_trioeval_reduce_dev", "yakamd_teopt_init", "yakamd_trioeval",
     "yakamd_inspect_dev", "yakamd_inopt_init", "yakamd_inspect", "yakamd_inspect_tables",
+    "yakamd_chkerr_lookup_dev", "yakamd_chkerr_streaks_dev", "yakamd_ceopt_init", "yakamd_chkerr",
+    "yakamd_sexchr_reduce_dev", "yakamd_scopt_init", "yakamd_sexchr",
 ]
 
 
@@ -71,6 +73,14 @@ class TeoptT(C.Structure):                     # yakamd_teopt_t, include/yak_amd
 
 class InoptT(C.Structure):                     # yakamd_inopt_t, include/yak_amd.h
     _fields_ = [("max_cnt", C.c_int32), ("ref_probe", C.c_int32), ("n_threads", C.c_int32), ("batch_keys", C.c_int64)]
+
+
+class CeoptT(C.Structure):                     # yakamd_ceopt_t, include/yak_amd.h
+    _fields_ = [("min_cnt", C.c_int32), ("min_streak", C.c_int32), ("n_threads", C.c_int32), ("chunk_size", C.c_int64)]
+
+
+class ScoptT(C.Structure):                     # yakamd_scopt_t, include/yak_amd.h
+    _fields_ = [("n_threads", C.c_int32), ("chunk_size", C.c_int64)]
 
 
 class StreakT(C.Structure):                    # yakamd_streak_t, include/yak_amd.h
@@ -228,6 +238,16 @@ def lib():
     L.yakamd_inopt_init.restype = None; L.yakamd_inopt_init.argtypes = [P(InoptT)]
     L.yakamd_inspect.restype = C.c_int; L.yakamd_inspect.argtypes = [P(InoptT), C.c_char_p, C.c_char_p, C.c_char_p]
     L.yakamd_inspect_tables.restype = C.c_int; L.yakamd_inspect_tables.argtypes = [P(ChT), P(ChT), C.c_int, P(C.c_int64)]
+    L.yakamd_chkerr_lookup_dev.restype = C.c_int
+    L.yakamd_chkerr_lookup_dev.argtypes = [P(ChT), C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
+    L.yakamd_chkerr_streaks_dev.restype = C.c_int
+    L.yakamd_chkerr_streaks_dev.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, P(C.c_void_p), P(C.c_int64), C.c_void_p]
+    L.yakamd_ceopt_init.restype = None; L.yakamd_ceopt_init.argtypes = [P(CeoptT)]
+    L.yakamd_chkerr.restype = C.c_int; L.yakamd_chkerr.argtypes = [P(CeoptT), P(ChT), C.c_char_p, C.c_char_p]
+    L.yakamd_sexchr_reduce_dev.restype = C.c_int
+    L.yakamd_sexchr_reduce_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    L.yakamd_scopt_init.restype = None; L.yakamd_scopt_init.argtypes = [P(ScoptT)]
+    L.yakamd_sexchr.restype = C.c_int; L.yakamd_sexchr.argtypes = [P(ScoptT), P(ChT), C.c_char_p, C.c_char_p, C.c_char_p]
     _lib = L
     return L
 
@@ -468,6 +488,73 @@ def trioeval(pat_yak, mat_yak, seq_fn, min_cnt=2, mid_cnt=5, min_n=2, print_err=
             out = os.path.join(d, "trioeval.txt")
             if L.yakamd_trioeval(C.byref(o), h, seq_fn.encode(), out.encode()) != 0:
                 raise RuntimeError("yakamd_trioeval failed: " + _err())
+            return open(out, "rb").read()
+    finally:
+        L.yak_ch_destroy(h)
+
+
+def chkerr(count_yak, seq, min_cnt=3, min_streak=5, chunk=None):
+    """`yak chkerr` through the C ABI (yak_ch_restore + yakamd_chkerr): the bytes the reference writes to stdout with -t1"""
+    import tempfile
+    L = lib()
+    h = L.yak_ch_restore(count_yak.encode())
+    if not h:
+        raise RuntimeError("yak_ch_restore failed: " + _err())
+    try:
+        o = CeoptT()
+        L.yakamd_ceopt_init(C.byref(o))
+        o.min_cnt, o.min_streak = min_cnt, min_streak
+        if chunk is not None:
+            o.chunk_size = chunk
+        with tempfile.TemporaryDirectory() as d:
+            out = os.path.join(d, "chkerr.txt")
+            if L.yakamd_chkerr(C.byref(o), h, seq.encode(), out.encode()) != 0:
+                raise RuntimeError("yakamd_chkerr failed: " + _err())
+            return open(out, "rb").read()
+    finally:
+        L.yak_ch_destroy(h)
+
+
+def yak_header(fn):
+    """(k, pre) of a .yak file's header"""
+    import struct
+    with open(fn, "rb") as f:
+        b = f.read(16)
+    if len(b) < 16 or b[:4] != b"YAK\x02":
+        raise ValueError("%s: not a .yak file" % fn)
+    return struct.unpack("<3I", b[4:])[:2]
+
+
+def sexchr_table(y, x, par):
+    """the table of `yak sexchr` (reference sexchr.c:116-118): flags 1 | 2 | 4 from the chrY, chrX and PAR tables, which must agree on k and pre"""
+    hdr = [yak_header(f) for f in (y, x, par)]
+    if len(set(hdr)) != 1:
+        raise ValueError("sexchr: the three tables differ in k or pre: %s" % hdr)
+    L = lib()
+    h = L.yak_ch_restore_core(None, y.encode(), 4)            # YAK_LOAD_SEXCHR1
+    if h:
+        h = L.yak_ch_restore_core(h, x.encode(), 5)           # YAK_LOAD_SEXCHR2
+    if h:
+        h = L.yak_ch_restore_core(h, par.encode(), 6)         # YAK_LOAD_SEXCHR3
+    if not h:
+        raise RuntimeError("yak_ch_restore_core (SEXCHR) failed: " + _err())
+    return h
+
+
+def sexchr(y, x, par, hap1, hap2, chunk=None):
+    """`yak sexchr` through the C ABI (three SEXCHR loads + yakamd_sexchr): the bytes the reference writes to stdout with -t1"""
+    import tempfile
+    L = lib()
+    h = sexchr_table(y, x, par)
+    try:
+        o = ScoptT()
+        L.yakamd_scopt_init(C.byref(o))
+        if chunk is not None:
+            o.chunk_size = chunk
+        with tempfile.TemporaryDirectory() as d:
+            out = os.path.join(d, "sexchr.txt")
+            if L.yakamd_sexchr(C.byref(o), h, hap1.encode(), hap2.encode(), out.encode()) != 0:
+                raise RuntimeError("yakamd_sexchr failed: " + _err())
             return open(out, "rb").read()
     finally:
         L.yak_ch_destroy(h)

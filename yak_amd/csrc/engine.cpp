@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <stdarg.h>
+#include <limits.h>
 #include <vector>
 #include <map>
 #include <string>
@@ -1176,6 +1177,54 @@ struct TeScratch {
 TeScratch g_te;
 }
 
+/* the ordered list of kept runs over bytes [0, n_bytes) of `flag` (kern_trioeval.inc): low = 0 trioeval's typed runs, with its per-record counters
+ * into cnt6 when cnt6 != 0; low = 1 chkerr's runs of low k-mers.  d_streaks: as yakamd_trioeval_reduce_dev's */
+static int te_streaks(const char *what, int low, int k, int min_n, const uint8_t *flag, const uint64_t *d_seq_off, int64_t n_seq, int64_t n_bytes,
+                      int32_t *cnt6, void **d_streaks, int64_t *n_streaks, hipStream_t st)
+{
+	std::lock_guard<std::mutex> lk(g_te.mu);
+	int dev = 0;
+	HIPCK(hipGetDevice(&dev));
+	g_te.on(dev);
+	TeScratch &s = g_te;
+	const int64_t nt = yk_te_tiles(n_bytes);
+	if (!s.tcnt.fit((size_t)nt * 8) || !s.toff.fit((size_t)(nt + 1) * 16)) return fail("%s: out of device memory", what);
+	if (!s.host) HIPCK(hipHostMalloc((void**)&s.host, 16));
+	yk_launch_te_runs(flag, n_bytes, (u32*)s.tcnt.p, 0, 0, 0, 0, st, low);
+	yk_launch_te_scan((const u32*)s.tcnt.p, nt, 2, (u64*)s.toff.p, st);
+	HIPCK(hipGetLastError());
+	HIPCK(hipMemcpyAsync(s.host, (const u64*)s.toff.p + nt, 8, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
+	const u64 n_runs = s.host[0];
+	void *list = 0;
+	s.host[1] = 0;
+	if (n_runs > 0) {                                  /* the list is sized by the runs: the number kept stays on the device until the end */
+		if (!s.st.fit(n_runs * 8) || !s.en.fit(n_runs * 8)) return fail("%s: out of device memory for %llu runs", what, (unsigned long long)n_runs);
+		const int64_t nb = yk_te_keep_blocks((int64_t)n_runs);
+		if (!s.kcnt.fit((size_t)nb * 4) || !s.koff.fit((size_t)(nb + 1) * 8)) return fail("%s: out of device memory", what);
+		if (d_streaks) { if (hipMalloc(&list, n_runs * 16) != hipSuccess) return fail("%s: out of device memory for %llu runs", what, (unsigned long long)n_runs); }
+		else if (!s.list.fit(n_runs * 16)) return fail("%s: out of device memory", what);
+		else list = s.list.p;
+		yk_launch_te_runs(flag, n_bytes, 0, (const u64*)s.toff.p, (u64*)s.st.p, (u64*)s.en.p, 1, st, low);
+		yk_launch_te_keep((const u64*)s.st.p, (const u64*)s.en.p, flag, (int64_t)n_runs, min_n, (u32*)s.kcnt.p, 0, (const u64*)d_seq_off, n_seq, 0, 0, st, low);
+		yk_launch_te_scan((const u32*)s.kcnt.p, nb, 1, (u64*)s.koff.p, st);
+		yk_launch_te_keep((const u64*)s.st.p, (const u64*)s.en.p, flag, (int64_t)n_runs, min_n, 0, (const u64*)s.koff.p, (const u64*)d_seq_off, n_seq, list, 1, st, low);
+		if (cnt6) yk_launch_te_seq(list, (const u64*)s.koff.p + nb, (int64_t)n_runs, k, (int*)cnt6, st);
+		const hipError_t e = hipGetLastError();
+		if (e == hipSuccess) (void)hipMemcpyAsync(s.host + 1, (const u64*)s.koff.p + nb, 8, hipMemcpyDeviceToHost, st);
+	}
+	const hipError_t e = hipGetLastError(), e2 = hipStreamSynchronize(st);
+	const u64 n_keep = s.host[1];
+	if (e != hipSuccess || e2 != hipSuccess) {
+		if (d_streaks) (void)hipFree(list);
+		return fail("%s: %s", what, hipGetErrorString(e != hipSuccess ? e : e2));
+	}
+	if (d_streaks && n_keep == 0) { (void)hipFree(list); list = 0; }
+	if (d_streaks) *d_streaks = list;
+	if (n_streaks) *n_streaks = (int64_t)n_keep;
+	return 0;
+}
+
 extern "C" int yakamd_trioeval_reduce_dev(int k, int min_n, const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
                                           int64_t n_bytes, int32_t *d_cnt_i32x6, void **d_streaks, int64_t *n_streaks, void *stream)
 {
@@ -1187,47 +1236,47 @@ extern "C" int yakamd_trioeval_reduce_dev(int k, int min_n, const void *d_flag_u
 	const hipStream_t st = (hipStream_t)stream;
 	if (n_seq > 0) HIPCK(hipMemsetAsync(d_cnt_i32x6, 0, (size_t)n_seq * 24, st));
 	if (n_seq == 0 || n_bytes == 0) { HIPCK(hipStreamSynchronize(st)); return 0; }
-	const uint8_t *flag = (const uint8_t*)d_flag_u8;
-	std::lock_guard<std::mutex> lk(g_te.mu);
-	int dev = 0;
-	HIPCK(hipGetDevice(&dev));
-	g_te.on(dev);
-	TeScratch &s = g_te;
-	const int64_t nt = yk_te_tiles(n_bytes);
-	if (!s.tcnt.fit((size_t)nt * 8) || !s.toff.fit((size_t)(nt + 1) * 16)) return fail("trioeval reduce: out of device memory");
-	if (!s.host) HIPCK(hipHostMalloc((void**)&s.host, 16));
-	yk_launch_te_runs(flag, n_bytes, (u32*)s.tcnt.p, 0, 0, 0, 0, st);
-	yk_launch_te_scan((const u32*)s.tcnt.p, nt, 2, (u64*)s.toff.p, st);
+	return te_streaks("trioeval reduce", 0, k, min_n, (const uint8_t*)d_flag_u8, d_seq_off, n_seq, n_bytes, d_cnt_i32x6, d_streaks, n_streaks, st);
+}
+
+/* ---- yak chkerr and yak sexchr ---- */
+extern "C" int yakamd_chkerr_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, int min_cnt, void *d_low_u8)
+{
+	yakamd_ctx *c = ctx_of(h);
+	if (lookup_sharded(h, c)) return fail("chkerr lookup: not available on a table sharded over prefix ranges");
+	if (!c) return fail("not an engine table");
+	if (c->in_pass) return fail("lookup during an open pass");
+	if (c->k < 1 || c->k >= 64) return fail("chkerr lookup: k must be in [1, 63]");
+	if (((uintptr_t)d_bases & 15) != 0) return fail("device base image must be 16-byte aligned");
+	HIPCK(hipSetDevice(c->dev));
+	yk_launch_ce_lookup((const uint8_t*)d_bases, n_bytes, c->k, img_view(c), (uint8_t*)d_low_u8, min_cnt, c->st);
 	HIPCK(hipGetLastError());
-	HIPCK(hipMemcpyAsync(s.host, (const u64*)s.toff.p + nt, 8, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(c->st));
+	return 0;
+}
+
+extern "C" int yakamd_chkerr_streaks_dev(int min_streak, const void *d_low_u8, const uint64_t *d_seq_off, int64_t n_seq, int64_t n_bytes,
+                                         void **d_streaks, int64_t *n_streaks, void *stream)
+{
+	if (d_streaks) *d_streaks = 0;
+	if (n_streaks) *n_streaks = 0;
+	if (n_seq < 0 || n_seq > (int64_t)0xfffffffe || n_bytes < 0) return fail("chkerr streaks: bad n_seq or n_bytes");
+	const hipStream_t st = (hipStream_t)stream;
+	if (n_seq == 0 || n_bytes == 0) { HIPCK(hipStreamSynchronize(st)); return 0; }
+	/* chkerr.c:63-64 prints a streak when e - s > min_streak: keep e - s >= min_streak + 1, saturated; a negative min_streak keeps every run */
+	const int min_n = min_streak < 0 ? 0 : min_streak >= INT_MAX - 1 ? INT_MAX : min_streak + 1;
+	return te_streaks("chkerr streaks", 1, 1, min_n, (const uint8_t*)d_low_u8, d_seq_off, n_seq, n_bytes, 0, d_streaks, n_streaks, st);
+}
+
+extern "C" int yakamd_sexchr_reduce_dev(const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq, int64_t n_bytes,
+                                        uint64_t *d_cnt_u64x4, void *stream)
+{
+	if (n_seq < 0 || n_seq > (int64_t)0xfffffffe || n_bytes < 0) return fail("sexchr reduce: bad n_seq or n_bytes");
+	const hipStream_t st = (hipStream_t)stream;
+	if (n_seq > 0) HIPCK(hipMemsetAsync(d_cnt_u64x4, 0, (size_t)n_seq * 32, st));
+	yk_launch_sc_reduce((const uint8_t*)d_flag_u8, n_bytes, (const u64*)d_seq_off, d_seq_len, n_seq, (u64*)d_cnt_u64x4, st);
+	HIPCK(hipGetLastError());
 	HIPCK(hipStreamSynchronize(st));
-	const u64 n_runs = s.host[0];
-	void *list = 0;
-	s.host[1] = 0;
-	if (n_runs > 0) {                                  /* the list is sized by the runs: the number kept stays on the device until the end */
-		if (!s.st.fit(n_runs * 8) || !s.en.fit(n_runs * 8)) return fail("trioeval reduce: out of device memory for %llu runs", (unsigned long long)n_runs);
-		const int64_t nb = yk_te_keep_blocks((int64_t)n_runs);
-		if (!s.kcnt.fit((size_t)nb * 4) || !s.koff.fit((size_t)(nb + 1) * 8)) return fail("trioeval reduce: out of device memory");
-		if (d_streaks) { if (hipMalloc(&list, n_runs * 16) != hipSuccess) return fail("trioeval reduce: out of device memory for %llu runs", (unsigned long long)n_runs); }
-		else if (!s.list.fit(n_runs * 16)) return fail("trioeval reduce: out of device memory");
-		else list = s.list.p;
-		yk_launch_te_runs(flag, n_bytes, 0, (const u64*)s.toff.p, (u64*)s.st.p, (u64*)s.en.p, 1, st);
-		yk_launch_te_keep((const u64*)s.st.p, (const u64*)s.en.p, flag, (int64_t)n_runs, min_n, (u32*)s.kcnt.p, 0, (const u64*)d_seq_off, n_seq, 0, 0, st);
-		yk_launch_te_scan((const u32*)s.kcnt.p, nb, 1, (u64*)s.koff.p, st);
-		yk_launch_te_keep((const u64*)s.st.p, (const u64*)s.en.p, flag, (int64_t)n_runs, min_n, 0, (const u64*)s.koff.p, (const u64*)d_seq_off, n_seq, list, 1, st);
-		yk_launch_te_seq(list, (const u64*)s.koff.p + nb, (int64_t)n_runs, k, (int*)d_cnt_i32x6, st);
-		const hipError_t e = hipGetLastError();
-		if (e == hipSuccess) (void)hipMemcpyAsync(s.host + 1, (const u64*)s.koff.p + nb, 8, hipMemcpyDeviceToHost, st);
-	}
-	const hipError_t e = hipGetLastError(), e2 = hipStreamSynchronize(st);
-	const u64 n_keep = s.host[1];
-	if (e != hipSuccess || e2 != hipSuccess) {
-		if (d_streaks) (void)hipFree(list);
-		return fail("trioeval reduce: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-	}
-	if (d_streaks && n_keep == 0) { (void)hipFree(list); list = 0; }
-	if (d_streaks) *d_streaks = list;
-	if (n_streaks) *n_streaks = (int64_t)n_keep;
 	return 0;
 }
 

@@ -678,6 +678,7 @@ __device__ __forceinline__ int64_t img_find(const ImgView &img, u64 key)
  *   2-bit class per parent into the count field, so a flag is 4 bits.
  * ------------------------------------------------------------------------------------------ */
 #define QV_NOKMER 0xffffu
+__device__ __forceinline__ bool lk_used(const ImgView &img, u64 slot) { return img.used[slot >> 5] >> (slot & 31) & 1; }
 #define TB_NOKMER 0xffu
 __device__ u32 d_tb_over;          /* triobin: a probed count field above 15 was met */
 /* yak_ch_get() clamped at 0 (qv.c:59-60, triobin.c:62-84), read-only and on the key array alone: the image keeps every unused slot at YK_EMPTY
@@ -688,13 +689,21 @@ __device__ u32 d_tb_over;          /* triobin: a probed count field above 15 was
  * The sub-tables' {offset, log2 capacity} sit in LDS (dynamic: 8 bytes per sub-table while pre <= 12): a probe is then one dependent global read,
  * not three; LK_U positions of a lane are hashed first and their home slots requested together (the probe of one position used to wait for the
  * one before it) */
+/* CE (`yak chkerr`, reference chkerr.c:60-61): the byte is 1 where the signed yak_ch_get() < min_cnt (-1 for an absent k-mer, so min_cnt 0 marks the
+ * absent ones alone), 0 where it is not, CE_NOKMER where no k-mer ends.  The table is a YAK_LOAD_ALL one: at k >= 32 a stored key at count 1023 can
+ * equal YK_EMPTY, so there a YK_EMPTY slot asks the `used` bitmap before the probe stops (as img_find and k_inspect<., true> do).  CE = false
+ * compiles to the code it did before the mode existed (min_cnt unused). */
 #define LK_U 2                             /* probes a lane keeps in flight */
-template <typename T, bool LONG>           /* T: unsigned short (qv) or uint8_t (triobin's flag); LONG: k in [32, 63], yak_hash_long (triobin.c:78-81) */
+#define CE_NOKMER 0xffu
+template <typename T, bool LONG, bool CE = false>   /* T: unsigned short (qv) or uint8_t (triobin's flag, chkerr's low byte); LONG: k in [32, 63],
+                                                     * yak_hash_long (triobin.c:78-81) */
 __global__ __launch_bounds__(XT_THREADS)
-void k_lookup(const uint8_t *__restrict__ bases, int64_t n, int k, ImgView img, T *__restrict__ out, int tab)
+void k_lookup(const uint8_t *__restrict__ bases, int64_t n, int k, ImgView img, T *__restrict__ out, int tab, int min_cnt)
 {
-	constexpr u32 NOKMER = (T)~0u;
-	constexpr bool FLAG = sizeof(T) == 1;  /* a flag holds 4 bits */
+	static_assert(!CE || sizeof(T) == 1, "chkerr writes one byte per position");
+	constexpr u32 NOKMER = CE ? 0xffffffffu : (u32)(T)~0u;   /* CE: a count of 255 is not "no k-mer" */
+	constexpr u32 ABSENT = 1024u;          /* CE: above every count field */
+	constexpr bool FLAG = sizeof(T) == 1 && !CE;   /* a flag holds 4 bits */
 	__shared__ XtTile S;
 	extern __shared__ __attribute__((aligned(16))) u64 s_tab[];
 	const u32 pmask = (1u << img.pre) - 1;
@@ -718,7 +727,7 @@ void k_lookup(const uint8_t *__restrict__ bases, int64_t n, int k, ImgView img, 
 				u64 h;
 				const bool ok = LONG ? xt_kmer_long(S, q, k, img.pre, tile0, n, &h) : xt_kmer(S, q, k, mask, kones, tile0, n, &h);
 				const u32 p = (u32)h & pmask;
-				v[u] = ok ? 0u : NOKMER;
+				v[u] = ok ? (CE ? ABSENT : 0u) : NOKMER;
 				/* htab.c:93-100 compares (hash >> pre) << 10 >> 10: the stored key keeps 54 bits of it, all of them at k < 32 (pre >= 10) */
 				live[u] = false; kid[u] = LONG ? (h >> img.pre) & (~0ull >> 10) : h >> img.pre; keys[u] = karena; idx[u] = 0; nmask[u] = 0;
 				if (ok) {
@@ -733,13 +742,14 @@ void k_lookup(const uint8_t *__restrict__ bases, int64_t n, int k, ImgView img, 
 #pragma unroll
 			for (int u = 0; u < LK_U; ++u) {
 				const u32 first = idx[u];
-				while (kc[u] != YK_EMPTY) {
+				while (kc[u] != YK_EMPTY || (CE && LONG && live[u] && lk_used(img, (u64)(keys[u] - karena) + idx[u]))) {
 					if (kc[u] >> 10 == kid[u]) { v[u] = (u32)(kc[u] & 1023u); break; }
 					idx[u] = (idx[u] + 1) & nmask[u];
 					if (idx[u] == first) break;
 					kc[u] = keys[u][idx[u]];
 				}
 				if (FLAG && v[u] != NOKMER && v[u] > 15u) { over = 1; v[u] &= 15u; }
+				if (CE) v[u] = v[u] == NOKMER ? CE_NOKMER : (v[u] == ABSENT ? -1 : (int)v[u]) < min_cnt ? 1u : 0u;
 				const int64_t pos = tile0 + (r0 + u) * XT_THREADS + (int)threadIdx.x;
 				if (pos < n) out[pos] = (T)v[u];
 			}
@@ -839,11 +849,22 @@ void yk_launch_lookup(const uint8_t *bases, int64_t n, int k, ImgView img, void 
 	const int tab = img.pre <= 12;
 	const size_t lds = tab ? (size_t)8 << img.pre : 0;
 	const dim3 grid(yk_xpart_blocks(n)), block(XT_THREADS);
-	if (width == 2) { hipLaunchKernelGGL((k_lookup<unsigned short, false>), grid, block, lds, st, bases, n, k, img, (unsigned short*)out, tab); return; }
+	if (width == 2) { hipLaunchKernelGGL((k_lookup<unsigned short, false>), grid, block, lds, st, bases, n, k, img, (unsigned short*)out, tab, 0); return; }
 	void *over = 0;
 	if (hipGetSymbolAddress(&over, HIP_SYMBOL(d_tb_over)) == hipSuccess) (void)hipMemsetAsync(over, 0, 4, st);
-	if (k < 32) hipLaunchKernelGGL((k_lookup<uint8_t, false>), grid, block, lds, st, bases, n, k, img, (uint8_t*)out, tab);
-	else hipLaunchKernelGGL((k_lookup<uint8_t, true>), grid, block, lds, st, bases, n, k, img, (uint8_t*)out, tab);
+	if (k < 32) hipLaunchKernelGGL((k_lookup<uint8_t, false>), grid, block, lds, st, bases, n, k, img, (uint8_t*)out, tab, 0);
+	else hipLaunchKernelGGL((k_lookup<uint8_t, true>), grid, block, lds, st, bases, n, k, img, (uint8_t*)out, tab, 0);
+}
+
+/* chkerr's low byte per position (1 / 0 / CE_NOKMER), k in [1, 63] */
+void yk_launch_ce_lookup(const uint8_t *bases, int64_t n, int k, ImgView img, uint8_t *out, int min_cnt, hipStream_t st)
+{
+	if (n <= 0) return;
+	const int tab = img.pre <= 12;
+	const size_t lds = tab ? (size_t)8 << img.pre : 0;
+	const dim3 grid(yk_xpart_blocks(n)), block(XT_THREADS);
+	if (k < 32) hipLaunchKernelGGL((k_lookup<uint8_t, false, true>), grid, block, lds, st, bases, n, k, img, out, tab, min_cnt);
+	else hipLaunchKernelGGL((k_lookup<uint8_t, true, true>), grid, block, lds, st, bases, n, k, img, out, tab, min_cnt);
 }
 
 int yk_tb_over_seen(hipStream_t st)

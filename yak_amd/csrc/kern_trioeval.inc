@@ -15,6 +15,16 @@
  *                  ordered by record), so a record with millions of streaks costs one atomic per counter and wave
  * Buffers are sized from the counts, never from one run per position: the host reads the number of runs back once, and sizes the
  * streak list by it (k_te_seq reads the number kept on the device).
+ *
+ * The run finder's map from a byte to a type is its template parameter M: TeMapTrio above, or TeMapLow for `yak chkerr` (reference
+ * chkerr.c:60-67), whose bytes k_lookup<uint8_t, ., true> writes: 1 where the k-mer is low, so a run of type 1 is a streak of low k-mers at
+ * consecutive end positions, broken by a k-mer that is not low and by a position where none ends.  chkerr keeps a run when e - s > min_streak
+ * (min_n = min_streak + 1) and needs no per-record counters: k_te_seq is trioeval's alone.
+ *
+ * k_sc_reduce is `yak sexchr`'s tally (reference sexchr.c:57-65) over the flags of the three SEXCHR loads, also flat over the array: each thread
+ * folds TE_PER positions (one 16-byte load) of each of SC_ITERS tiles, their record found by a binary search over off[] and searched again when
+ * a later record starts; a record closed inside a thread is added with atomics, the one open at its end by a segmented scan over the wave
+ * (records ascend with the lanes), so a chromosome-length record costs one atomic per counter and wave.
  */
 #define TE_THREADS 256
 #define TE_PER 16                              /* positions per thread: one 16-byte load */
@@ -22,7 +32,9 @@
 #define TE_ITEMS 16                            /* runs or streaks per thread in k_te_keep / k_te_seq */
 #define TE_NONE 0xffffffffu
 
-__device__ __forceinline__ u32 te_type(u32 v) { return v == 2u ? 1u : v == 8u ? 2u : 0u; }
+/* the position-to-type maps of the run finder: trioeval's flags (2 -> 1, 8 -> 2) and chkerr's low bytes (1 -> 1; 0 and CE_NOKMER -> 0) */
+struct TeMapTrio { static __device__ __forceinline__ u32 type(u32 v) { return v == 2u ? 1u : v == 8u ? 2u : 0u; } };
+struct TeMapLow { static __device__ __forceinline__ u32 type(u32 v) { return v == 1u ? 1u : 0u; } };
 
 /* exclusive prefix of x over the block's TE_THREADS threads; *total = the block's sum */
 __device__ __forceinline__ u32 te_block_scan(u32 x, u32 *total)
@@ -44,7 +56,7 @@ __device__ __forceinline__ u32 te_block_scan(u32 x, u32 *total)
 
 /* SCATTER = 0: tcnt[tile] = run starts, tcnt[n_tiles + tile] = run ends of the tile.  SCATTER = 1: starts at st[toff[tile] ..], exclusive
  * ends at en[toff[n_tiles + 1 + tile] ..] (toff = the two scans, n_tiles + 1 entries each) */
-template <bool SCATTER>
+template <bool SCATTER, typename M>
 __global__ __launch_bounds__(TE_THREADS)
 void k_te_runs(const uint8_t *__restrict__ flag, int64_t n, int64_t n_tiles, u32 *__restrict__ tcnt, const u64 *__restrict__ toff,
                u64 *__restrict__ st, u64 *__restrict__ en)
@@ -56,13 +68,13 @@ void k_te_runs(const uint8_t *__restrict__ flag, int64_t n, int64_t n_tiles, u32
 		const uint4 w = *(const uint4*)(flag + p0);
 		const u32 ws[4] = { w.x, w.y, w.z, w.w };
 #pragma unroll
-		for (int j = 0; j < TE_PER; ++j) t[j] = te_type(ws[j >> 2] >> (8 * (j & 3)) & 0xffu);
+		for (int j = 0; j < TE_PER; ++j) t[j] = M::type(ws[j >> 2] >> (8 * (j & 3)) & 0xffu);
 	} else {
 #pragma unroll
-		for (int j = 0; j < TE_PER; ++j) t[j] = p0 + j < n ? te_type(flag[p0 + j]) : 0u;
+		for (int j = 0; j < TE_PER; ++j) t[j] = p0 + j < n ? M::type(flag[p0 + j]) : 0u;
 	}
-	u32 prev = p0 > 0 && p0 - 1 < n ? te_type(flag[p0 - 1]) : 0u;
-	const u32 after = p0 + TE_PER < n ? te_type(flag[p0 + TE_PER]) : 0u;
+	u32 prev = p0 > 0 && p0 - 1 < n ? M::type(flag[p0 - 1]) : 0u;
+	const u32 after = p0 + TE_PER < n ? M::type(flag[p0 + TE_PER]) : 0u;
 	u32 smask = 0, emask = 0;
 #pragma unroll
 	for (int j = 0; j < TE_PER; ++j) {
@@ -108,7 +120,7 @@ void k_te_scan(const u32 *__restrict__ cnt, int64_t m, u64 *__restrict__ off)
 
 /* TE_ITEMS consecutive runs per thread.  SCATTER = 0: kcnt[block] = runs of the block with e - s >= min_n.  SCATTER = 1: those runs to
  * list[koff[block] ..] in order as {record, s - off[record], e - off[record], type} */
-template <bool SCATTER>
+template <bool SCATTER, typename M>
 __global__ __launch_bounds__(TE_THREADS)
 void k_te_keep(const u64 *__restrict__ st, const u64 *__restrict__ en, const uint8_t *__restrict__ flag, int64_t n_runs, int min_n,
                u32 *__restrict__ kcnt, const u64 *__restrict__ koff, const u64 *__restrict__ seq_off, int64_t n_seq, uint4 *__restrict__ list)
@@ -134,7 +146,7 @@ void k_te_keep(const u64 *__restrict__ st, const u64 *__restrict__ en, const uin
 		while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (seq_off[mid] <= s) lo = mid + 1; else hi = mid; }
 		const int64_t j = lo > 0 ? lo - 1 : 0;
 		const u64 base = seq_off[j];
-		*o++ = make_uint4((u32)j, (u32)(s - base), (u32)(e - base), te_type(flag[s]));
+		*o++ = make_uint4((u32)j, (u32)(s - base), (u32)(e - base), M::type(flag[s]));
 	}
 }
 
@@ -180,12 +192,19 @@ void k_te_seq(const uint4 *__restrict__ list, const u64 *__restrict__ n_list, in
 int64_t yk_te_tiles(int64_t n) { return (n + TE_TILE - 1) / TE_TILE; }
 int64_t yk_te_keep_blocks(int64_t n_runs) { return (n_runs + TE_THREADS * TE_ITEMS - 1) / (TE_THREADS * TE_ITEMS); }
 
-void yk_launch_te_runs(const uint8_t *flag, int64_t n, u32 *tcnt, const u64 *toff, u64 *st, u64 *en, int scatter, hipStream_t s)
+template <typename M>
+static void te_runs(const uint8_t *flag, int64_t n, u32 *tcnt, const u64 *toff, u64 *st, u64 *en, int scatter, hipStream_t s)
 {
 	const int64_t nt = yk_te_tiles(n);
 	if (nt <= 0) return;
-	if (scatter) hipLaunchKernelGGL(k_te_runs<true>, dim3((unsigned)nt), dim3(TE_THREADS), 0, s, flag, n, nt, tcnt, toff, st, en);
-	else hipLaunchKernelGGL(k_te_runs<false>, dim3((unsigned)nt), dim3(TE_THREADS), 0, s, flag, n, nt, tcnt, toff, st, en);
+	if (scatter) hipLaunchKernelGGL((k_te_runs<true, M>), dim3((unsigned)nt), dim3(TE_THREADS), 0, s, flag, n, nt, tcnt, toff, st, en);
+	else hipLaunchKernelGGL((k_te_runs<false, M>), dim3((unsigned)nt), dim3(TE_THREADS), 0, s, flag, n, nt, tcnt, toff, st, en);
+}
+
+void yk_launch_te_runs(const uint8_t *flag, int64_t n, u32 *tcnt, const u64 *toff, u64 *st, u64 *en, int scatter, hipStream_t s, int low)
+{
+	if (low) te_runs<TeMapLow>(flag, n, tcnt, toff, st, en, scatter, s);
+	else te_runs<TeMapTrio>(flag, n, tcnt, toff, st, en, scatter, s);
 }
 
 void yk_launch_te_scan(const u32 *cnt, int64_t m, int n_arrays, u64 *off, hipStream_t s)
@@ -193,13 +212,21 @@ void yk_launch_te_scan(const u32 *cnt, int64_t m, int n_arrays, u64 *off, hipStr
 	hipLaunchKernelGGL(k_te_scan, dim3((unsigned)n_arrays), dim3(1024), 0, s, cnt, m, off);
 }
 
-void yk_launch_te_keep(const u64 *st, const u64 *en, const uint8_t *flag, int64_t n_runs, int min_n, u32 *kcnt, const u64 *koff,
-                       const u64 *seq_off, int64_t n_seq, void *list, int scatter, hipStream_t s)
+template <typename M>
+static void te_keep(const u64 *st, const u64 *en, const uint8_t *flag, int64_t n_runs, int min_n, u32 *kcnt, const u64 *koff,
+                    const u64 *seq_off, int64_t n_seq, void *list, int scatter, hipStream_t s)
 {
 	const int64_t nb = yk_te_keep_blocks(n_runs);
 	if (nb <= 0) return;
-	if (scatter) hipLaunchKernelGGL(k_te_keep<true>, dim3((unsigned)nb), dim3(TE_THREADS), 0, s, st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, (uint4*)list);
-	else hipLaunchKernelGGL(k_te_keep<false>, dim3((unsigned)nb), dim3(TE_THREADS), 0, s, st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, (uint4*)list);
+	if (scatter) hipLaunchKernelGGL((k_te_keep<true, M>), dim3((unsigned)nb), dim3(TE_THREADS), 0, s, st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, (uint4*)list);
+	else hipLaunchKernelGGL((k_te_keep<false, M>), dim3((unsigned)nb), dim3(TE_THREADS), 0, s, st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, (uint4*)list);
+}
+
+void yk_launch_te_keep(const u64 *st, const u64 *en, const uint8_t *flag, int64_t n_runs, int min_n, u32 *kcnt, const u64 *koff,
+                       const u64 *seq_off, int64_t n_seq, void *list, int scatter, hipStream_t s, int low)
+{
+	if (low) te_keep<TeMapLow>(st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, list, scatter, s);
+	else te_keep<TeMapTrio>(st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, list, scatter, s);
 }
 
 void yk_launch_te_seq(const void *list, const u64 *n_list, int64_t n_max, int k, int *cnt6, hipStream_t s)
@@ -207,4 +234,84 @@ void yk_launch_te_seq(const void *list, const u64 *n_list, int64_t n_max, int k,
 	const int64_t nb = yk_te_keep_blocks(n_max);
 	if (nb <= 0) return;
 	hipLaunchKernelGGL(k_te_seq, dim3((unsigned)nb), dim3(TE_THREADS), 0, s, (const uint4*)list, n_list, k, cnt6);
+}
+
+/* cnt[4 j ..] += n_k, n_sexchr, n_sex1, n_sex2 of record j (sexchr.c:57-65: flag > 0, == 1, == 2 over the positions where a k-mer ends); a position
+ * counts for record j when it lies in [off[j], off[j] + len[j]).  A workgroup folds SC_ITERS consecutive tiles, thread t the TE_PER positions at
+ * t * TE_PER of each (a wave reads 1 KiB per step); a thread's record only moves forward.  It ends on the record of its last position plast, which
+ * grows with the lane, so equal records are adjacent lanes for the segmented scan.  Same-address atomics were the cost on long contigs (four
+ * records: every wave adds to the same four words): folding 16 tiles per workgroup takes them from 47 % of the lookup's time to a few. */
+#define SC_ITERS 16
+__device__ __forceinline__ int64_t sc_record(const u64 *__restrict__ seq_off, int64_t n_seq, u64 p)
+{
+	int64_t lo = 0, hi = n_seq;                       /* the last record with off <= p */
+	while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (seq_off[mid] <= p) lo = mid + 1; else hi = mid; }
+	return lo > 0 ? lo - 1 : 0;
+}
+
+__global__ __launch_bounds__(TE_THREADS)
+void k_sc_reduce(const uint8_t *__restrict__ flag, int64_t n, const u64 *__restrict__ seq_off, const u32 *__restrict__ seq_len, int64_t n_seq,
+                 unsigned long long *__restrict__ cnt)
+{
+	const u32 lane = threadIdx.x & (WAVE - 1);
+	const int64_t b0 = (int64_t)blockIdx.x * SC_ITERS * TE_TILE + (int64_t)threadIdx.x * TE_PER;
+	const int64_t last = b0 + (int64_t)(SC_ITERS - 1) * TE_TILE + TE_PER - 1;
+	const u64 plast = (u64)(last < n ? last : n - 1);
+	u32 a[4] = { 0, 0, 0, 0 };
+	int64_t j = sc_record(seq_off, n_seq, (u64)(b0 < n ? b0 : n - 1));
+	u64 nxt = j + 1 < n_seq ? seq_off[j + 1] : ~0ull, end = seq_off[j] + seq_len[j];
+	for (int it = 0; it < SC_ITERS; ++it) {
+		const int64_t p0 = b0 + (int64_t)it * TE_TILE;
+		if (p0 >= n) break;
+		u32 f[TE_PER];
+		if (p0 + TE_PER <= n && ((uintptr_t)(flag + p0) & 15) == 0) {
+			const uint4 w = *(const uint4*)(flag + p0);
+			const u32 ws[4] = { w.x, w.y, w.z, w.w };
+#pragma unroll
+			for (int q = 0; q < TE_PER; ++q) f[q] = ws[q >> 2] >> (8 * (q & 3)) & 0xffu;
+		} else {
+#pragma unroll
+			for (int q = 0; q < TE_PER; ++q) f[q] = p0 + q < n ? flag[p0 + q] : TB_NOKMER;
+		}
+#pragma unroll
+		for (int q = 0; q < TE_PER; ++q) {
+			const u32 v = f[q];
+			if (v == TB_NOKMER) continue;
+			const u64 p = (u64)(p0 + q);
+			if (p >= nxt) {                           /* a later record: close this one */
+#pragma unroll
+				for (int c = 0; c < 4; ++c) { if (a[c]) atomicAdd(&cnt[j * 4 + c], (unsigned long long)a[c]); a[c] = 0; }
+				j = sc_record(seq_off, n_seq, p);
+				nxt = j + 1 < n_seq ? seq_off[j + 1] : ~0ull;
+				end = seq_off[j] + seq_len[j];
+			}
+			if (p >= end) continue;
+			a[0] += 1u; a[1] += v > 0u; a[2] += v == 1u; a[3] += v == 2u;
+		}
+	}
+	if (plast >= nxt) {                               /* end on plast's record */
+#pragma unroll
+		for (int c = 0; c < 4; ++c) { if (a[c]) atomicAdd(&cnt[j * 4 + c], (unsigned long long)a[c]); a[c] = 0; }
+		j = sc_record(seq_off, n_seq, plast);
+	}
+	const u32 cur = (u32)j;
+	/* the record open at the end: an inclusive segmented scan over the wave (equal records are adjacent lanes), added by its last lane */
+#pragma unroll
+	for (int o = 1; o < WAVE; o <<= 1) {
+		const u32 os = __shfl_up(cur, o);
+		const bool take = lane >= (u32)o && os == cur;
+#pragma unroll
+		for (int c = 0; c < 4; ++c) { const u32 y = __shfl_up(a[c], o); a[c] += take ? y : 0u; }
+	}
+	const u32 ns = __shfl_down(cur, 1);
+	if (lane == WAVE - 1 || ns != cur)
+#pragma unroll
+		for (int c = 0; c < 4; ++c) if (a[c]) atomicAdd(&cnt[(u64)cur * 4 + c], (unsigned long long)a[c]);
+}
+
+void yk_launch_sc_reduce(const uint8_t *flag, int64_t n, const u64 *seq_off, const u32 *seq_len, int64_t n_seq, u64 *cnt, hipStream_t s)
+{
+	const int64_t nt = yk_te_tiles(n), nb = (nt + SC_ITERS - 1) / SC_ITERS;
+	if (nt <= 0 || n_seq <= 0) return;
+	hipLaunchKernelGGL(k_sc_reduce, dim3((unsigned)nb), dim3(TE_THREADS), 0, s, flag, n, seq_off, seq_len, n_seq, (unsigned long long*)cnt);
 }

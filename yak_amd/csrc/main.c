@@ -2,7 +2,7 @@
  * main.c -- `yak-amd`: the repo's own small command-line driver of libyak_amd.so, plain C against
  * include/yak.h (and include/yak_amd.h for triobin and -X).  It is a test and benchmark vehicle (tests/, bench.py's e2e_cli figure), not a
  * re-creation of the reference's CLI: that one runs unmodified on the library (INTEGRATION.md section 2,
- * oracle/_ref/yak_on_amd).  Five sub-commands drive the call sequences the library serves:
+ * oracle/_ref/yak_on_amd).  Seven sub-commands drive the call sequences the library serves:
  *     count    the counting protocol behind reference main.c:53-61 (one pass, or two passes + shrink
  *              when a bloom filter is asked for)
  *     qv       the lookup protocol behind reference main.c:163-215 (restore, histogram, yak_qv, solve)
@@ -10,6 +10,8 @@
  *     trioeval the phasing evaluation of reference trioeval.c:153-212 (two TRIOBIN loads, yakamd_trioeval)
  *     inspect  the table statistics of reference inspect.c (yakamd_inspect: the k-mer histogram of one table, or the joint
  *              spectrum of two; -R probes the second table as inspect.c:58 does)
+ *     chkerr   the streaks of low k-mers of reference chkerr.c:99-133 (yak_ch_restore, yakamd_chkerr)
+ *     sexchr   the sex-chromosome tally of reference sexchr.c:104-140 (three SEXCHR loads, yakamd_sexchr)
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
  */
@@ -18,7 +20,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "yak.h"
-#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval and yakamd_inspect */
+#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr and yakamd_sexchr */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
 enum arg_kind { ARG_FLAG, ARG_I32, ARG_SIZE, ARG_I64SIZE, ARG_F64, ARG_TEXT };
@@ -228,6 +230,70 @@ static int cmd_inspect(int argc, char **argv)
 	return yakamd_inspect(&o, argv[first], first + 1 < argc ? argv[first + 1] : 0, 0) == 0 ? 0 : 2;
 }
 
+/* ---- chkerr ---- */
+static int cmd_chkerr(int argc, char **argv)
+{
+	yakamd_ceopt_t o;
+	yakamd_ceopt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'c', ARG_I32, &o.min_cnt, "min k-mer count" },
+		{ 's', ARG_I32, &o.min_streak, "min k-mer streak" },
+		{ 't', ARG_I32, &o.n_threads, "host threads (accepted for the reference's command line)" },
+		{ 'K', ARG_I64SIZE, &o.chunk_size, "bases per chunk" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 1 >= argc) { arg_help("chkerr [options] <count.yak> <seq.fa>", defs, nd); return 1; }
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd chkerr: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	const int rc = yakamd_chkerr(&o, tab, argv[first + 1], 0) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
+/* ---- sexchr ---- */
+/* k and pre of a .yak file's header (htab.c:381-384); 0 if it cannot be read */
+static int yak_header(const char *fn, uint32_t *k, uint32_t *pre)
+{
+	FILE *fp = fopen(fn, "rb");
+	char magic[4];
+	uint32_t t[3];
+	int ok = fp && fread(magic, 1, 4, fp) == 4 && memcmp(magic, YAK_MAGIC, 4) == 0 && fread(t, 4, 3, fp) == 3;
+	if (fp) fclose(fp);
+	if (ok) { *k = t[0]; *pre = t[1]; }
+	return ok;
+}
+
+static int cmd_sexchr(int argc, char **argv)
+{
+	yakamd_scopt_t o;
+	yakamd_scopt_init(&o);
+	const struct arg_def defs[] = {
+		{ 't', ARG_I32, &o.n_threads, "host threads (accepted for the reference's command line)" },
+		{ 'K', ARG_I64SIZE, &o.chunk_size, "chunk size (bases; k, m, g suffixes)" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 4 >= argc) { arg_help("sexchr [options] <chrY.yak> <chrX.yak> <PAR.yak> <hap1.fa> <hap2.fa>", defs, nd); return 1; }
+	/* the three loads must agree on k and pre (htab.c:437 asserts it): read the headers before loading anything */
+	uint32_t k[3], pre[3];
+	for (int i = 0; i < 3; ++i)
+		if (!yak_header(argv[first + i], &k[i], &pre[i])) { fprintf(stderr, "yak-amd sexchr: %s is not a readable .yak file\n", argv[first + i]); return 2; }
+	for (int i = 1; i < 3; ++i)
+		if (k[i] != k[0] || pre[i] != pre[0]) {
+			fprintf(stderr, "yak-amd sexchr: %s has k = %u and pre = %u, %s has k = %u and pre = %u: the three tables must agree\n",
+			        argv[first], k[0], pre[0], argv[first + i], k[i], pre[i]);
+			return 2;
+		}
+	yak_ch_t *tab = yak_ch_restore_core(0, argv[first], YAK_LOAD_SEXCHR1);
+	if (tab) tab = yak_ch_restore_core(tab, argv[first + 1], YAK_LOAD_SEXCHR2);
+	if (tab) tab = yak_ch_restore_core(tab, argv[first + 2], YAK_LOAD_SEXCHR3);
+	if (!tab) { fprintf(stderr, "yak-amd sexchr: cannot load %s, %s and %s (or no MI355X)\n", argv[first], argv[first + 1], argv[first + 2]); return 2; }
+	const int rc = yakamd_sexchr(&o, tab, argv[first + 3], argv[first + 4], 0) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 int main(int argc, char **argv)
 {
 	static const struct { const char *name; int (*run)(int, char**); const char *what; } cmds[] = {
@@ -236,6 +302,8 @@ int main(int argc, char **argv)
 		{ "triobin", cmd_triobin, "bin reads by the k-mers of the two parents' .yak tables" },
 		{ "trioeval", cmd_trioeval, "evaluate the phasing of an assembly by the k-mers of the two parents' .yak tables" },
 		{ "inspect", cmd_inspect, "the k-mer histogram of a .yak table, or the joint spectrum of two" },
+		{ "chkerr", cmd_chkerr, "report the streaks of low k-mers of sequences against a .yak table" },
+		{ "sexchr", cmd_sexchr, "count the sex-chromosome k-mers of two haplotype assemblies" },
 	};
 	/* -X name=value (anywhere on the line, any number of times): a test switch of the library (yakamd_test_set) -- tests force code paths with it */
 	for (int i = 1; i + 1 < argc; ) {

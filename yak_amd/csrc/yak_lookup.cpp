@@ -1,8 +1,8 @@
 /*
- * yak_lookup.cpp -- the lookup-only commands on the device: `yak qv` (reference qv.c), `yak triobin` (reference triobin.c) and
- * `yak trioeval` (reference trioeval.c).  The table is resident on the device; every chunk of records is uploaded, its k-mers are looked
- * up there (k_lookup) and reduced per record (k_qv_reduce, k_tb_reduce, the k_te_* streak kernels), and what the command prints comes
- * from the values copied back.
+ * yak_lookup.cpp -- the lookup-only commands on the device: `yak qv` (reference qv.c), `yak triobin` (reference triobin.c),
+ * `yak trioeval` (reference trioeval.c), `yak chkerr` (reference chkerr.c) and `yak sexchr` (reference sexchr.c).  The table is resident on
+ * the device; every chunk of records is uploaded, its k-mers are looked up there (k_lookup) and reduced per record (k_qv_reduce, k_tb_reduce,
+ * the k_te_* streak kernels, k_sc_reduce), and what the command prints comes from the values copied back.
  */
 #include "yak_host.h"
 #include "yak_amd.h"
@@ -366,5 +366,139 @@ int yakamd_trioeval(const yakamd_teopt_t *opt, const yak_ch_t *ch, const char *f
 	if (out_fn) { if (fclose(out) != 0) ok = false; }
 	else fflush(out);
 	fx.close_file();
+	return ok ? 0 : -1;
+}
+
+/* reference chkerr.c:104-106 */
+void yakamd_ceopt_init(yakamd_ceopt_t *opt)
+{
+	memset(opt, 0, sizeof(yakamd_ceopt_t));
+	opt->min_cnt = 3;
+	opt->min_streak = 5;
+	opt->n_threads = 8;
+	opt->chunk_size = 1000000000;
+}
+
+/* reference chkerr.c:22-69 and 99-133 with one device and -t1's output order: per chunk, the streak lines of every sequence in input order.
+ * Each chunk is looked up into one byte per position (yakamd_chkerr_lookup_dev: 1 = low) and its streaks listed in order
+ * (yakamd_chkerr_streaks_dev).  With min_streak < 0, te_worker also prints its initial `streak = 0, last = -1` (chkerr.c:62-64 when the first
+ * low k-mer is not at position 0, chkerr.c:67 when there is none): `name \t 1-k \t 0 \t 0` ahead of the sequence's streaks, unless its first
+ * streak starts at position 0 (k = 1).  The next chunk is read on a second thread while the device and the writer work on this one. */
+int yakamd_chkerr(const yakamd_ceopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn)
+{
+	yak_ch_t *h = (yak_ch_t*)ch;
+	const int k = ch->k;
+	if (multi_refuse(ch, __func__)) return -1;                  /* the lookup kernel reads one table image */
+	FxReader fx;
+	if (!fx.open_file(fn)) { fprintf(stderr, "[E::%s] cannot open '%s'\n", __func__, fn ? fn : "-"); return -1; }
+	FILE *out = out_fn ? fopen(out_fn, "wb") : stdout;
+	if (!out) { fprintf(stderr, "[E::%s] cannot write '%s'\n", __func__, out_fn); fx.close_file(); return -1; }
+	const int64_t chunk_size = opt->chunk_size > 0 ? opt->chunk_size : 1;
+	const bool phantom = opt->min_streak < 0;
+	DevChunk d;
+	DevBuf d_low;
+	std::vector<yakamd_streak_t> sk;
+	std::string line;
+	Chunk cur, nxt;
+	read_chunk(fx, chunk_size, SIZE_MAX, true, &cur);
+	bool ok = true;
+	char buf[64];
+	const int nb_ph = snprintf(buf, sizeof buf, "\t%d\t0\t0\n", 1 - k);
+	const std::string ph(buf, (size_t)nb_ph);
+	while (ok && !cur.len.empty()) {
+		std::thread reader([&]() { read_chunk(fx, chunk_size, SIZE_MAX, true, &nxt); });
+		const size_t ns = cur.len.size();
+		fprintf(stderr, "[M::%s] read %ld sequences\n", __func__, (long)ns);
+		const size_t nb = cur.pad();
+		void *d_sk = 0;
+		int64_t n_sk = 0;
+		ok = d.put(cur) && d_low.fit(nb) && yakamd_chkerr_lookup_dev(h, d.img.p, (int64_t)nb, opt->min_cnt, d_low.p) == 0
+		     && yakamd_chkerr_streaks_dev(opt->min_streak, d_low.p, (const uint64_t*)d.off.p, (int64_t)ns, (int64_t)nb, &d_sk, &n_sk, 0) == 0;
+		sk.resize((size_t)n_sk);
+		if (ok && n_sk > 0) ok = yakamd_memcpy_d2h(sk.data(), d_sk, (size_t)n_sk * sizeof(yakamd_streak_t)) == 0;
+		yakamd_dev_free(d_sk);
+		for (size_t j = 0, i = 0; ok && j < ns; ++j) {             /* the sequences in input order, each with its streaks */
+			if (phantom && !(i < sk.size() && sk[i].seq == j && sk[i].st == 0)) { line += cur.names[j]; line += ph; }
+			for (; i < sk.size() && sk[i].seq == j; ++i) {
+				const yakamd_streak_t &s = sk[i];
+				line += cur.names[j];
+				line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%d\t%d\t%d\n", (int)s.st + 1 - k, (int)s.en, (int)(s.en - s.st)));
+			}
+			if (line.size() >= (1u << 20)) { ok = fwrite(line.data(), 1, line.size(), out) == line.size(); line.clear(); }
+		}
+		ok = ok && fwrite(line.data(), 1, line.size(), out) == line.size();
+		line.clear();
+		reader.join();
+		std::swap(cur, nxt);
+	}
+	if (!ok) fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error());
+	if (out_fn) { if (fclose(out) != 0) ok = false; }
+	else fflush(out);
+	fx.close_file();
+	return ok ? 0 : -1;
+}
+
+/* reference sexchr.c:113-114 and 13 */
+void yakamd_scopt_init(yakamd_scopt_t *opt)
+{
+	memset(opt, 0, sizeof(yakamd_scopt_t));
+	opt->n_threads = 8;
+	opt->chunk_size = 1000000000;
+}
+
+/* reference sexchr.c:28-140 with one device and -t1's output order: the two C lines, then one S line per sequence of hap1, then of hap2.  Each
+ * chunk is looked up into flags (yakamd_triobin_lookup_dev: the three SEXCHR loads OR 1, 2 and 4 into a count field) and tallied per sequence
+ * (yakamd_sexchr_reduce_dev).  The next chunk is read on a second thread while the device and the writer work on this one. */
+int yakamd_sexchr(const yakamd_scopt_t *opt, const yak_ch_t *ch, const char *fn_hap1, const char *fn_hap2, const char *out_fn)
+{
+	yak_ch_t *h = (yak_ch_t*)ch;
+	if (multi_refuse(ch, __func__)) return -1;
+	FxReader fx[2];
+	const char *fns[2] = { fn_hap1, fn_hap2 };
+	for (int i = 0; i < 2; ++i)
+		if (!fx[i].open_file(fns[i])) {
+			fprintf(stderr, "[E::%s] cannot open '%s'\n", __func__, fns[i] ? fns[i] : "-");
+			if (i) fx[0].close_file();
+			return -1;
+		}
+	FILE *out = out_fn ? fopen(out_fn, "wb") : stdout;
+	if (!out) { fprintf(stderr, "[E::%s] cannot write '%s'\n", __func__, out_fn); fx[0].close_file(); fx[1].close_file(); return -1; }
+	const int64_t chunk_size = opt->chunk_size > 0 ? opt->chunk_size : 1;
+	std::string line = "C\tS  seqName  originalHap  0  #k-mer  #sexchr  #sex1-specifc  #sex2-specific\nC\n";   /* sexchr.c:120-121, its spelling */
+	DevChunk d;
+	DevBuf d_flag, d_cnt;
+	std::vector<uint64_t> cnt;
+	Chunk cur, nxt;
+	bool ok = true;
+	char buf[128];
+	for (int hap = 1; ok && hap <= 2; ++hap) {
+		FxReader &f = fx[hap - 1];
+		read_chunk(f, chunk_size, SIZE_MAX, true, &cur);
+		while (ok && !cur.len.empty()) {
+			std::thread reader([&]() { read_chunk(f, chunk_size, SIZE_MAX, true, &nxt); });
+			const size_t ns = cur.len.size();
+			fprintf(stderr, "[M::%s] read %ld sequences\n", __func__, (long)ns);
+			const size_t nb = cur.pad();
+			cnt.resize(ns * 4);
+			ok = d.put(cur) && d_flag.fit(nb) && d_cnt.fit(ns * 32)
+			     && yakamd_triobin_lookup_dev(h, d.img.p, (int64_t)nb, d_flag.p) == 0
+			     && yakamd_sexchr_reduce_dev(d_flag.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, (int64_t)nb, (uint64_t*)d_cnt.p, 0) == 0
+			     && yakamd_memcpy_d2h(cnt.data(), d_cnt.p, ns * 32) == 0;
+			for (size_t j = 0; ok && j < ns; ++j) {
+				const uint64_t *c = cnt.data() + j * 4;
+				line += "S\t"; line += cur.names[j];
+				line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%d\t0\t%ld\t%ld\t%ld\t%ld\n", hap, (long)c[0], (long)c[1], (long)c[2], (long)c[3]));
+				if (line.size() >= (1u << 20)) { ok = fwrite(line.data(), 1, line.size(), out) == line.size(); line.clear(); }
+			}
+			reader.join();
+			std::swap(cur, nxt);
+		}
+		cur.clear();
+	}
+	ok = ok && fwrite(line.data(), 1, line.size(), out) == line.size();
+	if (!ok) fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error());
+	if (out_fn) { if (fclose(out) != 0) ok = false; }
+	else fflush(out);
+	fx[0].close_file(); fx[1].close_file();
 	return ok ? 0 : -1;
 }

@@ -99,11 +99,16 @@ int yk_launch_inspect(const u64 *keys, const u64 *off, u64 n, int n_sub, int sub
 void yk_launch_tb_reduce(const uint8_t *flag, const u64 *roff, const u32 *rlen, int64_t n_reads, int k, int *cnt, hipStream_t st);
 int64_t yk_te_tiles(int64_t n);                               /* trioeval's streak reduction (kern_trioeval.inc) */
 int64_t yk_te_keep_blocks(int64_t n_runs);
-void yk_launch_te_runs(const uint8_t *flag, int64_t n, u32 *tcnt, const u64 *toff, u64 *st, u64 *en, int scatter, hipStream_t s);
+/* low = 0: trioeval's flags (2 -> type 1, 8 -> type 2); low = 1: chkerr's low bytes (1 -> type 1) */
+void yk_launch_te_runs(const uint8_t *flag, int64_t n, u32 *tcnt, const u64 *toff, u64 *st, u64 *en, int scatter, hipStream_t s, int low = 0);
 void yk_launch_te_scan(const u32 *cnt, int64_t m, int n_arrays, u64 *off, hipStream_t s);
 void yk_launch_te_keep(const u64 *st, const u64 *en, const uint8_t *flag, int64_t n_runs, int min_n, u32 *kcnt, const u64 *koff,
-                       const u64 *seq_off, int64_t n_seq, void *list, int scatter, hipStream_t s);
+                       const u64 *seq_off, int64_t n_seq, void *list, int scatter, hipStream_t s, int low = 0);
 void yk_launch_te_seq(const void *list, const u64 *n_list, int64_t n_max, int k, int *cnt6, hipStream_t s);
+/* yak chkerr's lookup (kern_extract.inc): out[i] = 1 where yak_ch_get() < min_cnt (-1 when absent), 0 where not, 0xff where no k-mer ends */
+void yk_launch_ce_lookup(const uint8_t *bases, int64_t n, int k, ImgView img, uint8_t *out, int min_cnt, hipStream_t st);
+/* yak sexchr's tally (kern_trioeval.inc): cnt[4 j ..] += n_k, n_sexchr, n_sex1, n_sex2 of record j over the flags (zeroed by the caller) */
+void yk_launch_sc_reduce(const uint8_t *flag, int64_t n, const u64 *seq_off, const u32 *seq_len, int64_t n_seq, u64 *cnt, hipStream_t s);
 int yk_launch_img_count_lds(const void *rec, int hash_only, const u64 *bstart, ImgView img, int plo, int phi, size_t lds, u64 *compact, u32 stride, hipStream_t st);
 void yk_launch_img_count_h(const u64 *hash, int64_t n, ImgView img, hipStream_t st);
 void yk_launch_img_inc(ImgView img, u64 hash, u64 *out2, hipStream_t st);
