@@ -256,6 +256,17 @@ def _err():
     return (lib().yakamd_last_error() or b"").decode()
 
 
+def _output_of(name, call):
+    """what a command wrote: `call(path)` is the C call writing to `path`; a non-zero return raises with the library's error text"""
+    import tempfile
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, name + ".txt")
+        if call(out.encode()) != 0:
+            raise RuntimeError(name + " failed: " + _err())
+        with open(out, "rb") as f:
+            return f.read()
+
+
 class Table:
     """Thin owner of a ``yak_ch_t *`` created through the C ABI."""
 
@@ -455,7 +466,6 @@ def triobin_table(pat_yak, mat_yak, min_cnt=2, mid_cnt=5):
 
 def triobin(pat_yak, mat_yak, seq_fn, min_cnt=2, mid_cnt=5, ratio=0.33, print_diff=False, chunk=None):
     """`yak triobin` through the C ABI (two TRIOBIN loads + yakamd_triobin): the bytes the reference writes with -t1"""
-    import tempfile
     L = lib()
     h = triobin_table(pat_yak, mat_yak, min_cnt, mid_cnt)
     try:
@@ -464,18 +474,13 @@ def triobin(pat_yak, mat_yak, seq_fn, min_cnt=2, mid_cnt=5, ratio=0.33, print_di
         o.ratio_thres, o.print_diff = ratio, int(bool(print_diff))
         if chunk is not None:
             o.chunk_size = chunk
-        with tempfile.TemporaryDirectory() as d:
-            out = os.path.join(d, "triobin.txt")
-            if L.yakamd_triobin(C.byref(o), h, seq_fn.encode(), out.encode()) != 0:
-                raise RuntimeError("yakamd_triobin failed: " + _err())
-            return open(out, "rb").read()
+        return _output_of("yakamd_triobin", lambda out: L.yakamd_triobin(C.byref(o), h, seq_fn.encode(), out))
     finally:
         L.yak_ch_destroy(h)
 
 
 def trioeval(pat_yak, mat_yak, seq_fn, min_cnt=2, mid_cnt=5, min_n=2, print_err=False, print_frag=True, chunk=None):
     """`yak trioeval` through the C ABI (two TRIOBIN loads + yakamd_trioeval): the bytes the reference writes to stdout with -t1"""
-    import tempfile
     L = lib()
     h = triobin_table(pat_yak, mat_yak, min_cnt, mid_cnt)
     try:
@@ -484,18 +489,13 @@ def trioeval(pat_yak, mat_yak, seq_fn, min_cnt=2, mid_cnt=5, min_n=2, print_err=
         o.min_n, o.print_err, o.print_frag = min_n, int(bool(print_err)), int(bool(print_frag))
         if chunk is not None:
             o.chunk_size = chunk
-        with tempfile.TemporaryDirectory() as d:
-            out = os.path.join(d, "trioeval.txt")
-            if L.yakamd_trioeval(C.byref(o), h, seq_fn.encode(), out.encode()) != 0:
-                raise RuntimeError("yakamd_trioeval failed: " + _err())
-            return open(out, "rb").read()
+        return _output_of("yakamd_trioeval", lambda out: L.yakamd_trioeval(C.byref(o), h, seq_fn.encode(), out))
     finally:
         L.yak_ch_destroy(h)
 
 
 def chkerr(count_yak, seq, min_cnt=3, min_streak=5, chunk=None):
     """`yak chkerr` through the C ABI (yak_ch_restore + yakamd_chkerr): the bytes the reference writes to stdout with -t1"""
-    import tempfile
     L = lib()
     h = L.yak_ch_restore(count_yak.encode())
     if not h:
@@ -506,11 +506,7 @@ def chkerr(count_yak, seq, min_cnt=3, min_streak=5, chunk=None):
         o.min_cnt, o.min_streak = min_cnt, min_streak
         if chunk is not None:
             o.chunk_size = chunk
-        with tempfile.TemporaryDirectory() as d:
-            out = os.path.join(d, "chkerr.txt")
-            if L.yakamd_chkerr(C.byref(o), h, seq.encode(), out.encode()) != 0:
-                raise RuntimeError("yakamd_chkerr failed: " + _err())
-            return open(out, "rb").read()
+        return _output_of("yakamd_chkerr", lambda out: L.yakamd_chkerr(C.byref(o), h, seq.encode(), out))
     finally:
         L.yak_ch_destroy(h)
 
@@ -543,7 +539,6 @@ def sexchr_table(y, x, par):
 
 def sexchr(y, x, par, hap1, hap2, chunk=None):
     """`yak sexchr` through the C ABI (three SEXCHR loads + yakamd_sexchr): the bytes the reference writes to stdout with -t1"""
-    import tempfile
     L = lib()
     h = sexchr_table(y, x, par)
     try:
@@ -551,29 +546,20 @@ def sexchr(y, x, par, hap1, hap2, chunk=None):
         L.yakamd_scopt_init(C.byref(o))
         if chunk is not None:
             o.chunk_size = chunk
-        with tempfile.TemporaryDirectory() as d:
-            out = os.path.join(d, "sexchr.txt")
-            if L.yakamd_sexchr(C.byref(o), h, hap1.encode(), hap2.encode(), out.encode()) != 0:
-                raise RuntimeError("yakamd_sexchr failed: " + _err())
-            return open(out, "rb").read()
+        return _output_of("yakamd_sexchr", lambda out: L.yakamd_sexchr(C.byref(o), h, hap1.encode(), hap2.encode(), out))
     finally:
         L.yak_ch_destroy(h)
 
 
 def inspect(in1, in2=None, max_cnt=20, ref_probe=False, batch_keys=None):
     """`yak inspect` through the C ABI (yakamd_inspect): the bytes the reference's inspect.c writes to stdout (ref_probe: its probe of in2)"""
-    import tempfile
     L = lib()
     o = InoptT()
     L.yakamd_inopt_init(C.byref(o))
     o.max_cnt, o.ref_probe = max_cnt, int(bool(ref_probe))
     if batch_keys is not None:
         o.batch_keys = batch_keys
-    with tempfile.TemporaryDirectory() as d:
-        out = os.path.join(d, "inspect.txt")
-        if L.yakamd_inspect(C.byref(o), in1.encode(), in2.encode() if in2 else None, out.encode()) != 0:
-            raise RuntimeError("yakamd_inspect failed: " + _err())
-        return open(out, "rb").read()
+    return _output_of("yakamd_inspect", lambda out: L.yakamd_inspect(C.byref(o), in1.encode(), in2.encode() if in2 else None, out))
 
 
 def inspect_tables(a, b=None, ref_probe=False):

@@ -17,7 +17,6 @@
 #include <stdlib.h>
 #include <string.h>
 #include <stdarg.h>
-#include <limits.h>
 #include <vector>
 #include <map>
 #include <string>
@@ -48,20 +47,7 @@ extern "C" int yakamd_device_count(void)
 /* ------------------------------------------------------------------------------------------ */
 
 
-static yakamd_ctx *ctx_of(const yak_ch_t *h)
-{
-	const yak_ch_ext *e = (const yak_ch_ext*)h;
-	return (h && e->magic == EXT_MAGIC) ? e->ctx : 0;
-}
 extern "C" yakamd_ctx *yakamd_ctx_of(yak_ch_t *h) { return ctx_of(h); }
-
-static ImgView img_view(yakamd_ctx *c)
-{
-	ImgView v;
-	v.bits = c->d_bits; v.off = c->d_off; v.keys = c->d_keys; v.used = c->d_used; v.delta = c->d_delta;
-	v.pre = c->pre; v.k = c->k;
-	return v;
-}
 
 static BloomView bloom_view(yakamd_ctx *c)
 {
@@ -1046,240 +1032,7 @@ bool yk_ctx_same_source(yakamd_ctx *c, const uint64_t id[4], int64_t *n_seq)
 	return true;
 }
 
-/* ---- lookup-only paths (yak qv, yak triobin) ---- */
-/* what the two lookup exports share, after their own checks: the kernel writes `width` bytes per position (yk_launch_lookup) */
-static int lookup_dev(yakamd_ctx *c, const void *d_bases, int64_t n_bytes, void *d_out, int width)
-{
-	if (((uintptr_t)d_bases & 15) != 0) return fail("device base image must be 16-byte aligned");
-	HIPCK(hipSetDevice(c->dev));
-	yk_launch_lookup((const uint8_t*)d_bases, n_bytes, c->k, img_view(c), d_out, width, c->st);
-	if (width == 1) HIPCK(hipGetLastError());          /* triobin's export reports a failed launch here; qv's leaves it to the synchronise */
-	HIPCK(hipStreamSynchronize(c->st));
-	return 0;
-}
-
-/* the kernel reads one whole table image: refused are several GPUs' tables (which have no context of their own) and a yakamd_set_shard range */
-static bool lookup_sharded(const yak_ch_t *h, const yakamd_ctx *c)
-{
-	const yak_ch_ext *e = (const yak_ch_ext*)h;
-	return (h && e->magic == EXT_MAGIC && e->n_sub > 1) || (c && (c->plo != 0 || c->phi != c->P));
-}
-
-extern "C" int yakamd_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, void *d_out_u16)
-{
-	yakamd_ctx *c = ctx_of(h);
-	if (lookup_sharded(h, c)) return fail("lookup: not available on a table sharded over prefix ranges");
-	if (!c) return fail("not an engine table");
-	if (c->in_pass) return fail("lookup during an open pass");
-	if (c->k < 1 || c->k >= 32) return fail("lookup: k must be below 32 (reference qv.c:44)");
-	return lookup_dev(c, d_bases, n_bytes, d_out_u16, 2);
-}
-
-extern "C" int yakamd_qv_reduce_dev(yak_ch_t *h, const void *d_t_u16, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
-                                    int min_len, double min_frac, uint32_t *d_tot, uint32_t *d_non0, uint64_t *d_hist1024)
-{
-	yakamd_ctx *c = ctx_of(h);
-	if (!c) return fail("not an engine table");
-	HIPCK(hipSetDevice(c->dev));
-	yk_launch_qv_reduce((const unsigned short*)d_t_u16, (const u64*)d_seq_off, d_seq_len, n_seq, min_len, min_frac, d_tot, d_non0, (u64*)d_hist1024, c->st);
-	HIPCK(hipStreamSynchronize(c->st));
-	return 0;
-}
-
-extern "C" int yakamd_triobin_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, void *d_flag_u8)
-{
-	yakamd_ctx *c = ctx_of(h);
-	if (lookup_sharded(h, c)) return fail("triobin lookup: not available on a table sharded over prefix ranges");
-	if (!c) return fail("not an engine table");
-	if (c->in_pass) return fail("lookup during an open pass");
-	if (c->k < 1 || c->k >= 64) return fail("triobin lookup: k must be in [1, 63]");
-	if (lookup_dev(c, d_bases, n_bytes, d_flag_u8, 1)) return -1;
-	if (n_bytes > 0 && yk_tb_over_seen(c->st))
-		return fail("triobin lookup: a count above 15 in the table -- it was not loaded with yak_ch_restore_core(..., YAK_LOAD_TRIOBIN1 / 2, ...)");
-	return 0;
-}
-
-extern "C" int yakamd_triobin_reduce_dev(int k, const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
-                                         int32_t *d_cnt_i32x19, void *stream)
-{
-	if (k < 1 || k >= 64) return fail("triobin reduce: k must be in [1, 63]");
-	yk_launch_tb_reduce((const uint8_t*)d_flag_u8, (const u64*)d_seq_off, d_seq_len, n_seq, k, (int*)d_cnt_i32x19, (hipStream_t)stream);
-	HIPCK(hipGetLastError());
-	HIPCK(hipStreamSynchronize((hipStream_t)stream));
-	return 0;
-}
-
-/* ---- yak inspect's join (kern_inspect.inc) ---- */
-/* the engines behind a table: its own, or one per rank of a table sharded over prefix ranges */
-static int engines_of(const yak_ch_t *h, std::vector<yakamd_ctx*> *out)
-{
-	const yak_ch_ext *e = (const yak_ch_ext*)h;
-	out->clear();
-	if (!h || e->magic != EXT_MAGIC) return fail("not an engine table");
-	if (e->n_sub > 1) for (int r = 0; r < e->n_sub; ++r) out->push_back(ctx_of(e->sub[r]));
-	else out->push_back(e->ctx);
-	for (yakamd_ctx *c : *out) {
-		if (!c) return fail("not an engine table");
-		if (c->dev != (*out)[0]->dev) return fail("inspect: the table is spread over several devices (device %d and %d); count it on one", (*out)[0]->dev, c->dev);
-		if (c->in_pass) return fail("inspect during an open pass");
-	}
-	return 0;
-}
-
-extern "C" int yakamd_inspect_dev(yak_ch_t *b, int k, int pre_a, int sub_lo, int sub_hi, const void *d_keys, int64_t n_keys,
-                                  const uint64_t *d_sub_off, int headers, int ref_probe, uint64_t *d_joint, void *stream)
-{
-	if (pre_a < YAK_COUNTER_BITS || pre_a > 30) return fail("inspect: pre %d of the first table is outside [10, 30]", pre_a);
-	if (sub_lo < 0 || sub_hi < sub_lo || sub_hi > 1 << pre_a) return fail("inspect: sub-tables [%d, %d) of %d", sub_lo, sub_hi, 1 << pre_a);
-	if (n_keys < 0 || (n_keys > 0 && sub_hi == sub_lo)) return fail("inspect: %ld keys in no sub-table", (long)n_keys);
-	if (k < 1 || k >= 64) return fail("inspect: k must be in [1, 63]");
-	if (((uintptr_t)d_keys & 7) != 0) return fail("inspect: the keys must be 8-byte aligned");
-	const hipStream_t st = (hipStream_t)stream;
-	if (!b) {                                                  /* one table: c1 = 0 */
-		if (yakamd_device_count() < 1) return fail("no gfx950 GPU visible: the join has no CPU fallback");
-		ImgView none;
-		memset(&none, 0, sizeof(none));
-		if (yk_launch_inspect((const u64*)d_keys, (const u64*)d_sub_off, (u64)n_keys, sub_hi - sub_lo, sub_lo, headers != 0, pre_a, 0, none, 0, 0,
-		                      0, (u64*)d_joint, st)) return fail("inspect: the join did not launch");
-		HIPCK(hipStreamSynchronize(st));
-		return 0;
-	}
-	std::vector<yakamd_ctx*> eng;
-	if (engines_of(b, &eng)) return -1;
-	if (b->k != k) return fail("inspect: the tables have different k (%d and %d)", k, b->k);
-	if (!ref_probe && k >= 32 && b->pre != pre_a)
-		return fail("inspect: at k >= 32 a stored key holds hash bits [pre, pre + 54): the tables must have the same pre (%d and %d)", pre_a, b->pre);
-	HIPCK(hipSetDevice(eng[0]->dev));
-	for (yakamd_ctx *c : eng)                                  /* every key is probed by the one rank that owns its sub-table of B */
-		if (yk_launch_inspect((const u64*)d_keys, (const u64*)d_sub_off, (u64)n_keys, sub_hi - sub_lo, sub_lo, headers != 0, pre_a, 1, img_view(c),
-		                      c->plo, c->phi, ref_probe != 0, (u64*)d_joint, st)) return fail("inspect: the join did not launch");
-	HIPCK(hipStreamSynchronize(st));
-	return 0;
-}
-
-/* the .yak body of a table's own sub-tables (one rank of a sharded table, or all), for yakamd_inspect_tables */
-int yk_inspect_engines(const yak_ch_t *h, std::vector<yakamd_ctx*> *eng) { return engines_of(h, eng); }
-
-/* trioeval's scratch (kern_trioeval.inc): kept from one call to the next, grown when a call needs more, on the device of the last call */
-namespace {
-struct TeBuf {
-	void *p = 0;
-	size_t cap = 0;
-	bool fit(size_t n) { if (n <= cap) return true; (void)hipFree(p); p = 0; cap = n + n / 8; if (hipMalloc(&p, cap) != hipSuccess) { p = 0; cap = 0; } return p != 0; }
-};
-struct TeScratch {
-	std::mutex mu;
-	int dev = -1;
-	TeBuf tcnt, toff, st, en, kcnt, koff, list;
-	u64 *host = 0;                                     /* pinned: the two totals read back */
-	void on(int d) { if (d == dev) return; for (TeBuf *b : { &tcnt, &toff, &st, &en, &kcnt, &koff, &list }) { (void)hipFree(b->p); *b = TeBuf(); } dev = d; }
-};
-TeScratch g_te;
-}
-
-/* the ordered list of kept runs over bytes [0, n_bytes) of `flag` (kern_trioeval.inc): low = 0 trioeval's typed runs, with its per-record counters
- * into cnt6 when cnt6 != 0; low = 1 chkerr's runs of low k-mers.  d_streaks: as yakamd_trioeval_reduce_dev's */
-static int te_streaks(const char *what, int low, int k, int min_n, const uint8_t *flag, const uint64_t *d_seq_off, int64_t n_seq, int64_t n_bytes,
-                      int32_t *cnt6, void **d_streaks, int64_t *n_streaks, hipStream_t st)
-{
-	std::lock_guard<std::mutex> lk(g_te.mu);
-	int dev = 0;
-	HIPCK(hipGetDevice(&dev));
-	g_te.on(dev);
-	TeScratch &s = g_te;
-	const int64_t nt = yk_te_tiles(n_bytes);
-	if (!s.tcnt.fit((size_t)nt * 8) || !s.toff.fit((size_t)(nt + 1) * 16)) return fail("%s: out of device memory", what);
-	if (!s.host) HIPCK(hipHostMalloc((void**)&s.host, 16));
-	yk_launch_te_runs(flag, n_bytes, (u32*)s.tcnt.p, 0, 0, 0, 0, st, low);
-	yk_launch_te_scan((const u32*)s.tcnt.p, nt, 2, (u64*)s.toff.p, st);
-	HIPCK(hipGetLastError());
-	HIPCK(hipMemcpyAsync(s.host, (const u64*)s.toff.p + nt, 8, hipMemcpyDeviceToHost, st));
-	HIPCK(hipStreamSynchronize(st));
-	const u64 n_runs = s.host[0];
-	void *list = 0;
-	s.host[1] = 0;
-	if (n_runs > 0) {                                  /* the list is sized by the runs: the number kept stays on the device until the end */
-		if (!s.st.fit(n_runs * 8) || !s.en.fit(n_runs * 8)) return fail("%s: out of device memory for %llu runs", what, (unsigned long long)n_runs);
-		const int64_t nb = yk_te_keep_blocks((int64_t)n_runs);
-		if (!s.kcnt.fit((size_t)nb * 4) || !s.koff.fit((size_t)(nb + 1) * 8)) return fail("%s: out of device memory", what);
-		if (d_streaks) { if (hipMalloc(&list, n_runs * 16) != hipSuccess) return fail("%s: out of device memory for %llu runs", what, (unsigned long long)n_runs); }
-		else if (!s.list.fit(n_runs * 16)) return fail("%s: out of device memory", what);
-		else list = s.list.p;
-		yk_launch_te_runs(flag, n_bytes, 0, (const u64*)s.toff.p, (u64*)s.st.p, (u64*)s.en.p, 1, st, low);
-		yk_launch_te_keep((const u64*)s.st.p, (const u64*)s.en.p, flag, (int64_t)n_runs, min_n, (u32*)s.kcnt.p, 0, (const u64*)d_seq_off, n_seq, 0, 0, st, low);
-		yk_launch_te_scan((const u32*)s.kcnt.p, nb, 1, (u64*)s.koff.p, st);
-		yk_launch_te_keep((const u64*)s.st.p, (const u64*)s.en.p, flag, (int64_t)n_runs, min_n, 0, (const u64*)s.koff.p, (const u64*)d_seq_off, n_seq, list, 1, st, low);
-		if (cnt6) yk_launch_te_seq(list, (const u64*)s.koff.p + nb, (int64_t)n_runs, k, (int*)cnt6, st);
-		const hipError_t e = hipGetLastError();
-		if (e == hipSuccess) (void)hipMemcpyAsync(s.host + 1, (const u64*)s.koff.p + nb, 8, hipMemcpyDeviceToHost, st);
-	}
-	const hipError_t e = hipGetLastError(), e2 = hipStreamSynchronize(st);
-	const u64 n_keep = s.host[1];
-	if (e != hipSuccess || e2 != hipSuccess) {
-		if (d_streaks) (void)hipFree(list);
-		return fail("%s: %s", what, hipGetErrorString(e != hipSuccess ? e : e2));
-	}
-	if (d_streaks && n_keep == 0) { (void)hipFree(list); list = 0; }
-	if (d_streaks) *d_streaks = list;
-	if (n_streaks) *n_streaks = (int64_t)n_keep;
-	return 0;
-}
-
-extern "C" int yakamd_trioeval_reduce_dev(int k, int min_n, const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
-                                          int64_t n_bytes, int32_t *d_cnt_i32x6, void **d_streaks, int64_t *n_streaks, void *stream)
-{
-	(void)d_seq_len;                                   /* the records are told apart by their separators; off[] places a streak */
-	if (d_streaks) *d_streaks = 0;
-	if (n_streaks) *n_streaks = 0;
-	if (k < 1 || k >= 64) return fail("trioeval reduce: k must be in [1, 63]");
-	if (n_seq < 0 || n_seq > (int64_t)0xfffffffe || n_bytes < 0) return fail("trioeval reduce: bad n_seq or n_bytes");
-	const hipStream_t st = (hipStream_t)stream;
-	if (n_seq > 0) HIPCK(hipMemsetAsync(d_cnt_i32x6, 0, (size_t)n_seq * 24, st));
-	if (n_seq == 0 || n_bytes == 0) { HIPCK(hipStreamSynchronize(st)); return 0; }
-	return te_streaks("trioeval reduce", 0, k, min_n, (const uint8_t*)d_flag_u8, d_seq_off, n_seq, n_bytes, d_cnt_i32x6, d_streaks, n_streaks, st);
-}
-
-/* ---- yak chkerr and yak sexchr ---- */
-extern "C" int yakamd_chkerr_lookup_dev(yak_ch_t *h, const void *d_bases, int64_t n_bytes, int min_cnt, void *d_low_u8)
-{
-	yakamd_ctx *c = ctx_of(h);
-	if (lookup_sharded(h, c)) return fail("chkerr lookup: not available on a table sharded over prefix ranges");
-	if (!c) return fail("not an engine table");
-	if (c->in_pass) return fail("lookup during an open pass");
-	if (c->k < 1 || c->k >= 64) return fail("chkerr lookup: k must be in [1, 63]");
-	if (((uintptr_t)d_bases & 15) != 0) return fail("device base image must be 16-byte aligned");
-	HIPCK(hipSetDevice(c->dev));
-	yk_launch_ce_lookup((const uint8_t*)d_bases, n_bytes, c->k, img_view(c), (uint8_t*)d_low_u8, min_cnt, c->st);
-	HIPCK(hipGetLastError());
-	HIPCK(hipStreamSynchronize(c->st));
-	return 0;
-}
-
-extern "C" int yakamd_chkerr_streaks_dev(int min_streak, const void *d_low_u8, const uint64_t *d_seq_off, int64_t n_seq, int64_t n_bytes,
-                                         void **d_streaks, int64_t *n_streaks, void *stream)
-{
-	if (d_streaks) *d_streaks = 0;
-	if (n_streaks) *n_streaks = 0;
-	if (n_seq < 0 || n_seq > (int64_t)0xfffffffe || n_bytes < 0) return fail("chkerr streaks: bad n_seq or n_bytes");
-	const hipStream_t st = (hipStream_t)stream;
-	if (n_seq == 0 || n_bytes == 0) { HIPCK(hipStreamSynchronize(st)); return 0; }
-	/* chkerr.c:63-64 prints a streak when e - s > min_streak: keep e - s >= min_streak + 1, saturated; a negative min_streak keeps every run */
-	const int min_n = min_streak < 0 ? 0 : min_streak >= INT_MAX - 1 ? INT_MAX : min_streak + 1;
-	return te_streaks("chkerr streaks", 1, 1, min_n, (const uint8_t*)d_low_u8, d_seq_off, n_seq, n_bytes, 0, d_streaks, n_streaks, st);
-}
-
-extern "C" int yakamd_sexchr_reduce_dev(const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq, int64_t n_bytes,
-                                        uint64_t *d_cnt_u64x4, void *stream)
-{
-	if (n_seq < 0 || n_seq > (int64_t)0xfffffffe || n_bytes < 0) return fail("sexchr reduce: bad n_seq or n_bytes");
-	const hipStream_t st = (hipStream_t)stream;
-	if (n_seq > 0) HIPCK(hipMemsetAsync(d_cnt_u64x4, 0, (size_t)n_seq * 32, st));
-	yk_launch_sc_reduce((const uint8_t*)d_flag_u8, n_bytes, (const u64*)d_seq_off, d_seq_len, n_seq, (u64*)d_cnt_u64x4, st);
-	HIPCK(hipGetLastError());
-	HIPCK(hipStreamSynchronize(st));
-	return 0;
-}
-
+/* ---- the hashes of a base image (the device-level exports of the lookup commands are in lookup_dev.cpp) ---- */
 extern "C" int64_t yakamd_extract_dev(int k, const void *d_bases, int64_t n_bytes, void *d_hash, void *d_t,
                                       int pre, int plo, int phi, void *stream)
 {

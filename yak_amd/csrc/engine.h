@@ -1,9 +1,26 @@
-/* engine.h -- internal interface between pool.cpp, engine.cpp and the yak.h surface (yak_api.cpp, yak_reader.cpp, yak_multi.cpp) */
+/* engine.h -- internal interface between pool.cpp, engine.cpp, lookup_dev.cpp and the yak.h surface (yak_api.cpp, yak_reader.cpp, yak_multi.cpp) */
 #ifndef YK_ENGINE_H
 #define YK_ENGINE_H
 #include <vector>
 #include "../../include/yak_amd.h"
 #include "yk_device.h"
+
+/* what a command or export says of a table it cannot read as one image (yak_api.cpp multi_refuse, lookup_dev.cpp lookup_ctx) */
+#define YK_MSG_SHARDED "not available on a table sharded over prefix ranges"
+
+/* a device buffer kept from one chunk, batch or call to the next and grown when one needs more (yakamd_dev_alloc / yakamd_dev_free are hipMalloc /
+ * hipFree).  An instance that lives until the process ends is held through a pointer that is never deleted: its destructor must not run after
+ * the HIP runtime has shut down */
+struct GrowBuf {
+	void *p = 0;
+	size_t cap = 0;
+	GrowBuf() = default;
+	GrowBuf(const GrowBuf&) = delete;
+	GrowBuf &operator=(const GrowBuf&) = delete;
+	~GrowBuf() { drop(); }
+	bool fit(size_t n) { if (n <= cap) return true; drop(); p = yakamd_dev_alloc(n + n / 8); if (p) cap = n + n / 8; return p != 0; }
+	void drop() { yakamd_dev_free(p); p = 0; cap = 0; }
+};
 
 struct yak_ht_t;
 yakamd_ctx *yk_ctx_create(int k, int pre, int n_hash, int n_shift);

@@ -1,4 +1,5 @@
-/* engine_int.h -- what the engine's own translation units (engine.cpp: passes; layout.cpp: exact slot layout) share and nobody else sees:
+/* engine_int.h -- what the engine's own translation units (engine.cpp: passes; layout.cpp: exact slot layout; lookup_dev.cpp: the device-level
+ * exports of the lookup commands) share and nobody else sees:
  * the context of a table, the device-buffer helpers on top of the pool, the error macro. */
 #ifndef YK_ENGINE_INT_H
 #define YK_ENGINE_INT_H
@@ -121,6 +122,20 @@ struct yakamd_ctx {
 
 struct yak_ch_ext { yak_ch_t pub; yakamd_ctx *ctx; u32 magic; int n_sub; yak_ch_t **sub; };   /* n_sub > 1: a table sharded over several GPUs (yak_api.cpp) */
 #define EXT_MAGIC 0x59414b41u
+
+static inline yakamd_ctx *ctx_of(const yak_ch_t *h)
+{
+	const yak_ch_ext *e = (const yak_ch_ext*)h;
+	return (h && e->magic == EXT_MAGIC) ? e->ctx : 0;
+}
+
+static inline ImgView img_view(yakamd_ctx *c)
+{
+	ImgView v;
+	v.bits = c->d_bits; v.off = c->d_off; v.keys = c->d_keys; v.used = c->d_used; v.delta = c->d_delta;
+	v.pre = c->pre; v.k = c->k;
+	return v;
+}
 
 /* layout.cpp: the exact khashl slot layout (khashl.h:152-221) of `m[p]` new keys per sub-table, sorted by insertion time, on top of the table image */
 int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_seg_off, const u64 *d_rec_kc, const u64 *d_rec_t,

@@ -158,7 +158,16 @@ static int cmd_qv(int argc, char **argv)
 	return 0;
 }
 
-/* ---- triobin ---- */
+/* ---- triobin, trioeval ---- */
+/* both parents' classes in one table (reference triobin.c:187-188), from argv[first] and argv[first + 1]; 0 after a message */
+static yak_ch_t *load_trio(char **argv, int first, int min_cnt, int mid_cnt, const char *cmd)
+{
+	yak_ch_t *tab = yak_ch_restore_core(0, argv[first], YAK_LOAD_TRIOBIN1, min_cnt, mid_cnt);
+	if (tab) tab = yak_ch_restore_core(tab, argv[first + 1], YAK_LOAD_TRIOBIN2, min_cnt, mid_cnt);
+	if (!tab) fprintf(stderr, "yak-amd %s: cannot load %s and %s (or no MI355X)\n", cmd, argv[first], argv[first + 1]);
+	return tab;
+}
+
 static int cmd_triobin(int argc, char **argv)
 {
 	yakamd_tbopt_t o;
@@ -175,15 +184,13 @@ static int cmd_triobin(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 2 >= argc) { arg_help("triobin [options] <pat.yak> <mat.yak> <seq.fa>", defs, nd); return 1; }
-	yak_ch_t *tab = yak_ch_restore_core(0, argv[first], YAK_LOAD_TRIOBIN1, min_cnt, mid_cnt);
-	if (tab) tab = yak_ch_restore_core(tab, argv[first + 1], YAK_LOAD_TRIOBIN2, min_cnt, mid_cnt);
-	if (!tab) { fprintf(stderr, "yak-amd triobin: cannot load %s and %s (or no MI355X)\n", argv[first], argv[first + 1]); return 2; }
+	yak_ch_t *tab = load_trio(argv, first, min_cnt, mid_cnt, "triobin");
+	if (!tab) return 2;
 	const int rc = yakamd_triobin(&o, tab, argv[first + 2], 0) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
 }
 
-/* ---- trioeval ---- */
 static int cmd_trioeval(int argc, char **argv)
 {
 	yakamd_teopt_t o;
@@ -202,9 +209,8 @@ static int cmd_trioeval(int argc, char **argv)
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 2 >= argc) { arg_help("trioeval [options] <pat.yak> <mat.yak> <seq.fa>", defs, nd); return 1; }
 	if (no_frag) o.print_frag = 0;
-	yak_ch_t *tab = yak_ch_restore_core(0, argv[first], YAK_LOAD_TRIOBIN1, min_cnt, mid_cnt);
-	if (tab) tab = yak_ch_restore_core(tab, argv[first + 1], YAK_LOAD_TRIOBIN2, min_cnt, mid_cnt);
-	if (!tab) { fprintf(stderr, "yak-amd trioeval: cannot load %s and %s (or no MI355X)\n", argv[first], argv[first + 1]); return 2; }
+	yak_ch_t *tab = load_trio(argv, first, min_cnt, mid_cnt, "trioeval");
+	if (!tab) return 2;
 	static int64_t cnt[YAK_N_COUNTS];
 	yak_ch_hist(tab, cnt, o.n_threads);
 	fprintf(stderr, "[M::%s] %ld file1-specific k-mers and %ld file2-specific k-mers\n", "main_trioeval", (long)cnt[0<<2|2], (long)cnt[2<<2|0]);

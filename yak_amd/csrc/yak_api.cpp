@@ -107,7 +107,7 @@ yak_ch_t *yak_ch_init(int k, int pre, int n_hash, int n_shift)
 int multi_refuse(const yak_ch_t *h, const char *what)
 {
 	if (!YK_MULTI((const yak_ch_ext*)h)) return 0;
-	fprintf(stderr, "[E::%s] not available on a table sharded over prefix ranges (several GPUs, or a large unfiltered count taken in sweeps: YAKAMD_GPUS / YAKAMD_AUTO_SWEEP_GB)\n", what);
+	fprintf(stderr, "[E::%s] " YK_MSG_SHARDED " (several GPUs, or a large unfiltered count taken in sweeps: YAKAMD_GPUS / YAKAMD_AUTO_SWEEP_GB)\n", what);
 	return 1;
 }
 

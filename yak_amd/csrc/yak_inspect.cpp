@@ -10,14 +10,6 @@ namespace {
 
 const int NC = YAK_N_COUNTS;
 
-/* a device buffer kept from one batch to the next, grown when a batch needs more */
-struct DevBuf {
-	void *p = 0;
-	size_t cap = 0;
-	bool fit(size_t n) { if (n <= cap) return true; yakamd_dev_free(p); cap = n + n / 8; p = yakamd_dev_alloc(cap); if (!p) cap = 0; return p != 0; }
-	~DevBuf() { yakamd_dev_free(p); }
-};
-
 struct YakHead { int k, pre; };
 
 /* the 16-byte header of a .yak file (htab.c:378-380); false after a message */
@@ -81,7 +73,7 @@ struct BodyReader {
 };
 
 /* one batch on the device and joined into d_joint */
-bool join_batch(const Batch &b, yak_ch_t *ch, int k, int pre, int ref_probe, DevBuf &d_keys, DevBuf &d_off, uint64_t *d_joint)
+bool join_batch(const Batch &b, yak_ch_t *ch, int k, int pre, int ref_probe, GrowBuf &d_keys, GrowBuf &d_off, uint64_t *d_joint)
 {
 	if (b.keys.empty()) return true;
 	const size_t nk = b.keys.size(), no = b.off.size();
@@ -188,7 +180,7 @@ int yakamd_inspect(const yakamd_inopt_t *opt, const char *fn1, const char *fn2, 
 	rd.fp = fp; rd.fn = fn1; rd.P = 1 << h1.pre;
 	const int64_t cap = opt->batch_keys > 0 ? opt->batch_keys : 1;
 	Batch cur, nxt;
-	DevBuf d_keys, d_off;
+	GrowBuf d_keys, d_off;
 	double t_read = 0, t_join = 0;
 	{
 		const double a = yk_realtime();
@@ -248,7 +240,7 @@ int yakamd_inspect_tables(const yak_ch_t *a, const yak_ch_t *b, int ref_probe, i
 	uint64_t *d_joint = (uint64_t*)yakamd_dev_alloc((size_t)NC * NC * 8);
 	std::vector<int64_t> J((size_t)NC * NC, 0);
 	bool ok = d_joint && yakamd_memcpy_h2d(d_joint, J.data(), J.size() * 8) == 0;
-	DevBuf d_off;
+	GrowBuf d_off;
 	for (int r = 0; ok && r < n_rank; ++r) {
 		yak_ch_t *s = YK_MULTI(e) ? e->sub[r] : (yak_ch_t*)a;
 		yakamd_ctx *c = ea[r];

@@ -36,17 +36,9 @@ bool read_chunk(FxReader &fx, int64_t chunk_size, size_t max_bytes, bool want_na
 	return false;
 }
 
-/* a device buffer kept from one chunk to the next, grown when a chunk needs more */
-struct DevBuf {
-	void *p = 0;
-	size_t cap = 0;
-	bool fit(size_t n) { if (n <= cap) return true; yakamd_dev_free(p); cap = n + n / 8; p = yakamd_dev_alloc(cap); if (!p) cap = 0; return p != 0; }
-	~DevBuf() { yakamd_dev_free(p); }
-};
-
 /* a padded chunk's image, offsets and lengths on the device */
 struct DevChunk {
-	DevBuf img, off, len;
+	GrowBuf img, off, len;
 	bool put(const Chunk &c) {
 		const size_t ns = c.len.size();
 		return img.fit(c.img.size()) && off.fit(ns * 8) && len.fit(ns * 4) && yakamd_memcpy_h2d(img.p, c.img.data(), c.img.size()) == 0
@@ -69,6 +61,74 @@ char tb_classify(const int32_t *c, const int32_t *sc, int k, double ratio)
 	if (sc[0] >= k - 4 + sc[1] && sc[0] * 0.05 >= sc[1] && pat * ratio > mat) return 'p';
 	if (sc[1] >= k - 4 + sc[0] && sc[1] * 0.05 >= sc[0] && mat * ratio > pat) return 'm';
 	return 'a';
+}
+
+/* the lines a command writes, gathered and written out when 1 MiB has come together (drain) and after every chunk (flush); after a failed write
+ * nothing more is written */
+struct LineOut {
+	std::string s;
+	FILE *fp = 0;
+	bool ok = true;
+	void append(const char *t) { s += t; }
+	void append(const std::string &t) { s += t; }
+	void appendf(const char *fmt, ...) __attribute__((format(printf, 2, 3))) {
+		char buf[256];
+		va_list ap;
+		va_start(ap, fmt);
+		s.append(buf, (size_t)vsnprintf(buf, sizeof buf, fmt, ap));
+		va_end(ap);
+	}
+	void drain() { if (s.size() >= (1u << 20)) flush(); }
+	void flush() { ok = ok && fwrite(s.data(), 1, s.size(), fp) == s.size(); s.clear(); }
+};
+
+/* body(index of the input, chunk, the chunk on the device, length of its image before padding, out): the command's lookup, reduction and lines;
+ * false after a device error */
+typedef std::function<bool(int, const Chunk&, const DevChunk&, size_t, LineOut&)> ChunkBody;
+
+/* What triobin, trioeval, chkerr and sexchr share: every input in turn is read in chunks of `chunk_size` bases (bseq.c:54), each chunk uploaded and
+ * handed to `body`; the output (out_fn, or stdout) is `header`, body's lines, and what `tail` adds after the last chunk.  The next chunk is read on
+ * a second thread while the device and the writer work on this one (the reference's two-step kt_pipeline).  -1 after a message when an input or the
+ * output cannot be opened, a chunk fails (nothing from that chunk on is written) or a write fails */
+int run_chunks(const char *who, std::initializer_list<const char*> fns, const char *out_fn, int64_t chunk_size, const char *header,
+               const ChunkBody &body, const std::function<void(LineOut&)> &tail = nullptr)
+{
+	std::vector<FxReader> fx(fns.size());
+	auto close_all = [&]() { for (FxReader &f : fx) f.close_file(); };
+	size_t n_open = 0;
+	for (const char *fn : fns)                                       /* every input before the output is created */
+		if (!fx[n_open++].open_file(fn)) { fprintf(stderr, "[E::%s] cannot open '%s'\n", who, fn ? fn : "-"); close_all(); return -1; }
+	LineOut out;
+	out.fp = out_fn ? fopen(out_fn, "wb") : stdout;
+	if (!out.fp) { fprintf(stderr, "[E::%s] cannot write '%s'\n", who, out_fn); close_all(); return -1; }
+	if (chunk_size < 1) chunk_size = 1;
+	out.s = header;
+	DevChunk d;
+	Chunk cur, nxt;
+	bool ok = true;
+	for (size_t f = 0; ok && f < fx.size(); ++f) {
+		read_chunk(fx[f], chunk_size, SIZE_MAX, true, &cur);
+		while (ok && !cur.len.empty()) {
+			std::thread reader([&]() { read_chunk(fx[f], chunk_size, SIZE_MAX, true, &nxt); });
+			fprintf(stderr, "[M::%s] read %ld sequences\n", who, (long)cur.len.size());
+			const size_t nb = cur.pad();
+			ok = d.put(cur) && body((int)f, cur, d, nb, out) && out.ok;
+			if (ok) { out.flush(); ok = out.ok; }
+			reader.join();                                           /* nxt is the reader's until here, whatever became of this chunk */
+			std::swap(cur, nxt);
+		}
+		cur.clear();
+	}
+	if (ok) {
+		if (tail) tail(out);
+		out.flush();
+		ok = out.ok;
+	}
+	if (!ok) fprintf(stderr, "[E::%s] %s\n", who, yakamd_last_error());
+	if (out_fn) { if (fclose(out.fp) != 0) ok = false; }
+	else fflush(out.fp);
+	close_all();
+	return ok ? 0 : -1;
 }
 
 }   // namespace
@@ -103,7 +163,7 @@ void yak_qv(const yak_qopt_t *opt, const char *fn, const yak_ch_t *ch, int64_t *
 	std::vector<unsigned short> h_t;
 	Chunk chunk;
 	DevChunk d;
-	DevBuf d_t, d_tot, d_non0;
+	GrowBuf d_t, d_tot, d_non0;
 	bool ok = d_hist && yakamd_memcpy_h2d(d_hist, zero.data(), n_cnt * 8) == 0;
 	auto flush = [&]() {
 		const size_t ns = chunk.len.size();
@@ -188,70 +248,43 @@ void yakamd_tbopt_init(yakamd_tbopt_t *opt)
 
 /* reference triobin.c:123-197 with one device and -t1's output order: per chunk, the D lines of -p (triobin.c:89-90) of every
  * read in input order, then one line per read (triobin.c:144-145).  A chunk closes on the sum of the lengths alone: the D lines
- * are printed per chunk.  The next chunk is read on a second thread while the device and the writer work on this one (the
- * reference's two-step kt_pipeline). */
+ * are printed per chunk. */
 int yakamd_triobin(const yakamd_tbopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn)
 {
 	yak_ch_t *h = (yak_ch_t*)ch;
 	const int k = ch->k;
-	FxReader fx;
-	if (!fx.open_file(fn)) { fprintf(stderr, "[E::%s] cannot open '%s'\n", __func__, fn ? fn : "-"); return -1; }
-	FILE *out = out_fn ? fopen(out_fn, "wb") : stdout;
-	if (!out) { fprintf(stderr, "[E::%s] cannot write '%s'\n", __func__, out_fn); fx.close_file(); return -1; }
-	const int64_t chunk_size = opt->chunk_size > 0 ? opt->chunk_size : 1;
-	DevChunk d;
-	DevBuf d_flag, d_cnt;
+	GrowBuf d_flag, d_cnt;
 	std::vector<uint8_t> flag;
 	std::vector<int32_t> cnt;
-	std::string line;
-	Chunk cur, nxt;
-	read_chunk(fx, chunk_size, SIZE_MAX, true, &cur);
-	bool ok = true;
-	while (ok && !cur.len.empty()) {
-		std::thread reader([&]() { read_chunk(fx, chunk_size, SIZE_MAX, true, &nxt); });
+	return run_chunks(__func__, { fn }, out_fn, opt->chunk_size, "", [&](int, const Chunk &cur, const DevChunk &d, size_t nb, LineOut &out) {
 		const size_t ns = cur.len.size();
-		fprintf(stderr, "[M::%s] read %ld sequences\n", __func__, (long)ns);
-		const size_t nb = cur.pad();
 		cnt.resize(ns * 19);
-		ok = d.put(cur) && d_flag.fit(nb) && d_cnt.fit(ns * 19 * 4)
-		     && yakamd_triobin_lookup_dev(h, d.img.p, (int64_t)nb, d_flag.p) == 0
-		     && yakamd_triobin_reduce_dev(k, d_flag.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, (int32_t*)d_cnt.p, 0) == 0
-		     && yakamd_memcpy_d2h(cnt.data(), d_cnt.p, ns * 19 * 4) == 0;
+		bool ok = d_flag.fit(nb) && d_cnt.fit(ns * 19 * 4)
+		          && yakamd_triobin_lookup_dev(h, d.img.p, (int64_t)nb, d_flag.p) == 0
+		          && yakamd_triobin_reduce_dev(k, d_flag.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, (int32_t*)d_cnt.p, 0) == 0
+		          && yakamd_memcpy_d2h(cnt.data(), d_cnt.p, ns * 19 * 4) == 0;
 		if (ok && opt->print_diff) {
 			flag.resize(nb);
 			ok = yakamd_memcpy_d2h(flag.data(), d_flag.p, nb) == 0;
-			char buf[64];
-			for (size_t j = 0; ok && j < ns; ++j) {
+			for (size_t j = 0; ok && out.ok && j < ns; ++j) {
 				const uint8_t *f = flag.data() + cur.off[j];
 				for (uint32_t i = 0; i < cur.len[j]; ++i) {
 					const int v = f[i];
 					if (v == 0xff || (v >> 2 & 3) == (v & 3)) continue;     /* no k-mer ends here, or both parents agree */
-					line += "D\t"; line += cur.names[j];
-					line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%u\t%d\t%d\n", i, v & 3, v >> 2 & 3));
+					out.append("D\t"); out.append(cur.names[j]);
+					out.appendf("\t%u\t%d\t%d\n", i, v & 3, v >> 2 & 3);
 				}
-				if (line.size() >= (1u << 20)) { ok = fwrite(line.data(), 1, line.size(), out) == line.size(); line.clear(); }
+				out.drain();
 			}
 		}
-		if (ok) {
-			char buf[160];
-			for (size_t j = 0; j < ns; ++j) {
-				const int32_t *c = cnt.data() + j * 19, *sc = c + 16;
-				line += cur.names[j];
-				line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%c\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", tb_classify(c, sc, k, opt->ratio_thres),
-				                                  sc[0], sc[1], c[2], c[8], c[1], c[4], c[18], c[0]));
-				if (line.size() >= (1u << 20)) { ok = fwrite(line.data(), 1, line.size(), out) == line.size(); line.clear(); if (!ok) break; }
-			}
-			ok = ok && fwrite(line.data(), 1, line.size(), out) == line.size();
-			line.clear();
+		for (size_t j = 0; ok && out.ok && j < ns; ++j) {
+			const int32_t *c = cnt.data() + j * 19, *sc = c + 16;
+			out.append(cur.names[j]);
+			out.appendf("\t%c\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", tb_classify(c, sc, k, opt->ratio_thres), sc[0], sc[1], c[2], c[8], c[1], c[4], c[18], c[0]);
+			out.drain();
 		}
-		reader.join();
-		std::swap(cur, nxt);
-	}
-	if (!ok) fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error());
-	if (out_fn) { if (fclose(out) != 0) ok = false; }
-	else fflush(out);
-	fx.close_file();
-	return ok ? 0 : -1;
+		return ok;
+	});
 }
 
 /* reference trioeval.c:146-147 */
@@ -267,19 +300,13 @@ void yakamd_teopt_init(yakamd_teopt_t *opt)
 
 /* reference trioeval.c:119-212 with one device and -t1's output order: the C header, then per chunk the F / E lines of every sequence in
  * input order (trioeval.c:101-116, from the ordered streak list) and one S line per sequence (trioeval.c:136-145), then the W / H / N
- * lines.  A chunk closes where bseq_read(fp, 1000000000) closes it.  The next chunk is read on a second thread while the device and the
- * writer work on this one (the reference's two-step kt_pipeline). */
+ * lines.  A chunk closes where bseq_read(fp, 1000000000) closes it. */
 int yakamd_trioeval(const yakamd_teopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn)
 {
 	yak_ch_t *h = (yak_ch_t*)ch;
 	const int k = ch->k;
-	FxReader fx;
-	if (!fx.open_file(fn)) { fprintf(stderr, "[E::%s] cannot open '%s'\n", __func__, fn ? fn : "-"); return -1; }
-	FILE *out = out_fn ? fopen(out_fn, "wb") : stdout;
-	if (!out) { fprintf(stderr, "[E::%s] cannot write '%s'\n", __func__, out_fn); fx.close_file(); return -1; }
-	const int64_t chunk_size = opt->chunk_size > 0 ? opt->chunk_size : 1;
 	const bool want_list = opt->print_err || opt->print_frag;
-	std::string line =
+	const char *header =
 		"C\tS  seqName     #patKmer  #matKmer  #pat-pat  #pat-mat  #mat-pat  #mat-mat  seqLen\n"
 		"C\tF  seqName     type      startPos  endPos    count\n"
 		"C\tW  #switchErr  denominator  switchErrRate\n"
@@ -287,46 +314,37 @@ int yakamd_trioeval(const yakamd_teopt_t *opt, const yak_ch_t *ch, const char *f
 		"C\tN  #totPatKmer #totMatKmer  errRate\n"
 		"C\n";
 	int64_t n_pair = 0, n_site = 0, n_switch = 0, n_err = 0, n_par[2] = { 0, 0 };
-	DevChunk d;
-	DevBuf d_flag, d_cnt;
+	GrowBuf d_flag, d_cnt;
 	std::vector<int32_t> cnt;
 	std::vector<yakamd_streak_t> sk;
-	Chunk cur, nxt;
-	read_chunk(fx, chunk_size, SIZE_MAX, true, &cur);
-	bool ok = true;
-	auto drain = [&]() { if (line.size() >= (1u << 20)) { ok = ok && fwrite(line.data(), 1, line.size(), out) == line.size(); line.clear(); } };
-	while (ok && !cur.len.empty()) {
-		std::thread reader([&]() { read_chunk(fx, chunk_size, SIZE_MAX, true, &nxt); });
+	return run_chunks(__func__, { fn }, out_fn, opt->chunk_size, header, [&](int, const Chunk &cur, const DevChunk &d, size_t nb, LineOut &out) {
 		const size_t ns = cur.len.size();
-		fprintf(stderr, "[M::%s] read %ld sequences\n", __func__, (long)ns);
-		const size_t nb = cur.pad();
 		cnt.resize(ns * 6);
 		void *d_sk = 0;
 		int64_t n_sk = 0;
-		ok = d.put(cur) && d_flag.fit(nb) && d_cnt.fit(ns * 6 * 4)
-		     && yakamd_triobin_lookup_dev(h, d.img.p, (int64_t)nb, d_flag.p) == 0
-		     && yakamd_trioeval_reduce_dev(k, opt->min_n, d_flag.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, (int64_t)nb,
-		                                   (int32_t*)d_cnt.p, want_list ? &d_sk : 0, &n_sk, 0) == 0
-		     && yakamd_memcpy_d2h(cnt.data(), d_cnt.p, ns * 6 * 4) == 0;
+		bool ok = d_flag.fit(nb) && d_cnt.fit(ns * 6 * 4)
+		          && yakamd_triobin_lookup_dev(h, d.img.p, (int64_t)nb, d_flag.p) == 0
+		          && yakamd_trioeval_reduce_dev(k, opt->min_n, d_flag.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, (int64_t)nb,
+		                                        (int32_t*)d_cnt.p, want_list ? &d_sk : 0, &n_sk, 0) == 0
+		          && yakamd_memcpy_d2h(cnt.data(), d_cnt.p, ns * 6 * 4) == 0;
 		sk.resize(want_list ? (size_t)n_sk : 0);
 		if (ok && want_list && n_sk > 0) ok = yakamd_memcpy_d2h(sk.data(), d_sk, (size_t)n_sk * sizeof(yakamd_streak_t)) == 0;
 		yakamd_dev_free(d_sk);
 		if (ok && want_list) {                                    /* trioeval.c:101-116 per sequence, in input order */
-			char buf[96];
 			uint32_t seq = UINT32_MAX, last = 0, f_type = 0;
 			int f_st = 0, f_en = 0, f_cnt = 0;
 			auto frag = [&]() {
 				if (f_type > 0 && opt->print_frag) {
-					line += "F\t"; line += cur.names[seq];
-					line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%d\n", (int)f_type, f_st, f_en, f_cnt));
+					out.append("F\t"); out.append(cur.names[seq]);
+					out.appendf("\t%d\t%d\t%d\t%d\n", (int)f_type, f_st, f_en, f_cnt);
 				}
 			};
-			for (int64_t i = 0; ok && i < n_sk; ++i) {
+			for (int64_t i = 0; out.ok && i < n_sk; ++i) {
 				const yakamd_streak_t &s = sk[i];
-				if (s.seq != seq) { if (seq != UINT32_MAX) frag(); seq = s.seq; last = 0; f_type = 0; drain(); }
+				if (s.seq != seq) { if (seq != UINT32_MAX) frag(); seq = s.seq; last = 0; f_type = 0; out.drain(); }
 				if (last > 0 && opt->print_err && last != s.type) {
-					line += "E\t"; line += cur.names[seq];
-					line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%d\t%d\t%d\n", (int)s.en, (int)last, (int)s.type));
+					out.append("E\t"); out.append(cur.names[seq]);
+					out.appendf("\t%d\t%d\t%d\n", (int)s.en, (int)last, (int)s.type);
 				}
 				if (f_type != s.type) { frag(); f_type = s.type; f_st = (int)s.st + 1 - k; f_cnt = 0; }
 				++f_cnt; f_en = (int)s.en + 1;
@@ -334,39 +352,25 @@ int yakamd_trioeval(const yakamd_teopt_t *opt, const yak_ch_t *ch, const char *f
 			}
 			if (seq != UINT32_MAX) frag();
 		}
-		if (ok) {
-			char buf[160];
-			for (size_t j = 0; j < ns; ++j) {                      /* trioeval.c:136-145 */
-				const int32_t *dd = cnt.data() + j * 6, *c = dd + 2;
-				n_par[0] += dd[0]; n_par[1] += dd[1];
-				if (dd[0] + dd[1] >= 2) {
-					n_pair += c[0] + c[1] + c[2] + c[3];
-					n_switch += c[1] + c[2];
-					n_site += dd[0] + dd[1];
-					n_err += dd[0] < dd[1] ? dd[0] : dd[1];
-				}
-				line += "S\t"; line += cur.names[j];
-				line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", dd[0], dd[1], c[0], c[1], c[2], c[3], (int)cur.len[j]));
-				drain();
-				if (!ok) break;
+		for (size_t j = 0; ok && out.ok && j < ns; ++j) {          /* trioeval.c:136-145 */
+			const int32_t *dd = cnt.data() + j * 6, *c = dd + 2;
+			n_par[0] += dd[0]; n_par[1] += dd[1];
+			if (dd[0] + dd[1] >= 2) {
+				n_pair += c[0] + c[1] + c[2] + c[3];
+				n_switch += c[1] + c[2];
+				n_site += dd[0] + dd[1];
+				n_err += dd[0] < dd[1] ? dd[0] : dd[1];
 			}
+			out.append("S\t"); out.append(cur.names[j]);
+			out.appendf("\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n", dd[0], dd[1], c[0], c[1], c[2], c[3], (int)cur.len[j]);
+			out.drain();
 		}
-		reader.join();
-		std::swap(cur, nxt);
-	}
-	if (ok) {                                                     /* trioeval.c:207-209: the operands' order and types as there */
-		char buf[256];
-		line.append(buf, (size_t)snprintf(buf, sizeof buf, "W\t%ld\t%ld\t%.6f\n", (long)n_switch, (long)n_pair, (double)n_switch / n_pair));
-		line.append(buf, (size_t)snprintf(buf, sizeof buf, "H\t%ld\t%ld\t%.6f\n", (long)n_err, (long)n_site, (double)n_err / n_site));
-		line.append(buf, (size_t)snprintf(buf, sizeof buf, "N\t%ld\t%ld\t%.6f\n", (long)n_par[0], (long)n_par[1],
-		                                  (double)(n_par[0] < n_par[1] ? n_par[0] : n_par[1]) / (n_par[0] + n_par[1])));
-		ok = fwrite(line.data(), 1, line.size(), out) == line.size();
-	}
-	if (!ok) fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error());
-	if (out_fn) { if (fclose(out) != 0) ok = false; }
-	else fflush(out);
-	fx.close_file();
-	return ok ? 0 : -1;
+		return ok;
+	}, [&](LineOut &out) {                                         /* trioeval.c:207-209: the operands' order and types as there */
+		out.appendf("W\t%ld\t%ld\t%.6f\n", (long)n_switch, (long)n_pair, (double)n_switch / n_pair);
+		out.appendf("H\t%ld\t%ld\t%.6f\n", (long)n_err, (long)n_site, (double)n_err / n_site);
+		out.appendf("N\t%ld\t%ld\t%.6f\n", (long)n_par[0], (long)n_par[1], (double)(n_par[0] < n_par[1] ? n_par[0] : n_par[1]) / (n_par[0] + n_par[1]));
+	});
 }
 
 /* reference chkerr.c:104-106 */
@@ -383,59 +387,35 @@ void yakamd_ceopt_init(yakamd_ceopt_t *opt)
  * Each chunk is looked up into one byte per position (yakamd_chkerr_lookup_dev: 1 = low) and its streaks listed in order
  * (yakamd_chkerr_streaks_dev).  With min_streak < 0, te_worker also prints its initial `streak = 0, last = -1` (chkerr.c:62-64 when the first
  * low k-mer is not at position 0, chkerr.c:67 when there is none): `name \t 1-k \t 0 \t 0` ahead of the sequence's streaks, unless its first
- * streak starts at position 0 (k = 1).  The next chunk is read on a second thread while the device and the writer work on this one. */
+ * streak starts at position 0 (k = 1). */
 int yakamd_chkerr(const yakamd_ceopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn)
 {
 	yak_ch_t *h = (yak_ch_t*)ch;
 	const int k = ch->k;
 	if (multi_refuse(ch, __func__)) return -1;                  /* the lookup kernel reads one table image */
-	FxReader fx;
-	if (!fx.open_file(fn)) { fprintf(stderr, "[E::%s] cannot open '%s'\n", __func__, fn ? fn : "-"); return -1; }
-	FILE *out = out_fn ? fopen(out_fn, "wb") : stdout;
-	if (!out) { fprintf(stderr, "[E::%s] cannot write '%s'\n", __func__, out_fn); fx.close_file(); return -1; }
-	const int64_t chunk_size = opt->chunk_size > 0 ? opt->chunk_size : 1;
 	const bool phantom = opt->min_streak < 0;
-	DevChunk d;
-	DevBuf d_low;
+	GrowBuf d_low;
 	std::vector<yakamd_streak_t> sk;
-	std::string line;
-	Chunk cur, nxt;
-	read_chunk(fx, chunk_size, SIZE_MAX, true, &cur);
-	bool ok = true;
-	char buf[64];
-	const int nb_ph = snprintf(buf, sizeof buf, "\t%d\t0\t0\n", 1 - k);
-	const std::string ph(buf, (size_t)nb_ph);
-	while (ok && !cur.len.empty()) {
-		std::thread reader([&]() { read_chunk(fx, chunk_size, SIZE_MAX, true, &nxt); });
+	return run_chunks(__func__, { fn }, out_fn, opt->chunk_size, "", [&](int, const Chunk &cur, const DevChunk &d, size_t nb, LineOut &out) {
 		const size_t ns = cur.len.size();
-		fprintf(stderr, "[M::%s] read %ld sequences\n", __func__, (long)ns);
-		const size_t nb = cur.pad();
 		void *d_sk = 0;
 		int64_t n_sk = 0;
-		ok = d.put(cur) && d_low.fit(nb) && yakamd_chkerr_lookup_dev(h, d.img.p, (int64_t)nb, opt->min_cnt, d_low.p) == 0
-		     && yakamd_chkerr_streaks_dev(opt->min_streak, d_low.p, (const uint64_t*)d.off.p, (int64_t)ns, (int64_t)nb, &d_sk, &n_sk, 0) == 0;
+		bool ok = d_low.fit(nb) && yakamd_chkerr_lookup_dev(h, d.img.p, (int64_t)nb, opt->min_cnt, d_low.p) == 0
+		          && yakamd_chkerr_streaks_dev(opt->min_streak, d_low.p, (const uint64_t*)d.off.p, (int64_t)ns, (int64_t)nb, &d_sk, &n_sk, 0) == 0;
 		sk.resize((size_t)n_sk);
 		if (ok && n_sk > 0) ok = yakamd_memcpy_d2h(sk.data(), d_sk, (size_t)n_sk * sizeof(yakamd_streak_t)) == 0;
 		yakamd_dev_free(d_sk);
-		for (size_t j = 0, i = 0; ok && j < ns; ++j) {             /* the sequences in input order, each with its streaks */
-			if (phantom && !(i < sk.size() && sk[i].seq == j && sk[i].st == 0)) { line += cur.names[j]; line += ph; }
+		for (size_t j = 0, i = 0; ok && out.ok && j < ns; ++j) {   /* the sequences in input order, each with its streaks */
+			if (phantom && !(i < sk.size() && sk[i].seq == j && sk[i].st == 0)) { out.append(cur.names[j]); out.appendf("\t%d\t0\t0\n", 1 - k); }
 			for (; i < sk.size() && sk[i].seq == j; ++i) {
 				const yakamd_streak_t &s = sk[i];
-				line += cur.names[j];
-				line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%d\t%d\t%d\n", (int)s.st + 1 - k, (int)s.en, (int)(s.en - s.st)));
+				out.append(cur.names[j]);
+				out.appendf("\t%d\t%d\t%d\n", (int)s.st + 1 - k, (int)s.en, (int)(s.en - s.st));
 			}
-			if (line.size() >= (1u << 20)) { ok = fwrite(line.data(), 1, line.size(), out) == line.size(); line.clear(); }
+			out.drain();
 		}
-		ok = ok && fwrite(line.data(), 1, line.size(), out) == line.size();
-		line.clear();
-		reader.join();
-		std::swap(cur, nxt);
-	}
-	if (!ok) fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error());
-	if (out_fn) { if (fclose(out) != 0) ok = false; }
-	else fflush(out);
-	fx.close_file();
-	return ok ? 0 : -1;
+		return ok;
+	});
 }
 
 /* reference sexchr.c:113-114 and 13 */
@@ -448,57 +428,27 @@ void yakamd_scopt_init(yakamd_scopt_t *opt)
 
 /* reference sexchr.c:28-140 with one device and -t1's output order: the two C lines, then one S line per sequence of hap1, then of hap2.  Each
  * chunk is looked up into flags (yakamd_triobin_lookup_dev: the three SEXCHR loads OR 1, 2 and 4 into a count field) and tallied per sequence
- * (yakamd_sexchr_reduce_dev).  The next chunk is read on a second thread while the device and the writer work on this one. */
+ * (yakamd_sexchr_reduce_dev). */
 int yakamd_sexchr(const yakamd_scopt_t *opt, const yak_ch_t *ch, const char *fn_hap1, const char *fn_hap2, const char *out_fn)
 {
 	yak_ch_t *h = (yak_ch_t*)ch;
 	if (multi_refuse(ch, __func__)) return -1;
-	FxReader fx[2];
-	const char *fns[2] = { fn_hap1, fn_hap2 };
-	for (int i = 0; i < 2; ++i)
-		if (!fx[i].open_file(fns[i])) {
-			fprintf(stderr, "[E::%s] cannot open '%s'\n", __func__, fns[i] ? fns[i] : "-");
-			if (i) fx[0].close_file();
-			return -1;
-		}
-	FILE *out = out_fn ? fopen(out_fn, "wb") : stdout;
-	if (!out) { fprintf(stderr, "[E::%s] cannot write '%s'\n", __func__, out_fn); fx[0].close_file(); fx[1].close_file(); return -1; }
-	const int64_t chunk_size = opt->chunk_size > 0 ? opt->chunk_size : 1;
-	std::string line = "C\tS  seqName  originalHap  0  #k-mer  #sexchr  #sex1-specifc  #sex2-specific\nC\n";   /* sexchr.c:120-121, its spelling */
-	DevChunk d;
-	DevBuf d_flag, d_cnt;
+	const char *header = "C\tS  seqName  originalHap  0  #k-mer  #sexchr  #sex1-specifc  #sex2-specific\nC\n";   /* sexchr.c:120-121, its spelling */
+	GrowBuf d_flag, d_cnt;
 	std::vector<uint64_t> cnt;
-	Chunk cur, nxt;
-	bool ok = true;
-	char buf[128];
-	for (int hap = 1; ok && hap <= 2; ++hap) {
-		FxReader &f = fx[hap - 1];
-		read_chunk(f, chunk_size, SIZE_MAX, true, &cur);
-		while (ok && !cur.len.empty()) {
-			std::thread reader([&]() { read_chunk(f, chunk_size, SIZE_MAX, true, &nxt); });
-			const size_t ns = cur.len.size();
-			fprintf(stderr, "[M::%s] read %ld sequences\n", __func__, (long)ns);
-			const size_t nb = cur.pad();
-			cnt.resize(ns * 4);
-			ok = d.put(cur) && d_flag.fit(nb) && d_cnt.fit(ns * 32)
-			     && yakamd_triobin_lookup_dev(h, d.img.p, (int64_t)nb, d_flag.p) == 0
-			     && yakamd_sexchr_reduce_dev(d_flag.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, (int64_t)nb, (uint64_t*)d_cnt.p, 0) == 0
-			     && yakamd_memcpy_d2h(cnt.data(), d_cnt.p, ns * 32) == 0;
-			for (size_t j = 0; ok && j < ns; ++j) {
-				const uint64_t *c = cnt.data() + j * 4;
-				line += "S\t"; line += cur.names[j];
-				line.append(buf, (size_t)snprintf(buf, sizeof buf, "\t%d\t0\t%ld\t%ld\t%ld\t%ld\n", hap, (long)c[0], (long)c[1], (long)c[2], (long)c[3]));
-				if (line.size() >= (1u << 20)) { ok = fwrite(line.data(), 1, line.size(), out) == line.size(); line.clear(); }
-			}
-			reader.join();
-			std::swap(cur, nxt);
+	return run_chunks(__func__, { fn_hap1, fn_hap2 }, out_fn, opt->chunk_size, header, [&](int file, const Chunk &cur, const DevChunk &d, size_t nb, LineOut &out) {
+		const size_t ns = cur.len.size();
+		cnt.resize(ns * 4);
+		const bool ok = d_flag.fit(nb) && d_cnt.fit(ns * 32)
+		                && yakamd_triobin_lookup_dev(h, d.img.p, (int64_t)nb, d_flag.p) == 0
+		                && yakamd_sexchr_reduce_dev(d_flag.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, (int64_t)nb, (uint64_t*)d_cnt.p, 0) == 0
+		                && yakamd_memcpy_d2h(cnt.data(), d_cnt.p, ns * 32) == 0;
+		for (size_t j = 0; ok && out.ok && j < ns; ++j) {
+			const uint64_t *c = cnt.data() + j * 4;
+			out.append("S\t"); out.append(cur.names[j]);
+			out.appendf("\t%d\t0\t%ld\t%ld\t%ld\t%ld\n", file + 1, (long)c[0], (long)c[1], (long)c[2], (long)c[3]);
+			out.drain();
 		}
-		cur.clear();
-	}
-	ok = ok && fwrite(line.data(), 1, line.size(), out) == line.size();
-	if (!ok) fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error());
-	if (out_fn) { if (fclose(out) != 0) ok = false; }
-	else fflush(out);
-	fx[0].close_file(); fx[1].close_file();
-	return ok ? 0 : -1;
+		return ok;
+	});
 }
