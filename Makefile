@@ -33,10 +33,12 @@ yak_amd/yak_lookup.o: $(CSRC)/yak_lookup.cpp $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/yak_inspect.o: $(CSRC)/yak_inspect.cpp $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/pool.o yak_amd/engine.o yak_amd/layout.o yak_amd/lookup_dev.o yak_amd/yak_api.o yak_amd/yak_reader.o yak_amd/yak_multi.o yak_amd/yak_lookup.o yak_amd/yak_inspect.o $(CSRC)/libyak_amd.map
+yak_amd/yak_print.o: $(CSRC)/yak_print.cpp $(HOSTDEPS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/pool.o yak_amd/engine.o yak_amd/layout.o yak_amd/lookup_dev.o yak_amd/yak_api.o yak_amd/yak_reader.o yak_amd/yak_multi.o yak_amd/yak_lookup.o yak_amd/yak_inspect.o yak_amd/yak_print.o $(CSRC)/libyak_amd.map
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(CSRC)/libyak_amd.map -o $@ $(filter %.o,$^) -lz
 
-yak_amd/yak-amd: $(CSRC)/main.c include/yak.h yak_amd/libyak_amd.so
+yak_amd/yak-amd: $(CSRC)/main.c include/yak.h include/yak_amd.h yak_amd/libyak_amd.so
 	gcc -O2 -Wall -Iinclude $(CSRC)/main.c -o $@ -Lyak_amd -lyak_amd -Wl,-rpath,'$$ORIGIN' -lz
 
 tools:

@@ -219,6 +219,31 @@ typedef struct {
 void yakamd_scopt_init(yakamd_scopt_t *opt);
 int yakamd_sexchr(const yakamd_scopt_t *opt, const yak_ch_t *ch, const char *fn_hap1, const char *fn_hap2, const char *out_fn);
 
+/* `yak print` (reference main.c:286-323) on the device: the stored k-mers of sub-tables [sub_lo, sub_hi), sub-table after sub-table in ascending
+ * slot order -- what yak_ch_getseq() returns for each of them, without a host mirror of the table.  k must be below 32 (htab.c:359); the table is
+ * listed as it is (yak_ch_tighten() first for the reference's order).  A table sharded over prefix ranges is served when its shards are on one
+ * device (yakamd_print: on any), not inside an open pass.
+ * yakamd_kmers_dev(): k-mer i as d_x_u64[i] (2 bits per base, the first base highest) and its count as d_c_u16[i], caller-owned device arrays of
+ * `cap` elements.  Returns the number of k-mers; when cap is smaller or a pointer is NULL, the number needed, and nothing is written.
+ * yakamd_print_dev(): the bytes main.c:308-317 writes for them -- k letters and '\n', or with_counts letters, '\t', the count in decimal and '\n' --
+ * into d_text (cap_bytes); the same convention for the byte count.  -1 after a message (yakamd_last_error()). */
+int64_t yakamd_kmers_dev(yak_ch_t *h, int sub_lo, int sub_hi, void *d_x_u64, void *d_c_u16, int64_t cap);
+int64_t yakamd_print_dev(yak_ch_t *h, int sub_lo, int sub_hi, int with_counts, void *d_text, int64_t cap_bytes);
+/* the whole table as text to out_fn (NULL or "-" = stdout; a pipe works), in ranges of whole sub-tables whose text fits batch_bytes of device
+ * memory (two such buffers are held) -- a sub-table is never split, so the largest sub-table's text is the floor of a range whatever
+ * batch_bytes says.  The text crosses the bus in pinned pieces and is written while the next range is formatted.  0, or -1 after a message
+ * (k >= 32: before anything is written) */
+typedef struct {
+	int32_t with_counts;      /* -c, 0: a tab and the count behind every k-mer */
+	int32_t n_threads;        /* 4: accepted for symmetry with the other commands; one thread copies and writes */
+	int64_t batch_bytes;      /* device bytes of one range's text, 256 MiB */
+} yakamd_propt_t;
+void yakamd_propt_init(yakamd_propt_t *opt);
+int yakamd_print(const yakamd_propt_t *opt, const yak_ch_t *ch, const char *out_fn);
+/* how often this process has copied a table image to its host mirror (yakamd_sync_host and the yak.h calls that read the mirror: yak_ch_get,
+ * yak_ch_getseq); the listing above never does */
+int64_t yakamd_host_syncs(void);
+
 /* `yak inspect` (reference inspect.c) on the device.  yakamd_inspect_dev() is its join: every stored key of table A adds one to
  * d_joint[c0 * 1024 + c1] (uint64 bins, accumulated: zero them first), c0 = key & 1023 its count in A, c1 = max(0, yak_ch_get(b, h)) its count in
  * b (0 when b is NULL: one table).  The keys are those of A's sub-tables [sub_lo, sub_hi) in dump order, d_sub_off[j] = keys before sub-table

@@ -39,6 +39,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_inspect_dev", "yakamd_inopt_init", "yakamd_inspect", "yakamd_inspect_tables",
     "yakamd_chkerr_lookup_dev", "yakamd_chkerr_streaks_dev", "yakamd_ceopt_init", "yakamd_chkerr",
     "yakamd_sexchr_reduce_dev", "yakamd_scopt_init", "yakamd_sexchr",
+    "yakamd_kmers_dev", "yakamd_print_dev", "yakamd_propt_init", "yakamd_print", "yakamd_host_syncs",
 ]
 
 
@@ -81,6 +82,10 @@ class CeoptT(C.Structure):                     # yakamd_ceopt_t, include/yak_amd
 
 class ScoptT(C.Structure):                     # yakamd_scopt_t, include/yak_amd.h
     _fields_ = [("n_threads", C.c_int32), ("chunk_size", C.c_int64)]
+
+
+class PropT(C.Structure):                      # yakamd_propt_t, include/yak_amd.h
+    _fields_ = [("with_counts", C.c_int32), ("n_threads", C.c_int32), ("batch_bytes", C.c_int64)]
 
 
 class StreakT(C.Structure):                    # yakamd_streak_t, include/yak_amd.h
@@ -248,6 +253,14 @@ def lib():
     L.yakamd_sexchr_reduce_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     L.yakamd_scopt_init.restype = None; L.yakamd_scopt_init.argtypes = [P(ScoptT)]
     L.yakamd_sexchr.restype = C.c_int; L.yakamd_sexchr.argtypes = [P(ScoptT), P(ChT), C.c_char_p, C.c_char_p, C.c_char_p]
+    L.yakamd_kmers_dev.restype = C.c_int64
+    L.yakamd_kmers_dev.argtypes = [P(ChT), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+    L.yakamd_print_dev.restype = C.c_int64
+    L.yakamd_print_dev.argtypes = [P(ChT), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+    L.yakamd_propt_init.restype = None; L.yakamd_propt_init.argtypes = [P(PropT)]
+    L.yakamd_print.restype = C.c_int; L.yakamd_print.argtypes = [P(PropT), P(ChT), C.c_char_p]
+    L.yakamd_host_syncs.restype = C.c_int64; L.yakamd_host_syncs.argtypes = []
+    L.yak_ch_tighten.restype = None; L.yak_ch_tighten.argtypes = [P(ChT)]
     _lib = L
     return L
 
@@ -572,6 +585,60 @@ def inspect_tables(a, b=None, ref_probe=False):
     if L.yakamd_inspect_tables(ha, hb, int(bool(ref_probe)), J.ctypes.data_as(C.POINTER(C.c_int64))) != 0:
         raise RuntimeError("yakamd_inspect_tables failed: " + _err())
     return J
+
+
+def print_table(h, counts=False, batch_bytes=None):
+    """yakamd_print of a resident table (a ``yak_ch_t *``), as it is: the bytes `yak print [-c]` writes"""
+    L = lib()
+    o = PropT()
+    L.yakamd_propt_init(C.byref(o))
+    o.with_counts = int(bool(counts))
+    if batch_bytes is not None:
+        o.batch_bytes = batch_bytes
+    return _output_of("yakamd_print", lambda out: L.yakamd_print(C.byref(o), h, out))
+
+
+def print_kmers(table_fn, counts=False, batch_bytes=None, tighten=True):
+    """`yak print [-c]` through the C ABI (yak_ch_restore, yak_ch_tighten, yakamd_print): the bytes the reference writes to stdout"""
+    L = lib()
+    h = L.yak_ch_restore(table_fn.encode())
+    if not h:
+        raise RuntimeError("print: cannot load " + table_fn)
+    try:
+        if tighten:
+            L.yak_ch_tighten(h)
+        return print_table(h, counts, batch_bytes)
+    finally:
+        L.yak_ch_destroy(h)
+
+
+def kmers(table, sub_lo=0, sub_hi=None):
+    """the k-mers of sub-tables [sub_lo, sub_hi) of a .yak file (restored, not tightened) or of a resident table (``yak_ch_t *``), in
+    yak_ch_getseq's order (yakamd_kmers_dev): (numpy uint64 k-mers, numpy uint16 counts)"""
+    import numpy as np
+    L = lib()
+    own = isinstance(table, str)
+    h = L.yak_ch_restore(table.encode()) if own else table
+    if not h:
+        raise RuntimeError("kmers: cannot load %s" % (table,))
+    dx = dc = None
+    try:
+        hi = (1 << h.contents.pre) if sub_hi is None else sub_hi
+        n = L.yakamd_kmers_dev(h, sub_lo, hi, None, None, 0)
+        if n < 0:
+            raise RuntimeError("yakamd_kmers_dev failed: " + _err())
+        x, c = np.zeros(n, np.uint64), np.zeros(n, np.uint16)
+        if n:
+            dx, dc = L.yakamd_dev_alloc(n * 8), L.yakamd_dev_alloc(n * 2)
+            if not dx or not dc or L.yakamd_kmers_dev(h, sub_lo, hi, dx, dc, n) != n:
+                raise RuntimeError("yakamd_kmers_dev failed: " + _err())
+            if L.yakamd_memcpy_d2h(x.ctypes.data, dx, n * 8) != 0 or L.yakamd_memcpy_d2h(c.ctypes.data, dc, n * 2) != 0:
+                raise RuntimeError("kmers: copy back failed")
+        return x, c
+    finally:
+        L.yakamd_dev_free(dx); L.yakamd_dev_free(dc)
+        if own:
+            L.yak_ch_destroy(h)
 
 
 def pack_bases_host(buf):

@@ -23,6 +23,7 @@
 #include <mutex>
 #include <algorithm>
 #include <chrono>
+#include <atomic>
 #include "engine_int.h"
 
 static thread_local char g_err[512] = "";
@@ -1835,6 +1836,9 @@ int yk_ctx_load(yakamd_ctx *c, const uint32_t *caps, const uint32_t *sizes, cons
  * ------------------------------------------------------------------------------------------ */
 struct yak_ht_t { uint32_t bits, count; uint32_t *used; uint64_t *keys; };   /* same shape as khashl.h:104-109 */
 
+static std::atomic<int64_t> g_host_syncs{0};
+extern "C" int64_t yakamd_host_syncs(void) { return g_host_syncs.load(); }
+
 int yk_ctx_sync_host(yakamd_ctx *c, yak_ch_t *h)
 {
 	/* yak_ch_get() is called concurrently by the reference's kt_for workers (qv.c:59, triobin.c): the
@@ -1844,6 +1848,7 @@ int yk_ctx_sync_host(yakamd_ctx *c, yak_ch_t *h)
 	std::lock_guard<std::mutex> lk(mu);
 	if (c->host_valid) return 0;
 	HIPCK(hipSetDevice(c->dev));
+	++g_host_syncs;
 	if (c->hm_slots < c->n_slots) {
 		if (c->hm_keys) hipHostFree(c->hm_keys);
 		if (c->hm_used) hipHostFree(c->hm_used);

@@ -10,6 +10,7 @@
  *   srt k_seg_sort_pass  per sub-table LSD radix sort by insertion time
  *   K5  k_replay         exact khashl layout: staged FCFS placement + in-place doubling [khashl.h:152-221]
  * `yak inspect` (inspect.c:47-62): k_inspect joins the stored keys of one table with another table's image into a 1024 x 1024 histogram.
+ * `yak print` (main.c:302-320): k_kmers and k_print turn the stored keys back into k-mers and into the text the reference writes.
  * All work is 64-bit integer arithmetic; the bound is HBM / L2-atomic traffic, never MFMA.
  *
  * One translation unit, cut by stage into the kern_*.inc files included at the end of this file (device helpers and __device__ globals are
@@ -97,4 +98,5 @@ __device__ const unsigned char d_nt4[256] = {
 #include "kern_count.inc"
 #include "kern_pass2.inc"
 #include "kern_inspect.inc"
+#include "kern_print.inc"
 #include "kern_launch.inc"

@@ -2,7 +2,7 @@
  * main.c -- `yak-amd`: the repo's own small command-line driver of libyak_amd.so, plain C against
  * include/yak.h (and include/yak_amd.h for triobin and -X).  It is a test and benchmark vehicle (tests/, bench.py's e2e_cli figure), not a
  * re-creation of the reference's CLI: that one runs unmodified on the library (INTEGRATION.md section 2,
- * oracle/_ref/yak_on_amd).  Seven sub-commands drive the call sequences the library serves:
+ * oracle/_ref/yak_on_amd).  Thirteen sub-commands -- the reference's whole list -- drive the call sequences the library serves:
  *     count    the counting protocol behind reference main.c:53-61 (one pass, or two passes + shrink
  *              when a bloom filter is asked for)
  *     qv       the lookup protocol behind reference main.c:163-215 (restore, histogram, yak_qv, solve)
@@ -12,6 +12,11 @@
  *              spectrum of two; -R probes the second table as inspect.c:58 does)
  *     chkerr   the streaks of low k-mers of reference chkerr.c:99-133 (yak_ch_restore, yakamd_chkerr)
  *     sexchr   the sex-chromosome tally of reference sexchr.c:104-140 (three SEXCHR loads, yakamd_sexchr)
+ *     print    the k-mers of a table as text, reference main.c:286-323 (restore, tighten, yakamd_print)
+ *     cntasm   the per-assembly presence counts of reference main.c:90-161 (yak_count per file, shrink / setcnt / merge, tighten)
+ *     recount  the counts of a table's k-mers in other sequences, reference main.c:66-88 (restore, tighten, yak_recount)
+ *     subtract, isec   the k-mers of the first table absent from / present in the others, reference main.c:217-284
+ *     version  the library's YAKS_VERSION
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
  */
@@ -20,7 +25,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "yak.h"
-#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr and yakamd_sexchr */
+#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr and yakamd_print */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
 enum arg_kind { ARG_FLAG, ARG_I32, ARG_SIZE, ARG_I64SIZE, ARG_F64, ARG_TEXT };
@@ -300,6 +305,137 @@ static int cmd_sexchr(int argc, char **argv)
 	return rc;
 }
 
+/* ---- print ---- */
+static int cmd_print(int argc, char **argv)
+{
+	yakamd_propt_t o;
+	int with_counts = 0;
+	yakamd_propt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'c', ARG_FLAG, &with_counts, "a tab and the count behind every k-mer" },
+		{ 'B', ARG_I64SIZE, &o.batch_bytes, "device bytes of text per range of sub-tables" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first >= argc) { arg_help("print [options] <in.yak>", defs, nd); return 1; }
+	uint32_t k = 0, pre = 0;
+	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd print: %s is not a readable .yak file\n", argv[first]); return 2; }
+	if (k >= 32) { fprintf(stderr, "yak-amd print: %s has k = %u: a k-mer can be rebuilt from its hash for k below 32 only\n", argv[first], k); return 2; }
+	o.with_counts = with_counts;
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd print: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_tighten(tab);
+	const int rc = yakamd_print(&o, tab, 0) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
+/* ---- cntasm ---- */
+static int cmd_cntasm(int argc, char **argv)
+{
+	yak_copt_t o;
+	const char *in = 0, *out = 0;
+	int min_cnt = 1, max_cnt = 1, max_out = 0, check_n = 10, pre_resize = 0;   /* reference main.c:94 */
+	yak_copt_init(&o);
+	o.chunk_size = 1900000000;                               /* -K 1.9g, main.c:98 */
+	const struct arg_def defs[] = {
+		{ 'k', ARG_I32, &o.k, "k-mer length, below 32" },
+		{ 'c', ARG_I32, &min_cnt, "min count in an assembly" },
+		{ 'x', ARG_I32, &max_cnt, "max count in an assembly" },
+		{ 'p', ARG_I32, &o.pre, "bits of the hash that pick the sub-table" },
+		{ 'r', ARG_FLAG, &pre_resize, "resize before merging" },
+		{ 't', ARG_I32, &o.n_thread, "host threads (parser)" },
+		{ 'e', ARG_I32, &max_out, "drop a k-mer absent from this many assemblies" },
+		{ 's', ARG_I32, &check_n, "shrink the table every this many assemblies" },
+		{ 'K', ARG_I64SIZE, &o.chunk_size, "bases per host batch" },
+		{ 'i', ARG_TEXT, &in, "start from this table (.yak); the same name as -o: written over" },
+		{ 'o', ARG_TEXT, &out, "write the table (.yak) here" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first >= argc) { arg_help("cntasm [options] <a.fa> [b.fa ...]", defs, nd); return 1; }
+	if (o.pre < YAK_COUNTER_BITS || o.k < 1 || o.k >= 32) { fprintf(stderr, "yak-amd cntasm: need 1 <= k < 32 and p >= %d\n", YAK_COUNTER_BITS); return 1; }
+	yak_ch_t *tab = 0;
+	if (in && !(tab = yak_ch_restore(in))) fprintf(stderr, "yak-amd cntasm: cannot load %s: starting from nothing\n", in);
+	for (int i = first; i < argc; ++i) {
+		const int done = i - first + 1;
+		yak_ch_t *one = yak_count(argv[i], &o, 0);
+		if (!one) { fprintf(stderr, "yak-amd cntasm: no table for %s (unreadable input, or no MI355X)\n", argv[i]); yak_ch_destroy(tab); return 2; }
+		if (!tab) {
+			tab = one;
+			yak_ch_shrink(tab, min_cnt, max_cnt, o.n_thread);
+			yak_ch_setcnt(tab, 1, o.n_thread);
+		} else yak_ch_merge(tab, one, min_cnt, max_cnt, o.n_thread, pre_resize);   /* consumes `one` */
+		if (i == argc - 1 || (done > max_out && done % check_n == 0)) yak_ch_shrink(tab, done - max_out, YAK_MAX_COUNT, o.n_thread);   /* main.c:152 */
+		fprintf(stderr, "[M::yak-amd] %s done; %ld distinct k-mers in the table\n", argv[i], (long)tab->tot);
+	}
+	yak_ch_tighten(tab);
+	int rc = 0;
+	if (out && yak_ch_dump(tab, out) != 0) { fprintf(stderr, "yak-amd cntasm: cannot write %s\n", out); rc = 3; }
+	yak_ch_destroy(tab);
+	return rc;
+}
+
+/* ---- recount ---- */
+static int cmd_recount(int argc, char **argv)
+{
+	const char *out = "-";
+	const struct arg_def defs[] = {
+		{ 'o', ARG_TEXT, &out, "write the table (.yak) here; - (the default) = stdout" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 1 >= argc) { arg_help("recount [options] <in.yak> <seq.fa>", defs, nd); return 1; }
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd recount: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_tighten(tab);
+	int rc = 0;
+	yak_recount(argv[first + 1], tab);
+	if (yak_ch_dump(tab, out) != 0) { fprintf(stderr, "yak-amd recount: cannot write %s\n", out); rc = 3; }
+	yak_ch_destroy(tab);
+	return rc;
+}
+
+/* ---- subtract, isec ---- */
+/* the first table keeps its k-mers that are absent from (subtract) / present in (isec) every further one */
+static int keep_cmd(int argc, char **argv, int isec)
+{
+	const char *out = "-", *cmd = isec ? "isec" : "subtract";
+	int n_thread = 8;                                        /* reference main.c:220 */
+	const struct arg_def defs[] = {
+		{ 't', ARG_I32, &n_thread, "host threads (accepted for the reference's command line)" },
+		{ 'o', ARG_TEXT, &out, "write the table (.yak) here; - (the default) = stdout" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 1 >= argc) { arg_help(isec ? "isec [options] <a.yak> <b.yak> [c.yak ...]" : "subtract [options] <a.yak> <b.yak>", defs, nd); return 1; }
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd %s: cannot load %s (or no MI355X)\n", cmd, argv[first]); return 2; }
+	const int last = isec ? argc : first + 2;
+	for (int i = first + 1; i < last; ++i) {
+		yak_ch_t *other = yak_ch_restore(argv[i]);
+		if (!other) { fprintf(stderr, "yak-amd %s: cannot load %s\n", cmd, argv[i]); yak_ch_destroy(tab); return 2; }
+		if (isec) yak_ch_isec(tab, other, n_thread);
+		else yak_ch_subtract(tab, other, n_thread);
+		yak_ch_destroy(other);
+	}
+	yak_ch_tighten(tab);
+	int rc = 0;
+	if (yak_ch_dump(tab, out) != 0) { fprintf(stderr, "yak-amd %s: cannot write %s\n", cmd, out); rc = 3; }
+	yak_ch_destroy(tab);
+	return rc;
+}
+static int cmd_subtract(int argc, char **argv) { return keep_cmd(argc, argv, 0); }
+static int cmd_isec(int argc, char **argv) { return keep_cmd(argc, argv, 1); }
+
+/* ---- version ---- */
+static int cmd_version(int argc, char **argv)
+{
+	(void)argc; (void)argv;
+	puts(YAKS_VERSION);
+	return 0;
+}
+
 int main(int argc, char **argv)
 {
 	static const struct { const char *name; int (*run)(int, char**); const char *what; } cmds[] = {
@@ -310,6 +446,12 @@ int main(int argc, char **argv)
 		{ "inspect", cmd_inspect, "the k-mer histogram of a .yak table, or the joint spectrum of two" },
 		{ "chkerr", cmd_chkerr, "report the streaks of low k-mers of sequences against a .yak table" },
 		{ "sexchr", cmd_sexchr, "count the sex-chromosome k-mers of two haplotype assemblies" },
+		{ "print", cmd_print, "list the k-mers of a .yak table as text" },
+		{ "cntasm", cmd_cntasm, "count in how many assemblies each k-mer occurs, write a .yak table" },
+		{ "recount", cmd_recount, "count the k-mers of a .yak table in other sequences" },
+		{ "subtract", cmd_subtract, "the k-mers of a .yak table that are absent from a second one" },
+		{ "isec", cmd_isec, "the k-mers of a .yak table that are present in every further one" },
+		{ "version", cmd_version, "print the version" },
 	};
 	/* -X name=value (anywhere on the line, any number of times): a test switch of the library (yakamd_test_set) -- tests force code paths with it */
 	for (int i = 1; i + 1 < argc; ) {
@@ -324,6 +466,6 @@ int main(int argc, char **argv)
 		for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i)
 			if (strcmp(argv[1], cmds[i].name) == 0) return cmds[i].run(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
-	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-7s %s\n", cmds[i].name, cmds[i].what);
+	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-8s %s\n", cmds[i].name, cmds[i].what);
 	return 1;
 }

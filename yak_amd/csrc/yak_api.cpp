@@ -387,19 +387,6 @@ void yak_ch_setcnt(yak_ch_t *h, int cnt, int n_thread)        /* reference htab.
 	if (yk_ctx_setcnt(((yak_ch_ext*)h)->ctx, cnt)) fprintf(stderr, "[E::yak_ch_setcnt] %s\n", yakamd_last_error());
 }
 
-static uint64_t hash64_inv(uint64_t x, uint64_t m)           /* reference yak-priv.h:41-68 */
-{
-	uint64_t t;
-	t = x - (x << 31); x = (x - (t << 31)) & m;
-	t = x ^ x >> 28; x = x ^ t >> 28;
-	x = (x * 14933078535860113213ULL) & m;
-	t = x ^ x >> 14; t = x ^ t >> 14; t = x ^ t >> 14; x = x ^ t >> 14;
-	x = (x * 15244667743933553977ULL) & m;
-	t = x ^ x >> 24; x = x ^ t >> 24;
-	t = ~x; t = ~(x - (t << 21)); t = ~(x - (t << 21)); x = ~(x - (t << 21)) & m;
-	return x;
-}
-
 yak_knt_t *yak_ch_getseq(const yak_ch_t *h, int w, uint32_t *n) /* reference htab.c:353-367 */
 {
 	assert(h->k < 32 && w < 1 << h->pre);
@@ -412,7 +399,7 @@ yak_knt_t *yak_ch_getseq(const yak_ch_t *h, int w, uint32_t *n) /* reference hta
 	uint32_t j = 0;
 	for (uint32_t i = 0, cap = ht_cap(g); i < cap; ++i)
 		if (g->used[i >> 5] >> (i & 31) & 1) {
-			a[j].x = hash64_inv(g->keys[i] >> YAK_COUNTER_BITS << h->pre | (uint64_t)w, mask);
+			a[j].x = yk_hash64_inv(g->keys[i] >> YAK_COUNTER_BITS << h->pre | (uint64_t)w, mask);
 			a[j++].c = (int)(g->keys[i] & YAK_MAX_COUNT);
 		}
 	*n = g->count;

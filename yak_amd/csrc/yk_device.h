@@ -17,6 +17,20 @@ typedef ulonglong2 Rec;                  /* one k-mer instance: .x = yak_hash64 
 #define YK_NOCAP   0xFFFFFFFFu               /* sub-table without a slot array (kh_capacity == 0) */
 #define YK_FLAG_FP 1u                        /* first occurrence passed the bloom gate */
 
+/* the inverse of yak_hash64 (reference yak-priv.h:41-68): one definition for the host (yak_ch_getseq) and the device (kern_print.inc) */
+__host__ __device__ static inline u64 yk_hash64_inv(u64 x, u64 m)
+{
+	u64 t;
+	t = x - (x << 31); x = (x - (t << 31)) & m;
+	t = x ^ x >> 28; x = x ^ t >> 28;
+	x = (x * 14933078535860113213ULL) & m;
+	t = x ^ x >> 14; t = x ^ t >> 14; t = x ^ t >> 14; x = x ^ t >> 14;
+	x = (x * 15244667743933553977ULL) & m;
+	t = x ^ x >> 24; x = x ^ t >> 24;
+	t = ~x; t = ~(x - (t << 21)); t = ~(x - (t << 21)); x = ~(x - (t << 21)) & m;
+	return x;
+}
+
 /* accumulator slot: one per distinct hashed k-mer seen by the current pass (32 B, one sector) */
 struct __attribute__((aligned(32))) AccSlot {
 	u64 key;        /* full yak_hash64 value, YK_EMPTY if free */
@@ -96,6 +110,15 @@ int yk_tb_over_seen(hipStream_t st);
  * InArgs), probed in B's image on its sub-tables [blo, bhi) (has_b = 0: c1 = 0); 0, or -1 if the launch failed */
 int yk_launch_inspect(const u64 *keys, const u64 *off, u64 n, int n_sub, int sub_lo, int hdr, int pre_a, int has_b, ImgView img, int blo, int bhi,
                       int ref, u64 *J, hipStream_t st);
+/* yak print's listing (kern_print.inc) of the n keys of sub-tables [sub_lo, sub_lo + n_sub) in `img`, the .yak body yk_ctx_dump_image_dev() makes
+ * of them; off[j] = keys before sub-table sub_lo + j (n_sub + 1 words, off[n_sub] = n).  kmers: x[i] and c[i] of key i.  print: the lines of reference
+ * main.c:308-317 to `text`; with counts, tile_bytes[t] = bytes of tile t's lines (print_sizes) and tile_off their exclusive scan (yk_print_tiles(n) + 1
+ * words).  0, or -1 if the launch failed */
+u64 yk_print_tiles(u64 n);
+int yk_launch_kmers(const u64 *img, const u64 *off, u64 n, int n_sub, int sub_lo, int k, int pre, u64 *x, unsigned short *c, hipStream_t st);
+int yk_launch_print_sizes(const u64 *img, const u64 *off, u64 n, int n_sub, int k, u32 *tile_bytes, hipStream_t st);
+int yk_launch_print(const u64 *img, const u64 *off, u64 n, int n_sub, int sub_lo, int k, int pre, int with_counts, const u64 *tile_off,
+                    uint8_t *text, hipStream_t st);
 void yk_launch_tb_reduce(const uint8_t *flag, const u64 *roff, const u32 *rlen, int64_t n_reads, int k, int *cnt, hipStream_t st);
 int64_t yk_te_tiles(int64_t n);                               /* trioeval's streak reduction (kern_trioeval.inc) */
 int64_t yk_te_keep_blocks(int64_t n_runs);
