@@ -269,6 +269,20 @@ int yakamd_inspect(const yakamd_inopt_t *opt, const char *fn1, const char *fn2, 
  * may be sharded over prefix ranges of one device; both on the same device.  0, or -1 after a message */
 int yakamd_inspect_tables(const yak_ch_t *a, const yak_ch_t *b, int ref_probe, int64_t *joint);
 
+/* Add the counts of two tables (not in the reference: yak_ch_merge is cntasm's presence merge, which adds ONE per k-mer of h1 whatever its count).
+ * Afterwards h0 holds every k-mer that was in h0, or in h1 with a count of at least 1, at min(1023, count in h0 + count in h1), a k-mer absent
+ * from a table counting 0 there; h0->tot = the number of stored keys.  h1 is only read and is NOT consumed; its keys of count 0 contribute
+ * nothing and do not enter h0.  The sum is exact for unfiltered tables (`yak count -b0`: the table of lane 1 plus the table of lane 2 is the table
+ * of both); two bloom-filtered tables are summed as they are -- what their filters and the shrink to counts >= 2 dropped stays dropped.
+ * Layout: h0 gets exactly the slots yak_ch_merge(h0, h1', 1, 1023, n_thread, pre_resize) gives it, h1' a throw-away copy of h1 -- the put-calls
+ * are h1's keys of count >= 1, sub-table by sub-table in h1's slot order, khashl growing at the next put-call after 75 % load, the optional
+ * pre-resize (htab.c:262-266) included -- and only the count fields differ from what that merge stores; the .yak bytes are a function of the two
+ * operands.  On the device: that merge's create pass, then one probe per listed key that rewrites its count field; no host mirror is read.
+ * k in [1, 63] (the stored key holds hash bits [pre, pre + 54), which the listing hands back unchanged).  Either table may be sharded over prefix
+ * ranges; operands on different devices take yak_ch_merge's routes (peer access, or a staged copy).  0, or -1 after a message
+ * (yakamd_last_error()) -- NULL or not an engine table, the same table twice, different k or pre, an open pass on either table: h0 is then untouched */
+int yakamd_ch_sum(yak_ch_t *h0, const yak_ch_t *h1, int pre_resize);
+
 /* Host-only test hook (no device needed): the base image yak_count() hands to the device for a
  * FASTA/FASTQ(.gz) file -- sequences of >= min_len bases, each followed by '\n'.  use_fast_path = 0
  * forces the general record reader for every record.  *out is malloc()ed; returns its length or -1. */

@@ -40,6 +40,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_chkerr_lookup_dev", "yakamd_chkerr_streaks_dev", "yakamd_ceopt_init", "yakamd_chkerr",
     "yakamd_sexchr_reduce_dev", "yakamd_scopt_init", "yakamd_sexchr",
     "yakamd_kmers_dev", "yakamd_print_dev", "yakamd_propt_init", "yakamd_print", "yakamd_host_syncs",
+    "yakamd_ch_sum",
 ]
 
 
@@ -261,6 +262,7 @@ def lib():
     L.yakamd_print.restype = C.c_int; L.yakamd_print.argtypes = [P(PropT), P(ChT), C.c_char_p]
     L.yakamd_host_syncs.restype = C.c_int64; L.yakamd_host_syncs.argtypes = []
     L.yak_ch_tighten.restype = None; L.yak_ch_tighten.argtypes = [P(ChT)]
+    L.yakamd_ch_sum.restype = C.c_int; L.yakamd_ch_sum.argtypes = [P(ChT), P(ChT), C.c_int]
     _lib = L
     return L
 
@@ -639,6 +641,36 @@ def kmers(table, sub_lo=0, sub_hi=None):
         L.yakamd_dev_free(dx); L.yakamd_dev_free(dc)
         if own:
             L.yak_ch_destroy(h)
+
+
+def sum_tables(paths, out=None, pre_resize=False):
+    """`yak-amd sum` through the C ABI: restore the first .yak file, yakamd_ch_sum every further one into it, yak_ch_tighten.  With `out` the
+    table is dumped to that path, which is returned; without it the .yak bytes are returned"""
+    L = lib()
+    if len(paths) < 2:
+        raise ValueError("sum_tables: at least two tables")
+    def restore(fn):
+        h = L.yak_ch_restore(fn.encode())
+        if not h:
+            raise RuntimeError("sum_tables: cannot load %s (not a readable .yak file, or no MI355X)" % fn)
+        return Table(ptr=h)
+    t = restore(paths[0])
+    try:
+        for fn in paths[1:]:
+            other = restore(fn)
+            try:
+                if L.yakamd_ch_sum(t.h, other.h, int(bool(pre_resize))) != 0:
+                    raise RuntimeError("yakamd_ch_sum failed: " + _err())
+            finally:
+                other.close()
+        L.yak_ch_tighten(t.h)
+        if out is None:
+            return t.dump_bytes()
+        if L.yak_ch_dump(t.h, out.encode()) != 0:
+            raise OSError("sum_tables: cannot write " + out)
+        return out
+    finally:
+        t.close()
 
 
 def pack_bases_host(buf):

@@ -533,7 +533,7 @@ static int count_own(yakamd_ctx *c, int64_t n_rec, const u64 *d_bstart, int hash
 static int consume_records(yakamd_ctx *c, int64_t n_rec, u64 t0, u64 batch_lo, u64 batch_hi, const u64 *d_bstart, int hash_only, int ytag)
 {
 	if (n_rec <= 0) return 0;
-	const ImgView img = img_view(c);
+	ImgView img = img_view(c);
 	c->st_cur.n_instances += n_rec;
 	if (batch_hi > c->t_end) c->t_end = batch_hi;
 	if (!c->create_new) {
@@ -572,7 +572,7 @@ static int consume_records(yakamd_ctx *c, int64_t n_rec, u64 t0, u64 batch_lo, u
 		return 0;
 	}
 	const int img_nonempty = c->img_keys_total > 0;
-	if (img_nonempty) { if (delta_ensure(c)) return -1; c->delta_dirty = true; }
+	if (img_nonempty) { if (delta_ensure(c)) return -1; c->delta_dirty = true; img = img_view(c); }   /* the view above was taken before the delta array existed: k_acc_insert adds to img.delta */
 	if (c->bloom_mode && bloom_materialise(c)) return -1;
 	if (acc_reserve(c, (u64)n_rec) || new_reserve(c, n_rec)) return -1;
 	u64 h_cnt[YKC_N];
@@ -1752,29 +1752,53 @@ int yk_ctx_merge_presize(yakamd_ctx *c, yakamd_ctx *other)
 }
 
 /* keys of `c` with cmin <= count <= cmax, sub-table by sub-table in slot order, as full hashes +
- * list positions on the device (caller frees both with yakamd_dev_free-compatible pool_free) */
-int yk_ctx_list_hashes(yakamd_ctx *c, int cmin, int cmax, u64 **d_hash, u32 **d_t, u64 *n)
+ * list positions on the device (caller frees both with yakamd_dev_free-compatible pool_free); with d_cnt, their 10-bit counts as well */
+int yk_ctx_list_hashes(yakamd_ctx *c, int cmin, int cmax, u64 **d_hash, u32 **d_t, u64 *n, unsigned short **d_cnt)
 {
 	HIPCK(hipSetDevice(c->dev));
 	const int P = c->P;
 	std::vector<u32> m(P);
 	std::vector<u64> seg_off(P + 1, 0);
-	DevBuf<u32> t; DevBuf<u64> hash, d_kc, d_segoff; DevBuf<u32> d_segcnt;
+	DevBuf<u32> t; DevBuf<u64> hash, d_kc, d_segoff; DevBuf<u32> d_segcnt; DevBuf<unsigned short> cnt;
 	*d_hash = 0; *d_t = 0;
+	if (d_cnt) *d_cnt = 0;
 	if (d_segcnt.alloc(P) || d_segoff.alloc(P + 1)) return -1;
 	yk_launch_shrink_count(img_view(c), P, cmin, cmax, 0, img_view(c), d_segcnt, c->st);
 	HIPCK(hipMemcpyAsync(m.data(), d_segcnt, P * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
 	for (int p = 0; p < P; ++p) seg_off[p + 1] = seg_off[p] + m[p];
 	*n = seg_off[P];
-	if (d_kc.alloc(seg_off[P]) || hash.alloc(seg_off[P]) || t.alloc(seg_off[P])) return -1;
+	if (d_kc.alloc(seg_off[P]) || hash.alloc(seg_off[P]) || t.alloc(seg_off[P]) || (d_cnt && cnt.alloc(seg_off[P]))) return -1;
 	HIPCK(hipMemcpyAsync(d_segoff, seg_off.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
 	yk_launch_shrink_scatter(img_view(c), P, cmin, cmax, 0, img_view(c), d_segoff, d_kc, c->st);
-	yk_launch_keys_to_hashes(d_kc, d_segoff, P, c->pre, hash, t, c->st);
+	yk_launch_keys_to_hashes(d_kc, d_segoff, P, c->pre, hash, t, c->st, d_cnt ? cnt.get() : 0);
 	HIPCK(hipStreamSynchronize(c->st));
 	*d_hash = hash.release(); *d_t = t.release();
+	if (d_cnt) *d_cnt = cnt.release();
 	return 0;
 }
+
+/* yakamd_ch_sum's count step (k_img_add_counts): entry i of a listing of another table's keys, d_hash[i] with count d_cnt[i] >= 1, which a create
+ * pass has just put into `c`, gets min(1023, its count here + d_cnt[i] - 1); the entries of sub-tables outside c's prefix range are skipped.  The
+ * listing may lie on a peer device.  Fails, after the kernel, when a listed key was not found */
+int yk_ctx_add_counts(yakamd_ctx *c, const u64 *d_hash, const unsigned short *d_cnt, u64 n)
+{
+	if (c->in_pass) return fail("yk_ctx_add_counts during an open pass");
+	if (n == 0) return 0;
+	HIPCK(hipSetDevice(c->dev));
+	DevBuf<u32> d_missing;
+	u32 missing = 0;
+	if (d_missing.alloc(1)) return -1;
+	HIPCK(hipMemsetAsync(d_missing, 0, 4, c->st));
+	yk_launch_img_add_counts(d_hash, d_cnt, n, img_view(c), c->plo, c->phi, d_missing, c->st);
+	HIPCK(hipGetLastError());
+	HIPCK(hipMemcpyAsync(&missing, d_missing, 4, hipMemcpyDeviceToHost, c->st));
+	HIPCK(hipStreamSynchronize(c->st));
+	c->host_valid = false;
+	if (missing) return fail("sum: a listed key is not in the table after its create pass: the counts were not all added");
+	return 0;
+}
+int yk_ctx_in_pass(yakamd_ctx *c) { return c->in_pass; }
 
 /* the .yak bytes of sub-tables [lo, hi) -- per sub-table capacity and size (4 bytes each) and the stored keys in ascending slot order,
  * htab.c:385-389 -- put together on the device: *d_img (pool memory: yk_pool_release) holds *n_words 8-byte words, ready on the table's stream */

@@ -35,7 +35,9 @@ int  yk_ctx_subtract(yakamd_ctx *c, yakamd_ctx *other, u64 *tot);
 int  yk_ctx_isec(yakamd_ctx *c, yakamd_ctx *other, u64 *tot);
 int  yk_ctx_tighten(yakamd_ctx *c);
 int  yk_ctx_merge_presize(yakamd_ctx *c, yakamd_ctx *other);
-int  yk_ctx_list_hashes(yakamd_ctx *c, int cmin, int cmax, u64 **d_hash, u32 **d_t, u64 *n);
+int  yk_ctx_list_hashes(yakamd_ctx *c, int cmin, int cmax, u64 **d_hash, u32 **d_t, u64 *n, unsigned short **d_cnt = 0);   /* d_cnt: the listed keys' counts too */
+int  yk_ctx_add_counts(yakamd_ctx *c, const u64 *d_hash, const unsigned short *d_cnt, u64 n);   /* the count step of yakamd_ch_sum; not inside a pass */
+int  yk_ctx_in_pass(yakamd_ctx *c);
 void yk_pool_release(void *p);
 int yk_set_error(const char *fmt, ...);                      /* this thread's yakamd_last_error() text (+ a line on stderr); returns -1 */
 int64_t yk_knob(const char *name, int64_t dflt);             /* a run-time setting: the test hook's value, else (public names only) the environment's, else dflt */

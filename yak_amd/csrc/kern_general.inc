@@ -282,6 +282,81 @@ void k_img_clear(ImgView img, u64 n_slots)                   /* reference htab.c
 		if (img.used[i >> 5] >> (i & 31) & 1) img.keys[i] &= ~1023ull;
 }
 
+/* yakamd_ch_sum, second step: entry i of a listing of ANOTHER table's keys -- hash[i] the key's full hash, cnt[i] its count c1 >= 1 there -- is
+ * looked up in the image, where the create pass before (the one yak_ch_merge runs) has put every listed key and added one to its count; the count
+ * field becomes min(1023, cur + c1 - 1): c1 for a key that pass created, old + c1 for one it found, and 1023 stays 1023.
+ * The keys of a table are distinct, so a slot has at most one writer: a plain 8-byte load and store, no atomics, no delta array, no fold.  A lane
+ * that probes past a slot another lane is rewriting reads the old or the new word; the two differ in the count field alone, which no compare
+ * looks at (LONG: a word that turns into YK_EMPTY asks the bitmap, which says used).
+ * The probe is k_lookup's: the sub-tables' {offset, log2 capacity} in LDS while pre <= 12 (`tab`), AC_U entries of a lane hashed first and their
+ * home slots requested together, then one dependent global read per step.  The listing is read coalesced (entry base + u * AC_THREADS + lane)
+ * and is grouped by sub-table, so a wave's probes fall into one or two sub-tables.  LONG (k >= 32): a YAK_LOAD_ALL key at count 1023 can equal
+ * YK_EMPTY, so there a YK_EMPTY slot asks the `used` bitmap before the probe stops, as img_find and k_lookup<., true, true> do.
+ * Entries of sub-tables outside [plo, phi) belong to another shard of the image's table and are skipped, as the feed of the create pass skipped
+ * them.  A listed key of the range that is NOT found -- there is none after that pass -- raises *missing: the caller fails, the sum is never
+ * silently short. */
+#define AC_THREADS 256
+#define AC_U 2                             /* probes a lane keeps in flight */
+template <bool LONG>
+__global__ __launch_bounds__(AC_THREADS)
+void k_img_add_counts(const u64 *__restrict__ hash, const unsigned short *__restrict__ cnt, u64 n, ImgView img, int plo, int phi, int tab, u32 *missing)
+{
+	extern __shared__ __attribute__((aligned(16))) u64 s_ac[];
+	const u32 pmask = (1u << img.pre) - 1;
+	if (tab) {
+		for (u32 p = threadIdx.x; p <= pmask; p += AC_THREADS) { const u32 b = img.bits[p]; s_ac[p] = img.off[p] | (u64)(b == YK_NOCAP ? 63u : b) << 58; }
+		__syncthreads();
+	}
+	const u64 YK_GLOBAL *ghash = yk_global(u64, hash);
+	const unsigned short YK_GLOBAL *gcnt = yk_global(unsigned short, cnt);
+	u64 YK_GLOBAL *karena = yk_global_rw(u64, img.keys);
+	bool miss = false;
+	const u64 step = (u64)gridDim.x * AC_THREADS * AC_U;
+	for (u64 base = (u64)blockIdx.x * AC_THREADS * AC_U; base < n; base += step) {
+		u64 kid[AC_U], kc[AC_U], slot[AC_U];
+		u32 idx[AC_U], nmask[AC_U], c1[AC_U];
+		bool live[AC_U];
+#pragma unroll
+		for (int u = 0; u < AC_U; ++u) {
+			const u64 i = base + (u64)u * AC_THREADS + threadIdx.x;
+			live[u] = false; kid[u] = 0; slot[u] = 0; idx[u] = 0; nmask[u] = 0; c1[u] = 0;
+			if (i >= n) continue;
+			const u64 h = ghash[i];
+			c1[u] = gcnt[i];
+			const u32 p = (u32)h & pmask;
+			if ((int)p < plo || (int)p >= phi || c1[u] == 0) continue;
+			kid[u] = (h >> img.pre) & (~0ull >> 10);               /* the stored key keeps 54 bits of hash >> pre (htab.c:97) */
+			u64 off; u32 bits;
+			if (tab) { const u64 e = s_ac[p]; off = e & ((1ull << 58) - 1); bits = (u32)(e >> 58); bits = bits == 63u ? YK_NOCAP : bits; }
+			else { bits = img.bits[p]; off = img.off[p]; }
+			if (bits == YK_NOCAP) { miss = true; continue; }
+			live[u] = true; slot[u] = off; nmask[u] = (1u << bits) - 1; idx[u] = yk_h2b((u32)kid[u], bits);
+		}
+#pragma unroll
+		for (int u = 0; u < AC_U; ++u) kc[u] = live[u] ? karena[slot[u] + idx[u]] : YK_EMPTY;
+#pragma unroll
+		for (int u = 0; u < AC_U; ++u) {
+			if (!live[u]) continue;
+			const u32 first = idx[u];
+			bool found = false;
+			for (;;) {
+				if (kc[u] == YK_EMPTY && !(LONG && lk_used(img, slot[u] + idx[u]))) break;
+				if (kc[u] >> 10 == kid[u]) {
+					const u32 c = (u32)(kc[u] & 1023u) + c1[u] - 1u;       /* cur >= 1: the create pass counted this key once */
+					karena[slot[u] + idx[u]] = (kc[u] & ~1023ull) | (c > 1023u ? 1023u : c);
+					found = true;
+					break;
+				}
+				idx[u] = (idx[u] + 1) & nmask[u];
+				if (idx[u] == first) break;
+				kc[u] = karena[slot[u] + idx[u]];
+			}
+			miss |= !found;
+		}
+	}
+	if (miss) *missing = 1u;
+}
+
 /* ------------------------------------------------------------------------------------------
  * last put-call per sub-table.  khashl grows at the NEXT put-call after the load factor reaches
  * 0.75 (khashl.h:202), even when that call finds its key.  So the layout needs, per sub-table, the

@@ -288,9 +288,20 @@ void yk_launch_resize(const ResizeTask *tasks, int P, const u64 *old_keys, const
 	hipLaunchKernelGGL(k_resize, dim3(P), dim3(256), 0, st, tasks, old_keys, old_used, new_keys, new_used, scr_used);
 }
 
-void yk_launch_keys_to_hashes(const u64 *kc, const u64 *seg_off, int P, int pre, u64 *hash, u32 *t, hipStream_t st)
+void yk_launch_keys_to_hashes(const u64 *kc, const u64 *seg_off, int P, int pre, u64 *hash, u32 *t, hipStream_t st, unsigned short *cnt)
 {
-	hipLaunchKernelGGL(k_keys_to_hashes, dim3(P), dim3(256), 0, st, kc, seg_off, pre, hash, t);
+	hipLaunchKernelGGL(k_keys_to_hashes, dim3(P), dim3(256), 0, st, kc, seg_off, pre, hash, t, cnt);
+}
+
+/* yakamd_ch_sum's count step over a listing of n {hash, count} entries; *missing is raised when a listed key of [plo, phi) is not in the image */
+void yk_launch_img_add_counts(const u64 *hash, const unsigned short *cnt, u64 n, ImgView img, int plo, int phi, u32 *missing, hipStream_t st)
+{
+	if (n == 0) return;
+	const int tab = img.pre <= 12;
+	const size_t lds = tab ? (size_t)8 << img.pre : 0;
+	const dim3 grid(grid_for(n, AC_THREADS * AC_U)), block(AC_THREADS);
+	if (img.k < 32) hipLaunchKernelGGL(k_img_add_counts<false>, grid, block, lds, st, hash, cnt, n, img, plo, phi, tab, missing);
+	else hipLaunchKernelGGL(k_img_add_counts<true>, grid, block, lds, st, hash, cnt, n, img, plo, phi, tab, missing);
 }
 
 /* one sweep of the sort by insertion time (k_part2<.., TS>): {key, time} pairs in and out, bin = (time >> fp.ssh) mod 2^fp.s2_bits */

@@ -41,12 +41,16 @@ void k_resize(const ResizeTask *tasks, const u64 *__restrict__ old_keys, const u
 	for (u32 i = tid; i < span; i += 256) if (i >= N || !bm_get(nu, i)) keys[i] = YK_EMPTY;
 }
 
-/* table keys of one sub-table (slot order) -> full hashes + list positions, for a merge pass */
+/* table keys of one sub-table (slot order) -> full hashes + list positions, for a merge pass; cnt != 0: and their 10-bit counts (yakamd_ch_sum) */
 __global__ __launch_bounds__(256)
-void k_keys_to_hashes(const u64 *__restrict__ kc, const u64 *__restrict__ seg_off, int pre, u64 *__restrict__ hash, u32 *__restrict__ t)
+void k_keys_to_hashes(const u64 *__restrict__ kc, const u64 *__restrict__ seg_off, int pre, u64 *__restrict__ hash, u32 *__restrict__ t,
+                      unsigned short *__restrict__ cnt)
 {
 	const u64 a = seg_off[blockIdx.x], b = seg_off[blockIdx.x + 1];
-	for (u64 i = a + threadIdx.x; i < b; i += 256) { hash[i] = (kc[i] >> 10) << pre | blockIdx.x; t[i] = (u32)i; }
+	for (u64 i = a + threadIdx.x; i < b; i += 256) {
+		hash[i] = (kc[i] >> 10) << pre | blockIdx.x; t[i] = (u32)i;
+		if (cnt) cnt[i] = (unsigned short)(kc[i] & 1023u);
+	}
 }
 
 /* ==========================================================================================

@@ -428,6 +428,35 @@ static int keep_cmd(int argc, char **argv, int isec)
 static int cmd_subtract(int argc, char **argv) { return keep_cmd(argc, argv, 0); }
 static int cmd_isec(int argc, char **argv) { return keep_cmd(argc, argv, 1); }
 
+/* ---- sum (not in the reference) ---- */
+/* the first table plus the counts of every further one (yakamd_ch_sum) */
+static int cmd_sum(int argc, char **argv)
+{
+	const char *out = "-";
+	int pre_resize = 0;
+	const struct arg_def defs[] = {
+		{ 'r', ARG_FLAG, &pre_resize, "resize before adding a table" },
+		{ 'o', ARG_TEXT, &out, "write the table (.yak) here; - (the default) = stdout" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 1 >= argc) { arg_help("sum [options] <a.yak> <b.yak> [c.yak ...]", defs, nd); return 1; }
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd sum: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	for (int i = first + 1; i < argc; ++i) {
+		yak_ch_t *other = yak_ch_restore(argv[i]);
+		if (!other) { fprintf(stderr, "yak-amd sum: cannot load %s\n", argv[i]); yak_ch_destroy(tab); return 2; }
+		const int r = yakamd_ch_sum(tab, other, pre_resize);
+		yak_ch_destroy(other);
+		if (r != 0) { fprintf(stderr, "yak-amd sum: %s: %s\n", argv[i], yakamd_last_error()); yak_ch_destroy(tab); return 3; }
+	}
+	yak_ch_tighten(tab);
+	int rc = 0;
+	if (yak_ch_dump(tab, out) != 0) { fprintf(stderr, "yak-amd sum: cannot write %s\n", out); rc = 3; }
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 /* ---- version ---- */
 static int cmd_version(int argc, char **argv)
 {
@@ -465,7 +494,9 @@ int main(int argc, char **argv)
 	if (argc >= 2)
 		for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i)
 			if (strcmp(argv[1], cmds[i].name) == 0) return cmds[i].run(argc - 1, argv + 1);
+	if (argc >= 2 && strcmp(argv[1], "sum") == 0) return cmd_sum(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
 	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-8s %s\n", cmds[i].name, cmds[i].what);
+	fprintf(stderr, "  beyond the reference:\n      yak-amd %-8s %s\n", "sum", "add the counts of two or more .yak tables together");
 	return 1;
 }
