@@ -283,6 +283,35 @@ int yakamd_inspect_tables(const yak_ch_t *a, const yak_ch_t *b, int ref_probe, i
  * (yakamd_last_error()) -- NULL or not an engine table, the same table twice, different k or pre, an open pass on either table: h0 is then untouched */
 int yakamd_ch_sum(yak_ch_t *h0, const yak_ch_t *h1, int pre_resize);
 
+/* Per-sequence and per-window k-mer depth (not in the reference): how often the k-mers along a sequence occur in a count
+ * table.  A sequence of L bases is cut into windows of w k-mer START positions, window j covering the starts [j w, min(L, (j + 1) w)); w = 0 is one
+ * window, the whole sequence; a sequence has max(1, ceil(L / w)) windows, an empty one too.  The k-mer starting at s is element s + k - 1 of the array
+ * yakamd_lookup_dev() writes for the sequence, so a window is a shifted slice of it; its k-mers are the elements of that slice inside the sequence that
+ * are not 0xffff (starts >= L - k + 1 have none), an absent k-mer counting 0.  Per window: n_kmer, n_present (count > 0), sum of the counts, median
+ * -- the LOWER median, index (n_kmer - 1) / 2 of the sorted counts -- and max; median and max are 0 without a k-mer.  All integers, a pure function of
+ * the array.
+ * yakamd_depth_reduce_dev(): d_cnt_u16 = that array for a base image of n_bytes bytes (16-byte aligned, its allocation a multiple of 16 bytes; an
+ * element above 1023 other than 0xffff is read as 1023), sequence j = elements [d_seq_off[j], d_seq_off[j] + d_seq_len[j]) (disjoint), d_win_off[j] =
+ * the windows of the sequences before j (n_seq + 1 device words: the exclusive scan of the windows per sequence and their total); d_win receives one
+ * yakamd_win_t per window, sequences in order, windows ascending.  k below 32.  It needs no table.  `stream` = a hipStream_t or 0; returns when the
+ * device is done. */
+typedef struct { uint32_t n_kmer, n_present, median, max; uint64_t sum; } yakamd_win_t;
+int yakamd_depth_reduce_dev(int k, int64_t w, const void *d_cnt_u16, const uint64_t *d_seq_off, const uint32_t *d_seq_len,
+                            const uint64_t *d_win_off, int64_t n_seq, int64_t n_bytes, yakamd_win_t *d_win, void *stream);
+/* `yak-amd depth` as a library call: every sequence of `fn` (FASTA/FASTQ, .gz, "-" = stdin) against `ch`, a YAK_LOAD_ALL table (yak_ch_restore) or a
+ * resident one, k below 32.  To out_fn (NULL = stdout): the line `#name start end n_kmer n_present mean median max` (tab-separated, as all lines), then
+ * one line per window, sequences in input order, windows ascending: start and end are the window's bounds in bases, mean is "%.3f" of sum / n_kmer
+ * (0.000 without a k-mer).  Per chunk of chunk_size bases the lookup, then the reduction; no host mirror of the table is built.  0 on success, -1
+ * after a message on stderr -- before anything is written for k >= 32, a negative window, a table sharded over prefix ranges or spread over several
+ * devices, an open pass and an input that cannot be opened. */
+typedef struct {
+	int64_t window;           /* -w, 0: k-mer starts per window; 0 = one window per sequence */
+	int n_threads;            /* -t, 8: accepted for symmetry with the other commands; a second thread reads ahead */
+	int64_t chunk_size;       /* -K, bases per chunk, 1000000000 (as yakamd_ceopt_t's) */
+} yakamd_dpopt_t;
+void yakamd_dpopt_init(yakamd_dpopt_t *opt);
+int yakamd_depth(const yakamd_dpopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn);
+
 /* Host-only test hook (no device needed): the base image yak_count() hands to the device for a
  * FASTA/FASTQ(.gz) file -- sequences of >= min_len bases, each followed by '\n'.  use_fast_path = 0
  * forces the general record reader for every record.  *out is malloc()ed; returns its length or -1. */

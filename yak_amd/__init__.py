@@ -41,6 +41,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_sexchr_reduce_dev", "yakamd_scopt_init", "yakamd_sexchr",
     "yakamd_kmers_dev", "yakamd_print_dev", "yakamd_propt_init", "yakamd_print", "yakamd_host_syncs",
     "yakamd_ch_sum",
+    "yakamd_depth_reduce_dev", "yakamd_dpopt_init", "yakamd_depth",
 ]
 
 
@@ -87,6 +88,14 @@ class ScoptT(C.Structure):                     # yakamd_scopt_t, include/yak_amd
 
 class PropT(C.Structure):                      # yakamd_propt_t, include/yak_amd.h
     _fields_ = [("with_counts", C.c_int32), ("n_threads", C.c_int32), ("batch_bytes", C.c_int64)]
+
+
+class DpoptT(C.Structure):                     # yakamd_dpopt_t, include/yak_amd.h
+    _fields_ = [("window", C.c_int64), ("n_threads", C.c_int32), ("chunk_size", C.c_int64)]
+
+
+class WinT(C.Structure):                       # yakamd_win_t, include/yak_amd.h
+    _fields_ = [("n_kmer", C.c_uint32), ("n_present", C.c_uint32), ("median", C.c_uint32), ("max", C.c_uint32), ("sum", C.c_uint64)]
 
 
 class StreakT(C.Structure):                    # yakamd_streak_t, include/yak_amd.h
@@ -263,6 +272,10 @@ def lib():
     L.yakamd_host_syncs.restype = C.c_int64; L.yakamd_host_syncs.argtypes = []
     L.yak_ch_tighten.restype = None; L.yak_ch_tighten.argtypes = [P(ChT)]
     L.yakamd_ch_sum.restype = C.c_int; L.yakamd_ch_sum.argtypes = [P(ChT), P(ChT), C.c_int]
+    L.yakamd_depth_reduce_dev.restype = C.c_int
+    L.yakamd_depth_reduce_dev.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+    L.yakamd_dpopt_init.restype = None; L.yakamd_dpopt_init.argtypes = [P(DpoptT)]
+    L.yakamd_depth.restype = C.c_int; L.yakamd_depth.argtypes = [P(DpoptT), P(ChT), C.c_char_p, C.c_char_p]
     _lib = L
     return L
 
@@ -522,6 +535,24 @@ def chkerr(count_yak, seq, min_cnt=3, min_streak=5, chunk=None):
         if chunk is not None:
             o.chunk_size = chunk
         return _output_of("yakamd_chkerr", lambda out: L.yakamd_chkerr(C.byref(o), h, seq.encode(), out))
+    finally:
+        L.yak_ch_destroy(h)
+
+
+def depth(table_yak, seq, window=0, chunk=None):
+    """`yak-amd depth` through the C ABI (yak_ch_restore + yakamd_depth): one line per sequence (window = 0) or per window of `window` k-mer
+    start positions -- name, start, end, n_kmer, n_present, mean, median, max -- behind a `#` header line"""
+    L = lib()
+    h = L.yak_ch_restore(table_yak.encode())
+    if not h:
+        raise RuntimeError("yak_ch_restore failed: " + _err())
+    try:
+        o = DpoptT()
+        L.yakamd_dpopt_init(C.byref(o))
+        o.window = window
+        if chunk is not None:
+            o.chunk_size = chunk
+        return _output_of("yakamd_depth", lambda out: L.yakamd_depth(C.byref(o), h, seq.encode(), out))
     finally:
         L.yak_ch_destroy(h)
 

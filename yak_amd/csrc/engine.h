@@ -60,6 +60,11 @@ int  yk_ctx_sync_host(yakamd_ctx *c, yak_ch_t *h);
 u64  yk_ctx_list_time(yakamd_ctx *c, u64 n);
 int  yk_ctx_device(yakamd_ctx *c);
 int  yk_inspect_engines(const yak_ch_t *h, std::vector<yakamd_ctx*> *eng);   /* the engines of a table (one per rank of a sharded one), all on one device and out of a pass */
+/* lookup_dev.cpp, `yak-amd depth`: windows [g0, g0 + n_win) of a call as yakamd_depth_reduce_dev() takes it into d_win[0 .. n_win) (24 bytes each),
+ * n_win at most yk_depth_batch_max() (2^24; the test switch YAKAMD_DEPTH_BATCH lowers it); the caller synchronises `st` */
+int64_t yk_depth_batch_max(void);
+int  yk_depth_batch(int k, int64_t w, const void *d_cnt_u16, const uint64_t *d_seq_off, const uint32_t *d_seq_len, const uint64_t *d_win_off,
+                    int64_t n_seq, int64_t n_bytes, uint64_t g0, uint32_t n_win, void *d_win, hipStream_t st);
 size_t yk_pool_cached_bytes(void);
 size_t yk_pool_held_bytes(int dev);
 void yk_pool_report(const char *what);

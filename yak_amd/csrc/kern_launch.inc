@@ -682,4 +682,27 @@ int yk_launch_inspect(const u64 *keys, const u64 *off, u64 n, int n_sub, int sub
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+/* `yak-amd depth` (kern_depth.inc).  short: the n_win windows from g0 on, out[i] = window g0 + i; the long ones (more than T positions) go to
+ * long_list / tile_base (long_cap entries) and are counted, with their tiles, in *counter (zeroed by the caller).  long: the tiles [tile0, tile0 +
+ * n_tiles) of the slots [slot0, slot0 + n_slots) into hist (1024 zeroed u64 bins per slot); finish: those slots' windows from their bins */
+int yk_dp_run(void) { return DP_RUN; }
+void yk_launch_dp_short(DpArgs a, u64 g0, u32 n_win, u32 T, void *out, u32 *long_list, u64 *tile_base, u32 long_cap, u64 *counter, hipStream_t st)
+{
+	if (n_win == 0) return;
+	const u64 want = ((u64)n_win + DP_THREADS / WAVE - 1) / (DP_THREADS / WAVE);
+	hipLaunchKernelGGL(k_dp_short, dim3((unsigned)std::min<u64>(want, 65536)), dim3(DP_THREADS), 0, st, a, g0, n_win, T, (DpOut*)out, long_list, tile_base,
+	                   long_cap, (unsigned long long*)counter);
+}
+void yk_launch_dp_long(DpArgs a, u64 g0, const u32 *long_list, const u64 *tile_base, u32 slot0, u32 n_slots, u64 tile0, u64 n_tiles, u64 *hist, hipStream_t st)
+{
+	if (n_tiles) hipLaunchKernelGGL(k_dp_long, dim3((unsigned)n_tiles), dim3(DP_THREADS), 0, st, a, g0, long_list, tile_base, slot0, n_slots, tile0,
+	                                (unsigned long long*)hist);
+}
+void yk_launch_dp_finish(const u64 *hist, const u32 *long_list, u32 slot0, u32 n_slots, void *out, hipStream_t st)
+{
+	if (n_slots == 0) return;
+	const u32 want = (n_slots + DP_THREADS / WAVE - 1) / (DP_THREADS / WAVE);
+	hipLaunchKernelGGL(k_dp_finish, dim3(std::min<u32>(want, 65536)), dim3(DP_THREADS), 0, st, (const unsigned long long*)hist, long_list, slot0, n_slots, (DpOut*)out);
+}
+
 } /* extern "C" */

@@ -217,6 +217,98 @@ extern "C" int yakamd_chkerr_streaks_dev(int min_streak, const void *d_low_u8, c
 	return te_streaks("chkerr streaks", 1, 1, min_n, (const uint8_t*)d_low_u8, d_seq_off, n_seq, n_bytes, 0, d_streaks, n_streaks, st);
 }
 
+/* ---- yak-amd depth (kern_depth.inc) ---- */
+namespace {
+struct DpScratch {                                     /* kept from one call to the next, on the device of the last call */
+	std::mutex mu;
+	int dev = -1;
+	GrowBuf list, tbase, hist, ctr;
+	u64 *host = 0;                                     /* pinned: the words read back */
+	void on(int d) { if (d == dev) return; for (GrowBuf *b : { &list, &tbase, &hist, &ctr }) b->drop(); dev = d; }
+};
+DpScratch &g_dp = *new DpScratch;                       /* never deleted, as g_te */
+const u32 DP_LONG_DEFAULT = 2048;                       /* positions from which a window goes through the histogram kernels */
+const u32 DP_GROUP = 16384;                             /* long windows whose histograms are held at once: 128 MiB */
+}
+
+int64_t yk_depth_batch_max(void)
+{
+	const int64_t b = yk_knob("YAKAMD_DEPTH_BATCH", (int64_t)1 << 24);
+	return b < 1 ? 1 : b > ((int64_t)1 << 24) ? (int64_t)1 << 24 : b;
+}
+
+/* windows [g0, g0 + n_win) of the call's numbering into d_win[0 .. n_win): one batch, n_win <= yk_depth_batch_max().  Asynchronous on `st` but for
+ * the read-back of the long windows' number */
+int yk_depth_batch(int k, int64_t w, const void *d_cnt_u16, const uint64_t *d_seq_off, const uint32_t *d_seq_len, const uint64_t *d_win_off,
+                   int64_t n_seq, int64_t n_bytes, uint64_t g0, uint32_t n_win, void *d_win, hipStream_t st)
+{
+	if (n_win == 0) return 0;
+	std::lock_guard<std::mutex> lk(g_dp.mu);
+	int dev = 0;
+	HIPCK(hipGetDevice(&dev));
+	g_dp.on(dev);
+	DpScratch &s = g_dp;
+	const int64_t knob = yk_knob("YAKAMD_DEPTH_LONG", DP_LONG_DEFAULT);
+	const u32 T = (u32)(knob < 0 ? 0 : knob > (1 << 20) ? 1 << 20 : knob);
+	/* long windows are disjoint slices of more than T positions each; with w <= T there is none */
+	const u64 most = w > 0 && (u64)w <= T ? 0 : std::min<u64>(n_win, (u64)n_bytes / ((u64)T + 1));
+	if (!s.host) HIPCK(hipHostMalloc((void**)&s.host, 16));
+	if (!s.ctr.fit(8) || !s.list.fit(most * 4 + 4) || !s.tbase.fit(most * 8 + 8)) return fail("depth reduce: out of device memory");
+	DpArgs a;
+	a.cnt = (const unsigned short*)d_cnt_u16; a.seq_off = (const u64*)d_seq_off; a.seq_len = d_seq_len; a.win_off = (const u64*)d_win_off;
+	a.n_seq = n_seq; a.n_bytes = n_bytes; a.w = (u64)w; a.k = k;
+	HIPCK(hipMemsetAsync(s.ctr.p, 0, 8, st));
+	yk_launch_dp_short(a, g0, n_win, T, d_win, (u32*)s.list.p, (u64*)s.tbase.p, (u32)most, (u64*)s.ctr.p, st);
+	HIPCK(hipGetLastError());
+	if (most == 0) return 0;
+	HIPCK(hipMemcpyAsync(s.host, s.ctr.p, 8, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
+	const u64 n_long = s.host[0] >> 40, n_tiles = s.host[0] & ((1ull << 40) - 1);
+	if (n_long > most) return fail("depth reduce: the sequences overlap (%llu windows of more than %u positions in %ld)", (unsigned long long)n_long, T, (long)n_bytes);
+	for (u64 slot0 = 0; slot0 < n_long; slot0 += DP_GROUP) {   /* a group's tiles are [its first slot's base, the next group's) */
+		const u32 ns = (u32)std::min<u64>(DP_GROUP, n_long - slot0);
+		u64 t0 = 0, t1 = n_tiles;
+		if (slot0 > 0) { HIPCK(hipMemcpyAsync(s.host, (const u64*)s.tbase.p + slot0, 8, hipMemcpyDeviceToHost, st)); }
+		if (slot0 + ns < n_long) { HIPCK(hipMemcpyAsync(s.host + 1, (const u64*)s.tbase.p + slot0 + ns, 8, hipMemcpyDeviceToHost, st)); }
+		if (slot0 > 0 || slot0 + ns < n_long) {
+			HIPCK(hipStreamSynchronize(st));
+			if (slot0 > 0) t0 = s.host[0];
+			if (slot0 + ns < n_long) t1 = s.host[1];
+		}
+		if (t1 < t0 || t1 > n_tiles) return fail("depth reduce: bad tile ranges");
+		if (!s.hist.fit((size_t)ns * 8192)) return fail("depth reduce: out of device memory");
+		HIPCK(hipMemsetAsync(s.hist.p, 0, (size_t)ns * 8192, st));
+		yk_launch_dp_long(a, g0, (const u32*)s.list.p, (const u64*)s.tbase.p, (u32)slot0, ns, t0, t1 - t0, (u64*)s.hist.p, st);
+		yk_launch_dp_finish((const u64*)s.hist.p, (const u32*)s.list.p, (u32)slot0, ns, d_win, st);
+		HIPCK(hipGetLastError());
+	}
+	return 0;
+}
+
+static int depth_args(const char *what, int k, int64_t w, const void *d_cnt_u16, const void *d_win)
+{
+	if (k < 1 || k >= 32) return fail("%s: k must be below 32 (reference qv.c:44)", what);
+	if (w < 0) return fail("%s: a window of %ld k-mer starts", what, (long)w);
+	if (((uintptr_t)d_cnt_u16 & 15) != 0 || ((uintptr_t)d_win & 7) != 0) return fail("%s: the counts must be 16-byte and the windows 8-byte aligned", what);
+	return 0;
+}
+
+extern "C" int yakamd_depth_reduce_dev(int k, int64_t w, const void *d_cnt_u16, const uint64_t *d_seq_off, const uint32_t *d_seq_len,
+                                       const uint64_t *d_win_off, int64_t n_seq, int64_t n_bytes, yakamd_win_t *d_win, void *stream)
+{
+	if (depth_args("depth reduce", k, w, d_cnt_u16, d_win) || check_counts("depth reduce", n_seq, n_bytes)) return -1;
+	const hipStream_t st = (hipStream_t)stream;
+	uint64_t n_win = 0;
+	if (n_seq > 0) HIPCK(hipMemcpyAsync(&n_win, d_win_off + n_seq, 8, hipMemcpyDeviceToHost, st));
+	HIPCK(hipStreamSynchronize(st));
+	if (n_win < (uint64_t)n_seq || (w == 0 && n_win != (uint64_t)n_seq)) return fail("depth reduce: %llu windows for %ld sequences", (unsigned long long)n_win, (long)n_seq);
+	const uint64_t batch = (uint64_t)yk_depth_batch_max();
+	for (uint64_t g0 = 0; g0 < n_win; g0 += batch)
+		if (yk_depth_batch(k, w, d_cnt_u16, d_seq_off, d_seq_len, d_win_off, n_seq, n_bytes, g0, (uint32_t)std::min<uint64_t>(batch, n_win - g0), d_win + g0, st)) return -1;
+	HIPCK(hipStreamSynchronize(st));
+	return 0;
+}
+
 extern "C" int yakamd_sexchr_reduce_dev(const void *d_flag_u8, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq, int64_t n_bytes,
                                         uint64_t *d_cnt_u64x4, void *stream)
 {

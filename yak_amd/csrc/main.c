@@ -17,6 +17,7 @@
  *     recount  the counts of a table's k-mers in other sequences, reference main.c:66-88 (restore, tighten, yak_recount)
  *     subtract, isec   the k-mers of the first table absent from / present in the others, reference main.c:217-284
  *     version  the library's YAKS_VERSION
+ * and two beyond the reference: sum (yakamd_ch_sum) and depth (yakamd_depth: the depth of every sequence or window in a count table).
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
  */
@@ -25,7 +26,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "yak.h"
-#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr and yakamd_print */
+#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum and yakamd_depth */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
 enum arg_kind { ARG_FLAG, ARG_I32, ARG_SIZE, ARG_I64SIZE, ARG_F64, ARG_TEXT };
@@ -457,6 +458,33 @@ static int cmd_sum(int argc, char **argv)
 	return rc;
 }
 
+/* ---- depth (not in the reference) ---- */
+/* how often the k-mers of each sequence, or of each window of it, occur in a count table (yakamd_depth) */
+static int cmd_depth(int argc, char **argv)
+{
+	yakamd_dpopt_t o;
+	const char *out = 0;
+	yakamd_dpopt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'w', ARG_I64SIZE, &o.window, "k-mer start positions per window; 0 (the default) = one window per sequence" },
+		{ 't', ARG_I32, &o.n_threads, "host threads (accepted for symmetry with the other commands)" },
+		{ 'K', ARG_I64SIZE, &o.chunk_size, "bases per chunk" },
+		{ 'o', ARG_TEXT, &out, "write the lines here; stdout without it" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 1 >= argc) { arg_help("depth [options] <table.yak> <seq.fa>", defs, nd); return 1; }
+	uint32_t k = 0, pre = 0;
+	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd depth: %s is not a readable .yak file\n", argv[first]); return 2; }
+	if (k >= 32) { fprintf(stderr, "yak-amd depth: %s has k = %u: the per-position lookup serves k below 32 only\n", argv[first], k); return 2; }
+	if (o.window < 0) { fprintf(stderr, "yak-amd depth: -w must not be negative\n"); return 1; }
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd depth: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	const int rc = yakamd_depth(&o, tab, argv[first + 1], out) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 /* ---- version ---- */
 static int cmd_version(int argc, char **argv)
 {
@@ -495,8 +523,10 @@ int main(int argc, char **argv)
 		for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i)
 			if (strcmp(argv[1], cmds[i].name) == 0) return cmds[i].run(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "sum") == 0) return cmd_sum(argc - 1, argv + 1);
+	if (argc >= 2 && strcmp(argv[1], "depth") == 0) return cmd_depth(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
 	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-8s %s\n", cmds[i].name, cmds[i].what);
 	fprintf(stderr, "  beyond the reference:\n      yak-amd %-8s %s\n", "sum", "add the counts of two or more .yak tables together");
+	fprintf(stderr, "      yak-amd %-8s %s\n", "depth", "the depth of the k-mers of each sequence, or window, in a .yak table");
 	return 1;
 }

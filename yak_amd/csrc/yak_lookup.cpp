@@ -452,3 +452,61 @@ int yakamd_sexchr(const yakamd_scopt_t *opt, const yak_ch_t *ch, const char *fn_
 		return ok;
 	});
 }
+
+/* as yakamd_ceopt_init: the chunk is chkerr's */
+void yakamd_dpopt_init(yakamd_dpopt_t *opt)
+{
+	memset(opt, 0, sizeof(yakamd_dpopt_t));
+	opt->window = 0;
+	opt->n_threads = 8;
+	opt->chunk_size = 1000000000;
+}
+
+/* `yak-amd depth` (not in the reference): per chunk the lookup of chkerr's driver into one u16 per position (yakamd_lookup_dev),
+ * then the windows' reduction in batches of at most 2^24 windows (yk_depth_batch), each batch's 24 bytes per window copied back and its lines
+ * formatted here -- the output buffer stays bounded whatever the window is.  Refused before the output is created: what the lookup itself
+ * would refuse at the first chunk (k >= 32, a sharded table, an open pass) and a negative window */
+int yakamd_depth(const yakamd_dpopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn)
+{
+	yak_ch_t *h = (yak_ch_t*)ch;
+	const yak_ch_ext *e = (const yak_ch_ext*)ch;
+	const int k = ch->k;
+	const int64_t w = opt->window;
+	if (k >= 32) { fprintf(stderr, "[E::%s] k = %d: k must be below 32 (reference qv.c:44)\n", __func__, k); return -1; }
+	if (w < 0) { fprintf(stderr, "[E::%s] a window of %ld k-mer starts\n", __func__, (long)w); return -1; }
+	if (multi_refuse(ch, __func__)) return -1;                  /* the lookup kernel reads one table image */
+	if (e->magic != EXT_MAGIC || !e->ctx) { fprintf(stderr, "[E::%s] not an engine table\n", __func__); return -1; }
+	if (yk_ctx_in_pass(e->ctx)) { fprintf(stderr, "[E::%s] lookup during an open pass\n", __func__); return -1; }
+	GrowBuf d_t, d_woff, d_win;
+	std::vector<uint64_t> woff;
+	std::vector<yakamd_win_t> win;
+	const char *header = "#name\tstart\tend\tn_kmer\tn_present\tmean\tmedian\tmax\n";
+	return run_chunks(__func__, { fn }, out_fn, opt->chunk_size, header, [&](int, const Chunk &cur, const DevChunk &d, size_t nb, LineOut &out) {
+		const size_t ns = cur.len.size();
+		woff.resize(ns + 1);
+		woff[0] = 0;
+		for (size_t j = 0; j < ns; ++j) woff[j + 1] = woff[j] + (w > 0 && cur.len[j] > 0 ? ((uint64_t)cur.len[j] + w - 1) / w : 1);
+		const uint64_t n_win = woff[ns], batch = (uint64_t)yk_depth_batch_max();
+		bool ok = d_t.fit(cur.img.size() * 2) && d_woff.fit((ns + 1) * 8) && d_win.fit((size_t)std::min(n_win, batch) * sizeof(yakamd_win_t))
+		          && yakamd_memcpy_h2d(d_woff.p, woff.data(), (ns + 1) * 8) == 0 && yakamd_lookup_dev(h, d.img.p, (int64_t)nb, d_t.p) == 0;
+		size_t j = 0;                                              /* the sequence of the window being printed */
+		for (uint64_t g0 = 0; ok && out.ok && g0 < n_win; g0 += batch) {
+			const uint64_t nw = std::min(batch, n_win - g0);
+			win.resize(nw);
+			ok = yk_depth_batch(k, w, d_t.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (const uint64_t*)d_woff.p, (int64_t)ns, (int64_t)nb, g0,
+			                    (uint32_t)nw, d_win.p, 0) == 0
+			     && (hipStreamSynchronize(0) == hipSuccess || yk_set_error("depth reduce: %s", hipGetErrorString(hipGetLastError())) == 0)
+			     && yakamd_memcpy_d2h(win.data(), d_win.p, nw * sizeof(yakamd_win_t)) == 0;
+			for (uint64_t g = g0; ok && out.ok && g < g0 + nw; ++g) {
+				while (g >= woff[j + 1]) ++j;
+				const yakamd_win_t &x = win[g - g0];
+				const uint64_t L = cur.len[j], st = w > 0 ? (g - woff[j]) * (uint64_t)w : 0, en = w > 0 && st + (uint64_t)w < L ? st + (uint64_t)w : L;
+				out.append(cur.names[j]);
+				out.appendf("\t%llu\t%llu\t%u\t%u\t%.3f\t%u\t%u\n", (unsigned long long)st, (unsigned long long)en, x.n_kmer, x.n_present,
+				            x.n_kmer ? (double)x.sum / x.n_kmer : 0.0, x.median, x.max);
+				out.drain();
+			}
+		}
+		return ok;
+	});
+}

@@ -132,6 +132,13 @@ void yk_launch_te_seq(const void *list, const u64 *n_list, int64_t n_max, int k,
 void yk_launch_ce_lookup(const uint8_t *bases, int64_t n, int k, ImgView img, uint8_t *out, int min_cnt, hipStream_t st);
 /* yak sexchr's tally (kern_trioeval.inc): cnt[4 j ..] += n_k, n_sexchr, n_sex1, n_sex2 of record j over the flags (zeroed by the caller) */
 void yk_launch_sc_reduce(const uint8_t *flag, int64_t n, const u64 *seq_off, const u32 *seq_len, int64_t n_seq, u64 *cnt, hipStream_t s);
+/* `yak-amd depth` (kern_depth.inc): the windows of a u16 count array.  DpArgs: the array of n_bytes elements, sequence j at seq_off[j] with seq_len[j]
+ * positions, win_off[j] = windows of the sequences before j (n_seq + 1 words), w = k-mer starts per window (0: one window per sequence) */
+struct DpArgs { const unsigned short *cnt; const u64 *seq_off; const u32 *seq_len; const u64 *win_off; int64_t n_seq, n_bytes; u64 w; int k; };
+int yk_dp_run(void);                                          /* positions of a long window per tile */
+void yk_launch_dp_short(DpArgs a, u64 g0, u32 n_win, u32 T, void *out, u32 *long_list, u64 *tile_base, u32 long_cap, u64 *counter, hipStream_t st);
+void yk_launch_dp_long(DpArgs a, u64 g0, const u32 *long_list, const u64 *tile_base, u32 slot0, u32 n_slots, u64 tile0, u64 n_tiles, u64 *hist, hipStream_t st);
+void yk_launch_dp_finish(const u64 *hist, const u32 *long_list, u32 slot0, u32 n_slots, void *out, hipStream_t st);
 int yk_launch_img_count_lds(const void *rec, int hash_only, const u64 *bstart, ImgView img, int plo, int phi, size_t lds, u64 *compact, u32 stride, hipStream_t st);
 void yk_launch_img_count_h(const u64 *hash, int64_t n, ImgView img, hipStream_t st);
 void yk_launch_img_inc(ImgView img, u64 hash, u64 *out2, hipStream_t st);
