@@ -312,6 +312,35 @@ typedef struct {
 void yakamd_dpopt_init(yakamd_dpopt_t *opt);
 int yakamd_depth(const yakamd_dpopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn);
 
+/* The het-mer pairs of a count table (not in the reference): the k-mers that differ in the middle base alone, with the counts
+ * of both -- the input of a Smudgeplot / PloidyPlot style ploidy analysis.  The table is a YAK_LOAD_ALL one (yak_ch_restore) or a resident one
+ * (yak_count), k odd and below 32; a stored k-mer whose count is below min_cnt (in [1, 1023]) is absent, as a member and as a partner.  x = a stored
+ * canonical k-mer as yakamd_kmers_dev() lists it; for d = 1, 2, 3: y' = x ^ d << (k - 1), y = min(y', revcomp_k(y')); the partners of x are the
+ * distinct y != x in the table.  x and its partners are a group of 1 to 4 members, counted once; a group of two {x < y} is a pair and adds one to
+ * J[min(cx, cy)][max(cx, cy)].  All of it is a pure function of the table's contents and min_cnt.
+ * yakamd_hetmers_dev(): d_joint[lo * 1024 + hi] = J (1024 x 1024 uint64 device bins, accumulated: zero them first), d_group[s] += groups of s
+ * members (5 uint64 device words, [0] unused).  `stream` = a hipStream_t or 0; returns when the device is done.
+ * yakamd_hetmer_pairs_dev(): the pairs as records with x < y, in the table's listing order of x (sub-tables ascending, slots ascending -- the order
+ * of yakamd_kmers_dev()), into d_pairs (cap records, device memory).  Returns their number = the sum of J; when cap is smaller or d_pairs is NULL,
+ * the number needed, and nothing is written.
+ * Both stage the table's keys in ranges of whole sub-tables of at most 2^24 keys and probe the whole resident table; neither builds a host mirror.
+ * -1 after a message (yakamd_last_error()), before any device work: NULL or not an engine table, an even k, k >= 32, min_cnt outside [1, 1023], an
+ * open pass, a table sharded over prefix ranges or spread over several devices, no gfx950 GPU. */
+typedef struct { uint64_t x, y; uint32_t cx, cy; } yakamd_hetpair_t;   /* x < y */
+int yakamd_hetmers_dev(yak_ch_t *h, int min_cnt, uint64_t *d_joint, uint64_t *d_group, void *stream);
+int64_t yakamd_hetmer_pairs_dev(yak_ch_t *h, int min_cnt, void *d_pairs, int64_t cap);
+/* `yak-amd hetmers` as a library call.  To out_fn (NULL or "-" = stdout), tab-separated: the line `#hetmers k=<k> min_cnt=<min_cnt>`; with
+ * print_pairs one line `K <k-mer x> <cx> <k-mer y> <cy>` per pair in listing order (letters as yak print writes them), produced range by range;
+ * `G <s> <groups of s members>` for s = 1 .. 4; `P <lo> <hi> <J[lo][hi]>` for every non-zero bin, lo ascending, then hi.  0 on success; -1 after
+ * a message on stderr -- on one of the refusals above before the output is created. */
+typedef struct {
+	int32_t min_cnt;          /* -c, 1: a k-mer below this count is absent */
+	int32_t print_pairs;      /* -p, 0: the K lines */
+	int64_t batch_keys;       /* keys staged per range of whole sub-tables, 2^24 */
+} yakamd_hmopt_t;
+void yakamd_hmopt_init(yakamd_hmopt_t *opt);
+int yakamd_hetmers(const yakamd_hmopt_t *opt, const yak_ch_t *ch, const char *out_fn);
+
 /* Host-only test hook (no device needed): the base image yak_count() hands to the device for a
  * FASTA/FASTQ(.gz) file -- sequences of >= min_len bases, each followed by '\n'.  use_fast_path = 0
  * forces the general record reader for every record.  *out is malloc()ed; returns its length or -1. */

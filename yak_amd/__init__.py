@@ -42,6 +42,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_kmers_dev", "yakamd_print_dev", "yakamd_propt_init", "yakamd_print", "yakamd_host_syncs",
     "yakamd_ch_sum",
     "yakamd_depth_reduce_dev", "yakamd_dpopt_init", "yakamd_depth",
+    "yakamd_hetmers_dev", "yakamd_hetmer_pairs_dev", "yakamd_hmopt_init", "yakamd_hetmers",
 ]
 
 
@@ -96,6 +97,14 @@ class DpoptT(C.Structure):                     # yakamd_dpopt_t, include/yak_amd
 
 class WinT(C.Structure):                       # yakamd_win_t, include/yak_amd.h
     _fields_ = [("n_kmer", C.c_uint32), ("n_present", C.c_uint32), ("median", C.c_uint32), ("max", C.c_uint32), ("sum", C.c_uint64)]
+
+
+class HmoptT(C.Structure):                     # yakamd_hmopt_t, include/yak_amd.h
+    _fields_ = [("min_cnt", C.c_int32), ("print_pairs", C.c_int32), ("batch_keys", C.c_int64)]
+
+
+class HetpairT(C.Structure):                   # yakamd_hetpair_t, include/yak_amd.h
+    _fields_ = [("x", C.c_uint64), ("y", C.c_uint64), ("cx", C.c_uint32), ("cy", C.c_uint32)]
 
 
 class StreakT(C.Structure):                    # yakamd_streak_t, include/yak_amd.h
@@ -276,6 +285,10 @@ def lib():
     L.yakamd_depth_reduce_dev.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     L.yakamd_dpopt_init.restype = None; L.yakamd_dpopt_init.argtypes = [P(DpoptT)]
     L.yakamd_depth.restype = C.c_int; L.yakamd_depth.argtypes = [P(DpoptT), P(ChT), C.c_char_p, C.c_char_p]
+    L.yakamd_hetmers_dev.restype = C.c_int; L.yakamd_hetmers_dev.argtypes = [P(ChT), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.yakamd_hetmer_pairs_dev.restype = C.c_int64; L.yakamd_hetmer_pairs_dev.argtypes = [P(ChT), C.c_int, C.c_void_p, C.c_int64]
+    L.yakamd_hmopt_init.restype = None; L.yakamd_hmopt_init.argtypes = [P(HmoptT)]
+    L.yakamd_hetmers.restype = C.c_int; L.yakamd_hetmers.argtypes = [P(HmoptT), P(ChT), C.c_char_p]
     _lib = L
     return L
 
@@ -433,6 +446,51 @@ class Table:
         C.CDLL(None).free(out)
         return h.hexdigest(), n
 
+    def hetmers(self, min_cnt=1):
+        """the het-mer pairs of the table (yakamd_hetmers_dev): (J as a dict {(lo, hi): pairs with those two counts}, n_group as a list of 5,
+        [s] = groups of s k-mers that differ in the middle base alone)"""
+        import struct
+        n = 1024 * 1024 * 8 + 64                                # J, then the five group counts
+        d = self.L.yakamd_dev_alloc(n)
+        if not d:
+            raise RuntimeError("yakamd_dev_alloc failed: " + _err())
+        try:
+            if self.L.yakamd_memcpy_h2d(d, bytes(n), n) != 0 or self.L.yakamd_hetmers_dev(self.h, min_cnt, d, d + 1024 * 1024 * 8, None) != 0:
+                raise RuntimeError("yakamd_hetmers_dev failed: " + _err())
+            buf = C.create_string_buffer(n)
+            if self.L.yakamd_memcpy_d2h(buf, d, n) != 0:
+                raise RuntimeError(_err())
+        finally:
+            self.L.yakamd_dev_free(d)
+        raw = buf.raw
+        group = list(struct.unpack_from("<5Q", raw, 1024 * 1024 * 8))
+        J = {}
+        for lo in range(1024):
+            row = raw[lo * 8192:(lo + 1) * 8192]
+            if any(row):
+                J.update({(lo, hi): v for hi, v in enumerate(struct.unpack("<1024Q", row)) if v})
+        return J, group
+
+    def hetmer_pairs(self, min_cnt=1):
+        """the het-mer pairs themselves (yakamd_hetmer_pairs_dev): [(x, y, cx, cy)] with x < y, in the table's listing order of x"""
+        n = self.L.yakamd_hetmer_pairs_dev(self.h, min_cnt, None, 0)
+        if n < 0:
+            raise RuntimeError("yakamd_hetmer_pairs_dev failed: " + _err())
+        if n == 0:
+            return []
+        d = self.L.yakamd_dev_alloc(n * C.sizeof(HetpairT))
+        if not d:
+            raise RuntimeError("yakamd_dev_alloc failed: " + _err())
+        try:
+            if self.L.yakamd_hetmer_pairs_dev(self.h, min_cnt, d, n) != n:
+                raise RuntimeError("yakamd_hetmer_pairs_dev failed: " + _err())
+            recs = (HetpairT * n)()
+            if self.L.yakamd_memcpy_d2h(recs, d, n * C.sizeof(HetpairT)) != 0:
+                raise RuntimeError(_err())
+        finally:
+            self.L.yakamd_dev_free(d)
+        return [(r.x, r.y, r.cx, r.cy) for r in recs]
+
     def subtable(self, i):
         cap, size = C.c_uint32(), C.c_uint32()
         self.L.yakamd_subtable(self.h, i, C.byref(cap), C.byref(size))
@@ -553,6 +611,24 @@ def depth(table_yak, seq, window=0, chunk=None):
         if chunk is not None:
             o.chunk_size = chunk
         return _output_of("yakamd_depth", lambda out: L.yakamd_depth(C.byref(o), h, seq.encode(), out))
+    finally:
+        L.yak_ch_destroy(h)
+
+
+def hetmers(table_yak, min_cnt=1, pairs=False, batch_keys=None):
+    """`yak-amd hetmers` through the C ABI (yak_ch_restore + yakamd_hetmers): the `#hetmers` line, with `pairs` a K line per pair of k-mers that
+    differ in the middle base alone, the G lines (groups of 1 .. 4 such k-mers) and a P line per non-zero bin of the pairs' two counts"""
+    L = lib()
+    h = L.yak_ch_restore(table_yak.encode())
+    if not h:
+        raise RuntimeError("yak_ch_restore failed: " + _err())
+    try:
+        o = HmoptT()
+        L.yakamd_hmopt_init(C.byref(o))
+        o.min_cnt, o.print_pairs = min_cnt, int(bool(pairs))
+        if batch_keys is not None:
+            o.batch_keys = batch_keys
+        return _output_of("yakamd_hetmers", lambda out: L.yakamd_hetmers(C.byref(o), h, out))
     finally:
         L.yak_ch_destroy(h)
 

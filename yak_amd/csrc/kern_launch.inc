@@ -705,4 +705,38 @@ void yk_launch_dp_finish(const u64 *hist, const u32 *long_list, u32 slot0, u32 n
 	hipLaunchKernelGGL(k_dp_finish, dim3(std::min<u32>(want, 65536)), dim3(DP_THREADS), 0, st, (const unsigned long long*)hist, long_list, slot0, n_slots, (DpOut*)out);
 }
 
+/* `yak-amd hetmers` (kern_hetmer.inc): one persistent grid over the n staged keys of sub-tables [sub_lo, sub_lo + n_sub), probing the whole image.
+ * mode 0: the group tallies and J (LDS: the 64 KiB corner, the directory while pre <= 12, the offsets while n_sub <= 4096 -- 80 KiB at pre 10, two
+ * workgroups per CU); mode 1: the pairs per tile into tile_cnt; mode 2: the records at tile_off.  The three modes run the same grid -- the one
+ * mode 0's LDS allows -- so a key is taken by the same workgroup and step in each.  0, or -1 if the launch failed */
+u64 yk_hetmer_tiles(u64 n) { return (n + HM_THREADS - 1) / HM_THREADS; }
+int yk_launch_hetmer(int mode, const u64 *keys, const u64 *off, u64 n, int n_sub, int sub_lo, int min_cnt, ImgView img, u64 *J, u64 *group,
+                     u32 *tile_cnt, const u64 *tile_off, void *list, hipStream_t st)
+{
+	if (n == 0) return 0;
+	if (img.k < 1 || img.k > 31 || !(img.k & 1) || mode < 0 || mode > 2 || (yk_hetmer_tiles(n) >> 31)) return -1;
+	HmArgs a;
+	a.img = keys; a.off = off; a.n = n; a.J = J; a.group = group; a.tile_cnt = tile_cnt; a.tile_off = tile_off; a.list = (u64*)list;
+	a.n_sub = n_sub; a.sub_lo = sub_lo; a.k = img.k; a.min_cnt = min_cnt;
+	a.tab = img.pre <= 12;
+	a.tab_off = n_sub <= 4096;
+	const size_t lds = (mode == 0 ? HM_CORNER_BYTES : 0) + (a.tab ? (size_t)8 << img.pre : 0) + (a.tab_off ? (size_t)8 * n_sub : 0);
+	int dev = 0, n_cu = 0;
+	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
+	const u64 per_cu = std::max<u64>(1, std::min<u64>(4, (u64)(160 * 1024) / (lds + (mode == 0 ? 0 : HM_CORNER_BYTES))));
+	const u64 grid = std::max<u64>(std::min<u64>((u64)n_cu * per_cu, yk_hetmer_tiles(n)), (n >> 31) + 1);
+	static DevOnce attr;
+	if (!attr) {
+		/* 128 KiB is the most a launch asks for (the corner, 32 KiB of directory at pre 12, 32 KiB of offsets); COUNT and WRITE hold 32 bytes of static
+		 * LDS besides, so the whole 160 KiB cannot be asked for as dynamic */
+		for (const void *f : { (const void*)k_hetmer<HM_TALLY>, (const void*)k_hetmer<HM_COUNT>, (const void*)k_hetmer<HM_WRITE> })
+			if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) return -1;
+		attr = true;
+	}
+	if (mode == 0) hipLaunchKernelGGL((k_hetmer<HM_TALLY>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
+	else if (mode == 1) hipLaunchKernelGGL((k_hetmer<HM_COUNT>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
+	else hipLaunchKernelGGL((k_hetmer<HM_WRITE>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
+	return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 } /* extern "C" */

@@ -17,7 +17,8 @@
  *     recount  the counts of a table's k-mers in other sequences, reference main.c:66-88 (restore, tighten, yak_recount)
  *     subtract, isec   the k-mers of the first table absent from / present in the others, reference main.c:217-284
  *     version  the library's YAKS_VERSION
- * and two beyond the reference: sum (yakamd_ch_sum) and depth (yakamd_depth: the depth of every sequence or window in a count table).
+ * and three beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table) and hetmers
+ * (yakamd_hetmers: the pairs of k-mers of a count table that differ in the middle base alone).
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
  */
@@ -26,7 +27,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "yak.h"
-#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum and yakamd_depth */
+#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth and yakamd_hetmers */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
 enum arg_kind { ARG_FLAG, ARG_I32, ARG_SIZE, ARG_I64SIZE, ARG_F64, ARG_TEXT };
@@ -485,6 +486,35 @@ static int cmd_depth(int argc, char **argv)
 	return rc;
 }
 
+/* ---- hetmers (not in the reference) ---- */
+/* the pairs of k-mers of a count table that differ in the middle base alone, as a histogram of their two counts (yakamd_hetmers) */
+static int cmd_hetmers(int argc, char **argv)
+{
+	yakamd_hmopt_t o;
+	const char *out = 0;
+	int pairs = 0, min_cnt = 1;
+	yakamd_hmopt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'c', ARG_I32, &min_cnt, "a k-mer with a count below this is absent, 1 .. 1023 [1]" },
+		{ 'p', ARG_FLAG, &pairs, "list the pairs themselves (K lines)" },
+		{ 'o', ARG_TEXT, &out, "write the lines here; stdout without it" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first >= argc) { arg_help("hetmers [options] <table.yak>", defs, nd); return 1; }
+	uint32_t k = 0, pre = 0;
+	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd hetmers: %s is not a readable .yak file\n", argv[first]); return 2; }
+	if (!(k & 1)) { fprintf(stderr, "yak-amd hetmers: %s has k = %u: a k-mer of even length has no middle base\n", argv[first], k); return 2; }
+	if (k >= 32) { fprintf(stderr, "yak-amd hetmers: %s has k = %u: k must be below 32\n", argv[first], k); return 2; }
+	if (min_cnt < 1 || min_cnt > 1023) { fprintf(stderr, "yak-amd hetmers: -c must be in [1, 1023]\n"); return 1; }
+	o.min_cnt = min_cnt; o.print_pairs = pairs;
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd hetmers: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	const int rc = yakamd_hetmers(&o, tab, out) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 /* ---- version ---- */
 static int cmd_version(int argc, char **argv)
 {
@@ -524,9 +554,11 @@ int main(int argc, char **argv)
 			if (strcmp(argv[1], cmds[i].name) == 0) return cmds[i].run(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "sum") == 0) return cmd_sum(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "depth") == 0) return cmd_depth(argc - 1, argv + 1);
+	if (argc >= 2 && strcmp(argv[1], "hetmers") == 0) return cmd_hetmers(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
 	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-8s %s\n", cmds[i].name, cmds[i].what);
 	fprintf(stderr, "  beyond the reference:\n      yak-amd %-8s %s\n", "sum", "add the counts of two or more .yak tables together");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "depth", "the depth of the k-mers of each sequence, or window, in a .yak table");
+	fprintf(stderr, "      yak-amd %-8s %s\n", "hetmers", "the pairs of k-mers of a .yak table that differ in the middle base, by their two counts");
 	return 1;
 }

@@ -139,6 +139,13 @@ int yk_dp_run(void);                                          /* positions of a 
 void yk_launch_dp_short(DpArgs a, u64 g0, u32 n_win, u32 T, void *out, u32 *long_list, u64 *tile_base, u32 long_cap, u64 *counter, hipStream_t st);
 void yk_launch_dp_long(DpArgs a, u64 g0, const u32 *long_list, const u64 *tile_base, u32 slot0, u32 n_slots, u64 tile0, u64 n_tiles, u64 *hist, hipStream_t st);
 void yk_launch_dp_finish(const u64 *hist, const u32 *long_list, u32 slot0, u32 n_slots, void *out, hipStream_t st);
+/* `yak-amd hetmers` (kern_hetmer.inc): the middle-base neighbours of the n keys of sub-tables [sub_lo, sub_lo + n_sub) (keys / off as yk_launch_kmers
+ * takes them), probed in the whole image `img` (k odd, below 32); a key below min_cnt is absent.  mode 0: group[s] += groups of s members, J[lo * 1024
+ * + hi] += 1 per pair; mode 1: tile_cnt[t] = pairs of tile t (yk_hetmer_tiles(n) words); mode 2: the 24-byte records {x, y, cx, cy} of tile t from
+ * list[tile_off[t]] on (tile_off = the exclusive scan of tile_cnt).  0, or -1 if the launch failed */
+u64 yk_hetmer_tiles(u64 n);
+int yk_launch_hetmer(int mode, const u64 *keys, const u64 *off, u64 n, int n_sub, int sub_lo, int min_cnt, ImgView img, u64 *J, u64 *group,
+                     u32 *tile_cnt, const u64 *tile_off, void *list, hipStream_t st);
 int yk_launch_img_count_lds(const void *rec, int hash_only, const u64 *bstart, ImgView img, int plo, int phi, size_t lds, u64 *compact, u32 stride, hipStream_t st);
 void yk_launch_img_count_h(const u64 *hash, int64_t n, ImgView img, hipStream_t st);
 void yk_launch_img_inc(ImgView img, u64 hash, u64 *out2, hipStream_t st);
