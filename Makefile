@@ -20,6 +20,8 @@ yak_amd/layout.o: $(CSRC)/layout.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSR
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/lookup_dev.o: $(CSRC)/lookup_dev.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+yak_amd/yak_hpc.o: $(CSRC)/yak_hpc.cpp $(CSRC)/hpc_host.h $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/yak_hetmer.o: $(CSRC)/yak_hetmer.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/pool.o: $(CSRC)/pool.cpp $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
@@ -29,7 +31,7 @@ yak_amd/yak_api.o: $(CSRC)/yak_api.cpp $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/yak_reader.o: $(CSRC)/yak_reader.cpp $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/yak_multi.o: $(CSRC)/yak_multi.cpp $(HOSTDEPS)
+yak_amd/yak_multi.o: $(CSRC)/yak_multi.cpp $(CSRC)/hpc_host.h $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/yak_lookup.o: $(CSRC)/yak_lookup.cpp $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -37,7 +39,7 @@ yak_amd/yak_inspect.o: $(CSRC)/yak_inspect.cpp $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/yak_print.o: $(CSRC)/yak_print.cpp $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/pool.o yak_amd/engine.o yak_amd/layout.o yak_amd/lookup_dev.o yak_amd/yak_hetmer.o yak_amd/yak_api.o yak_amd/yak_reader.o yak_amd/yak_multi.o yak_amd/yak_lookup.o yak_amd/yak_inspect.o yak_amd/yak_print.o $(CSRC)/libyak_amd.map
+yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/pool.o yak_amd/engine.o yak_amd/layout.o yak_amd/lookup_dev.o yak_amd/yak_hetmer.o yak_amd/yak_hpc.o yak_amd/yak_api.o yak_amd/yak_reader.o yak_amd/yak_multi.o yak_amd/yak_lookup.o yak_amd/yak_inspect.o yak_amd/yak_print.o $(CSRC)/libyak_amd.map
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(CSRC)/libyak_amd.map -o $@ $(filter %.o,$^) -lz
 
 yak_amd/yak-amd: $(CSRC)/main.c include/yak.h include/yak_amd.h yak_amd/libyak_amd.so

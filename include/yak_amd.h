@@ -341,6 +341,35 @@ typedef struct {
 void yakamd_hmopt_init(yakamd_hmopt_t *opt);
 int yakamd_hetmers(const yakamd_hmopt_t *opt, const yak_ch_t *ch, const char *out_fn);
 
+/* Homopolymer compression (HPC; not in the reference): every run of the same base collapses to one base before k-mers are taken,
+ * the space long-read assemblers and their QV pipelines count in.  On a base image as described at the top of this file: a position is VALID when its
+ * byte has a code 0..3 under seq_nt4_table (in the packed form: its validity bit).  Position i is DROPPED iff i > 0, i and i - 1 are both valid and
+ * their codes are equal; every other position is KEPT, an invalid one too, so an invalid position ends the run before it (AANAA -> ANA; Aa and TU are
+ * one base each).  The output is the kept positions in order as an ASCII image -- 'A' 'C' 'G' 'T' for a valid one, '\n' for an invalid one -- and '\n'
+ * from n_out up to the next multiple of 16: what compressing every record's sequence on the host and building the image from the result gives.
+ * yakamd_hpc_dev(): the ASCII image; with n_seq > 0 also, for sequence j = bytes [d_seq_off[j], d_seq_off[j] + d_seq_len[j]) of the input,
+ * d_seq_off_out[j] = kept positions before d_seq_off[j] and d_seq_len_out[j] = kept positions inside it (the arrays may be NULL with n_seq 0).
+ * yakamd_hpc_packed_dev(): the packed image of yakamd_feed_packed_dev().  Inputs 16-byte aligned (d_valid: 4); d_out 16-byte aligned, not overlapping
+ * the input, with room for n rounded up to 16.  Both return n_out (0 for an empty image, without a launch) or -1 after a message, need no table and
+ * return when the device is done; `stream` = a hipStream_t or 0.  yakamd_hpc_host(): the same function in plain C++ on host memory, no device. */
+int64_t yakamd_hpc_dev(const void *d_bases, int64_t n_bytes, void *d_out, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
+                       uint64_t *d_seq_off_out, uint32_t *d_seq_len_out, void *stream);
+int64_t yakamd_hpc_packed_dev(const void *d_codes, const void *d_valid, int64_t n_bases, void *d_out, void *stream);
+int64_t yakamd_hpc_host(const void *ascii, int64_t n_bytes, void *out);
+/* Tables that live in HPC space.  The .yak format cannot record the space and yak_copt_t is the reference's: the mark is on the table (dump and restore
+ * do not carry it: mark a restored table again).  While a table is marked, every feed of BASES into it -- yakamd_feed_bases_*, yakamd_feed_packed_*,
+ * every reader route of yak_count() and the chunks of a multi-GPU job -- is compacted on the device first; t0 stays the uncompressed stream position of
+ * the feed.  Feeds of hashes or partitioned records are taken as they are: their producer chose the space.  yak_qv() on a marked table compacts every
+ * chunk before it looks it up, and min_len, the SQ lengths and the EK positions are in compressed coordinates; yakamd_triobin, yakamd_trioeval,
+ * yakamd_chkerr, yakamd_sexchr and yakamd_depth refuse a marked table with a message before any output.  Table-to-table calls ignore the mark.
+ * yakamd_ch_set_hpc(): 0, or -1 after a message inside an open pass; a table sharded over ranks has every shard marked.
+ * yakamd_count_hpc(): yak_count() in HPC space -- h0 == 0: the new table is marked before its first feed; h0 marked: its k-mers are counted
+ * (yak_count(fn, opt, h0) does the same: the mark governs, so the filtered two-pass protocol works with either call); h0 unmarked: refused, NULL.
+ * A sequence longer than a multi-GPU chunk is cut so that the next chunk opens with the last k - 1 KEPT positions of the one before. */
+int yakamd_ch_set_hpc(yak_ch_t *h, int on);
+int yakamd_ch_hpc(const yak_ch_t *h);
+yak_ch_t *yakamd_count_hpc(const char *fn, const yak_copt_t *opt, yak_ch_t *h0);
+
 /* Host-only test hook (no device needed): the base image yak_count() hands to the device for a
  * FASTA/FASTQ(.gz) file -- sequences of >= min_len bases, each followed by '\n'.  use_fast_path = 0
  * forces the general record reader for every record.  *out is malloc()ed; returns its length or -1. */

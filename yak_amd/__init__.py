@@ -43,6 +43,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_ch_sum",
     "yakamd_depth_reduce_dev", "yakamd_dpopt_init", "yakamd_depth",
     "yakamd_hetmers_dev", "yakamd_hetmer_pairs_dev", "yakamd_hmopt_init", "yakamd_hetmers",
+    "yakamd_hpc_dev", "yakamd_hpc_packed_dev", "yakamd_hpc_host", "yakamd_ch_set_hpc", "yakamd_ch_hpc", "yakamd_count_hpc",
 ]
 
 
@@ -148,6 +149,13 @@ def lib():
     L.yak_ch_dump.restype = C.c_int; L.yak_ch_dump.argtypes = [P(ChT), C.c_char_p]
     L.yak_ch_restore.restype = P(ChT); L.yak_ch_restore.argtypes = [C.c_char_p]
     L.yak_count.restype = P(ChT); L.yak_count.argtypes = [C.c_char_p, P(CoptT), P(ChT)]
+    L.yakamd_count_hpc.restype = P(ChT); L.yakamd_count_hpc.argtypes = [C.c_char_p, P(CoptT), P(ChT)]
+    L.yakamd_ch_set_hpc.restype = C.c_int; L.yakamd_ch_set_hpc.argtypes = [P(ChT), C.c_int]
+    L.yakamd_ch_hpc.restype = C.c_int; L.yakamd_ch_hpc.argtypes = [P(ChT)]
+    L.yakamd_hpc_dev.restype = C.c_int64
+    L.yakamd_hpc_dev.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.yakamd_hpc_packed_dev.restype = C.c_int64; L.yakamd_hpc_packed_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.yakamd_hpc_host.restype = C.c_int64; L.yakamd_hpc_host.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
     L.yak_bf_init.restype = C.c_void_p; L.yak_bf_init.argtypes = [C.c_int, C.c_int]
     L.yak_bf_insert.restype = C.c_int; L.yak_bf_insert.argtypes = [C.c_void_p, C.c_uint64]
     L.yak_bf_destroy.argtypes = [C.c_void_p]

@@ -106,6 +106,7 @@ yakamd_ctx *yk_ctx_create(int k, int pre, int n_hash, int n_shift)
 	c->in_pass = false; c->gate_off = false; c->or_mode = 0; c->acc.s = 0; c->acc_count = 0;
 	c->d_counters = 0; c->d_lastput = 0; c->d_lpbatch = 0; c->d_missing = 0; c->d_nmissing = 0;
 	c->d_rec = 0; c->rec_cap = 0; c->d_newlist = 0; c->d_miss = 0; c->d_cand = 0; c->new_cap = 0;
+	c->hpc = false; c->d_hpc = 0; c->hpc_cap = 0;
 	c->d_stage = 0; c->stage_cap = 0; c->t_end = 0; c->list_t = 0; c->d_scratch = 0; c->scratch_bytes = 0;
 	c->d_rows = 0; c->d_partial = 0; c->d_bstart = 0; c->rows_blk = 0;
 	c->nb_bits = (int)std::min<int64_t>(pre, env_i64("YAKAMD_PART_BITS", 13));
@@ -170,6 +171,7 @@ static void pass_free(yakamd_ctx *c)
 	c->kept.clear(); c->kept_bytes = 0;
 	dfree(c->acc.s); c->acc_count = 0;
 	dfree(c->d_rec); c->rec_cap = 0;
+	dfree(c->d_hpc); c->hpc_cap = 0;
 	dfree(c->d_newlist); dfree(c->d_miss); dfree(c->d_cand); c->new_cap = 0;
 	c->in_pass = false;
 }
@@ -711,6 +713,19 @@ static int feed_image(yak_ch_t *h, const void *d_bases, const u32 *d_valid, int6
 	if (c->k >= 64 || c->k < 1) return fail("k must be in [1, 63]");
 	if (((uintptr_t)d_bases & 15) != 0) return fail("device base image must be 16-byte aligned");
 	HIPCK(hipSetDevice(c->dev));
+	if (c->hpc && n_bytes > 0) {
+		/* a table in homopolymer-compressed space: the image is compacted, ASCII or packed, into the pass's buffer and the feed goes
+		 * on with that.  t0 stays the feed's position in the uncompressed stream: a compressed position is no larger than the original one, so the
+		 * feeds keep their order, and only the order of stream positions matters */
+		if (n_bytes > c->hpc_cap) {
+			dfree(c->d_hpc);
+			c->hpc_cap = ((n_bytes + (n_bytes >> 3) + 4096) + 15) & ~(int64_t)15;
+			if (dmalloc(&c->d_hpc, (size_t)c->hpc_cap)) { c->hpc_cap = 0; return -1; }
+		}
+		const int64_t n_out = yk_hpc_compact(d_bases, d_valid, n_bytes, c->d_hpc, 0, 0, 0, 0, 0, c->st);
+		if (n_out < 0) return -1;
+		d_bases = c->d_hpc; d_valid = 0; n_bytes = n_out;
+	}
 	int64_t batch = env_i64("YAKAMD_BATCH", (int64_t)1 << 31);
 	batch = std::min<int64_t>((int64_t)1 << 31, std::max<int64_t>(4096, batch & ~(int64_t)4095));   /* run starts are 31-bit (tagged records: bit 31 is the toggle) */
 	int hash_only = !c->create_new;                        /* counting existing keys needs no stream positions */
@@ -902,6 +917,30 @@ extern "C" int yakamd_feed_partitioned_lent_dev(yak_ch_t *h, const void *d_rec, 
 }
 
 /* 1 while the open pass of h runs on the exclusive-ownership path (the only one that takes tagged records) */
+/* the table's space.  The mark is the table's, not the file's: dump and restore do not carry it */
+extern "C" int yakamd_ch_set_hpc(yak_ch_t *h, int on)
+{
+	const yak_ch_ext *e = (const yak_ch_ext*)h;
+	if (!h || e->magic != EXT_MAGIC) return fail("not an engine table");
+	if (e->n_sub > 1) {                                        /* sharded over ranks: every shard, or none */
+		for (int r = 0; r < e->n_sub; ++r) { yakamd_ctx *c = ctx_of(e->sub[r]); if (!c) return fail("not an engine table"); if (c->in_pass) return fail("yakamd_ch_set_hpc inside an open pass"); }
+		for (int r = 0; r < e->n_sub; ++r) ctx_of(e->sub[r])->hpc = on != 0;
+		return 0;
+	}
+	yakamd_ctx *c = e->ctx;
+	if (!c) return fail("not an engine table");
+	if (c->in_pass) return fail("yakamd_ch_set_hpc inside an open pass");
+	c->hpc = on != 0;
+	return 0;
+}
+extern "C" int yakamd_ch_hpc(const yak_ch_t *h)
+{
+	const yak_ch_ext *e = (const yak_ch_ext*)h;
+	if (!h || e->magic != EXT_MAGIC) return 0;
+	const yakamd_ctx *c = e->n_sub > 1 ? ctx_of(e->sub[0]) : e->ctx;
+	return c && c->hpc;
+}
+
 extern "C" int yakamd_pass_fast(yak_ch_t *h) { yakamd_ctx *c = ctx_of(h); return c && c->in_pass && c->fast && !c->or_mode; }
 
 extern "C" int yakamd_feed_partitioned_tagged_dev(yak_ch_t *h, const void *d_rec8, int64_t n, const uint64_t *h_bstart, uint64_t t0, uint64_t t_span, int lent)

@@ -65,6 +65,10 @@ int  yk_inspect_engines(const yak_ch_t *h, std::vector<yakamd_ctx*> *eng);   /* 
 int64_t yk_depth_batch_max(void);
 int  yk_depth_batch(int k, int64_t w, const void *d_cnt_u16, const uint64_t *d_seq_off, const uint32_t *d_seq_len, const uint64_t *d_win_off,
                     int64_t n_seq, int64_t n_bytes, uint64_t g0, uint32_t n_win, void *d_win, hipStream_t st);
+/* yak_hpc.cpp: homopolymer compression (kern_hpc.inc) of an ASCII (valid == 0) or packed image on `st` into `out` (room for n rounded up to 16), with
+ * n_seq > 0 the sequences' offsets and lengths in the compressed image too; returns the compressed length, or -1 after a message.  Synchronises `st` */
+int64_t yk_hpc_compact(const void *in, const u32 *valid, int64_t n, void *out, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
+                       uint64_t *d_seq_off_out, uint32_t *d_seq_len_out, hipStream_t st);
 size_t yk_pool_cached_bytes(void);
 size_t yk_pool_held_bytes(int dev);
 void yk_pool_report(const char *what);

@@ -90,6 +90,8 @@ struct yakamd_ctx {
 	Rec *d_rec; int64_t rec_cap;
 	u64 *d_newlist, *d_miss, *d_cand; int64_t new_cap;
 	uint8_t *d_stage; int64_t stage_cap;
+	bool hpc;                          /* the table lives in homopolymer-compressed space (yakamd_ch_set_hpc): every feed of bases is compacted first */
+	uint8_t *d_hpc; int64_t hpc_cap;   /* ... into this buffer, kept for the pass */
 	u32 *d_rows; u64 *d_partial, *d_bstart; int rows_blk; int nb_bits;
 	/* fast path: level-1 partitioned batches kept until pass_end */
 	struct Kept { Rec *d_rec; u64 n; u64 t0, span; std::vector<u64> bstart; bool owned; int fmt; };   /* fmt 1: tagged 8-byte records (yk_device.h YK_R8_*) */

@@ -739,4 +739,30 @@ int yk_launch_hetmer(int mode, const u64 *keys, const u64 *off, u64 n, int n_sub
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+/* homopolymer compression (kern_hpc.inc).  valid == 0: `in` is the ASCII image; valid != 0: the packed one (code words at `in`).  Tiles of
+ * yk_hpc_tile(packed) positions; tcnt = yk_hpc_tiles() words, toff = their exclusive scan (yk_launch_te_scan), one word more */
+int64_t yk_hpc_tile(int packed) { return (int64_t)HP_THREADS * (packed ? (int)HpPacked::PER : (int)HpAscii::PER); }
+int64_t yk_hpc_tiles(int packed, int64_t n) { return (n + yk_hpc_tile(packed) - 1) / yk_hpc_tile(packed); }
+void yk_launch_hpc_count(const void *in, const u32 *valid, int64_t n, u32 *tcnt, hipStream_t st)
+{
+	const int64_t nt = yk_hpc_tiles(valid != 0, n);
+	if (nt <= 0) return;
+	if (valid) hipLaunchKernelGGL(k_hpc_count<HpPacked>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpPacked{ (const u32*)in, valid }, n, tcnt);
+	else hipLaunchKernelGGL(k_hpc_count<HpAscii>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpAscii{ (const uint8_t*)in }, n, tcnt);
+}
+void yk_launch_hpc_scatter(const void *in, const u32 *valid, int64_t n, const u64 *toff, uint8_t *out, hipStream_t st)
+{
+	const int64_t nt = yk_hpc_tiles(valid != 0, n);
+	if (nt <= 0) return;
+	if (valid) hipLaunchKernelGGL(k_hpc_scatter<HpPacked>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpPacked{ (const u32*)in, valid }, n, toff, nt, out);
+	else hipLaunchKernelGGL(k_hpc_scatter<HpAscii>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpAscii{ (const uint8_t*)in }, n, toff, nt, out);
+}
+/* one wave per sequence; toff = the scan of the ASCII form's tiles */
+void yk_launch_hpc_remap(const uint8_t *a, int64_t n, const u64 *toff, const u64 *off, const u32 *len, int64_t n_seq, u64 *off_out, u32 *len_out, hipStream_t st)
+{
+	if (n_seq <= 0) return;
+	const int64_t nb = (n_seq + HP_THREADS / WAVE - 1) / (HP_THREADS / WAVE);
+	hipLaunchKernelGGL(k_hpc_remap, dim3((unsigned)nb), dim3(HP_THREADS), 0, st, HpAscii{ a }, n, toff, off, len, n_seq, off_out, len_out);
+}
+
 } /* extern "C" */

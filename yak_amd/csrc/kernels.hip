@@ -10,6 +10,7 @@
  *   srt k_seg_sort_pass  per sub-table LSD radix sort by insertion time
  *   K5  k_replay         exact khashl layout: staged FCFS placement + in-place doubling [khashl.h:152-221]
  * `yak inspect` (inspect.c:47-62): k_inspect joins the stored keys of one table with another table's image into a 1024 x 1024 histogram.
+ * Homopolymer compression of the input (kern_hpc.inc): k_hpc_count, k_hpc_scatter and k_hpc_remap compact a base image in front of the kernels above.
  * `yak print` (main.c:302-320): k_kmers and k_print turn the stored keys back into k-mers and into the text the reference writes.
  * All work is 64-bit integer arithmetic; the bound is HBM / L2-atomic traffic, never MFMA.
  *
@@ -101,4 +102,5 @@ __device__ const unsigned char d_nt4[256] = {
 #include "kern_print.inc"
 #include "kern_depth.inc"
 #include "kern_hetmer.inc"
+#include "kern_hpc.inc"
 #include "kern_launch.inc"

@@ -18,7 +18,8 @@
  *     subtract, isec   the k-mers of the first table absent from / present in the others, reference main.c:217-284
  *     version  the library's YAKS_VERSION
  * and three beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table) and hetmers
- * (yakamd_hetmers: the pairs of k-mers of a count table that differ in the middle base alone).
+ * (yakamd_hetmers: the pairs of k-mers of a count table that differ in the middle base alone).  `count -c` and `qv -c` work in homopolymer-compressed
+ * space (yakamd_count_hpc; yakamd_ch_set_hpc on the restored table): every run of one base is one base before k-mers are taken.
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
  */
@@ -27,7 +28,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "yak.h"
-#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth and yakamd_hetmers */
+#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_count_hpc and yakamd_ch_set_hpc */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
 enum arg_kind { ARG_FLAG, ARG_I32, ARG_SIZE, ARG_I64SIZE, ARG_F64, ARG_TEXT };
@@ -90,6 +91,7 @@ static int cmd_count(int argc, char **argv)
 {
 	yak_copt_t o;
 	const char *out = 0;
+	int hpc = 0;
 	yak_copt_init(&o);
 	const struct arg_def defs[] = {
 		{ 'k', ARG_I32, &o.k, "k-mer length, below 64 (counts are approximate from 32 on)" },
@@ -99,6 +101,7 @@ static int cmd_count(int argc, char **argv)
 		{ 't', ARG_I32, &o.n_thread, "host threads (parser)" },
 		{ 'K', ARG_I64SIZE, &o.chunk_size, "bases per host batch" },
 		{ 'o', ARG_TEXT, &out, "write the table (.yak) here" },
+		{ 'c', ARG_FLAG, &hpc, "count in homopolymer-compressed space: every run of one base is one base (compacted on the device)" },
 	};
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
@@ -106,12 +109,12 @@ static int cmd_count(int argc, char **argv)
 	if (o.pre < YAK_COUNTER_BITS || o.k < 1 || o.k >= 64) { fprintf(stderr, "yak-amd count: need 1 <= k < 64 and p >= %d\n", YAK_COUNTER_BITS); return 1; }
 	if (o.k >= 32) fprintf(stderr, "yak-amd count: k >= 32 uses the 64-bit sum hash: counts are approximate\n");
 	const char *pass1 = argv[first], *pass2 = first + 1 < argc ? argv[first + 1] : argv[first];
-	yak_ch_t *tab = yak_count(pass1, &o, 0);
+	yak_ch_t *tab = hpc ? yakamd_count_hpc(pass1, &o, 0) : yak_count(pass1, &o, 0);
 	if (!tab) { fprintf(stderr, "yak-amd count: no table (unreadable input, or no MI355X)\n"); return 2; }
 	if (o.bf_shift > 0) {                                    /* filtered mode: pass 1 picked the keys, pass 2 counts them */
 		yak_ch_destroy_bf(tab);
 		yak_ch_clear(tab, o.n_thread);
-		if (!yak_count(pass2, &o, tab)) { yak_ch_destroy(tab); return 2; }
+		if (!(hpc ? yakamd_count_hpc(pass2, &o, tab) : yak_count(pass2, &o, tab))) { yak_ch_destroy(tab); return 2; }
 		yak_ch_shrink(tab, 2, YAK_MAX_COUNT, o.n_thread);
 		fprintf(stderr, "[M::yak-amd] %ld distinct k-mers after shrinking\n", (long)tab->tot);
 	}
@@ -134,6 +137,7 @@ static const char *const qv_legend[] = {                     /* output format of
 static int cmd_qv(int argc, char **argv)
 {
 	yak_qopt_t o;
+	int hpc = 0;
 	yak_qopt_init(&o);
 	const struct arg_def defs[] = {
 		{ 'l', ARG_SIZE, &o.min_len, "skip sequences shorter than this" },
@@ -143,12 +147,14 @@ static int cmd_qv(int argc, char **argv)
 		{ 'E', ARG_FLAG, &o.print_err_kmer, "one EK line per absent k-mer run" },
 		{ 't', ARG_I32, &o.n_threads, "host threads" },
 		{ 'K', ARG_I64SIZE, &o.chunk_size, "bases per device batch" },
+		{ 'c', ARG_FLAG, &hpc, "the table was counted with `count -c`: compress the sequences too (lengths and positions are then compressed ones)" },
 	};
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 1 >= argc) { arg_help("qv [options] <table.yak> <sequences.fa>", defs, nd); return 1; }
 	yak_ch_t *tab = yak_ch_restore(argv[first]);
 	if (!tab) { fprintf(stderr, "yak-amd qv: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	if (hpc && yakamd_ch_set_hpc(tab, 1) != 0) { yak_ch_destroy(tab); return 2; }
 	static int64_t in_table[YAK_N_COUNTS], in_seqs[YAK_N_COUNTS];
 	static yak_qstat_t st;
 	const int k = tab->k;

@@ -736,14 +736,26 @@ yak_ch_t *yak_ch_restore_core(yak_ch_t *ch0, const char *fn, int mode, ...)
 
 yak_ch_t *yak_ch_restore(const char *fn) { return yak_ch_restore_core(0, fn, YAK_LOAD_ALL); }   /* reference htab.c:478 */
 
-yak_ch_t *yak_count(const char *fn, const yak_copt_t *opt, yak_ch_t *h0)
+/* hpc: a new table is marked as living in homopolymer-compressed space before its first feed (yakamd_count_hpc); an existing table's own mark governs */
+static yak_ch_t *count_file(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, bool hpc);
+yak_ch_t *yak_count(const char *fn, const yak_copt_t *opt, yak_ch_t *h0) { return count_file(fn, opt, h0, false); }
+yak_ch_t *yakamd_count_hpc(const char *fn, const yak_copt_t *opt, yak_ch_t *h0)
+{
+	if (h0 && !yakamd_ch_hpc(h0)) {
+		yk_set_error("yakamd_count_hpc: the table is not marked as homopolymer-compressed (yakamd_ch_set_hpc); its keys were chosen in uncompressed space");
+		return 0;
+	}
+	return count_file(fn, opt, h0, true);
+}
+
+static yak_ch_t *count_file(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, bool hpc)
 {
 	{
 		std::vector<int> dev;
 		const int N = h0 ? ((yak_ch_ext*)h0)->n_sub : multi_gpus(opt, &dev, fn);
 		if (N > 1) {
 			if (h0) { dev.clear(); for (int r = 0; r < N; ++r) dev.push_back(yk_ctx_device(((yak_ch_ext*)((yak_ch_ext*)h0)->sub[r])->ctx)); }
-			return yak_count_multi(fn, opt, h0, N, dev);
+			return yak_count_multi(fn, opt, h0, N, dev, hpc);
 		}
 	}
 	/* the file's identity: the filtered protocol counts the same file twice (main.c:53-57); the first call then keeps its hashed k-mers on
@@ -795,6 +807,7 @@ yak_ch_t *yak_count(const char *fn, const yak_copt_t *opt, yak_ch_t *h0)
 	int ok = 0;
 	auto open_table = [&]() {                                /* a new table: runtime start-up, the filter's 2^bf_shift bits, the pass */
 		if (!h0) h = yak_ch_init(opt->k, opt->pre, opt->bf_n_hash, opt->bf_shift);
+		if (!h0 && h && hpc) yakamd_ch_set_hpc(h, 1);
 		if (!h0 && h && have_sid && opt->bf_shift > opt->pre) yakamd_retain_input(h, 1);   /* a filtered count: a second pass over this file is to be expected */
 		ok = h != 0 && (pass_open || yakamd_pass_begin(h, create_new) == 0);
 	};

@@ -447,5 +447,5 @@ extern "C" int multi_refuse(const yak_ch_t *h, const char *what);
 bool env_fast_default();
 int auto_sweeps(const yak_copt_t *opt, const char *fn);
 int multi_gpus(const yak_copt_t *opt, std::vector<int> *dev, const char *fn = 0);
-yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, int N, const std::vector<int> &dev);
+yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, int N, const std::vector<int> &dev, bool hpc = false);   /* hpc: a new table is marked (yakamd_ch_set_hpc) */
 #endif

@@ -131,6 +131,15 @@ int run_chunks(const char *who, std::initializer_list<const char*> fns, const ch
 	return ok ? 0 : -1;
 }
 
+/* a table in homopolymer-compressed space (yakamd_ch_set_hpc) looked up with uncompressed sequence answers wrongly without a sign:
+ * the commands that have no compressed form refuse it before they create any output */
+bool hpc_refuse(const yak_ch_t *ch, const char *who)
+{
+	if (!yakamd_ch_hpc(ch)) return false;
+	yk_set_error("%s: the table is marked as homopolymer-compressed (yakamd_ch_set_hpc) and this command reads uncompressed sequence: only yak_qv() compresses what it looks up", who);
+	return true;
+}
+
 }   // namespace
 
 /* reference qv.c:137-144 */
@@ -163,15 +172,35 @@ void yak_qv(const yak_qopt_t *opt, const char *fn, const yak_ch_t *ch, int64_t *
 	std::vector<unsigned short> h_t;
 	Chunk chunk;
 	DevChunk d;
-	GrowBuf d_t, d_tot, d_non0;
+	GrowBuf d_t, d_tot, d_non0, d_cimg, d_coff, d_clen;
+	std::vector<uint64_t> c_off;                                 /* a marked table: the chunk's offsets and lengths in its compressed image */
+	std::vector<uint32_t> c_len;
+	const bool hpc = yakamd_ch_hpc(ch) != 0;
 	bool ok = d_hist && yakamd_memcpy_h2d(d_hist, zero.data(), n_cnt * 8) == 0;
 	auto flush = [&]() {
 		const size_t ns = chunk.len.size();
 		if (ns == 0) return;
 		const size_t nb = chunk.pad();
-		ok = ok && d.put(chunk) && d_t.fit(chunk.img.size() * 2) && d_tot.fit(ns * 4) && d_non0.fit(ns * 4)
-		     && yakamd_lookup_dev(h, d.img.p, (int64_t)nb, d_t.p) == 0
-		     && yakamd_qv_reduce_dev(h, d_t.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, opt->min_len, opt->min_frac,
+		ok = ok && d.put(chunk) && d_t.fit(chunk.img.size() * 2) && d_tot.fit(ns * 4) && d_non0.fit(ns * 4);
+		const void *img = d.img.p, *off = d.off.p, *len = d.len.p;
+		int64_t n_img = (int64_t)nb;
+		const uint64_t *h_off = chunk.off.data();
+		const uint32_t *h_len = chunk.len.data();
+		if (ok && hpc) {
+			/* the table's k-mers are those of compressed sequence: the chunk is compacted on the device and everything behind -- the
+			 * lookup, min_len, the SQ lengths and the EK positions -- is in compressed coordinates, as a run on the host-compressed file gives them */
+			ok = d_cimg.fit(chunk.img.size()) && d_coff.fit(ns * 8) && d_clen.fit(ns * 4);
+			if (ok) n_img = yakamd_hpc_dev(d.img.p, (int64_t)nb, d_cimg.p, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, (uint64_t*)d_coff.p, (uint32_t*)d_clen.p, 0);
+			ok = ok && n_img >= 0;
+			img = d_cimg.p; off = d_coff.p; len = d_clen.p;
+			if (ok && want_names) {
+				c_off.resize(ns); c_len.resize(ns);
+				ok = yakamd_memcpy_d2h(c_off.data(), d_coff.p, ns * 8) == 0 && yakamd_memcpy_d2h(c_len.data(), d_clen.p, ns * 4) == 0;
+				h_off = c_off.data(); h_len = c_len.data();
+			}
+		}
+		ok = ok && yakamd_lookup_dev(h, img, n_img, d_t.p) == 0
+		     && yakamd_qv_reduce_dev(h, d_t.p, (const uint64_t*)off, (const uint32_t*)len, (int64_t)ns, opt->min_len, opt->min_frac,
 		                             (uint32_t*)d_tot.p, (uint32_t*)d_non0.p, d_hist) == 0;
 		if (ok && want_names) {
 			h_tot.resize(ns); h_non0.resize(ns);
@@ -180,8 +209,8 @@ void yak_qv(const yak_qopt_t *opt, const char *fn, const yak_ch_t *ch, int64_t *
 			for (size_t j = 0; ok && j < ns; ++j) {
 				if (h_tot[j] == 0xffffffffu) continue;                          /* below min_len: qv.c:45 */
 				if (opt->print_err_kmer)
-					for (uint32_t i = 0; i < chunk.len[j]; ++i)
-						if (h_t[chunk.off[j] + i] == 0) printf("EK\t%s\t%d\n", chunk.names[j].c_str(), (int)(i + 1 - ch->k));
+					for (uint32_t i = 0; i < h_len[j]; ++i)
+						if (h_t[h_off[j] + i] == 0) printf("EK\t%s\t%d\n", chunk.names[j].c_str(), (int)(i + 1 - ch->k));
 				if (opt->print_each) {
 					const int tot = (int)h_tot[j], non0 = (int)h_non0[j];
 					double qv = -1.0;
@@ -191,7 +220,7 @@ void yak_qv(const yak_qopt_t *opt, const char *fn, const yak_ch_t *ch, int64_t *
 							else qv = 99.0;
 						} else qv = 0.0;
 					}
-					printf("SQ\t%s\t%d\t%d\t%d\t%.2f\n", chunk.names[j].c_str(), (int)chunk.len[j], tot, non0, qv);
+					printf("SQ\t%s\t%d\t%d\t%d\t%.2f\n", chunk.names[j].c_str(), (int)h_len[j], tot, non0, qv);
 				}
 			}
 		}
@@ -253,6 +282,7 @@ int yakamd_triobin(const yakamd_tbopt_t *opt, const yak_ch_t *ch, const char *fn
 {
 	yak_ch_t *h = (yak_ch_t*)ch;
 	const int k = ch->k;
+	if (hpc_refuse(ch, __func__)) return -1;
 	GrowBuf d_flag, d_cnt;
 	std::vector<uint8_t> flag;
 	std::vector<int32_t> cnt;
@@ -306,6 +336,7 @@ int yakamd_trioeval(const yakamd_teopt_t *opt, const yak_ch_t *ch, const char *f
 	yak_ch_t *h = (yak_ch_t*)ch;
 	const int k = ch->k;
 	const bool want_list = opt->print_err || opt->print_frag;
+	if (hpc_refuse(ch, __func__)) return -1;
 	const char *header =
 		"C\tS  seqName     #patKmer  #matKmer  #pat-pat  #pat-mat  #mat-pat  #mat-mat  seqLen\n"
 		"C\tF  seqName     type      startPos  endPos    count\n"
@@ -392,7 +423,7 @@ int yakamd_chkerr(const yakamd_ceopt_t *opt, const yak_ch_t *ch, const char *fn,
 {
 	yak_ch_t *h = (yak_ch_t*)ch;
 	const int k = ch->k;
-	if (multi_refuse(ch, __func__)) return -1;                  /* the lookup kernel reads one table image */
+	if (multi_refuse(ch, __func__) || hpc_refuse(ch, __func__)) return -1;   /* the lookup kernel reads one table image */
 	const bool phantom = opt->min_streak < 0;
 	GrowBuf d_low;
 	std::vector<yakamd_streak_t> sk;
@@ -432,7 +463,7 @@ void yakamd_scopt_init(yakamd_scopt_t *opt)
 int yakamd_sexchr(const yakamd_scopt_t *opt, const yak_ch_t *ch, const char *fn_hap1, const char *fn_hap2, const char *out_fn)
 {
 	yak_ch_t *h = (yak_ch_t*)ch;
-	if (multi_refuse(ch, __func__)) return -1;
+	if (multi_refuse(ch, __func__) || hpc_refuse(ch, __func__)) return -1;
 	const char *header = "C\tS  seqName  originalHap  0  #k-mer  #sexchr  #sex1-specifc  #sex2-specific\nC\n";   /* sexchr.c:120-121, its spelling */
 	GrowBuf d_flag, d_cnt;
 	std::vector<uint64_t> cnt;
@@ -474,7 +505,7 @@ int yakamd_depth(const yakamd_dpopt_t *opt, const yak_ch_t *ch, const char *fn, 
 	const int64_t w = opt->window;
 	if (k >= 32) { fprintf(stderr, "[E::%s] k = %d: k must be below 32 (reference qv.c:44)\n", __func__, k); return -1; }
 	if (w < 0) { fprintf(stderr, "[E::%s] a window of %ld k-mer starts\n", __func__, (long)w); return -1; }
-	if (multi_refuse(ch, __func__)) return -1;                  /* the lookup kernel reads one table image */
+	if (multi_refuse(ch, __func__) || hpc_refuse(ch, __func__)) return -1;   /* the lookup kernel reads one table image */
 	if (e->magic != EXT_MAGIC || !e->ctx) { fprintf(stderr, "[E::%s] not an engine table\n", __func__); return -1; }
 	if (yk_ctx_in_pass(e->ctx)) { fprintf(stderr, "[E::%s] lookup during an open pass\n", __func__); return -1; }
 	GrowBuf d_t, d_woff, d_win;

@@ -3,6 +3,7 @@
  * (yakamd_count_multi_dev): SURVEY 8e, reference count.c:129-143.
  */
 #include "yak_host.h"
+#include "hpc_host.h"
 
 /* ------------------------------------------------------------------------------------------
  * Several GPUs behind yak_count() (replaces the kt_for over prefixes, count.c:129-143).
@@ -134,6 +135,8 @@ struct MultiJob {
 	std::vector<uint64_t*> d_send[2], d_recv[2];               /* [set][slot]: records grouped by prefix / slices received from the other slots */
 	int64_t chunk, send_words, recv_words;
 	bool ext_base;                                             /* d_base points at the caller's device buffers (yakamd_count_multi_dev) */
+	bool hpc = false;                                          /* the table lives in homopolymer-compressed space: a chunk is compacted before it is partitioned */
+	std::vector<uint8_t*> d_hpc;                               /* [slot]: the compacted chunk (pool memory, obtained by the first round that needs it) */
 };
 
 /* no filter + a plain file of more than YAKAMD_AUTO_SWEEP_GB (2.5) GB: nearly every k-mer instance may be a key of its own (an assembly),
@@ -226,7 +229,7 @@ static bool multi_open(MultiJob *J, int N, int P, const std::vector<int> &dev, i
 		J->slot_of[r] = s;
 	}
 	const int S = J->S = (int)J->sdev.size();
-	J->st.assign(S, 0); J->cp.assign(S, 0);
+	J->st.assign(S, 0); J->cp.assign(S, 0); J->d_hpc.assign(S, 0);
 	for (int x = 0; x < 2; ++x) { J->d_base[x].assign(S, 0); J->d_send[x].assign(S, 0); J->d_recv[x].assign(S, 0); }
 	const char *c = getenv("YAKAMD_MGPU_CHUNK");
 	J->chunk = c && atoll(c) > 0 ? atoll(c) : (int64_t)1 << 28;
@@ -285,6 +288,7 @@ static void multi_close(MultiJob *J)
 	for (int s = 0; s < J->S; ++s) {
 		hipSetDevice(J->sdev[s]);
 		for (int x = 0; x < 2; ++x) { if (!J->ext_base) yk_pool_release(J->d_base[x][s]); yk_pool_release(J->d_send[x][s]); yk_pool_release(J->d_recv[x][s]); J->d_base[x][s] = 0; J->d_send[x][s] = 0; J->d_recv[x][s] = 0; }
+		if (s < (int)J->d_hpc.size()) { yk_pool_release(J->d_hpc[s]); J->d_hpc[s] = 0; }
 		if (J->st[s]) { hipStreamDestroy(J->st[s]); J->st[s] = 0; }
 		if (J->cp[s]) { hipStreamDestroy(J->cp[s]); J->cp[s] = 0; }
 		if (!J->comm_cached && s < (int)J->comm.size() && J->comm[s]) { J->R.CommDestroy(J->comm[s]); J->comm[s] = 0; }
@@ -324,9 +328,17 @@ static bool round_partition(MultiJob *J, int x, int k, int pre, int create_new, 
 	for (int s = 0; s < S; ++s) th.emplace_back([&, s]() {
 		if (R->fill[s] <= 0) return;
 		hipSetDevice(J->sdev[s]);
-		const int64_t n = R->tagged ? yakamd_partition_tagged_dev(k, pre, J->d_base[x][s], R->fill[s], J->d_send[x][s], R->bst[s].data())
-		                : create_new ? yakamd_partition_dev(k, pre, J->d_base[x][s], R->fill[s], J->d_send[x][s], R->bst[s].data())
-		                             : yakamd_partition_hashes_dev(k, pre, J->d_base[x][s], R->fill[s], J->d_send[x][s], R->bst[s].data());
+		const uint8_t *base = J->d_base[x][s];
+		int64_t nb = R->fill[s];
+		if (J->hpc) {                                           /* the chunk's compacted image is what gets partitioned; t0 and the span stay the chunk's */
+			if (!J->d_hpc[s]) J->d_hpc[s] = (uint8_t*)yk_pool_get((size_t)J->chunk + 4096);
+			nb = J->d_hpc[s] ? yk_hpc_compact(base, 0, nb, J->d_hpc[s], 0, 0, 0, 0, 0, J->st[s]) : -1;
+			if (nb < 0) { if (!J->d_hpc[s]) yk_set_error("out of device memory for the compacted chunk"); ok[s] = 0; R->note(); return; }
+			base = J->d_hpc[s];
+		}
+		const int64_t n = R->tagged ? yakamd_partition_tagged_dev(k, pre, base, nb, J->d_send[x][s], R->bst[s].data())
+		                : create_new ? yakamd_partition_dev(k, pre, base, nb, J->d_send[x][s], R->bst[s].data())
+		                             : yakamd_partition_hashes_dev(k, pre, base, nb, J->d_send[x][s], R->bst[s].data());
 		if (n < 0) { ok[s] = 0; R->note(); }
 	});
 	for (auto &t : th) t.join();
@@ -434,7 +446,7 @@ static bool multi_round(MultiJob *J, int x, yak_ch_ext *e, int k, int pre, int c
 }
 
 static yak_ch_t *multi_table_new(const yak_copt_t *opt, int N, const std::vector<int> &dev);
-yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, int N, const std::vector<int> &dev)
+yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, int N, const std::vector<int> &dev, bool hpc)
 {
 	FxReader fx;
 	if (!fx.open_file(fn)) return 0;
@@ -444,9 +456,11 @@ yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, i
 	if (h0 == 0) {                                             /* N tables, one per rank, each owning its prefix range */
 		h = multi_table_new(opt, N, dev);
 		if (!h) { fx.close_file(); return 0; }
+		if (hpc) yakamd_ch_set_hpc(h, 1);
 	}
 	yak_ch_ext *e = (yak_ch_ext*)h;
 	MultiJob J;
+	J.hpc = yakamd_ch_hpc(h) != 0;
 	bool ok = multi_open(&J, N, P, dev);
 	const int S = J.S;
 	const double t_job0 = yk_realtime();
@@ -517,6 +531,14 @@ yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, i
 					 * next one starts k - 1 bases earlier -- the k-mers that end in this chunk are counted here, those that end behind it
 					 * there (a chunk's first k - 1 positions complete no k-mer), and stream positions simply continue */
 					m = room; back = (size_t)opt->k - 1;
+					if (J.hpc) {
+						/* in compressed space the next chunk must open with the last k - 1 KEPT positions of this one: it starts at the run that
+						 * holds the (k - 1)-th of them from the end.  (k = 1: this chunk ends in front of its last run instead, so that no run is
+						 * counted on both sides) */
+						const int64_t s = yk_hpc_back(seq_nt4_table, (const uint8_t*)img, (int64_t)m, opt->k > 1 ? opt->k - 1 : 1);
+						if (s <= 0) { fprintf(stderr, "[E::yak_count] a chunk of %lld bases (YAKAMD_MGPU_CHUNK) is one homopolymer run: it cannot be cut in compressed space\n", (long long)J.chunk); ok = false; break; }
+						if (opt->k > 1) back = m - (size_t)s; else { m = (size_t)s; back = 0; }
+					}
 				}
 			}
 			if (fill[cur][g] == 0) t0[cur][g] = t_stream;
@@ -630,6 +652,7 @@ extern "C" yak_ch_t *yakamd_count_multi_dev(const yak_copt_t *opt, yak_ch_t *h0,
 	if (N == 1) { memset(&one_rank, 0, sizeof(one_rank)); one_rank.n_sub = 1; one_rank.sub = only; e = &one_rank; }   /* the rounds address the owners as e->sub[rank] */
 	MultiJob J;
 	J.S = 0;
+	J.hpc = yakamd_ch_hpc(h) != 0;
 	int64_t cmax = 4096;
 	{	/* the distinct devices, in rank order: that is the order of the chunks inside a round */
 		std::vector<int> sd;

@@ -146,6 +146,15 @@ void yk_launch_dp_finish(const u64 *hist, const u32 *long_list, u32 slot0, u32 n
 u64 yk_hetmer_tiles(u64 n);
 int yk_launch_hetmer(int mode, const u64 *keys, const u64 *off, u64 n, int n_sub, int sub_lo, int min_cnt, ImgView img, u64 *J, u64 *group,
                      u32 *tile_cnt, const u64 *tile_off, void *list, hipStream_t st);
+/* homopolymer compression of a base image (kern_hpc.inc).  valid == 0: `in` is the ASCII image, valid != 0: the packed one.  Three
+ * launches: the kept positions per tile of yk_hpc_tile(packed) positions into tcnt (yk_hpc_tiles() words), their exclusive scan into toff
+ * (yk_launch_te_scan, one word more: toff[tiles] = the output's length), the kept bytes to `out` with '\n' up to the next multiple of 16.
+ * yk_launch_hpc_remap(): off_out / len_out of n_seq sequences of the ASCII image from its toff */
+int64_t yk_hpc_tile(int packed);
+int64_t yk_hpc_tiles(int packed, int64_t n);
+void yk_launch_hpc_count(const void *in, const u32 *valid, int64_t n, u32 *tcnt, hipStream_t st);
+void yk_launch_hpc_scatter(const void *in, const u32 *valid, int64_t n, const u64 *toff, uint8_t *out, hipStream_t st);
+void yk_launch_hpc_remap(const uint8_t *a, int64_t n, const u64 *toff, const u64 *off, const u32 *len, int64_t n_seq, u64 *off_out, u32 *len_out, hipStream_t st);
 int yk_launch_img_count_lds(const void *rec, int hash_only, const u64 *bstart, ImgView img, int plo, int phi, size_t lds, u64 *compact, u32 stride, hipStream_t st);
 void yk_launch_img_count_h(const u64 *hash, int64_t n, ImgView img, hipStream_t st);
 void yk_launch_img_inc(ImgView img, u64 hash, u64 *out2, hipStream_t st);
