@@ -81,7 +81,8 @@ int64_t yakamd_extract_dev(int k, const void *d_bases, int64_t n_bytes,
  * returns the 1<<pre + 1 group offsets in h_bstart; prefixes owned by one rank are contiguous, so a
  * rank's send buffer per destination is a slice.  The receiver hands every source's slice to
  * yakamd_feed_partitioned_dev() together with that slice's own offsets (h_bstart[p] = first record
- * of prefix p inside d_rec, entries outside the shard equal their neighbours). */
+ * of prefix p inside d_rec, entries outside the shard equal their neighbours).  n_bytes = 0 (no chunk)
+ * returns 0 with every offset 0 and launches nothing; the same holds for the tagged and the bare-hash partition. */
 int64_t yakamd_partition_dev(int k, int pre, const void *d_bases, int64_t n_bytes, void *d_rec_out, uint64_t *h_bstart);
 int yakamd_feed_partitioned_dev(yak_ch_t *h, const void *d_rec, int64_t n, const uint64_t *h_bstart,
                                 uint64_t t0, uint64_t t_span);

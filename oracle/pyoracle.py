@@ -31,6 +31,10 @@ class Ch(C.Structure):
                 ("tot", C.c_uint64), ("h", C.c_void_p)]
 
 
+class Kbuf(C.Structure):                       # yko_kbuf_t: one prefix's list of yko_extract
+    _fields_ = [("n", C.c_int64), ("m", C.c_int64), ("a", C.POINTER(C.c_uint64))]
+
+
 _lib = None
 
 
@@ -68,6 +72,8 @@ def lib():
         L.yko_ch_subtable.argtypes = [P(Ch), C.c_int, P(C.c_uint32), P(C.c_uint32)]
         L.yko_extract_pos.restype = C.c_int64
         L.yko_extract_pos.argtypes = [C.c_int, C.c_char_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.yko_extract.restype = None
+        L.yko_extract.argtypes = [P(Kbuf), C.c_int, C.c_int, C.c_int64, C.c_char_p]
         L.yko_count_mem.restype = P(Ch)
         L.yko_count_mem.argtypes = [C.c_char_p, C.c_int64, P(Copt), P(Ch)]
         L.yko_count_protocol_mem.restype = P(Ch)
@@ -165,6 +171,36 @@ def lookup_image(h, img, width):
     import numpy as np
     out = np.empty(len(img), np.uint16 if width == 2 else np.uint8)
     lib().yko_lookup_image(h, bytes(img), len(img), out.ctypes.data, width)
+    return out
+
+
+def nt4():
+    """the oracle's base table yko_nt4 (misc.c:4-21) as a numpy uint8 array of 256: 0..3 for a base, 4 for anything else"""
+    import numpy as np
+    return np.frombuffer(bytes((C.c_ubyte * 256).in_dll(lib(), "yko_nt4")), np.uint8).copy()
+
+
+def extract_pos(k, img):
+    """yko_extract_pos: every k-mer of the image (k in [1, 63]) in stream order -> (numpy uint64 hashes, numpy uint32 indices of the last base)"""
+    import numpy as np
+    n = len(img)
+    hh, tt = np.empty(max(n, 1), np.uint64), np.empty(max(n, 1), np.uint32)
+    m = lib().yko_extract_pos(k, bytes(img), n, hh.ctypes.data, tt.ctypes.data)
+    return hh[:m].copy(), tt[:m].copy()
+
+
+def extract_lists(k, pre, img):
+    """yko_extract (count.c:28-60, what the counting driver itself lists) on the whole image: one numpy uint64 array of hashes per prefix"""
+    import numpy as np
+    P = 1 << pre
+    buf = (Kbuf * P)()
+    lib().yko_extract(buf, k, pre, len(img), bytes(img))
+    out = []
+    free = C.CDLL(None).free
+    free.argtypes = [C.c_void_p]
+    for b in buf:
+        out.append(np.ctypeslib.as_array(b.a, shape=(b.n,)).copy() if b.n else np.empty(0, np.uint64))
+        free(C.cast(b.a, C.c_void_p))
     return out
 
 

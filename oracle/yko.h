@@ -102,6 +102,7 @@ void      yko_ch_subtable(const yko_ch_t *h, int i, uint32_t *cap, uint32_t *siz
 typedef struct { int64_t n, m; uint64_t *a; } yko_kbuf_t;
 void yko_extract(yko_kbuf_t *buf, int k, int pre, int64_t len, const char *seq);
 
+/* flat variant: every k-mer of a memory image (k in [1, 63]) with the index of its last base, in stream order; outputs hold n entries */
 int64_t yko_extract_pos(int k, const uint8_t *bases, int64_t n, uint64_t *out_hash, uint32_t *out_t);
 /* max(0, yko_ch_get()) of the k-mer ending at every byte of a memory image, all ones of the element where none ends (qv.c:50-62,
  * triobin.c:62-84); width 2 = uint16_t counts, 1 = uint8_t values.  What yakamd_lookup_dev / yakamd_triobin_lookup_dev compute */

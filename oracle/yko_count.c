@@ -73,9 +73,31 @@ void yko_extract(yko_kbuf_t *buf, int k, int pre, int64_t len, const char *seq)
 }
 
 /* flat variant for tests of the sharded path: every k-mer of a memory image with its stream
- * position (index of its last base), in stream order.  k < 32 only.  Returns the count. */
+ * position (index of its last base), in stream order.  k < 32: the 2k-bit canonical k-mer under yko_hash64
+ * (count.c:28-43); k in [32, 63]: the four planes of extract_long under yko_hash_long (count.c:45-60).
+ * Returns the count. */
+static int64_t extract_pos_long(int k, const uint8_t *bases, int64_t n, uint64_t *out_hash, uint32_t *out_t)
+{
+	const uint64_t mask = (1ULL << k) - 1;
+	const int shift = k - 1;
+	uint64_t x[4] = { 0, 0, 0, 0 };
+	int64_t i, m = 0;
+	int run = 0;
+	for (i = 0; i < n; ++i) {
+		int c = yko_nt4[bases[i]];
+		if (c >= 4) { run = 0; x[0] = x[1] = x[2] = x[3] = 0; continue; }
+		x[0] = (x[0] << 1 | (uint64_t)(c & 1)) & mask;
+		x[1] = (x[1] << 1 | (uint64_t)(c >> 1)) & mask;
+		x[2] = x[2] >> 1 | (uint64_t)(1 - (c & 1)) << shift;
+		x[3] = x[3] >> 1 | (uint64_t)(1 - (c >> 1)) << shift;
+		if (++run >= k) { out_hash[m] = yko_hash_long(x); out_t[m++] = (uint32_t)i; }
+	}
+	return m;
+}
+
 int64_t yko_extract_pos(int k, const uint8_t *bases, int64_t n, uint64_t *out_hash, uint32_t *out_t)
 {
+	if (k >= 32) return extract_pos_long(k, bases, n, out_hash, out_t);
 	const uint64_t mask = (1ULL << 2 * k) - 1;
 	const int shift = 2 * (k - 1);
 	uint64_t fw = 0, rv = 0;

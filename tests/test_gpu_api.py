@@ -482,12 +482,9 @@ def test_packed_image_feed_equals_ascii_feed(k, bf, ya, oracle, synth):
     # the packer itself against a host restatement
     codes = (C.c_uint32 * (2 * nw))(); valid = (C.c_uint32 * nw)()
     assert L.yakamd_memcpy_d2h(codes, d_c, 8 * nw) == 0 and L.yakamd_memcpy_d2h(valid, d_v, 4 * nw) == 0
-    nt4 = {65: 0, 97: 0, 67: 1, 99: 1, 71: 2, 103: 2, 84: 3, 116: 3}
-    for j in list(range(0, 200)) + list(range(n - 70, n)):
-        c = nt4.get(img[j])
-        assert (valid[j >> 5] >> (j & 31) & 1) == (c is not None)
-        if c is not None:
-            assert (codes[j >> 4] >> (2 * (j & 15)) & 3) == c
+    from exchange_util import expect_packed                  # every word of the image under the oracle's base table, the zero bits behind n included
+    want_codes, want_valid = expect_packed(oracle, img)
+    assert list(valid) == want_valid.tolist() and list(codes) == want_codes.tolist()
     tp = ya.Table(k, 10, 4, bf); ta = ya.Table(k, 10, 4, bf)
     tp.count_pass_packed(1, [(d_c, d_v, n, 0)]); ta.count_pass(1, [(d_a, n, 0)])
     assert tp.dump_bytes() == ta.dump_bytes() and tp.tot == ta.tot

@@ -840,6 +840,7 @@ static int64_t partition_dev(int k, int pre, const void *d_bases, int64_t n_byte
 	if (k < 1 || k > 63 || pre < 3 || pre > 13) { fail("partition: unsupported k / pre"); return -1; }
 	if (((uintptr_t)d_bases & 15) != 0 || n_bytes >= ((int64_t)1 << 32)) { fail("partition: base image must be 16-byte aligned and < 4 GiB"); return -1; }
 	const size_t NB = (size_t)1 << pre;
+	if (n_bytes <= 0) { memset(h_bstart, 0, (NB + 1) * 8); return 0; }   /* no chunk: nothing is launched (yk_launch_xpart would leave d_bstart as the pool handed it out) */
 	const int n_blk = yk_xpart_blocks(n_bytes);
 	DevBuf<u64> d_bstart, d_partial; DevBuf<u32> d_rows;
 	if (d_rows.alloc(NB * (size_t)n_blk) || d_partial.alloc(NB * yk_part_groups()) || d_bstart.alloc(NB + 1)) return -1;
