@@ -371,6 +371,49 @@ int yakamd_ch_set_hpc(yak_ch_t *h, int on);
 int yakamd_ch_hpc(const yak_ch_t *h);
 yak_ch_t *yakamd_count_hpc(const char *fn, const yak_copt_t *opt, yak_ch_t *h0);
 
+/* Which bases of a sequence lie inside k-mers that a table holds, lacks or holds too often (not in the reference).  t = the
+ * array yakamd_lookup_dev() writes for a base image of n_bytes bytes, k below 32, and a predicate [lo, hi] with 0 <= lo <= hi <= 1023:
+ *   hit(j)  = t[j] != 0xffff and lo <= min(t[j], 1023) <= hi (an absent k-mer reads 0, so 0:0 selects "the table lacks it")
+ *   cov(i)  = 1 if some j in [i, min(i + k - 1, n_bytes - 1)] has hit(j), else 0: base i lies inside at least one hitting k-mer
+ * over the flat array; on a real image no cover crosses a record and an invalid byte is never covered, because the k-mer ending at j contains every
+ * byte back to i.  Per sequence s = elements [off[s], off[s] + len[s]): n_kmer = elements that are not 0xffff, n_hit = elements with hit, n_cov =
+ * the sum of cov, n_run = positions with cov(i) = 1 and (i == off[s] or cov(i - 1) == 0).  The masked image m: soft, m[i] = b[i] | 0x20 where cov(i)
+ * and b[i] is an ASCII letter, else b[i] (raw bytes 0..3 stay); hard, m[i] = 'N' where cov(i), else b[i].
+ * yakamd_cover_dev(): one pass (kern_cover.inc).  d_cov_u8 receives cov, one byte per position -- what yakamd_chkerr_streaks_dev(-1, ...) takes to
+ * list the covered intervals per sequence -- and with mask 1 (soft) or 2 (hard) d_masked the masked image of d_bases; both are written up to the
+ * next multiple of 16 (0 and '\n' from n_bytes on) and not behind it.  d_tally[0 .. n_seq) is overwritten (it may be NULL with n_seq = 0); d_bases and
+ * d_masked may be NULL with mask 0.  The count, cover and image arrays are 16-byte aligned with room for n_bytes rounded up to 16 elements; the
+ * sequences ascend and are disjoint.  It needs no table.  `stream` = a hipStream_t or 0; returns when the device is done; n_bytes = 0 launches
+ * nothing.  -1 after yakamd_last_error() is set, before any device work: k outside [1, 31], lo / hi outside 0 <= lo <= hi <= 1023, mask outside
+ * 0..2, mask != 0 with a NULL image, a misaligned array, a negative size. */
+typedef struct { uint32_t n_kmer, n_hit, n_cov, n_run; } yakamd_cov_t;
+int yakamd_cover_dev(int k, int lo, int hi, const void *d_cnt_u16, int64_t n_bytes, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
+                     const void *d_bases, int mask, void *d_cov_u8, void *d_masked, yakamd_cov_t *d_tally, void *stream);
+/* `yak-amd cover` as a library call: every sequence of `fn` (FASTA/FASTQ, .gz, "-" = stdin) against `ch`, a YAK_LOAD_ALL table (yak_ch_restore) or a
+ * resident one, k below 32.  Per chunk of chunk_size bases the lookup, then yakamd_cover_dev, with intervals the run finder of chkerr on the cover
+ * bytes; the host gets tallies and intervals, never the cover bytes, and the masked image in FASTA mode alone.  A sequence is selected iff
+ * (n_hit >= min_hit && (double)n_cov >= min_frac * (double)len) != invert.  To out_fn (NULL = stdout), tab-separated:
+ *   mask < 0   `#cover k=<k> lo=<lo> hi=<hi>`; per selected sequence in input order `S name len n_kmer n_hit n_cov n_run` and, with intervals,
+ *              directly behind it its `B name start end` lines (0-based, half-open, in bases, ascending); last `T n_seq n_selected sum_len
+ *              sum_kmer sum_hit sum_cov`, the sums over all sequences, selected or not
+ *   mask >= 0  `>name`, then the sequence's bytes of the masked image (of the image itself with mask 0), per selected sequence and nothing else; the
+ *              chunk reader carries neither qualities nor header comments
+ * Sequences are never cut by a chunk, so the output does not depend on chunk_size.  0 on success, -1 after a message on stderr -- before the output
+ * is created for k >= 32, a table sharded over prefix ranges or spread over several devices, a table marked as homopolymer-compressed, an open
+ * pass, an input that cannot be opened, lo / hi outside 0 <= lo <= hi <= 1023, mask above 2, min_frac outside [0, 1] and a negative min_hit. */
+typedef struct {
+	int32_t lo, hi;           /* -c LO[:HI], 1:1023; -c N = N:1023 */
+	int32_t intervals;        /* -b, 0: B lines */
+	int32_t mask;             /* -m none|soft|hard (0, 1, 2): FASTA out instead of the table; -1 = table (default) */
+	int32_t invert;           /* -v, 0 */
+	int64_t min_hit;          /* -n, 0 */
+	double  min_frac;         /* -f, 0.0 */
+	int     n_threads;        /* -t, 8: accepted as in the other commands */
+	int64_t chunk_size;       /* -K, 1000000000 */
+} yakamd_cvopt_t;
+void yakamd_cvopt_init(yakamd_cvopt_t *opt);
+int yakamd_cover(const yakamd_cvopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn);
+
 /* Host-only test hook (no device needed): the base image yak_count() hands to the device for a
  * FASTA/FASTQ(.gz) file -- sequences of >= min_len bases, each followed by '\n'.  use_fast_path = 0
  * forces the general record reader for every record.  *out is malloc()ed; returns its length or -1. */

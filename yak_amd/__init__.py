@@ -42,6 +42,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_kmers_dev", "yakamd_print_dev", "yakamd_propt_init", "yakamd_print", "yakamd_host_syncs",
     "yakamd_ch_sum",
     "yakamd_depth_reduce_dev", "yakamd_dpopt_init", "yakamd_depth",
+    "yakamd_cover_dev", "yakamd_cvopt_init", "yakamd_cover",
     "yakamd_hetmers_dev", "yakamd_hetmer_pairs_dev", "yakamd_hmopt_init", "yakamd_hetmers",
     "yakamd_hpc_dev", "yakamd_hpc_packed_dev", "yakamd_hpc_host", "yakamd_ch_set_hpc", "yakamd_ch_hpc", "yakamd_count_hpc",
 ]
@@ -106,6 +107,15 @@ class HmoptT(C.Structure):                     # yakamd_hmopt_t, include/yak_amd
 
 class HetpairT(C.Structure):                   # yakamd_hetpair_t, include/yak_amd.h
     _fields_ = [("x", C.c_uint64), ("y", C.c_uint64), ("cx", C.c_uint32), ("cy", C.c_uint32)]
+
+
+class CvoptT(C.Structure):                     # yakamd_cvopt_t, include/yak_amd.h
+    _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("intervals", C.c_int32), ("mask", C.c_int32), ("invert", C.c_int32), ("min_hit", C.c_int64),
+                ("min_frac", C.c_double), ("n_threads", C.c_int32), ("chunk_size", C.c_int64)]
+
+
+class CovT(C.Structure):                       # yakamd_cov_t, include/yak_amd.h
+    _fields_ = [("n_kmer", C.c_uint32), ("n_hit", C.c_uint32), ("n_cov", C.c_uint32), ("n_run", C.c_uint32)]
 
 
 class StreakT(C.Structure):                    # yakamd_streak_t, include/yak_amd.h
@@ -293,6 +303,11 @@ def lib():
     L.yakamd_depth_reduce_dev.argtypes = [C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
     L.yakamd_dpopt_init.restype = None; L.yakamd_dpopt_init.argtypes = [P(DpoptT)]
     L.yakamd_depth.restype = C.c_int; L.yakamd_depth.argtypes = [P(DpoptT), P(ChT), C.c_char_p, C.c_char_p]
+    L.yakamd_cover_dev.restype = C.c_int
+    L.yakamd_cover_dev.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p]
+    L.yakamd_cvopt_init.restype = None; L.yakamd_cvopt_init.argtypes = [P(CvoptT)]
+    L.yakamd_cover.restype = C.c_int; L.yakamd_cover.argtypes = [P(CvoptT), P(ChT), C.c_char_p, C.c_char_p]
     L.yakamd_hetmers_dev.restype = C.c_int; L.yakamd_hetmers_dev.argtypes = [P(ChT), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.yakamd_hetmer_pairs_dev.restype = C.c_int64; L.yakamd_hetmer_pairs_dev.argtypes = [P(ChT), C.c_int, C.c_void_p, C.c_int64]
     L.yakamd_hmopt_init.restype = None; L.yakamd_hmopt_init.argtypes = [P(HmoptT)]
@@ -637,6 +652,28 @@ def hetmers(table_yak, min_cnt=1, pairs=False, batch_keys=None):
         if batch_keys is not None:
             o.batch_keys = batch_keys
         return _output_of("yakamd_hetmers", lambda out: L.yakamd_hetmers(C.byref(o), h, out))
+    finally:
+        L.yak_ch_destroy(h)
+
+
+def cover(table_yak, seq, lo=1, hi=1023, intervals=False, mask=None, min_frac=0.0, min_hit=0, invert=False, chunk=None):
+    """`yak-amd cover` through the C ABI (yak_ch_restore + yakamd_cover): which bases of every sequence lie inside k-mers whose count in the table
+    is in [lo, hi] -- the `#cover` line, one S line per selected sequence (with `intervals` its B lines behind it) and the T line; with mask =
+    "none", "soft" or "hard" the selected sequences as FASTA instead, covered bases as they are, in lower case or as N"""
+    L = lib()
+    masks = {None: -1, "none": 0, "soft": 1, "hard": 2}
+    if mask not in masks:
+        raise ValueError("mask is None, 'none', 'soft' or 'hard'")
+    h = L.yak_ch_restore(table_yak.encode())
+    if not h:
+        raise RuntimeError("yak_ch_restore failed: " + _err())
+    try:
+        o = CvoptT()
+        L.yakamd_cvopt_init(C.byref(o))
+        o.lo, o.hi, o.intervals, o.mask, o.invert, o.min_hit, o.min_frac = lo, hi, int(bool(intervals)), masks[mask], int(bool(invert)), min_hit, min_frac
+        if chunk is not None:
+            o.chunk_size = chunk
+        return _output_of("yakamd_cover", lambda out: L.yakamd_cover(C.byref(o), h, seq.encode(), out))
     finally:
         L.yak_ch_destroy(h)
 

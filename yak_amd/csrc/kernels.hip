@@ -101,6 +101,7 @@ __device__ const unsigned char d_nt4[256] = {
 #include "kern_inspect.inc"
 #include "kern_print.inc"
 #include "kern_depth.inc"
+#include "kern_cover.inc"
 #include "kern_hetmer.inc"
 #include "kern_hpc.inc"
 #include "kern_launch.inc"

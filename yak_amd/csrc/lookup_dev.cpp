@@ -217,6 +217,36 @@ extern "C" int yakamd_chkerr_streaks_dev(int min_streak, const void *d_low_u8, c
 	return te_streaks("chkerr streaks", 1, 1, min_n, (const uint8_t*)d_low_u8, d_seq_off, n_seq, n_bytes, 0, d_streaks, n_streaks, st);
 }
 
+/* ---- yak-amd cover (kern_cover.inc) ---- */
+extern "C" int yakamd_cover_dev(int k, int lo, int hi, const void *d_cnt_u16, int64_t n_bytes, const uint64_t *d_seq_off, const uint32_t *d_seq_len,
+                                int64_t n_seq, const void *d_bases, int mask, void *d_cov_u8, void *d_masked, yakamd_cov_t *d_tally, void *stream)
+{
+	if (k < 1 || k >= 32) return fail("cover: k must be below 32 (reference qv.c:44)");
+	if (lo < 0 || hi < lo || hi > 1023) return fail("cover: the counts [%d, %d] are not inside [0, 1023]", lo, hi);
+	if (mask < 0 || mask > 2) return fail("cover: mask %d is none of 0 (none), 1 (soft), 2 (hard)", mask);
+	if (check_counts("cover", n_seq, n_bytes)) return -1;
+	if (n_bytes > 0 && (!d_cnt_u16 || !d_cov_u8)) return fail("cover: no count array or no cover array");
+	if (mask != 0 && (!d_bases || !d_masked)) return fail("cover: mask %d without a base image or without room for the masked one", mask);
+	if (n_seq > 0 && (!d_seq_off || !d_seq_len || !d_tally)) return fail("cover: %ld sequences without their offsets, lengths or tallies", (long)n_seq);
+	if ((((uintptr_t)d_cnt_u16 | (uintptr_t)d_cov_u8 | (mask ? (uintptr_t)d_bases | (uintptr_t)d_masked : 0)) & 15) != 0 || ((uintptr_t)d_seq_off & 7) != 0
+	    || (((uintptr_t)d_seq_len | (uintptr_t)d_tally) & 3) != 0)
+		return fail("cover: the counts, the cover and the images must be 16-byte aligned, the offsets 8-byte, the lengths and tallies 4-byte");
+	if (n_bytes == 0 && n_seq == 0) return 0;
+	const hipStream_t st = (hipStream_t)stream;
+	if (n_seq > 0) HIPCK(hipMemsetAsync(d_tally, 0, (size_t)n_seq * sizeof(yakamd_cov_t), st));
+	if (n_bytes > 0) {
+		CvArgs a;
+		a.t = (const unsigned short*)d_cnt_u16; a.n = n_bytes;
+		a.seq_off = (const u64*)d_seq_off; a.seq_len = d_seq_len; a.n_seq = n_seq;
+		a.bases = (const uint8_t*)d_bases; a.cov = (uint8_t*)d_cov_u8; a.masked = (uint8_t*)d_masked; a.tally = (u32*)d_tally;
+		a.k = k; a.lo = (u32)lo; a.hi = (u32)hi;
+		yk_launch_cover(a, mask, st);
+		HIPCK(hipGetLastError());
+	}
+	HIPCK(hipStreamSynchronize(st));
+	return 0;
+}
+
 /* ---- yak-amd depth (kern_depth.inc) ---- */
 namespace {
 struct DpScratch {                                     /* kept from one call to the next, on the device of the last call */

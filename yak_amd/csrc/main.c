@@ -17,8 +17,9 @@
  *     recount  the counts of a table's k-mers in other sequences, reference main.c:66-88 (restore, tighten, yak_recount)
  *     subtract, isec   the k-mers of the first table absent from / present in the others, reference main.c:217-284
  *     version  the library's YAKS_VERSION
- * and three beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table) and hetmers
- * (yakamd_hetmers: the pairs of k-mers of a count table that differ in the middle base alone).  `count -c` and `qv -c` work in homopolymer-compressed
+ * and four beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table), hetmers
+ * (yakamd_hetmers: the pairs of k-mers of a count table that differ in the middle base alone) and cover (yakamd_cover: the bases of every sequence
+ * that lie inside k-mers a table holds, lacks or holds too often -- as a table, as intervals or as a masked FASTA).  `count -c` and `qv -c` work in homopolymer-compressed
  * space (yakamd_count_hpc; yakamd_ch_set_hpc on the restored table): every run of one base is one base before k-mers are taken.
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
@@ -28,7 +29,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "yak.h"
-#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_count_hpc and yakamd_ch_set_hpc */
+#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_cover, yakamd_count_hpc and yakamd_ch_set_hpc */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
 enum arg_kind { ARG_FLAG, ARG_I32, ARG_SIZE, ARG_I64SIZE, ARG_F64, ARG_TEXT };
@@ -492,6 +493,51 @@ static int cmd_depth(int argc, char **argv)
 	return rc;
 }
 
+/* ---- cover (not in the reference) ---- */
+/* which bases of each sequence lie inside k-mers whose count in a table is within LO:HI, as a table, as intervals or as a masked FASTA (yakamd_cover) */
+static int cmd_cover(int argc, char **argv)
+{
+	yakamd_cvopt_t o;
+	const char *out = 0, *range = 0, *mask = 0;
+	yakamd_cvopt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'c', ARG_TEXT, &range, "LO[:HI]: a k-mer hits when its count is in LO .. HI, an absent one counting 0; -c N = N:1023 [1:1023]" },
+		{ 'b', ARG_FLAG, &o.intervals, "behind each S line its covered intervals as B lines: name, start, end (0-based, half-open)" },
+		{ 'm', ARG_TEXT, &mask, "none|soft|hard: write the selected sequences as FASTA instead of the table, covered bases as they are, in lower case or as N (qualities and header comments are not carried)" },
+		{ 'f', ARG_F64, &o.min_frac, "select the sequences of which at least this fraction is covered [0]" },
+		{ 'n', ARG_I64SIZE, &o.min_hit, "select the sequences with at least this many hitting k-mers [0]" },
+		{ 'v', ARG_FLAG, &o.invert, "select the other sequences" },
+		{ 't', ARG_I32, &o.n_threads, "host threads (accepted for symmetry with the other commands)" },
+		{ 'K', ARG_I64SIZE, &o.chunk_size, "bases per chunk" },
+		{ 'o', ARG_TEXT, &out, "write the output here; stdout without it" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 1 >= argc) { arg_help("cover [options] <kmer.yak> <seq.fa>", defs, nd); return 1; }
+	if (range) {
+		char *end = 0;
+		const long a = strtol(range, &end, 10);
+		long b = 1023;
+		int bad = end == range;
+		if (!bad && *end == ':') { const char *q = end + 1; b = strtol(q, &end, 10); bad = end == q; }
+		if (bad || *end || a < 0 || b < a || b > 1023) { fprintf(stderr, "yak-amd cover: -c takes LO[:HI] with 0 <= LO <= HI <= 1023\n"); return 1; }
+		o.lo = (int32_t)a; o.hi = (int32_t)b;
+	}
+	if (mask) {
+		o.mask = strcmp(mask, "none") == 0 ? 0 : strcmp(mask, "soft") == 0 ? 1 : strcmp(mask, "hard") == 0 ? 2 : -1;
+		if (o.mask < 0) { fprintf(stderr, "yak-amd cover: -m takes none, soft or hard\n"); return 1; }
+	}
+	if (!(o.min_frac >= 0.0 && o.min_frac <= 1.0) || o.min_hit < 0) { fprintf(stderr, "yak-amd cover: -f must be in [0, 1] and -n must not be negative\n"); return 1; }
+	uint32_t k = 0, pre = 0;
+	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd cover: %s is not a readable .yak file\n", argv[first]); return 2; }
+	if (k >= 32) { fprintf(stderr, "yak-amd cover: %s has k = %u: the per-position lookup serves k below 32 only\n", argv[first], k); return 2; }
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd cover: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	const int rc = yakamd_cover(&o, tab, argv[first + 1], out) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 /* ---- hetmers (not in the reference) ---- */
 /* the pairs of k-mers of a count table that differ in the middle base alone, as a histogram of their two counts (yakamd_hetmers) */
 static int cmd_hetmers(int argc, char **argv)
@@ -561,10 +607,12 @@ int main(int argc, char **argv)
 	if (argc >= 2 && strcmp(argv[1], "sum") == 0) return cmd_sum(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "depth") == 0) return cmd_depth(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "hetmers") == 0) return cmd_hetmers(argc - 1, argv + 1);
+	if (argc >= 2 && strcmp(argv[1], "cover") == 0) return cmd_cover(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
 	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-8s %s\n", cmds[i].name, cmds[i].what);
 	fprintf(stderr, "  beyond the reference:\n      yak-amd %-8s %s\n", "sum", "add the counts of two or more .yak tables together");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "depth", "the depth of the k-mers of each sequence, or window, in a .yak table");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "hetmers", "the pairs of k-mers of a .yak table that differ in the middle base, by their two counts");
+	fprintf(stderr, "      yak-amd %-8s %s\n", "cover", "the bases of each sequence that lie inside k-mers a .yak table holds, lacks or holds too often");
 	return 1;
 }

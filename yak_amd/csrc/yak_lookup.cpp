@@ -541,3 +541,84 @@ int yakamd_depth(const yakamd_dpopt_t *opt, const yak_ch_t *ch, const char *fn, 
 		return ok;
 	});
 }
+
+/* the table, every sequence with count 1 .. 1023 k-mers, no filter; the chunk is chkerr's */
+void yakamd_cvopt_init(yakamd_cvopt_t *opt)
+{
+	memset(opt, 0, sizeof(yakamd_cvopt_t));
+	opt->lo = 1;
+	opt->hi = 1023;
+	opt->mask = -1;
+	opt->n_threads = 8;
+	opt->chunk_size = 1000000000;
+}
+
+/* `yak-amd cover` (not in the reference): per chunk the lookup of chkerr's driver into one u16 per position (yakamd_lookup_dev),
+ * then the fused pass of kern_cover.inc (yakamd_cover_dev) into one cover byte per position, the tallies per sequence and, in FASTA mode with a
+ * mask, the masked image; with -b the run finder of chkerr (yakamd_chkerr_streaks_dev) lists the runs of cover bytes.  Copied back are the tallies,
+ * the runs and, in FASTA mode, the masked image -- never the cover bytes.  Refused before the output is created: what the lookup itself would
+ * refuse at the first chunk (k >= 32, a sharded table, an open pass), a compressed table and options outside their ranges */
+int yakamd_cover(const yakamd_cvopt_t *opt, const yak_ch_t *ch, const char *fn, const char *out_fn)
+{
+	yak_ch_t *h = (yak_ch_t*)ch;
+	const yak_ch_ext *e = (const yak_ch_ext*)ch;
+	const int k = ch->k, lo = opt->lo, hi = opt->hi;
+	const bool fasta = opt->mask >= 0, invert = opt->invert != 0;
+	if (k >= 32) { fprintf(stderr, "[E::%s] k = %d: k must be below 32 (reference qv.c:44)\n", __func__, k); return -1; }
+	if (lo < 0 || hi < lo || hi > 1023) { fprintf(stderr, "[E::%s] the counts %d:%d are not inside 0:1023\n", __func__, lo, hi); return -1; }
+	if (!(opt->min_frac >= 0.0 && opt->min_frac <= 1.0)) { fprintf(stderr, "[E::%s] a covered fraction of %g is not inside [0, 1]\n", __func__, opt->min_frac); return -1; }
+	if (opt->min_hit < 0) { fprintf(stderr, "[E::%s] a minimum of %ld hits\n", __func__, (long)opt->min_hit); return -1; }
+	if (opt->mask > 2) { fprintf(stderr, "[E::%s] mask %d is none of none (0), soft (1) and hard (2)\n", __func__, (int)opt->mask); return -1; }
+	if (multi_refuse(ch, __func__) || hpc_refuse(ch, __func__)) return -1;   /* the lookup kernel reads one table image */
+	if (e->magic != EXT_MAGIC || !e->ctx) { fprintf(stderr, "[E::%s] not an engine table\n", __func__); return -1; }
+	if (yk_ctx_in_pass(e->ctx)) { fprintf(stderr, "[E::%s] lookup during an open pass\n", __func__); return -1; }
+	GrowBuf d_t, d_cov, d_masked, d_tally;
+	std::vector<yakamd_cov_t> tally;
+	std::vector<yakamd_streak_t> sk;
+	std::vector<char> masked;
+	int64_t n_seq = 0, n_sel = 0, sum_len = 0, sum_kmer = 0, sum_hit = 0, sum_cov = 0;
+	char header[96];
+	snprintf(header, sizeof header, "#cover\tk=%d\tlo=%d\thi=%d\n", k, lo, hi);
+	return run_chunks(__func__, { fn }, out_fn, opt->chunk_size, fasta ? "" : header, [&](int, const Chunk &cur, const DevChunk &d, size_t nb, LineOut &out) {
+		const size_t ns = cur.len.size(), room = cur.img.size();
+		const int mask = fasta ? opt->mask : 0;
+		void *d_sk = 0;
+		int64_t n_sk = 0;
+		tally.resize(ns);
+		bool ok = d_t.fit(room * 2) && d_cov.fit(room) && (mask == 0 || d_masked.fit(room)) && d_tally.fit(ns * sizeof(yakamd_cov_t))
+		          && yakamd_lookup_dev(h, d.img.p, (int64_t)nb, d_t.p) == 0
+		          && yakamd_cover_dev(k, lo, hi, d_t.p, (int64_t)nb, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)ns, d.img.p, mask, d_cov.p,
+		                              mask ? d_masked.p : 0, (yakamd_cov_t*)d_tally.p, 0) == 0
+		          && yakamd_memcpy_d2h(tally.data(), d_tally.p, ns * sizeof(yakamd_cov_t)) == 0;
+		if (ok && !fasta && opt->intervals) {
+			ok = yakamd_chkerr_streaks_dev(-1, d_cov.p, (const uint64_t*)d.off.p, (int64_t)ns, (int64_t)nb, &d_sk, &n_sk, 0) == 0;
+			sk.resize(ok ? (size_t)n_sk : 0);
+			if (ok && n_sk > 0) ok = yakamd_memcpy_d2h(sk.data(), d_sk, (size_t)n_sk * sizeof(yakamd_streak_t)) == 0;
+			yakamd_dev_free(d_sk);
+		} else sk.clear();
+		if (ok && mask) { masked.resize(nb); ok = yakamd_memcpy_d2h(masked.data(), d_masked.p, nb) == 0; }
+		const char *bytes = mask ? masked.data() : cur.img.data();
+		for (size_t j = 0, i = 0; ok && out.ok && j < ns; ++j) {   /* the sequences in input order, each with its runs */
+			const yakamd_cov_t &x = tally[j];
+			const bool sel = ((int64_t)x.n_hit >= opt->min_hit && (double)x.n_cov >= opt->min_frac * (double)cur.len[j]) != invert;
+			++n_seq; n_sel += sel; sum_len += cur.len[j]; sum_kmer += x.n_kmer; sum_hit += x.n_hit; sum_cov += x.n_cov;
+			if (sel && fasta) {
+				out.append(">"); out.append(cur.names[j]); out.append("\n");
+				out.s.append(bytes + cur.off[j], cur.len[j]);
+				out.append("\n");
+			} else if (sel) {
+				out.append("S\t"); out.append(cur.names[j]);
+				out.appendf("\t%u\t%u\t%u\t%u\t%u\n", cur.len[j], x.n_kmer, x.n_hit, x.n_cov, x.n_run);
+			}
+			for (; i < sk.size() && sk[i].seq <= j; ++i) {
+				if (!sel || sk[i].seq != j) continue;
+				out.append("B\t"); out.append(cur.names[j]);
+				out.appendf("\t%u\t%u\n", sk[i].st, sk[i].en);
+			}
+			out.drain();
+		}
+		return ok;
+	}, [&](LineOut &out) {
+		if (!fasta) out.appendf("T\t%ld\t%ld\t%ld\t%ld\t%ld\t%ld\n", (long)n_seq, (long)n_sel, (long)sum_len, (long)sum_kmer, (long)sum_hit, (long)sum_cov);
+	});
+}

@@ -139,6 +139,18 @@ int yk_dp_run(void);                                          /* positions of a 
 void yk_launch_dp_short(DpArgs a, u64 g0, u32 n_win, u32 T, void *out, u32 *long_list, u64 *tile_base, u32 long_cap, u64 *counter, hipStream_t st);
 void yk_launch_dp_long(DpArgs a, u64 g0, const u32 *long_list, const u64 *tile_base, u32 slot0, u32 n_slots, u64 tile0, u64 n_tiles, u64 *hist, hipStream_t st);
 void yk_launch_dp_finish(const u64 *hist, const u32 *long_list, u32 slot0, u32 n_slots, void *out, hipStream_t st);
+/* `yak-amd cover` (kern_cover.inc): one pass over the u16 count array t of n positions.  cov[i] = 1 where base i lies inside a k-mer whose count
+ * min(t, 1023) is in [lo, hi], else 0; with mask 1 / 2 `masked` = `bases` with the covered letters in lower case / the covered bytes as 'N'; tally[4 j ..]
+ * += n_kmer, n_hit, n_cov, n_run of sequence j (zeroed by the caller; n_seq = 0: no tally).  cov and masked are written up to the next multiple of 16 */
+struct CvArgs {
+	const unsigned short *t; int64_t n;
+	const u64 *seq_off; const u32 *seq_len; int64_t n_seq;
+	const uint8_t *bases; uint8_t *cov, *masked; u32 *tally;
+	int k; u32 lo, hi;
+};
+int64_t yk_cover_tile(void);                                  /* positions per tile, and per workgroup */
+int64_t yk_cover_group(void);
+void yk_launch_cover(CvArgs a, int mask, hipStream_t st);
 /* `yak-amd hetmers` (kern_hetmer.inc): the middle-base neighbours of the n keys of sub-tables [sub_lo, sub_lo + n_sub) (keys / off as yk_launch_kmers
  * takes them), probed in the whole image `img` (k odd, below 32); a key below min_cnt is absent.  mode 0: group[s] += groups of s members, J[lo * 1024
  * + hi] += 1 per pair; mode 1: tile_cnt[t] = pairs of tile t (yk_hetmer_tiles(n) words); mode 2: the 24-byte records {x, y, cx, cy} of tile t from
