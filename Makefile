@@ -12,21 +12,21 @@ all: lib cli tools oracle
 lib: yak_amd/libyak_amd.so
 cli: yak_amd/yak-amd
 
-yak_amd/kernels.o: $(CSRC)/kernels.hip $(wildcard $(CSRC)/kern_*.inc) $(CSRC)/yk_device.h
+yak_amd/kernels.o: $(CSRC)/kernels.hip $(wildcard $(CSRC)/kern_*.inc) $(CSRC)/yk_device.h $(CSRC)/replay_plan.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/engine.o: $(CSRC)/engine.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
+yak_amd/engine.o: $(CSRC)/engine.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/layout.o: $(CSRC)/layout.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
+yak_amd/layout.o: $(CSRC)/layout.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/lookup_dev.o: $(CSRC)/lookup_dev.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
+yak_amd/lookup_dev.o: $(CSRC)/lookup_dev.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/yak_hpc.o: $(CSRC)/yak_hpc.cpp $(CSRC)/hpc_host.h $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
+yak_amd/yak_hpc.o: $(CSRC)/yak_hpc.cpp $(CSRC)/hpc_host.h $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/yak_hetmer.o: $(CSRC)/yak_hetmer.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
+yak_amd/yak_hetmer.o: $(CSRC)/yak_hetmer.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/pool.o: $(CSRC)/pool.cpp $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
+yak_amd/pool.o: $(CSRC)/pool.cpp $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-HOSTDEPS = $(CSRC)/yak_host.h $(CSRC)/pgz.h $(CSRC)/engine.h $(CSRC)/yk_device.h include/yak.h include/yak_amd.h
+HOSTDEPS = $(CSRC)/yak_host.h $(CSRC)/pgz.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 yak_amd/yak_api.o: $(CSRC)/yak_api.cpp $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/yak_reader.o: $(CSRC)/yak_reader.cpp $(HOSTDEPS)

@@ -1532,7 +1532,7 @@ static int fast_finish(yakamd_ctx *c, bool last)
 	{
 		EvTimer tm(c->st);
 		s.ro.resize(c->P);
-		if (yk_run_replay(c, s.m, 0, s.kc[s.cur], s.tt[s.cur], c->d_lastput, 0, false, &s.ro)) return -1;
+		if (yk_run_replay(c, s.m, s.kc[s.cur], s.tt[s.cur], c->d_lastput, 0, false, &s.ro)) return -1;
 		c->st_cur.ms_replay += tm.stop();
 	}
 	s.lap(c, "exact layout");
@@ -1613,7 +1613,7 @@ static int64_t pass_end_body(yakamd_ctx *c)
 		}
 		{
 			EvTimer tm(c->st);
-			if (yk_run_replay(c, m, d_segoff, kc[cur], tt[cur], c->d_lastput, 0, false)) return -1;
+			if (yk_run_replay(c, m, kc[cur], tt[cur], c->d_lastput, 0, false)) return -1;
 			c->st_cur.ms_replay += tm.stop();
 		}
 		n_ins = (int64_t)(c->img_keys_total - before);
@@ -1710,7 +1710,7 @@ static int rebuild(yakamd_ctx *c, int cmin, int cmax, int which, yakamd_ctx *oth
 	HIPCK(hipMemcpyAsync(d_segoff, seg_off.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
 	yk_launch_shrink_scatter(img_view(c), P, cmin, cmax, which, ov, d_segoff, d_kc, c->st, d_segcnt);
 	EvTimer tm(c->st);
-	const int r = yk_run_replay(c, m, d_segoff, d_kc, 0, 0, &init, true);
+	const int r = yk_run_replay(c, m, d_kc, 0, 0, &init, true);
 	c->st_last.ms_shrink = tm.stop();
 	if (r) return r;
 	*tot = c->img_keys_total;
@@ -1892,7 +1892,7 @@ int yk_ctx_load(yakamd_ctx *c, const uint32_t *caps, const uint32_t *sizes, cons
 	DevBuf<u64> d_kc;
 	if (d_kc.alloc(tot)) return -1;
 	HIPCK(hipMemcpyAsync(d_kc, keys, tot * 8, hipMemcpyHostToDevice, c->st));
-	return yk_run_replay(c, m, 0, d_kc, 0, 0, &init, true);
+	return yk_run_replay(c, m, d_kc, 0, 0, &init, true);
 }
 
 /* ------------------------------------------------------------------------------------------

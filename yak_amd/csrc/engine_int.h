@@ -140,7 +140,7 @@ static inline ImgView img_view(yakamd_ctx *c)
 }
 
 /* layout.cpp: the exact khashl slot layout (khashl.h:152-221) of `m[p]` new keys per sub-table, sorted by insertion time, on top of the table image */
-int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_seg_off, const u64 *d_rec_kc, const u64 *d_rec_t,
+int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_rec_kc, const u64 *d_rec_t,
                   const u64 *d_lastput, const std::vector<u32> *init_bits, bool from_empty, const std::vector<u64> *rec_off = 0);
 /* layout.cpp: the new image replaces the context's -- `keys` / `used`, an arena of tot slots, sub-table p at new_off[p] with c->h_bits[p] / c->h_count[p] */
 int yk_image_commit(yakamd_ctx *c, u64 *keys, u32 *used, u64 tot, const std::vector<u64> &new_off);

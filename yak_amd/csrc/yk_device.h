@@ -7,14 +7,12 @@
 
 #include <stdint.h>
 #include <hip/hip_runtime.h>
+#include "replay_plan.h"                 /* u32 / u64, YK_NOCAP, and the parameter blocks of the layout replay: ReplayTask, R2Tab, R2Act, R2Load, R2Pub */
 
-typedef unsigned long long u64;
-typedef unsigned int u32;
 typedef ulonglong2 Rec;                  /* one k-mer instance: .x = yak_hash64 value, .y = stream position (32 bits used) */
 
 #define YK_EMPTY   0xFFFFFFFFFFFFFFFFull     /* unclaimed slot (accumulator and table image) */
 #define YK_TINF    0xFFFFFFFFFFFFFFFFull     /* "never" */
-#define YK_NOCAP   0xFFFFFFFFu               /* sub-table without a slot array (kh_capacity == 0) */
 #define YK_FLAG_FP 1u                        /* first occurrence passed the bloom gate */
 
 /* the inverse of yak_hash64 (reference yak-priv.h:41-68): one definition for the host (yak_ch_getseq) and the device (kern_print.inc) */
@@ -64,18 +62,6 @@ struct BloomView {
 	int nb;             /* log2 bits per sub-table (= bf_shift - pre) */
 	int n_hash;
 	int mw;             /* u64 words of a "missing probes" mask */
-};
-
-/* parameters of one replay task (one sub-table) */
-struct ReplayTask {
-	u32 old_bits, old_count;
-	u64 old_off;        /* slot offset in the old arena */
-	u64 new_off;        /* slot offset in the new arena (multiple of 32) */
-	u64 rec_off;        /* first record of this sub-table's sorted new keys */
-	u32 m;              /* number of new keys */
-	u32 init_bits;      /* pre-sized empty table (shrink), YK_NOCAP otherwise */
-	u32 cap_max_bits;   /* room reserved in the new arena */
-	u32 dbg;
 };
 
 #ifdef __cplusplus
@@ -275,11 +261,7 @@ void yk_launch_part2(const Chunk2 *chunks, int n_chunks, const u32 *chunk_first 
 void yk_launch_lds_count_ovf(FastParams fp, const u64 *sbstart, const Rec *rec,
                              u32 *bloom32, ImgView img, LcOut O, const u32 *ovf_list, u32 n_ovf, const u64 *scr_off,
                              u64 *scr, hipStream_t st);
-/* replay2 (layout replay of large sub-tables, kernels.hip) */
-struct R2Tab { u64 off, rec_off; };
-struct R2Act { u32 kind, bits, i0, batch, src, seg0, pad0, pad1; };
-struct R2Load { u64 src_off; u32 bits, from_src, dst, pad; };
-struct R2Pub { u64 new_off; u32 bits, src; };
+/* replay2 (layout replay of large sub-tables, kernels.hip; its parameter blocks: replay_plan.h) */
 void yk_r2_binit(const R2Tab *tabs, const R2Act *acts, int P, u32 bmax, u32 *OCC, u32 *USED, hipStream_t st);
 void yk_r2_dsmall(const R2Tab *tabs, const R2Act *acts, int P, u64 *K0, u64 *K1, u32 *TAG, u32 *OCC, u32 *USED, u32 *Fcur, u32 *Gcur, u32 *fail, hipStream_t st);
 int yk_r2_double(const R2Tab *tabs, const R2Act *acts, int P, int n_dbl, u64 *K0, u64 *K1, u32 *TAG, u32 *OCC, u32 *USED, const u32 *Fin, u32 *Fout, u32 *fail, hipStream_t st);
