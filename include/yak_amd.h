@@ -342,6 +342,56 @@ typedef struct {
 void yakamd_hmopt_init(yakamd_hmopt_t *opt);
 int yakamd_hetmers(const yakamd_hmopt_t *opt, const yak_ch_t *ch, const char *out_fn);
 
+/* The de Bruijn graph of a count table (not in the reference): the graph its k-mers span, its compacted form and its unitigs --
+ * what BCALM2, Cuttlefish or the first stage of ABySS build from a table of their own.  The table is a YAK_LOAD_ALL one or a resident one, k odd and
+ * below 32, min_cnt in [1, 1023]; everything is a pure function of the table's {(k-mer, count)} and of min_cnt.
+ * A NODE is a stored canonical k-mer x, coded as yakamd_kmers_dev() lists it, with a count of at least min_cnt; a stored key below it is absent, as
+ * a node and as a neighbour.  The LISTING INDEX of a stored key is its place in yakamd_kmers_dev(h, 0, 1 << pre, ...); a key that is no node keeps
+ * its index.  Side 0 (R) appends a base b: z = (x << 2 | b) & (4^k - 1); side 1 (L) prepends it: z = x >> 2 | b << 2 (k - 1); the neighbour is
+ * y = min(z, revcomp_k(z)).  `edges` has bit b set iff the R extension by b is a node, bit 4 + b iff the L extension is (y may be x itself); the
+ * degree of a side is the popcount of its four bits.  y faces x with side t: from R, t = L if y == z, else R; from L, t = R if y == z, else L.  Side
+ * (x, s) is LINKED to (y, t) iff it has one edge, y != x and (y, t) has one edge; links are symmetric.  A UNITIG is a maximal chain of linked nodes:
+ * open with two unlinked end sides (a node without a link is one), or a cycle; open unitigs = n_node - n_linked_side / 2.
+ * yakamd_graph_open() probes the table for every node's eight possible neighbours once and keeps about 1.125 bytes of device memory per slot of the
+ * table and 16 per sub-table until yakamd_graph_close(); the caller leaves the table unchanged in between.  NULL after a message
+ * (yakamd_last_error()), before any device work: NULL or not an engine table, an even k, k >= 32, min_cnt outside [1, 1023], an open pass (refused
+ * again at each later call), a table sharded over prefix ranges or spread over several devices, no gfx950 GPU.  A table marked as
+ * homopolymer-compressed is taken as it is.
+ * yakamd_graph_stats(): the tallies; deg[l][r] = nodes of l left and r right edges, n_arc = the sum of all degrees.  0, or -1 after a message.
+ * yakamd_graph_nodes_dev(): one record per stored key of sub-tables [sub_lo, sub_hi) in listing order into d_nodes (cap records of 32 bytes, device
+ * memory, 16-byte aligned), aligned with yakamd_kmers_dev() of the same range: x and count are its output; link[s] = the GLOBAL listing index of the
+ * node side s is linked to << 1 | the side of it that faces back, or YAKAMD_GRAPH_NONE; a key that is no node has edges = 0 and no link.  Returns the
+ * number of records; with a smaller cap or a NULL pointer the number needed, and nothing is written.  -1 after a message.
+ * No call builds a host mirror of the table. */
+typedef struct yakamd_graph yakamd_graph_t;
+#define YAKAMD_GRAPH_NONE (~(uint64_t)0)
+typedef struct { uint64_t n_key, n_node, n_arc, n_linked_side, deg[5][5]; } yakamd_gstat_t;
+typedef struct { uint64_t x, link[2]; uint32_t count, edges; } yakamd_gnode_t;
+yakamd_graph_t *yakamd_graph_open(yak_ch_t *h, int min_cnt);
+int     yakamd_graph_stats(yakamd_graph_t *g, yakamd_gstat_t *st);
+int64_t yakamd_graph_nodes_dev(yakamd_graph_t *g, int sub_lo, int sub_hi, void *d_nodes, int64_t cap);
+void    yakamd_graph_close(yakamd_graph_t *g);
+void    yakamd_graph_open_ms(yakamd_graph_t *g, double ms[3]);   /* measurement: the milliseconds of the open's edge, rank and link steps, taken only with YAKAMD_VERBOSE or the test switch YAKAMD_GRAPH_TIMED */
+/* `yak-amd unitigs` as a library call: the graph, its records pulled to the host in ranges of whole sub-tables of at most batch_keys keys, and the
+ * walk along the links there with n_threads threads (32 bytes of host memory per stored key; a table whose records do not fit fails with a message
+ * that says so).  Open unitigs come first, ascending by the listing index of their start node -- the end node with the smaller index, read away
+ * from its unlinked side; a node without a link as stored -- then the cycles, ascending by their smallest index, from that node as stored through
+ * R.  Reading a node "as stored" leaves it through R, reading its reverse complement through L.  A unitig of n nodes has n + k - 1 bases.
+ * To out_fn (NULL or "-" = stdout) as FASTA: `>u<j>\tLN:i:<bases>\tKC:i:<sum of its nodes' counts>\tkm:f:<KC / nodes, %.1f>\tCL:i:<1 for a cycle,
+ * else 0>` and the bases on one line, j from 0.  With stats_only, tab-separated instead: `#unitigs k=<k> min_cnt=<c>`; `N n_key n_node n_arc
+ * n_linked_side`; `D l r deg[l][r]` per non-zero bin, l ascending, then r; `U n_open n_cycle sum_len max_len n50` in bases, n50 = the largest L such
+ * that the unitigs of at least L bases hold half of sum_len or more (0 without a node).  0 on success; -1 after a message on stderr -- on one of the
+ * refusals above before the output is created. */
+typedef struct {
+	int32_t min_cnt;          /* -c, 1: a k-mer below this count is absent */
+	int32_t stats_only;       /* -s, 0: the N, D and U lines, not the FASTA */
+	int32_t n_threads;        /* -t, 8: threads of the host walk */
+	int64_t batch_keys;       /* keys per range of whole sub-tables pulled to the host, 2^24 */
+} yakamd_ugopt_t;
+void yakamd_ugopt_init(yakamd_ugopt_t *o);
+int  yakamd_unitigs(const yakamd_ugopt_t *o, const yak_ch_t *ch, const char *out_fn);
+void yakamd_unitigs_ms(double ms[4]);   /* measurement: the milliseconds the process' last yakamd_unitigs call spent on the graph, the records' way to the host, the host walk, the text */
+
 /* Homopolymer compression (HPC; not in the reference): every run of the same base collapses to one base before k-mers are taken,
  * the space long-read assemblers and their QV pipelines count in.  On a base image as described at the top of this file: a position is VALID when its
  * byte has a code 0..3 under seq_nt4_table (in the packed form: its validity bit).  Position i is DROPPED iff i > 0, i and i - 1 are both valid and

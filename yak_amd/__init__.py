@@ -44,6 +44,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_depth_reduce_dev", "yakamd_dpopt_init", "yakamd_depth",
     "yakamd_cover_dev", "yakamd_cvopt_init", "yakamd_cover",
     "yakamd_hetmers_dev", "yakamd_hetmer_pairs_dev", "yakamd_hmopt_init", "yakamd_hetmers",
+    "yakamd_graph_open", "yakamd_graph_stats", "yakamd_graph_nodes_dev", "yakamd_graph_close", "yakamd_graph_open_ms", "yakamd_ugopt_init", "yakamd_unitigs", "yakamd_unitigs_ms",
     "yakamd_hpc_dev", "yakamd_hpc_packed_dev", "yakamd_hpc_host", "yakamd_ch_set_hpc", "yakamd_ch_hpc", "yakamd_count_hpc",
 ]
 
@@ -107,6 +108,18 @@ class HmoptT(C.Structure):                     # yakamd_hmopt_t, include/yak_amd
 
 class HetpairT(C.Structure):                   # yakamd_hetpair_t, include/yak_amd.h
     _fields_ = [("x", C.c_uint64), ("y", C.c_uint64), ("cx", C.c_uint32), ("cy", C.c_uint32)]
+
+
+class GstatT(C.Structure):                     # yakamd_gstat_t, include/yak_amd.h
+    _fields_ = [("n_key", C.c_uint64), ("n_node", C.c_uint64), ("n_arc", C.c_uint64), ("n_linked_side", C.c_uint64), ("deg", (C.c_uint64 * 5) * 5)]
+
+
+class GnodeT(C.Structure):                     # yakamd_gnode_t, include/yak_amd.h
+    _fields_ = [("x", C.c_uint64), ("link", C.c_uint64 * 2), ("count", C.c_uint32), ("edges", C.c_uint32)]
+
+
+class UgoptT(C.Structure):                     # yakamd_ugopt_t, include/yak_amd.h
+    _fields_ = [("min_cnt", C.c_int32), ("stats_only", C.c_int32), ("n_threads", C.c_int32), ("batch_keys", C.c_int64)]
 
 
 class CvoptT(C.Structure):                     # yakamd_cvopt_t, include/yak_amd.h
@@ -312,6 +325,14 @@ def lib():
     L.yakamd_hetmer_pairs_dev.restype = C.c_int64; L.yakamd_hetmer_pairs_dev.argtypes = [P(ChT), C.c_int, C.c_void_p, C.c_int64]
     L.yakamd_hmopt_init.restype = None; L.yakamd_hmopt_init.argtypes = [P(HmoptT)]
     L.yakamd_hetmers.restype = C.c_int; L.yakamd_hetmers.argtypes = [P(HmoptT), P(ChT), C.c_char_p]
+    L.yakamd_graph_open.restype = C.c_void_p; L.yakamd_graph_open.argtypes = [P(ChT), C.c_int]
+    L.yakamd_graph_stats.restype = C.c_int; L.yakamd_graph_stats.argtypes = [C.c_void_p, P(GstatT)]
+    L.yakamd_graph_nodes_dev.restype = C.c_int64; L.yakamd_graph_nodes_dev.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+    L.yakamd_graph_close.restype = None; L.yakamd_graph_close.argtypes = [C.c_void_p]
+    L.yakamd_graph_open_ms.restype = None; L.yakamd_graph_open_ms.argtypes = [C.c_void_p, P(C.c_double)]
+    L.yakamd_ugopt_init.restype = None; L.yakamd_ugopt_init.argtypes = [P(UgoptT)]
+    L.yakamd_unitigs_ms.restype = None; L.yakamd_unitigs_ms.argtypes = [P(C.c_double)]
+    L.yakamd_unitigs.restype = C.c_int; L.yakamd_unitigs.argtypes = [P(UgoptT), P(ChT), C.c_char_p]
     _lib = L
     return L
 
@@ -514,6 +535,48 @@ class Table:
             self.L.yakamd_dev_free(d)
         return [(r.x, r.y, r.cx, r.cy) for r in recs]
 
+    def graph_stats(self, min_cnt=1):
+        """the tallies of the table's de Bruijn graph (yakamd_graph_open + yakamd_graph_stats): a dict of n_key, n_node, n_arc, n_linked_side and
+        deg, deg[l][r] = nodes of l left and r right edges"""
+        g = self.L.yakamd_graph_open(self.h, min_cnt)
+        if not g:
+            raise RuntimeError("yakamd_graph_open failed: " + _err())
+        try:
+            st = GstatT()
+            if self.L.yakamd_graph_stats(g, C.byref(st)) != 0:
+                raise RuntimeError("yakamd_graph_stats failed: " + _err())
+        finally:
+            self.L.yakamd_graph_close(g)
+        return dict(n_key=st.n_key, n_node=st.n_node, n_arc=st.n_arc, n_linked_side=st.n_linked_side, deg=[[st.deg[l][r] for r in range(5)] for l in range(5)])
+
+    def graph_nodes(self, min_cnt=1, sub_lo=0, sub_hi=None):
+        """the graph's records of the stored keys of sub-tables [sub_lo, sub_hi) in listing order (yakamd_graph_nodes_dev): [(x, link_r, link_l, count,
+        edges)], a link = the global listing index of the linked node << 1 | its facing side, or 2^64 - 1"""
+        sub_hi = (1 << self.h.contents.pre) if sub_hi is None else sub_hi
+        g = self.L.yakamd_graph_open(self.h, min_cnt)
+        if not g:
+            raise RuntimeError("yakamd_graph_open failed: " + _err())
+        d = None
+        try:
+            n = self.L.yakamd_graph_nodes_dev(g, sub_lo, sub_hi, None, 0)
+            if n < 0:
+                raise RuntimeError("yakamd_graph_nodes_dev failed: " + _err())
+            if n == 0:
+                return []
+            d = self.L.yakamd_dev_alloc(n * C.sizeof(GnodeT))
+            if not d:
+                raise RuntimeError("yakamd_dev_alloc failed: " + _err())
+            if self.L.yakamd_graph_nodes_dev(g, sub_lo, sub_hi, d, n) != n:
+                raise RuntimeError("yakamd_graph_nodes_dev failed: " + _err())
+            recs = (GnodeT * n)()
+            if self.L.yakamd_memcpy_d2h(recs, d, n * C.sizeof(GnodeT)) != 0:
+                raise RuntimeError(_err())
+        finally:
+            if d:
+                self.L.yakamd_dev_free(d)
+            self.L.yakamd_graph_close(g)
+        return [(r.x, r.link[0], r.link[1], r.count, r.edges) for r in recs]
+
     def subtable(self, i):
         cap, size = C.c_uint32(), C.c_uint32()
         self.L.yakamd_subtable(self.h, i, C.byref(cap), C.byref(size))
@@ -652,6 +715,26 @@ def hetmers(table_yak, min_cnt=1, pairs=False, batch_keys=None):
         if batch_keys is not None:
             o.batch_keys = batch_keys
         return _output_of("yakamd_hetmers", lambda out: L.yakamd_hetmers(C.byref(o), h, out))
+    finally:
+        L.yak_ch_destroy(h)
+
+
+def unitigs(table_yak, min_cnt=1, stats_only=False, threads=None, batch_keys=None):
+    """`yak-amd unitigs` through the C ABI (yak_ch_restore + yakamd_unitigs): the unitigs of the de Bruijn graph that the table's k-mers with a count
+    of at least min_cnt span, as FASTA (open unitigs first, then cycles), or with stats_only the `#unitigs`, N, D and U lines"""
+    L = lib()
+    h = L.yak_ch_restore(table_yak.encode())
+    if not h:
+        raise RuntimeError("yak_ch_restore failed: " + _err())
+    try:
+        o = UgoptT()
+        L.yakamd_ugopt_init(C.byref(o))
+        o.min_cnt, o.stats_only = min_cnt, int(bool(stats_only))
+        if threads is not None:
+            o.n_threads = threads
+        if batch_keys is not None:
+            o.batch_keys = batch_keys
+        return _output_of("yakamd_unitigs", lambda out: L.yakamd_unitigs(C.byref(o), h, out))
     finally:
         L.yak_ch_destroy(h)
 

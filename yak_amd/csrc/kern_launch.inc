@@ -739,6 +739,35 @@ int yk_launch_hetmer(int mode, const u64 *keys, const u64 *off, u64 n, int n_sub
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+/* `yak-amd unitigs` (kern_graph.inc).  The grids are persistent ones over the tiles [t_lo, t_hi) of the arena; the LDS is the sub-table directory
+ * while pre <= 12 (32 KiB at the most).  what 0: the edge bytes and the degree tallies, `inflight` (4, or 8) probes requested together; 1: the rank
+ * directory, one workgroup per sub-table; 2: tally[25] += linked sides; 3: the records of the tiles' keys.  grid_want > 0: that many workgroups
+ * instead of four per CU (a test switch: no result depends on it).  0, or -1 if the launch failed */
+u64 yk_graph_tile(void) { return GR_THREADS; }
+int yk_launch_graph(int what, int inflight, int grid_want, const u64 *tile0, const u64 *key0, uint8_t *edges, u32 *wrank, u64 *tally, u64 t_lo, u64 t_hi, u64 n_slots,
+                    int P, int min_cnt, void *out, u64 out_key0, u64 out_n, ImgView img, hipStream_t st)
+{
+	if (img.k < 1 || img.k > 31 || !(img.k & 1) || what < 0 || what > 3 || t_hi < t_lo || P != 1 << img.pre) return -1;
+	GrArgs a;
+	a.tile0 = tile0; a.key0 = key0; a.edges = edges; a.wrank = wrank; a.tally = tally; a.out = (u64*)out; a.out_key0 = out_key0; a.out_n = out_n;
+	a.t_lo = t_lo; a.t_hi = t_hi; a.n_slots = n_slots; a.P = P; a.k = img.k; a.min_cnt = min_cnt;
+	a.tab = img.pre <= 12;
+	if (what == 1) {
+		hipLaunchKernelGGL(k_graph_rank, dim3((unsigned)P), dim3(256), 0, st, a, img);
+		return hipGetLastError() == hipSuccess ? 0 : -1;
+	}
+	if (t_hi == t_lo) return 0;
+	const size_t lds = a.tab ? (size_t)8 << img.pre : 0;
+	int dev = 0, n_cu = 0;
+	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
+	const u64 grid = std::max<u64>(std::min<u64>(grid_want > 0 ? (u64)grid_want : (u64)n_cu * 4, t_hi - t_lo), 1);
+	if (what == 0 && inflight == 8) hipLaunchKernelGGL((k_graph_edges<8>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
+	else if (what == 0) hipLaunchKernelGGL((k_graph_edges<4>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
+	else if (what == 2) hipLaunchKernelGGL((k_graph_link<GR_COUNT>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
+	else hipLaunchKernelGGL((k_graph_link<GR_EMIT>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
+	return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 /* homopolymer compression (kern_hpc.inc).  valid == 0: `in` is the ASCII image; valid != 0: the packed one (code words at `in`).  Tiles of
  * yk_hpc_tile(packed) positions; tcnt = yk_hpc_tiles() words, toff = their exclusive scan (yk_launch_te_scan), one word more */
 int64_t yk_hpc_tile(int packed) { return (int64_t)HP_THREADS * (packed ? (int)HpPacked::PER : (int)HpAscii::PER); }

@@ -12,6 +12,7 @@
  * `yak inspect` (inspect.c:47-62): k_inspect joins the stored keys of one table with another table's image into a 1024 x 1024 histogram.
  * Homopolymer compression of the input (kern_hpc.inc): k_hpc_count, k_hpc_scatter and k_hpc_remap compact a base image in front of the kernels above.
  * `yak print` (main.c:302-320): k_kmers and k_print turn the stored keys back into k-mers and into the text the reference writes.
+ * `yak-amd unitigs` (kern_graph.inc): k_graph_edges, k_graph_rank and k_graph_link probe a table for its own de Bruijn neighbours.
  * All work is 64-bit integer arithmetic; the bound is HBM / L2-atomic traffic, never MFMA.
  *
  * One translation unit, cut by stage into the kern_*.inc files included at the end of this file (device helpers and __device__ globals are
@@ -103,5 +104,6 @@ __device__ const unsigned char d_nt4[256] = {
 #include "kern_depth.inc"
 #include "kern_cover.inc"
 #include "kern_hetmer.inc"
+#include "kern_graph.inc"
 #include "kern_hpc.inc"
 #include "kern_launch.inc"

@@ -17,9 +17,10 @@
  *     recount  the counts of a table's k-mers in other sequences, reference main.c:66-88 (restore, tighten, yak_recount)
  *     subtract, isec   the k-mers of the first table absent from / present in the others, reference main.c:217-284
  *     version  the library's YAKS_VERSION
- * and four beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table), hetmers
- * (yakamd_hetmers: the pairs of k-mers of a count table that differ in the middle base alone) and cover (yakamd_cover: the bases of every sequence
- * that lie inside k-mers a table holds, lacks or holds too often -- as a table, as intervals or as a masked FASTA).  `count -c` and `qv -c` work in homopolymer-compressed
+ * and five beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table), hetmers
+ * (yakamd_hetmers: the pairs of k-mers of a count table that differ in the middle base alone), cover (yakamd_cover: the bases of every sequence
+ * that lie inside k-mers a table holds, lacks or holds too often -- as a table, as intervals or as a masked FASTA) and unitigs (yakamd_unitigs: the
+ * de Bruijn graph the k-mers of a count table span, as its unitigs in FASTA or as its tallies).  `count -c` and `qv -c` work in homopolymer-compressed
  * space (yakamd_count_hpc; yakamd_ch_set_hpc on the restored table): every run of one base is one base before k-mers are taken.
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
@@ -29,7 +30,7 @@
 #include <string.h>
 #include <stdint.h>
 #include "yak.h"
-#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_cover, yakamd_count_hpc and yakamd_ch_set_hpc */
+#include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_cover, yakamd_unitigs, yakamd_count_hpc and yakamd_ch_set_hpc */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
 enum arg_kind { ARG_FLAG, ARG_I32, ARG_SIZE, ARG_I64SIZE, ARG_F64, ARG_TEXT };
@@ -538,6 +539,38 @@ static int cmd_cover(int argc, char **argv)
 	return rc;
 }
 
+/* ---- unitigs (not in the reference) ---- */
+/* the de Bruijn graph of a count table's k-mers: its unitigs as FASTA, or with -s its tallies (yakamd_unitigs) */
+static int cmd_unitigs(int argc, char **argv)
+{
+	yakamd_ugopt_t o;
+	const char *out = 0;
+	int stats = 0, min_cnt = 1, n_threads = 0;
+	yakamd_ugopt_init(&o);
+	n_threads = o.n_threads;
+	const struct arg_def defs[] = {
+		{ 'c', ARG_I32, &min_cnt, "a k-mer with a count below this is absent, 1 .. 1023 [1]" },
+		{ 's', ARG_FLAG, &stats, "the tallies of the graph and of its unitigs, not the FASTA" },
+		{ 't', ARG_I32, &n_threads, "threads of the host walk [8]" },
+		{ 'o', ARG_TEXT, &out, "write the output here; stdout without it" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first >= argc) { arg_help("unitigs [options] <table.yak>", defs, nd); return 1; }
+	uint32_t k = 0, pre = 0;
+	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd unitigs: %s is not a readable .yak file\n", argv[first]); return 2; }
+	if (!(k & 1)) { fprintf(stderr, "yak-amd unitigs: %s has k = %u: the graph is defined for an odd k only\n", argv[first], k); return 2; }
+	if (k >= 32) { fprintf(stderr, "yak-amd unitigs: %s has k = %u: k must be below 32\n", argv[first], k); return 2; }
+	if (min_cnt < 1 || min_cnt > 1023) { fprintf(stderr, "yak-amd unitigs: -c must be in [1, 1023]\n"); return 1; }
+	if (n_threads < 1) { fprintf(stderr, "yak-amd unitigs: -t must be at least 1\n"); return 1; }
+	o.min_cnt = min_cnt; o.stats_only = stats; o.n_threads = n_threads;
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd unitigs: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	const int rc = yakamd_unitigs(&o, tab, out) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 /* ---- hetmers (not in the reference) ---- */
 /* the pairs of k-mers of a count table that differ in the middle base alone, as a histogram of their two counts (yakamd_hetmers) */
 static int cmd_hetmers(int argc, char **argv)
@@ -608,11 +641,13 @@ int main(int argc, char **argv)
 	if (argc >= 2 && strcmp(argv[1], "depth") == 0) return cmd_depth(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "hetmers") == 0) return cmd_hetmers(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "cover") == 0) return cmd_cover(argc - 1, argv + 1);
+	if (argc >= 2 && strcmp(argv[1], "unitigs") == 0) return cmd_unitigs(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
 	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-8s %s\n", cmds[i].name, cmds[i].what);
 	fprintf(stderr, "  beyond the reference:\n      yak-amd %-8s %s\n", "sum", "add the counts of two or more .yak tables together");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "depth", "the depth of the k-mers of each sequence, or window, in a .yak table");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "hetmers", "the pairs of k-mers of a .yak table that differ in the middle base, by their two counts");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "cover", "the bases of each sequence that lie inside k-mers a .yak table holds, lacks or holds too often");
+	fprintf(stderr, "      yak-amd %-8s %s\n", "unitigs", "the unitigs of the de Bruijn graph that the k-mers of a .yak table span");
 	return 1;
 }

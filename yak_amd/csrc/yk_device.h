@@ -144,6 +144,14 @@ void yk_launch_cover(CvArgs a, int mask, hipStream_t st);
 u64 yk_hetmer_tiles(u64 n);
 int yk_launch_hetmer(int mode, const u64 *keys, const u64 *off, u64 n, int n_sub, int sub_lo, int min_cnt, ImgView img, u64 *J, u64 *group,
                      u32 *tile_cnt, const u64 *tile_off, void *list, hipStream_t st);
+/* `yak-amd unitigs` (kern_graph.inc): the de Bruijn graph of the whole image `img` (k odd, below 32; a key below min_cnt is absent).  A tile is
+ * yk_graph_tile() consecutive slots of one sub-table; tile0[p] / key0[p] = the tiles / stored keys of the sub-tables before p (P + 1 words each).
+ * what 0: edges[slot] = the edge mask of the slot's key and tally[l * 5 + r] += nodes of l left and r right edges, `inflight` (4, or 8) probes at a
+ * time; 1: wrank[w] = used slots of the sub-table in front of word w; 2: tally[25] += linked sides; 3: the 32-byte records of the keys of tiles
+ * [t_lo, t_hi) to out[listing index - out_key0], out_n of them.  grid_want > 0: that many workgroups.  0, or -1 if the launch failed */
+u64 yk_graph_tile(void);
+int yk_launch_graph(int what, int inflight, int grid_want, const u64 *tile0, const u64 *key0, uint8_t *edges, u32 *wrank, u64 *tally, u64 t_lo, u64 t_hi, u64 n_slots,
+                    int P, int min_cnt, void *out, u64 out_key0, u64 out_n, ImgView img, hipStream_t st);
 /* homopolymer compression of a base image (kern_hpc.inc).  valid == 0: `in` is the ASCII image, valid != 0: the packed one.  Three
  * launches: the kept positions per tile of yk_hpc_tile(packed) positions into tcnt (yk_hpc_tiles() words), their exclusive scan into toff
  * (yk_launch_te_scan, one word more: toff[tiles] = the output's length), the kept bytes to `out` with '\n' up to the next multiple of 16.
