@@ -12,19 +12,21 @@ all: lib cli tools oracle
 lib: yak_amd/libyak_amd.so
 cli: yak_amd/yak-amd
 
-yak_amd/kernels.o: $(CSRC)/kernels.hip $(wildcard $(CSRC)/kern_*.inc) $(CSRC)/yk_device.h $(CSRC)/replay_plan.h
+yak_amd/kernels.o: $(CSRC)/kernels.hip $(wildcard $(CSRC)/kern_*.inc) $(CSRC)/yk_device.h $(CSRC)/replay_plan.h $(CSRC)/tally.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/engine.o: $(CSRC)/engine.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
+yak_amd/tally.o: $(CSRC)/tally.cpp $(CSRC)/tally.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/layout.o: $(CSRC)/layout.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
+yak_amd/engine.o: $(CSRC)/engine.cpp $(CSRC)/engine_int.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/lookup_dev.o: $(CSRC)/lookup_dev.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
+yak_amd/layout.o: $(CSRC)/layout.cpp $(CSRC)/engine_int.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/yak_hpc.o: $(CSRC)/yak_hpc.cpp $(CSRC)/hpc_host.h $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
+yak_amd/lookup_dev.o: $(CSRC)/lookup_dev.cpp $(CSRC)/engine_int.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/yak_hetmer.o: $(CSRC)/yak_hetmer.cpp $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
+yak_amd/yak_hpc.o: $(CSRC)/yak_hpc.cpp $(CSRC)/hpc_host.h $(CSRC)/engine_int.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/yak_graph.o: $(CSRC)/yak_graph.cpp $(CSRC)/unitig_walk.h $(CSRC)/engine_int.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
+yak_amd/yak_hetmer.o: $(CSRC)/yak_hetmer.cpp $(CSRC)/engine_int.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+yak_amd/yak_graph.o: $(CSRC)/yak_graph.cpp $(CSRC)/unitig_walk.h $(CSRC)/engine_int.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/pool.o: $(CSRC)/pool.cpp $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -41,7 +43,7 @@ yak_amd/yak_inspect.o: $(CSRC)/yak_inspect.cpp $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/yak_print.o: $(CSRC)/yak_print.cpp $(HOSTDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/pool.o yak_amd/engine.o yak_amd/layout.o yak_amd/lookup_dev.o yak_amd/yak_hetmer.o yak_amd/yak_graph.o yak_amd/yak_hpc.o yak_amd/yak_api.o yak_amd/yak_reader.o yak_amd/yak_multi.o yak_amd/yak_lookup.o yak_amd/yak_inspect.o yak_amd/yak_print.o $(CSRC)/libyak_amd.map
+yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/tally.o yak_amd/pool.o yak_amd/engine.o yak_amd/layout.o yak_amd/lookup_dev.o yak_amd/yak_hetmer.o yak_amd/yak_graph.o yak_amd/yak_hpc.o yak_amd/yak_api.o yak_amd/yak_reader.o yak_amd/yak_multi.o yak_amd/yak_lookup.o yak_amd/yak_inspect.o yak_amd/yak_print.o $(CSRC)/libyak_amd.map
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(CSRC)/libyak_amd.map -o $@ $(filter %.o,$^) -lz
 
 yak_amd/yak-amd: $(CSRC)/main.c include/yak.h include/yak_amd.h yak_amd/libyak_amd.so

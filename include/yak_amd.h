@@ -480,6 +480,15 @@ int64_t yakamd_host_image_packed(const char *fn, int min_len, char **out);
  * them).  No environment variable reaches them; a value set here also overrides the environment for the public knobs.  reset: forget all. */
 void yakamd_test_set(const char *name, int64_t value);
 void yakamd_test_reset(void);
+/* The launch tally (tests/paths_util.py): one counter per kernel instantiation the library can launch, named as its launch site writes it
+ * (`k_part2_wc8<false,7>`), bumped once per launch; behind them the path events (`event:...`), decisions of the host that are not launches --
+ * a refused bitmap ranking, a streaming replay used or refused, sub-buckets k_lc2 passed on, slices of a pass, the path of the count pass ...
+ * (`event:par_ok` / `event:par_fail` advance when yakamd_debug_counters() reads the device's counters).  Host data only: the names are known
+ * once the library is loaded, no device is needed.  names: -> the number of counters, *names = their names (the library's, valid for its
+ * lifetime); read: the first n counts; reset: all to zero. */
+int yakamd_tally_names(const char *const **names);
+void yakamd_tally_read(uint64_t *out, int n);
+void yakamd_tally_reset(void);
 void yakamd_gz_tune(int64_t chunk_bytes, int64_t min_file_bytes, int64_t front_bytes);
 int64_t yakamd_gz_inflate(const char *fn, int n_threads, char **out);
 

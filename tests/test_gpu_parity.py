@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+import paths_util
 from conftest import GOLD, ROOT, args_to_opts, image_for_case
 
 pytestmark = pytest.mark.gpu
@@ -22,6 +23,13 @@ def ya():
     L = yak_amd.lib()
     assert L.yakamd_device_count() >= 1, "GPU tests need an MI355X; the engine has no CPU fallback"
     return yak_amd
+
+
+def _hold(ya, ran, table, request):
+    """the launch tally of the runs above against the entry of this case (tests/paths_util.py): the path its id names did run"""
+    case = [request.node.callspec.id] if request.node.callspec.id in table else [p for p in request.node.callspec.id.split("-") if p in table]
+    assert len(case) == 1, request.node.callspec.id
+    paths_util.hold(ran, table[case[0]], paths_util.names(ya.lib()), case[0])
 
 
 @pytest.mark.parametrize("name", CASES)
@@ -106,18 +114,20 @@ def test_grow_on_existing_key(ya, oracle, manifest):
     assert a == oracle.count_protocol_mem(one)[0] and b == oracle.count_protocol_mem(two)[0]
 
 
-@pytest.mark.parametrize("env", [dict(YAKAMD_BATCH="4096"), dict(YAKAMD_BATCH="8192", YAKAMD_LASTPUT_TAIL="100"),
-                                 dict(YAKAMD_BATCH="65536", YAKAMD_LASTPUT_TAIL="1"), dict(YAKAMD_MULTI_BITS="10")],
+@pytest.mark.parametrize("env", [dict(YAKAMD_FAST="0", YAKAMD_BATCH="4096"), dict(YAKAMD_FAST="0", YAKAMD_BATCH="8192", YAKAMD_LASTPUT_TAIL="100"),
+                                 dict(YAKAMD_FAST="0", YAKAMD_BATCH="65536", YAKAMD_LASTPUT_TAIL="1"), dict(YAKAMD_FAST="0", YAKAMD_MULTI_BITS="10")],
                          ids=["batch4k", "batch8k_tail100", "batch64k_tail1", "multi10"])
-def test_device_batching_is_invisible(env, ya, oracle, synth, monkeypatch, knob):
+def test_device_batching_is_invisible(env, ya, oracle, synth, monkeypatch, knob, request):
     """cutting the stream into many device batches (accumulator growth + rehash, per-batch bloom
     phases, last-put fallback scan, tiny `multi` filter) must not change a byte -- the reference's
-    independence of -K/-t"""
+    independence of -K/-t.  All of that is the accumulator path's (YAKAMD_FAST=0): the exclusive-ownership path keeps the batches and counts them at once"""
     img = synth(3000, g=15000, s=12)
     for k, v in env.items():
         knob(k, v)
-    for opt in (dict(k=31), dict(k=31, bf_shift=20), dict(k=31, bf_shift=24)):
-        assert ya.count_protocol_host(img, **opt)[0] == oracle.count_protocol_mem(img, **opt)[0]
+    with paths_util.tally(ya.lib()) as ran:
+        for opt in (dict(k=31), dict(k=31, bf_shift=20), dict(k=31, bf_shift=24)):
+            assert ya.count_protocol_host(img, **opt)[0] == oracle.count_protocol_mem(img, **opt)[0]
+    _hold(ya, ran, paths_util.DEVICE_BATCHING, request)
 
 
 def test_cli_drop_in(ya, oracle, tmp_path):
@@ -141,21 +151,23 @@ def test_cli_drop_in(ya, oracle, tmp_path):
     assert open(a, "rb").read() == open(b, "rb").read()
 
 
-@pytest.mark.parametrize("env", [dict(), dict(YAKAMD_BATCH="65536"), dict(YAKAMD_CNT2_WGS="3"), dict(YAKAMD_RETAIN2="0"), dict(YAKAMD_RETAIN2="0", YAKAMD_BATCH="65536"),
+@pytest.mark.parametrize("env", [dict(), dict(YAKAMD_BATCH="65536"), dict(YAKAMD_CNT2_FUSED="0", YAKAMD_CNT2_WGS="3"), dict(YAKAMD_RETAIN2="0"), dict(YAKAMD_RETAIN2="0", YAKAMD_BATCH="65536"),
                                  dict(YAKAMD_RETAIN_GB="0"), dict(YAKAMD_RETAIN2="0", YAKAMD_COUNT_OWN="0"),
-                                 dict(YAKAMD_CNT2_SMALL="-1"), dict(YAKAMD_CNT2_SMALL="1000000", YAKAMD_S2_BITS="0", big="1"), dict(YAKAMD_CNT2_SMALL="1000000", YAKAMD_CNT2_WGS="2"),
-                                 dict(YAKAMD_LC_FLAT="1"), dict(YAKAMD_S2_BITS="8", YAKAMD_P3_MIN="3", YAKAMD_P3_LOW="4")],
+                                 dict(YAKAMD_CNT2_FUSED="0", YAKAMD_CNT2_SMALL="-1"), dict(YAKAMD_CNT2_FUSED="0", YAKAMD_CNT2_SMALL="1000000", YAKAMD_S2_BITS="0", big="1"),
+                                 dict(YAKAMD_CNT2_FUSED="0", YAKAMD_CNT2_SMALL="1000000", YAKAMD_CNT2_WGS="2"),
+                                 dict(YAKAMD_LC_FLAT="1"), dict(YAKAMD_S2_BITS="8", YAKAMD_P3_MIN="3", YAKAMD_P3_LOW="4"), dict(YAKAMD_LC2_W6="0")],
                          ids=["subbucket_records", "subbucket_records_many_batches", "subbucket_records_3_workgroups", "prefix_records", "prefix_records_many_batches",
                               "budget_refuses", "count_kernel_not_applicable",
                               "subbucket_records_big_lds_table", "subbucket_records_small_lds_table_overfull", "subbucket_records_small_lds_table",
-                              "subbucket_records_flat_gather", "subbucket_records_level2_two_sweeps"])
+                              "subbucket_records_flat_gather", "subbucket_records_level2_two_sweeps", "subbucket_records_no_stage_five_waves"])
 @pytest.mark.parametrize("opt", [dict(k=31, bf_shift=24), dict(k=21, bf_shift=20), dict(k=31, bf_shift=22, n_hash=7)], ids=["k31b24", "k21b20", "k31b22H7"])
-def test_second_pass_counts_the_records_the_first_pass_retained(opt, env, ya, oracle, synth, monkeypatch, knob):
+def test_second_pass_counts_the_records_the_first_pass_retained(opt, env, ya, oracle, synth, monkeypatch, knob, request):
     """main.c:53-57: both passes read the same input.  With yakamd_retain_input the create_new pass keeps its hashed k-mers on the
     device -- grouped by sub-bucket together with the keys every sub-bucket put into the table (k_cnt2) when the pass was one slice into
     an empty table, else grouped by prefix (k_img_count_own) -- and the count pass counts those (yakamd_count_retained), or reports
     that nothing usable was kept and takes the input again; either way the bytes are the oracle's, and the retained path must really
-    have been taken where it applies"""
+    have been taken where it applies.  (k_cnt2's switches -- grid, LDS table -- mean something under YAKAMD_CNT2_FUSED=0 only: else the count pass
+    adds the counts k_lc2 found and k_cnt2 does not run)"""
     L = ya.lib()
     env = dict(env)
     big = env.pop("big", None)                                 # ~390 keys per sub-bucket (one sub-bucket per sub-table): more than the small LDS table of k_cnt2 takes
@@ -163,27 +175,29 @@ def test_second_pass_counts_the_records_the_first_pass_retained(opt, env, ya, or
         pytest.skip("one size is enough")
     for k_, v in env.items():
         knob(k_, v)
-    img = synth(40000, g=400000, s=23) if big else synth(9000, g=40000, s=19)
+    img = synth(30000, g=400000, s=23) if big else synth(9000, g=40000, s=19)      # big: below 2^12 records per sub-table, or the level-2 records take 16 bytes and are not kept
     want, wtot = oracle.count_protocol_mem(img, **opt)
     d = L.yakamd_dev_alloc(len(img) + 64)
     assert L.yakamd_memcpy_h2d(d, img, len(img)) == 0
     t = ya.Table(opt["k"], 10, opt.get("n_hash", 4), opt["bf_shift"])
-    assert L.yakamd_retain_input(t.h, 1) == 0
-    t.count_pass(1, [(d, len(img), 0)])
-    kept = L.yakamd_retained_instances(t.h)
-    assert (kept > 0) == (env.get("YAKAMD_RETAIN_GB") != "0")
-    t.destroy_bf(); t.clear()
-    assert L.yakamd_pass_begin(t.h, 0) == 0
-    r = L.yakamd_count_retained(t.h)
-    assert r == (0 if kept and "YAKAMD_COUNT_OWN" not in env else 1)
-    if r:
-        assert L.yakamd_feed_bases_dev(t.h, d, len(img), 0) == 0
-    n_ins = L.yakamd_pass_end(t.h)
-    assert n_ins == 0 and L.yakamd_retained_instances(t.h) == 0
-    t.shrink(2, 1023)
-    assert t.dump_bytes() == want and t.tot == wtot
+    with paths_util.tally(L) as ran:
+        assert L.yakamd_retain_input(t.h, 1) == 0
+        t.count_pass(1, [(d, len(img), 0)])
+        kept = L.yakamd_retained_instances(t.h)
+        assert (kept > 0) == (env.get("YAKAMD_RETAIN_GB") != "0")
+        t.destroy_bf(); t.clear()
+        assert L.yakamd_pass_begin(t.h, 0) == 0
+        r = L.yakamd_count_retained(t.h)
+        assert r == (0 if kept and "YAKAMD_COUNT_OWN" not in env else 1)
+        if r:
+            assert L.yakamd_feed_bases_dev(t.h, d, len(img), 0) == 0
+        n_ins = L.yakamd_pass_end(t.h)
+        assert n_ins == 0 and L.yakamd_retained_instances(t.h) == 0
+        t.shrink(2, 1023)
+        assert t.dump_bytes() == want and t.tot == wtot
     t.close()
     L.yakamd_dev_free(d)
+    _hold(ya, ran, paths_util.SECOND_PASS_RETAINED, request)
 
 
 def test_yak_count_reuses_the_first_pass_when_the_second_names_the_same_file(ya, oracle, tmp_path):
@@ -312,14 +326,14 @@ def test_prefix_sharded_path_on_one_gpu(bf, ya, oracle, synth):
                                  dict(YAKAMD_COUNT_OWN="0", YAKAMD_COUNT_LDS="0", YAKAMD_RNG_LOG="5", YAKAMD_XLIST_CAP="0"),
                                  dict(YAKAMD_COUNT_OWN="0", YAKAMD_COUNT_LDS="0", YAKAMD_RNG_LOG="6", YAKAMD_XLIST_CAP="7"),
                                  dict(YAKAMD_COUNT_OWN="0", YAKAMD_COUNT_LDS="0", YAKAMD_COUNT_RNG="0"), dict(YAKAMD_COUNT_OWN="0"),
-                                 dict(YAKAMD_OWN_LDS="18500", YAKAMD_OWN_MAXRB="12"), dict(YAKAMD_OWN_LDS="18500", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="0"),
+                                 dict(YAKAMD_OWN_LDS="18700", YAKAMD_OWN_MAXRB="12"), dict(YAKAMD_OWN_LDS="18700", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="0"),
                                  dict(YAKAMD_OWN_LDS="19500", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="5"), dict(YAKAMD_LC2="0"), dict(YAKAMD_LC2="0", YAKAMD_S2_BITS="4"),
-                                 dict(YAKAMD_LC2_WGS="3"), dict(YAKAMD_YTAG="0"), dict(YAKAMD_YTAG="0", YAKAMD_OWN_LDS="18500", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="5"), dict(YAKAMD_R2_SMALL_F="16"), dict(YAKAMD_R2_SMALL_F="1024"),
-                                 dict(YAKAMD_REC8="0"), dict(YAKAMD_REC8_OUT="0"), dict(YAKAMD_REC8_OUT="0", YAKAMD_BATCH="16384"), dict(YAKAMD_BATCH="8192", YAKAMD_S2_BITS="3"),
+                                 dict(YAKAMD_LC2_WGS="3"), dict(YAKAMD_YTAG="0"), dict(YAKAMD_YTAG="0", YAKAMD_OWN_LDS="18700", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="5"), dict(YAKAMD_R2_SMALL_F="16", YAKAMD_R2_SMALL_BITS="5"), dict(YAKAMD_R2_SMALL_F="1024", YAKAMD_R2_SMALL_BITS="5"),
+                                 dict(YAKAMD_REC8="0"), dict(YAKAMD_REC8_OUT="0", YAKAMD_S2_BITS="6"), dict(YAKAMD_REC8_OUT="0", YAKAMD_BATCH="16384"), dict(YAKAMD_BATCH="8192", YAKAMD_S2_BITS="3"),
                                  dict(YAKAMD_R2_SMALL_BITS="5"), dict(YAKAMD_R2_SMALL_BITS="5", YAKAMD_R2_SEG_LOG="10"), dict(YAKAMD_R2_SMALL_BITS="7", YAKAMD_R2_SEG_LOG="11"), dict(YAKAMD_REPLAY2="0"),
                                  dict(YAKAMD_R2_SMALL_BITS="5", YAKAMD_R2_SEG_LOG="10", YAKAMD_R2_PPART_G="3"), dict(YAKAMD_R2_SMALL_BITS="6", YAKAMD_R2_SEG_LOG="10", YAKAMD_R2_PPART_G="16", YAKAMD_R2_DBL="64"),
                                  dict(YAKAMD_FAST_BUDGET="3000000", YAKAMD_BATCH="65536"), dict(YAKAMD_FAST_BUDGET="1100000", YAKAMD_BATCH="65536"),
-                                 dict(YAKAMD_FAST_BUDGET="40000000", YAKAMD_BATCH="1048576"),
+                                 dict(YAKAMD_FAST_BUDGET="30000000", YAKAMD_BATCH="1048576"),
                                  dict(YAKAMD_S2_BITS="0", YAKAMD_OVF_SCRATCH_WORDS="200000"), dict(YAKAMD_SLICE_SB="1", YAKAMD_BATCH="65536"),
                                  dict(YAKAMD_S2_BITS="8", YAKAMD_P3_MIN="3", YAKAMD_P3_LOW="4"), dict(YAKAMD_S2_BITS="9", YAKAMD_P3_MIN="5", YAKAMD_P3_LOW="3", YAKAMD_BATCH="65536"),
                                  dict(YAKAMD_S2_BITS="8", YAKAMD_P3_MIN="3", YAKAMD_P3_LOW="4", YAKAMD_REC8_OUT="0"), dict(YAKAMD_S2_BITS="8", YAKAMD_P3_MIN="3", YAKAMD_REC8="0"),
@@ -327,7 +341,9 @@ def test_prefix_sharded_path_on_one_gpu(bf, ya, oracle, synth):
                                  dict(YAKAMD_TSORT="0"), dict(YAKAMD_TSORT="1"), dict(YAKAMD_TSORT="1", YAKAMD_TS_BITS="0"), dict(YAKAMD_TSORT="1", YAKAMD_TS_BITS="3", YAKAMD_LC_FLAT="1"), dict(YAKAMD_TSORT="1", YAKAMD_TS_BITS="6", YAKAMD_BATCH="65536"), dict(YAKAMD_TSORT="1", YAKAMD_TS_BITS="12", YAKAMD_CH2="4096"),
                                  dict(YAKAMD_TSORT="1", YAKAMD_TS_BITS="6", YAKAMD_TS_JOIN="3"), dict(YAKAMD_TSORT="1", YAKAMD_TS_BITS="4", YAKAMD_TS_JOIN="2", YAKAMD_TS_CAP="100"), dict(YAKAMD_TSORT="1", YAKAMD_TS_BITS="0", YAKAMD_TS_CAP="64"),
                                  dict(YAKAMD_POOL_FILL="166"), dict(YAKAMD_POOL_FILL="1", YAKAMD_POOL_VM="0"), dict(YAKAMD_POOL_VM_MIN="1048576", YAKAMD_POOL_FILL="166"), dict(YAKAMD_POOL_VM_MIN="4194304", YAKAMD_FAST_BUDGET="3000000", YAKAMD_BATCH="65536"),
-                                 dict(YAKAMD_POOL_VM_MIN="1048576", YAKAMD_POOL_VM_ROOMY="0", YAKAMD_POOL_FILL="90"), dict(YAKAMD_POOL_VM_MIN="2097152", YAKAMD_POOL_VM_ROOMY="0", YAKAMD_FAST_BUDGET="3000000", YAKAMD_BATCH="65536")],
+                                 dict(YAKAMD_POOL_VM_MIN="1048576", YAKAMD_POOL_VM_ROOMY="0", YAKAMD_POOL_FILL="90"), dict(YAKAMD_POOL_VM_MIN="2097152", YAKAMD_POOL_VM_ROOMY="0", YAKAMD_FAST_BUDGET="3000000", YAKAMD_BATCH="65536"),
+                                 dict(YAKAMD_P2_CAP7="0", YAKAMD_S2_BITS="6"), dict(YAKAMD_R2_SMALL_BITS="5", YAKAMD_R2_DBL="52"), dict(YAKAMD_R2_SMALL_BITS="5", YAKAMD_R2_DBL="61"),
+                                 dict(YAKAMD_LC2_CAPB="10", YAKAMD_FAST_BUDGET="3000000", YAKAMD_BATCH="65536"), dict(YAKAMD_LC2_CAPB="10", YAKAMD_REC8_OUT="0", YAKAMD_FAST_BUDGET="3000000", YAKAMD_BATCH="65536")],
                          ids=["general_path", "lds_overflow_to_global", "budget_exceeded_midpass", "s2_3_multibatch", "part6_general",
                               "write_combined_level2", "write_combined_level2_wide", "write_combined_level2_segments", "plain_scatters",
                               "range_count_whole_table", "range_count_split", "range_count_cross_sweep", "range_count_short_list",
@@ -343,21 +359,37 @@ def test_prefix_sharded_path_on_one_gpu(bf, ya, oracle, synth):
                               "sort_stable_radix_passes", "sort_bitmap_ranks", "sort_one_bin_per_sub_table", "sort_8_bins_plain_scatter", "sort_64_bins_multibatch", "sort_4096_bins_in_segments",
                               "sort_bins_joined_by_8", "sort_joined_bins_beyond_the_stage", "sort_one_bin_in_windows",
                               "every_buffer_prefilled_with_0xa5", "every_buffer_zeroed_superblocks_only", "mapped_ranges_from_1_mib_prefilled", "mapped_ranges_from_4_mib_pass_in_slices",
-                              "mapped_ranges_taken_apart_prefilled", "mapped_ranges_taken_apart_pass_in_slices"])
-def test_every_insert_path_is_exact(env, ya, oracle, synth, monkeypatch, knob):
+                              "mapped_ranges_taken_apart_prefilled", "mapped_ranges_taken_apart_pass_in_slices",
+                              "level2_8_entry_stacks", "doubling_5_waves_2_walks", "doubling_6_waves_1_walk", "lc2_1024_slot_table_in_slices", "lc2_1024_slot_table_in_slices_rec16_out"])
+def test_every_insert_path_is_exact(env, ya, oracle, synth, monkeypatch, knob, request):
     """the exclusive-ownership LDS path, its global-scratch overflow variant, the accumulator path
-    and the mid-pass switch between them all give the reference bytes"""
-    img = synth(20000, g=90000, s=21)
+    and the mid-pass switch between them all give the reference bytes, and each case ran the path its id names (paths_util.EVERY_INSERT_PATH)"""
+    case = request.node.callspec.id
+    img = synth(20000, g=2000000 if case in paths_util.THIN_INPUT else 90000, s=21)
     for k, v in env.items():
         knob(k, v)
-    for opt in (dict(k=31), dict(k=31, bf_shift=22), dict(k=31, bf_shift=28), dict(k=21, bf_shift=20)):
-        got, tot = ya.count_protocol_host(img, **opt)
-        want, wtot = oracle.count_protocol_mem(img, **opt)
-        assert (got == want, tot) == (True, wtot), opt
+    with paths_util.tally(ya.lib()) as ran:
+        for opt in (dict(k=31), dict(k=31, bf_shift=22), dict(k=31, bf_shift=28), dict(k=21, bf_shift=20)):
+            got, tot = ya.count_protocol_host(img, **opt)
+            want, wtot = oracle.count_protocol_mem(img, **opt)
+            assert (got == want, tot) == (True, wtot), opt
+            if opt == dict(k=31) and "YAKAMD_TS_CAP" in env and int(env.get("YAKAMD_TS_BITS", -1)) == 0:
+                # one bin per sub-table, and the unfiltered table's keys are the new keys of the pass: a sub-table with more keys than the ranking
+                # kernel's stage holds goes through its window loop (a branch inside k_ts_rank, which no launch shows)
+                assert max(_sub_table_sizes(want)) > int(env["YAKAMD_TS_CAP"])
+    _hold(ya, ran, paths_util.EVERY_INSERT_PATH, request)
+
+
+def _sub_table_sizes(yak_bytes, pre=10):
+    out, off = [], 16
+    for _ in range(1 << pre):
+        _, n = struct.unpack_from("<II", yak_bytes, off)
+        out.append(n); off += 8 + 8 * n
+    return out
 
 
 @pytest.mark.parametrize("env", [dict(), dict(YAKAMD_S2_BITS="5"), dict(YAKAMD_S2_BITS="8", YAKAMD_BATCH="65536")], ids=["auto", "s2_5", "s2_8_multibatch"])
-def test_low_complexity_bursts(env, ya, oracle, synth, monkeypatch, knob):
+def test_low_complexity_bursts(env, ya, oracle, synth, monkeypatch, knob, request):
     """homopolymer and short-period reads put thousands of consecutive k-mers into ONE partition
     bucket: the write-combining stacks overflow and the single-record path at the end of each run
     is taken; mixed with ordinary reads so the aligned groups and the singles share runs"""
@@ -370,25 +402,27 @@ def test_low_complexity_bursts(env, ya, oracle, synth, monkeypatch, knob):
     mixed = img[:len(img) // 2] + b"N" + b"N".join(parts) + b"N" + img[len(img) // 2:] + b"N" + b"N".join(parts[:50])
     for k, v in env.items():
         knob(k, v)
-    for opt in (dict(k=31), dict(k=31, bf_shift=28), dict(k=15, bf_shift=27), dict(k=33)):
-        got, tot = ya.count_protocol_host(mixed, **opt)
-        want, wtot = oracle.count_protocol_mem(mixed, **opt)
-        assert (got == want, tot) == (True, wtot), opt
+    with paths_util.tally(ya.lib()) as ran:
+        for opt in (dict(k=31), dict(k=31, bf_shift=28), dict(k=15, bf_shift=27), dict(k=33)):
+            got, tot = ya.count_protocol_host(mixed, **opt)
+            want, wtot = oracle.count_protocol_mem(mixed, **opt)
+            assert (got == want, tot) == (True, wtot), opt
+    _hold(ya, ran, paths_util.LOW_COMPLEXITY, request)
 
 
 @pytest.mark.parametrize("env", [dict(), dict(YAKAMD_REPLAY_LDS="0"), dict(YAKAMD_REPLAY_LDS="8192"), dict(YAKAMD_REPLAY_LDS="8192", YAKAMD_PAR_REPLAY="0"),
                                  dict(YAKAMD_COUNT_OWN="0", YAKAMD_COUNT_LDS="0", YAKAMD_RNG_LOG="10"), dict(YAKAMD_COUNT_OWN="0", YAKAMD_COUNT_LDS="0", YAKAMD_RNG_LOG="7", YAKAMD_XLIST_CAP="100"),
                                  dict(YAKAMD_R2_SMALL_BITS="10", YAKAMD_R2_SEG_LOG="11"), dict(YAKAMD_R2_SMALL_BITS="9", YAKAMD_R2_SEG_LOG="10"), dict(YAKAMD_REPLAY2="0"),
                                  dict(YAKAMD_R2_SMALL_BITS="9", YAKAMD_R2_SEG_LOG="10", YAKAMD_R2_PPART_G="4"), dict(YAKAMD_R2_SMALL_BITS="8", YAKAMD_R2_SEG_LOG="11", YAKAMD_R2_DBL="62"), dict(YAKAMD_R2_SMALL_BITS="8", YAKAMD_R2_SEG_LOG="11", YAKAMD_R2_DBL="54"),
-                                 dict(YAKAMD_OWN_LDS="30000", YAKAMD_OWN_MAXRB="12"), dict(YAKAMD_OWN_LDS="21000", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="64"), dict(YAKAMD_OWN_LDS="21000", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="64", YAKAMD_YTAG="0"), dict(YAKAMD_R2_SMALL_F="32"), dict(YAKAMD_REPLAY_LDS="32768"),
+                                 dict(YAKAMD_OWN_LDS="30000", YAKAMD_OWN_MAXRB="12"), dict(YAKAMD_OWN_LDS="21000", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="64"), dict(YAKAMD_OWN_LDS="21000", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="64", YAKAMD_YTAG="0"), dict(YAKAMD_R2_SMALL_F="32", YAKAMD_R2_SMALL_BITS="10"), dict(YAKAMD_REPLAY_LDS="32768"),
                                  dict(YAKAMD_REPLAY_LDS="2048"), dict(YAKAMD_REPLAY_LDS="1024", YAKAMD_REPLAY_THREADS="256"), dict(YAKAMD_REPLAY_LDS="2048", YAKAMD_DBG="256")],
                          ids=["lds_ranks", "global_ranks", "lds_16bit_ranks", "serial_doubling", "pass2_by_slot_ranges", "pass2_ranges_list_overflow",
                               "streaming_replay_2k_slot_segments", "streaming_replay_from_512_slots_1k_slot_segments", "k_replay_for_16k_slots",
                               "streaming_replay_keys_grouped_by_4_workgroups", "doubling_6_waves_2_walks", "doubling_5_waves_4_walks",
                               "pass2_key_owning_ranges", "pass2_key_owning_ranges_list_overflow", "pass2_key_owning_ranges_plain_hashes", "replay_prefix_32", "lds_keys_for_small_stages",
                               "segmented_lds_ranks", "segmented_lds_ranks_small", "global_ranks_for_large_stages"])
-def test_replay_variants_on_large_subtables(env, ya, oracle, synth, monkeypatch, knob):
-    """~7 M distinct k-mers (1x coverage): every sub-table grows to 16 Ki slots, so the layout replay
+def test_replay_variants_on_large_subtables(env, ya, oracle, synth, monkeypatch, knob, request):
+    """~6 M distinct k-mers (1x coverage): every sub-table grows to 8 Ki slots, so the layout replay
     goes through LDS-resident keys, 32- and 16-bit LDS owner ranks, global ranks, and the parallel
     doubling with its LDS base phase -- each variant must give the reference bytes"""
     img = synth(50000, g=8_000_000, s=77, e=0.0, N=0.0)
@@ -396,15 +430,102 @@ def test_replay_variants_on_large_subtables(env, ya, oracle, synth, monkeypatch,
         knob(k, v)
     dbg0 = (C.c_uint32 * 4)(); dbg1 = (C.c_uint32 * 4)()
     ya.lib().yakamd_debug_counters(dbg0)
-    for opt in (dict(k=31), dict(k=27, bf_shift=30)):
-        got, tot = ya.count_protocol_host(img, **opt)
-        want, wtot = oracle.count_protocol_mem(img, **opt)
-        assert (got == want, tot) == (True, wtot), opt
+    with paths_util.tally(ya.lib()) as ran:
+        for opt in (dict(k=31), dict(k=27, bf_shift=30)):
+            got, tot = ya.count_protocol_host(img, **opt)
+            want, wtot = oracle.count_protocol_mem(img, **opt)
+            assert (got == want, tot) == (True, wtot), opt
     ya.lib().yakamd_debug_counters(dbg1)
     if env.get("YAKAMD_REPLAY2") == "0":
         assert dbg1[2] == dbg0[2]
     elif "YAKAMD_R2_SMALL_BITS" in env:                       # 8 Ki-slot sub-tables: the streaming replay did them, and never handed one back
         assert dbg1[2] > dbg0[2] and dbg1[3] == dbg0[3], list(dbg1)
+    _hold(ya, ran, paths_util.REPLAY_VARIANTS, request)
+
+
+@pytest.mark.parametrize("env", [dict(YAKAMD_COUNT_OWN="0", YAKAMD_COUNT_LDS="0"), dict(YAKAMD_COUNT_OWN="0"), dict(YAKAMD_OWN_LDS="18700", YAKAMD_OWN_MAXRB="12"),
+                                 dict(YAKAMD_OWN_LDS="18700", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="0")],
+                         ids=["device_atomics", "lds_rank_kernel", "key_owning_ranges", "key_owning_ranges_cross_sweep"])
+def test_count_pass_over_hashed_records(env, ya, oracle, synth, knob, request):
+    """a count pass fed with {hash, position} records (yakamd_feed_hashed_dev: what an owner of a prefix-sharded job receives) goes through the
+    16-byte-record instances of the count kernels, which the passes over base images (8-byte hashes) never launch"""
+    L = ya.lib()
+    for k_, v in env.items():
+        knob(k_, v)
+    img = synth(20000, g=2000000, s=21)
+    nb = len(img)
+    d, xh, xt = L.yakamd_dev_alloc(nb + 64), L.yakamd_dev_alloc(nb * 8), L.yakamd_dev_alloc(nb * 4)
+    assert d and xh and xt and L.yakamd_memcpy_h2d(d, img, nb) == 0
+    t = ya.Table(31, 10, 4, 22)
+    try:
+        with paths_util.tally(L) as ran:
+            for create_new in (1, 0):
+                assert L.yakamd_pass_begin(t.h, create_new) == 0
+                n = L.yakamd_extract_dev(31, d, nb, xh, xt, 10, 0, 1024, None)
+                assert n > 0 and L.yakamd_feed_hashed_dev(t.h, xh, xt, n, 0, nb) == 0
+                n_ins = L.yakamd_pass_end(t.h)
+                assert n_ins >= 0
+                t.h.contents.tot += n_ins
+                if create_new:
+                    t.destroy_bf(); t.clear()
+            t.shrink(2, 1023)
+        assert (t.dump_bytes(), t.tot) == oracle.count_protocol_mem(img, k=31, bf_shift=22)
+    finally:
+        t.close()
+        for p in (d, xh, xt):
+            L.yakamd_dev_free(p)
+    _hold(ya, ran, paths_util.HASHED_RECORDS, request)
+
+
+def _kmers_of_sub_tables(lo, hi, per_sub, k=31, pre=10, seed=7):
+    """an image of one canonical k-mer per record, per_sub distinct ones for each of the sub-tables [lo, hi): hashes with the sub-table's number in
+    their low bits, turned back into k-mers (yak-priv.h's hash64_inv); the ones that are not their own canonical form would be counted as their
+    reverse complement, somewhere else, and are left out"""
+    import random
+    import numpy as np
+    from tablecmds_util import hash64_inv
+    rnd, mask = random.Random(seed), (1 << 2 * k) - 1
+    recs = []
+    for p in range(lo, hi):
+        xs = np.array([hash64_inv(h << pre | p, mask) for h in rnd.sample(range(1 << (2 * k - pre)), 3 * per_sub)], dtype=np.uint64)
+        rc = np.zeros_like(xs)
+        for j in range(k):
+            rc |= (np.uint64(3) - (xs >> np.uint64(2 * j) & np.uint64(3))) << np.uint64(2 * (k - 1 - j))
+        xs = xs[xs < rc][:per_sub]
+        assert len(xs) == per_sub
+        seq = np.empty((per_sub, k + 1), dtype=np.uint8)
+        for j in range(k):
+            seq[:, j] = np.frombuffer(b"ACGT", dtype=np.uint8)[(xs >> np.uint64(2 * (k - 1 - j)) & np.uint64(3)).astype(np.int64)]
+        seq[:, k] = ord("\n")
+        recs.append(seq)
+    out = np.concatenate(recs)
+    np.random.RandomState(seed).shuffle(out)
+    return out.tobytes()
+
+
+def test_seg_sort_pass_of_long_segments(ya, oracle, knob):
+    """the stable radix passes with 1024 threads per sub-table (k_seg_sort_pass<8, 1024>) take over from 30 000 new keys per active sub-table
+    (slice_sort: sort_big).  A whole-table input of that size would be tens of millions of k-mers; a shard of two sub-tables fed with k-mers that
+    hash into them is 2 x 33 000.  The shard's bytes are the oracle's for those sub-tables"""
+    import hashlib
+    lo, hi, per = 500, 502, 33000
+    img = _kmers_of_sub_tables(lo, hi, per)
+    want, _ = oracle.count_protocol_mem(img, k=31)
+    sizes = _sub_table_sizes(want)
+    assert sizes[lo:hi] == [per] * (hi - lo) and sum(sizes) == per * (hi - lo)        # every k-mer landed where it was meant to, once
+    off = 16 + sum(8 + 8 * n for n in sizes[:lo])
+    want_range = want[off:off + sum(8 + 8 * n for n in sizes[lo:hi])]
+    knob("YAKAMD_TSORT", 0)
+    t = ya.Table(31, 10, 4, 0)
+    try:
+        assert ya.lib().yakamd_set_shard(t.h, lo, hi) == 0
+        with paths_util.tally(ya.lib()) as ran:
+            t.count_pass_host(1, img)
+        md5, n = t.range_md5(lo, hi)
+        assert (n, md5) == (len(want_range), hashlib.md5(want_range).hexdigest())
+    finally:
+        t.close()
+    paths_util.hold(ran, paths_util.LONG_SEGMENTS[""], paths_util.names(ya.lib()), "long segments")
 
 
 @pytest.mark.parametrize("seed", range(32))

@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+import paths_util
 from conftest import ROOT
 
 pytestmark = pytest.mark.gpu
@@ -38,9 +39,25 @@ def _keys_of(oracle, o, pre=10):
     return out
 
 
-def _protocol(ya, oracle, img, opt, img2=None, between=None):
+def _hold(ya, ran, table, request=None):
+    """the launch tally of a _protocol run against the entry of the case (tests/paths_util.py)"""
+    case = [p for p in request.node.callspec.id.split("-") if p in table] if request is not None else [""]
+    assert len(case) == 1
+    paths_util.hold(ran, table[case[0]], paths_util.names(ya.lib()), case[0])
+
+
+def _protocol(ya, oracle, img, opt, img2=None, between=None, ran=None):
     """both passes on the device (the first one retaining its records) and in the oracle; `between(inc, shrink)` runs between the passes on
-    both tables.  -> (device bytes, device tot, oracle bytes, oracle tot, stats of the device's count pass)"""
+    both tables.  -> (device bytes, device tot, oracle bytes, oracle tot, stats of the device's count pass); ran: a dict that takes the launch
+    tally of the device's part"""
+    with paths_util.tally(ya.lib()) as got:
+        out = _protocol_body(ya, oracle, img, opt, img2, between)
+    if ran is not None:
+        ran.update(got)
+    return out
+
+
+def _protocol_body(ya, oracle, img, opt, img2, between):
     L, O = ya.lib(), oracle.lib()
     O.yko_ch_inc.restype = C.c_int; O.yko_ch_inc.argtypes = [C.POINTER(oracle.Ch), C.c_uint64]
     k, nh, bf = opt["k"], opt.get("n_hash", 4), opt["bf_shift"]
@@ -92,24 +109,28 @@ OPTS = [dict(k=31, bf_shift=24), dict(k=21, bf_shift=20), dict(k=31, bf_shift=22
 @pytest.mark.parametrize("fused", [1, 0], ids=["fused", "recount"])
 @pytest.mark.parametrize("opt", OPTS, ids=["k31b24", "k21b20", "k31b22H7"])
 @pytest.mark.parametrize("inp", sorted(INPUTS))
-def test_count_pass_from_the_first_pass_counts(inp, opt, fused, ya, oracle, synth, knob):
+def test_count_pass_from_the_first_pass_counts(inp, opt, fused, ya, oracle, synth, knob, request):
     knob("YAKAMD_CNT2_FUSED", fused)
-    got, tot, want, wtot, st = _protocol(ya, oracle, INPUTS[inp](synth), opt)
+    ran = {}
+    got, tot, want, wtot, st = _protocol(ya, oracle, INPUTS[inp](synth), opt, ran=ran)
     assert st["pass2_path"] == (FUSED if fused else RECOUNT)
     assert (got, tot) == (want, wtot)
+    _hold(ya, ran, paths_util.COUNT_PASS_FROM_FIRST, request)
 
 
 @pytest.mark.parametrize("env", [dict(YAKAMD_LC_FLAT="1"), dict(YAKAMD_LC_FLAT="0"), dict(YAKAMD_TSORT="1"), dict(YAKAMD_LC2="0"),
                                  dict(YAKAMD_LC2_NOSTAGE="0"), dict(YAKAMD_BF_DEFER="0")],
                          ids=["flat_gather", "compact_gather", "gather_to_pairs", "all_sub_buckets_to_the_scratch_tier", "filter_stage", "filter_written"])
-def test_fused_counts_on_every_gather_and_tier(env, ya, oracle, synth, knob):
+def test_fused_counts_on_every_gather_and_tier(env, ya, oracle, synth, knob, request):
     """the flat gather (k_lc_gather) and the per-sub-table one (k_lc_compact), into arrays or into {key, time} pairs for the sort, carry the
     counts in the order of the key list; the global-scratch tier (lc_body) emits them as k_lc2 does"""
     for k_, v in env.items():
         knob(k_, v)
-    got, tot, want, wtot, st = _protocol(ya, oracle, _repeats(synth), dict(k=31, bf_shift=24))
+    ran = {}
+    got, tot, want, wtot, st = _protocol(ya, oracle, _repeats(synth), dict(k=31, bf_shift=24), ran=ran)
     assert st["pass2_path"] == FUSED
     assert (got, tot) == (want, wtot)
+    _hold(ya, ran, paths_util.FUSED_GATHER_AND_TIER, request)
 
 
 def test_sub_buckets_k_lc2_passes_on(ya, oracle, synth, knob, capfd):
@@ -117,16 +138,19 @@ def test_sub_buckets_k_lc2_passes_on(ya, oracle, synth, knob, capfd):
     to the tier behind it, which counts them as well, in the same pass as the sub-buckets k_lc2 keeps"""
     knob("YAKAMD_VERBOSE", 1)
     img = synth(20000, g=20000000, s=3) + synth(9000, g=40000, s=19, first=50000)
-    got, tot, want, wtot, st = _protocol(ya, oracle, img, dict(k=31, bf_shift=24))
+    ran = {}
+    got, tot, want, wtot, st = _protocol(ya, oracle, img, dict(k=31, bf_shift=24), ran=ran)
     err = capfd.readouterr().err
     m = re.search(r"k_lc2: [0-9.]+ ms, (\d+) of (\d+) sub-buckets passed on", err)
     assert m and int(m.group(1)) > 0, err[-2000:]
     assert st["pass2_path"] == FUSED
     assert (got, tot) == (want, wtot)
+    assert ran.get("event:lc2_passed_on", 0) == int(m.group(1))      # the event counts what the line reports
+    _hold(ya, ran, paths_util.SUB_BUCKETS_PASSED_ON)
 
 
 @pytest.mark.parametrize("fused", [1, 0], ids=["fused", "recount"])
-def test_inc_and_shrink_between_the_passes(fused, ya, oracle, synth, knob):
+def test_inc_and_shrink_between_the_passes(fused, ya, oracle, synth, knob, request):
     """counts set between the passes (yak_ch_inc) stay under the count pass's saturating add; keys a shrink removed are not found by it"""
     knob("YAKAMD_CNT2_FUSED", fused)
 
@@ -136,9 +160,11 @@ def test_inc_and_shrink_between_the_passes(fused, ya, oracle, synth, knob):
         for _ in range(40):
             inc(keys[3])
         shrink(1, 1023)
-    got, tot, want, wtot, st = _protocol(ya, oracle, _repeats(synth), dict(k=31, bf_shift=24), between=between)
+    ran = {}
+    got, tot, want, wtot, st = _protocol(ya, oracle, _repeats(synth), dict(k=31, bf_shift=24), between=between, ran=ran)
     assert st["pass2_path"] == (FUSED if fused else RECOUNT)
     assert (got, tot) == (want, wtot)
+    _hold(ya, ran, paths_util.INC_AND_SHRINK, request)
 
 
 def test_count_pass_over_another_input_reads_it(ya, oracle, synth):

@@ -31,7 +31,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_memcpy_d2h", "yakamd_partition_dev", "yakamd_feed_partitioned_dev", "yakamd_debug_counters", "yakamd_count_hashes_dev",
     "yakamd_partition_hashes_dev", "yakamd_count_partitioned_dev", "yakamd_feed_partitioned_lent_dev",
     "yakamd_tagged_ok", "yakamd_pass_fast", "yakamd_partition_tagged_dev", "yakamd_feed_partitioned_tagged_dev",
-    "yakamd_lookup_dev", "yakamd_qv_reduce_dev", "yakamd_host_image", "yakamd_host_image_packed", "yakamd_gz_tune", "yakamd_gz_inflate", "yakamd_test_set", "yakamd_test_reset",
+    "yakamd_lookup_dev", "yakamd_qv_reduce_dev", "yakamd_host_image", "yakamd_host_image_packed", "yakamd_gz_tune", "yakamd_gz_inflate", "yakamd_test_set", "yakamd_test_reset", "yakamd_tally_names", "yakamd_tally_read", "yakamd_tally_reset",
     "yakamd_retain_input", "yakamd_count_retained", "yakamd_retained_instances", "yakamd_count_multi_dev",
     "yakamd_host_alloc", "yakamd_host_free", "yakamd_device_sync", "yakamd_mem_info", "yakamd_last_sweeps", "yakamd_pool_report",
     "yakamd_triobin_lookup_dev", "yakamd_triobin_reduce_dev", "yakamd_tbopt_init", "yakamd_triobin",
@@ -244,6 +244,12 @@ def lib():
     L.yakamd_test_set.argtypes = [C.c_char_p, C.c_int64]
     L.yakamd_test_reset.restype = None
     L.yakamd_test_reset.argtypes = []
+    L.yakamd_tally_names.restype = C.c_int
+    L.yakamd_tally_names.argtypes = [P(P(C.c_char_p))]
+    L.yakamd_tally_read.restype = None
+    L.yakamd_tally_read.argtypes = [P(C.c_uint64), C.c_int]
+    L.yakamd_tally_reset.restype = None
+    L.yakamd_tally_reset.argtypes = []
     L.yakamd_gz_tune.restype = None
     L.yakamd_gz_tune.argtypes = [C.c_int64, C.c_int64, C.c_int64]
     L.yakamd_gz_inflate.restype = C.c_int64

@@ -468,6 +468,7 @@ static int count_by_ranges(yakamd_ctx *c, int64_t n_rec, const u64 *d_bstart)
 	if (!r) {
 		HIPCK(hipMemcpyAsync(xn, d_ln, 8, hipMemcpyDeviceToHost, c->st));
 		HIPCK(hipStreamSynchronize(c->st));
+		if (xn[1]) yk_event(YKE_RNG_SWEEPS);
 		if (xn[1]) yk_launch_img_count_rng(d_h2, 1, d_sbstart, img, c->plo, c->phi, rb, max_len, d_list, d_ln, list_cap, c->st);   /* list too small: second sweep */
 		else if (xn[0]) yk_launch_img_count_h(d_list, (int64_t)xn[0], img, c->st);
 		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] range count: 2^%d ranges per sub-table, %u boundary-crossing instances%s\n", rb, xn[0], xn[1] ? " (list overflow: second sweep)" : "");
@@ -522,6 +523,7 @@ static int count_own(yakamd_ctx *c, int64_t n_rec, const u64 *d_bstart, int hash
 	u32 xn[2] = { 0, 0 };
 	if (!r && (hipMemcpyAsync(xn, d_ln, 8, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) r = fail("key-owning count kernel failed: %s", hipGetErrorString(hipGetLastError()));
 	if (!r) {
+		if (xn[1]) yk_event(YKE_OWN_SWEEPS);
 		if (xn[1]) yk_launch_img_count_own(c->d_rec, hash_only, 1, ytag, d_bstart, img, c->plo, c->phi, rb, rng_log, kmax, lds, d_list, d_ln, list_cap, c->st);   /* list too small: second sweep */
 		else if (xn[0]) yk_launch_img_count_h(d_list, (int64_t)xn[0], img, c->st);
 		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] key-owning count: 2^%d slots per range (up to 2^%d ranges per sub-table), %u keys of LDS room, %zu B of LDS, %u boundary-crossing instances%s\n",
@@ -611,6 +613,7 @@ static int fast_abandon(yakamd_ctx *c)
 {
 	for (auto &k : c->kept) if (k.fmt) return fail("a batch was fed out of stream order after tagged 8-byte batches were kept: feed in order, or set YAKAMD_REC8=0");
 	c->fast = false;
+	yk_event(YKE_FAST_ABANDONED);
 	c->retain_broken = true; retained_drop(c);                 /* the pass leaves the path whose records can be kept */
 	Rec *keep = c->d_rec;
 	int r = 0;
@@ -628,7 +631,7 @@ static int fast_finish(yakamd_ctx *c, bool last = false);
 static int fast_flush_slice(yakamd_ctx *c)
 {
 	if (fast_finish(c)) return -1;
-	++c->n_slices;
+	++c->n_slices; yk_event(YKE_EARLY_SLICES);
 	HIPCK(hipMemsetAsync(c->d_lastput, 0, c->P * 8, c->st));      /* the put-calls of the slice are accounted for */
 	HIPCK(hipMemsetAsync(c->d_counters, 0, YKC_N * 8, c->st));
 	if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] slice of the pass counted early (budget / 2^32-position limit): %llu keys in the table\n", (unsigned long long)c->img_keys_total);
@@ -1016,7 +1019,7 @@ extern "C" int yakamd_count_retained(yak_ch_t *h)
 		const double ms = insert_ms(c, tm);
 		const bool bad = hipGetLastError() != hipSuccess;
 		c->st_cur.n_instances += (int64_t)c->ret2.n_total;
-		c->st_cur.pass2_path = 1;
+		c->st_cur.pass2_path = 1; yk_event(YKE_PASS2_FUSED);
 		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] count pass: the counts of the pass before applied (%llu keys, %.2f ms)\n", (unsigned long long)c->ret2.n_keys, ms);
 		retained_drop(c);
 		return bad ? fail("applying the counts of the pass before failed") : 0;
@@ -1034,15 +1037,15 @@ extern "C" int yakamd_count_retained(yak_ch_t *h)
 		dfree(d_kcnt);
 		const bool bad = hipGetLastError() != hipSuccess;
 		c->st_cur.n_instances += (int64_t)c->ret2.n_total;
-		c->st_cur.pass2_path = 2;
+		c->st_cur.pass2_path = 2; yk_event(YKE_PASS2_RECOUNT);
 		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] count pass: k_cnt2 over the retained sub-bucket records (%llu keys, %.2f ms)\n", (unsigned long long)c->ret2.n_keys, ms);
 		retained_drop(c);
 		return bad ? fail("the count over the retained sub-bucket records failed") : 0;
 	}
-	if (c->retained.empty() || c->retain_broken) { retained_drop(c); return 1; }
+	if (c->retained.empty() || c->retain_broken) { yk_event(YKE_PASS2_NONE); retained_drop(c); return 1; }
 	{
 		int rl, rb; u32 km;
-		if (count_own_plan(c, &rl, &rb, &km) != 0) { retained_drop(c); return 1; }   /* tables beyond the key-owning count kernel: the general count path wants plain hashes */
+		if (count_own_plan(c, &rl, &rb, &km) != 0) { yk_event(YKE_PASS2_NONE); retained_drop(c); return 1; }   /* tables beyond the key-owning count kernel: the general count path wants plain hashes */
 	}
 	const size_t NB = (size_t)1 << c->nb_bits;
 	if (part_reserve(c, 1)) return -1;
@@ -1057,7 +1060,7 @@ extern "C" int yakamd_count_retained(yak_ch_t *h)
 	}
 	c->d_rec = keep;
 	retained_drop(c);
-	if (!r) c->st_cur.pass2_path = 3;
+	if (!r) { c->st_cur.pass2_path = 3; yk_event(YKE_PASS2_PREFIX); }
 	return r ? -1 : 0;
 }
 
@@ -1191,8 +1194,9 @@ static int slice_plan(yakamd_ctx *c, Slice &s, bool last)
 	fp.rec8_in = s.fmt_in; fp.tb = YK_R8_TAG_BITS + s2;
 	fp.rec8_out = 0;                                         /* set below, once the largest sub-table stream is known */
 	if (c->bloom_mode) {
-		const bool lc2_runs = env_i64("YAKAMD_LC2", 1) != 0 && c->n_hash <= 32;   /* (with the block range below: yk_lc2_ok) -- the tier behind k_lc2 works on the filter in memory and needs real zeros */
-		if (c->bf_virgin && lc2_runs && c->nb - 9 - s2 <= (nowb_plan ? 8 : 7)) fp.bf_virgin = 1;   /* LDS-staged ranges: skip the read, write every block of the shard (yakamd_set_shard refuses to move the shard afterwards) */
+		FastParams probe = fp;                                    /* will k_lc2 run (yk_lc2_ok, asked again by slice_count)?  The tier behind it works on the filter in memory and needs real zeros */
+		probe.bf_nowb = nowb_plan;
+		if (c->bf_virgin && yk_lc2_ok(probe)) fp.bf_virgin = 1;   /* LDS-staged ranges: skip the read, write every block of the shard (yakamd_set_shard refuses to move the shard afterwards) */
 		else if (bloom_materialise(c)) return -1;
 		c->bf_virgin = false;
 	}
@@ -1350,6 +1354,7 @@ static int slice_count(yakamd_ctx *c, Slice &s)
 		h_cnt[YKC_NOVF2] = n_all;
 	}
 	if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] %s: %.2f ms, %llu of %zu sub-buckets passed on\n", lc2 ? "k_lc2" : "k_lc2 not run", c->ms_lds, (unsigned long long)h_cnt[YKC_NOVF2], n_sb);
+	yk_event(YKE_LC2_PASSED_ON, h_cnt[YKC_NOVF2]);
 	if (h_cnt[YKC_NOVF2]) {     /* the same algorithm on tables in global scratch */
 		const u32 n_ovf = (u32)h_cnt[YKC_NOVF2];
 		std::vector<u32> ovf(n_ovf);
@@ -1375,6 +1380,7 @@ static int slice_count(yakamd_ctx *c, Slice &s)
 			if (scr.alloc(words)) return -1;
 			HIPCK(hipMemcpyAsync(scroff + i0, off.data() + i0, (size_t)(i1 - i0) * 8, hipMemcpyHostToDevice, c->st));
 			EvTimer tm(c->st);
+			yk_event(YKE_OVF_GROUPS); if (i0) yk_event(YKE_OVF_MORE_GROUPS);
 			yk_launch_lds_count_ovf(fp, s.sbstart, lc_rec_in, c->d_bf, img_view(c), s.lo(), s.ovf2 + i0, i1 - i0, scroff + i0, scr, c->st);
 			c->st_cur.ms_insert += tm.stop();
 			HIPCK(hipStreamSynchronize(c->st));
@@ -1494,6 +1500,7 @@ static int slice_sort(yakamd_ctx *c, Slice &s)
 			HIPCK(hipStreamSynchronize(c->st));
 		}
 		sorted = h_fail == 0;
+		if (!sorted) yk_event(YKE_RANK_REFUSED);
 		if (!sorted) {                                            /* a time seen twice, or the kernel could not be configured: the stable passes on the gathered pairs */
 			if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] sort by bitmap ranks refused: stable radix passes instead\n");
 			yk_launch_kt_split(rank_in, n_sel, s.kc[0], s.tt[0], c->st);
@@ -1518,6 +1525,7 @@ static int slice_sort(yakamd_ctx *c, Slice &s)
 static int fast_finish(yakamd_ctx *c, bool last)
 {
 	Slice s;
+	yk_event(YKE_SLICES);
 	if (slice_plan(c, s, last) || slice_partition(c, s, last) || slice_count(c, s)) return -1;
 	s.lap(c, "insert (k_lc2 + tiers)");
 	if (s.keep2) { c->ret2.d_r2 = s.r2.release(); c->ret2.n_total = s.n_total; c->ret2.fp = s.fp; c->ret2.fp.bf_nowb = 0; }
@@ -1630,6 +1638,11 @@ extern "C" void yakamd_debug_counters(uint32_t *out4)
 {
 	out4[0] = out4[1] = 0;
 	yk_par_counters(&out4[0], &out4[1]);
+	{   /* the tally's events count what has been added since the call before */
+		static std::atomic<uint32_t> seen_ok{0}, seen_fail{0};
+		yk_event(YKE_PAR_OK, (uint32_t)(out4[0] - seen_ok.exchange(out4[0])));
+		yk_event(YKE_PAR_FAIL, (uint32_t)(out4[1] - seen_fail.exchange(out4[1])));
+	}
 	yk_replay_counters(&out4[2], &out4[3]);
 }
 

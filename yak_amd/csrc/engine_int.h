@@ -13,6 +13,7 @@
 #include <mutex>
 #include <algorithm>
 #include "yk_device.h"
+#include "tally.h"
 #include "engine.h"
 
 #define fail(...) yk_set_error(__VA_ARGS__)                  /* this thread's yakamd_last_error() text + a line on stderr; -1 */

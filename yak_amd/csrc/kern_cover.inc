@@ -246,7 +246,7 @@ void yk_launch_cover(CvArgs a, int mask, hipStream_t st)
 {
 	const int64_t nt = yk_te_tiles(a.n), nb = (nt + CV_ITERS - 1) / CV_ITERS;
 	if (nt <= 0) return;
-	if (mask == 0) hipLaunchKernelGGL((k_cover<0>), dim3((unsigned)nb), dim3(TE_THREADS), 0, st, a);
-	else if (mask == 1) hipLaunchKernelGGL((k_cover<1>), dim3((unsigned)nb), dim3(TE_THREADS), 0, st, a);
-	else hipLaunchKernelGGL((k_cover<2>), dim3((unsigned)nb), dim3(TE_THREADS), 0, st, a);
+	if (mask == 0) YK_LAUNCH((k_cover<0>), dim3((unsigned)nb), dim3(TE_THREADS), 0, st, a);
+	else if (mask == 1) YK_LAUNCH((k_cover<1>), dim3((unsigned)nb), dim3(TE_THREADS), 0, st, a);
+	else YK_LAUNCH((k_cover<2>), dim3((unsigned)nb), dim3(TE_THREADS), 0, st, a);
 }

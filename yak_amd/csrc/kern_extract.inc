@@ -640,11 +640,11 @@ void k_part_fin(u32 *rows, int n_blk, int NB, const u64 *partial, const u64 *bst
 static void launch_part_scan(u32 *rows, int n_blk, int nb_bits, u64 *partial, u64 *bstart, hipStream_t st, bool par = false)
 {
 	const int NB = 1 << nb_bits;
-	if (par) hipLaunchKernelGGL(k_part_sum<true>, dim3((NB + 255) / 256, PS_G), dim3(256), 0, st, rows, n_blk, NB, partial);
-	else hipLaunchKernelGGL(k_part_sum<false>, dim3((NB + 255) / 256, PS_G), dim3(256), 0, st, rows, n_blk, NB, partial);
-	hipLaunchKernelGGL(k_part_mid, dim3(1), dim3(256), 0, st, partial, NB, bstart);
-	if (par) hipLaunchKernelGGL(k_part_fin<true>, dim3((NB + 255) / 256, PS_G), dim3(256), 0, st, rows, n_blk, NB, partial, bstart);
-	else hipLaunchKernelGGL(k_part_fin<false>, dim3((NB + 255) / 256, PS_G), dim3(256), 0, st, rows, n_blk, NB, partial, bstart);
+	if (par) YK_LAUNCH(k_part_sum<true>, dim3((NB + 255) / 256, PS_G), dim3(256), 0, st, rows, n_blk, NB, partial);
+	else YK_LAUNCH(k_part_sum<false>, dim3((NB + 255) / 256, PS_G), dim3(256), 0, st, rows, n_blk, NB, partial);
+	YK_LAUNCH(k_part_mid, dim3(1), dim3(256), 0, st, partial, NB, bstart);
+	if (par) YK_LAUNCH(k_part_fin<true>, dim3((NB + 255) / 256, PS_G), dim3(256), 0, st, rows, n_blk, NB, partial, bstart);
+	else YK_LAUNCH(k_part_fin<false>, dim3((NB + 255) / 256, PS_G), dim3(256), 0, st, rows, n_blk, NB, partial, bstart);
 }
 
 /* ------------------------------------------------------------------------------------------
@@ -849,11 +849,11 @@ void yk_launch_lookup(const uint8_t *bases, int64_t n, int k, ImgView img, void 
 	const int tab = img.pre <= 12;
 	const size_t lds = tab ? (size_t)8 << img.pre : 0;
 	const dim3 grid(yk_xpart_blocks(n)), block(XT_THREADS);
-	if (width == 2) { hipLaunchKernelGGL((k_lookup<unsigned short, false>), grid, block, lds, st, bases, n, k, img, (unsigned short*)out, tab, 0); return; }
+	if (width == 2) { YK_LAUNCH((k_lookup<unsigned short, false>), grid, block, lds, st, bases, n, k, img, (unsigned short*)out, tab, 0); return; }
 	void *over = 0;
 	if (hipGetSymbolAddress(&over, HIP_SYMBOL(d_tb_over)) == hipSuccess) (void)hipMemsetAsync(over, 0, 4, st);
-	if (k < 32) hipLaunchKernelGGL((k_lookup<uint8_t, false>), grid, block, lds, st, bases, n, k, img, (uint8_t*)out, tab, 0);
-	else hipLaunchKernelGGL((k_lookup<uint8_t, true>), grid, block, lds, st, bases, n, k, img, (uint8_t*)out, tab, 0);
+	if (k < 32) YK_LAUNCH((k_lookup<uint8_t, false>), grid, block, lds, st, bases, n, k, img, (uint8_t*)out, tab, 0);
+	else YK_LAUNCH((k_lookup<uint8_t, true>), grid, block, lds, st, bases, n, k, img, (uint8_t*)out, tab, 0);
 }
 
 /* chkerr's low byte per position (1 / 0 / CE_NOKMER), k in [1, 63] */
@@ -863,8 +863,8 @@ void yk_launch_ce_lookup(const uint8_t *bases, int64_t n, int k, ImgView img, ui
 	const int tab = img.pre <= 12;
 	const size_t lds = tab ? (size_t)8 << img.pre : 0;
 	const dim3 grid(yk_xpart_blocks(n)), block(XT_THREADS);
-	if (k < 32) hipLaunchKernelGGL((k_lookup<uint8_t, false, true>), grid, block, lds, st, bases, n, k, img, out, tab, min_cnt);
-	else hipLaunchKernelGGL((k_lookup<uint8_t, true, true>), grid, block, lds, st, bases, n, k, img, out, tab, min_cnt);
+	if (k < 32) YK_LAUNCH((k_lookup<uint8_t, false, true>), grid, block, lds, st, bases, n, k, img, out, tab, min_cnt);
+	else YK_LAUNCH((k_lookup<uint8_t, true, true>), grid, block, lds, st, bases, n, k, img, out, tab, min_cnt);
 }
 
 int yk_tb_over_seen(hipStream_t st)
@@ -880,7 +880,7 @@ void yk_launch_qv_reduce(const unsigned short *t, const u64 *roff, const u32 *rl
 {
 	if (n_reads <= 0) return;
 	const int64_t want = (n_reads + 3) / 4;
-	hipLaunchKernelGGL(k_qv_reduce, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, st, t, roff, rlen, n_reads, min_len, min_frac,
+	YK_LAUNCH(k_qv_reduce, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, st, t, roff, rlen, n_reads, min_len, min_frac,
 	                   tot_out, non0_out, (unsigned long long*)hist);
 }
 
@@ -888,5 +888,5 @@ void yk_launch_tb_reduce(const uint8_t *flag, const u64 *roff, const u32 *rlen, 
 {
 	if (n_reads <= 0) return;
 	const int64_t want = (n_reads + 3) / 4;
-	hipLaunchKernelGGL(k_tb_reduce, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, st, flag, roff, rlen, n_reads, k, cnt);
+	YK_LAUNCH(k_tb_reduce, dim3((unsigned)(want < 8192 ? want : 8192)), dim3(256), 0, st, flag, roff, rlen, n_reads, k, cnt);
 }

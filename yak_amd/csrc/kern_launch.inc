@@ -17,7 +17,7 @@ void yk_launch_extract(const uint8_t *bases, int64_t pos0, int64_t n, int64_t t_
 {
 	if (n <= pos0) return;
 	const u64 tiles = ((u64)(n - pos0) + XT_TILE - 1) / XT_TILE;
-	hipLaunchKernelGGL(k_extract, dim3((unsigned)tiles), dim3(XT_THREADS), 0, st, bases, pos0, n, t_sub, k, pre, plo, phi, out_hash, out_t, cursor);
+	YK_LAUNCH(k_extract, dim3((unsigned)tiles), dim3(XT_THREADS), 0, st, bases, pos0, n, t_sub, k, pre, plo, phi, out_hash, out_t, cursor);
 }
 
 /* ASCII image -> the packed image of yakamd_feed_packed_dev: 32 bases per lane, two code words and one validity word */
@@ -36,7 +36,7 @@ void k_pack(const uint8_t *__restrict__ a, int64_t n, u32 *__restrict__ codes, u
 }
 void yk_launch_pack(const uint8_t *a, int64_t n, u32 *codes, u32 *valid, hipStream_t st)
 {
-	if (n > 0) hipLaunchKernelGGL(k_pack, dim3((unsigned)((n + 32 * 256 - 1) / (32 * 256))), dim3(256), 0, st, a, n, codes, valid);
+	if (n > 0) YK_LAUNCH(k_pack, dim3((unsigned)((n + 32 * 256 - 1) / (32 * 256))), dim3(256), 0, st, a, n, codes, valid);
 }
 
 /* partitioning extraction: returns through bstart[1 << nb_bits] (device) the record count */
@@ -59,18 +59,18 @@ void yk_launch_xpart(const uint8_t *bases, int64_t pos0, int64_t n, int64_t t_su
 		if (k == 31) {                                                /* yak's default k: the variants with the constant folded in */
 			static DevOnce attr31;
 			if (!attr31) { hipFuncSetAttribute((const void*)k_xpart_wcs<true, 31>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096); attr31 = true; }
-			hipLaunchKernelGGL((k_xpart<3, 31>), dim3(n_blk), dim3(XT_THREADS), 3 * lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
+			YK_LAUNCH((k_xpart<3, 31>), dim3(n_blk), dim3(XT_THREADS), 3 * lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
 			launch_part_scan(rows, n_blk, nb_bits, partial, bstart, st, true);
-			hipLaunchKernelGGL((k_xpart_wcs<true, 31>), dim3(n_blk), dim3(1024), wlds, st, bases, pos0, n, k, pre, plo, phi, nb_bits, (const u32*)rows, (u64*)out, 0, valid);
+			YK_LAUNCH((k_xpart_wcs<true, 31>), dim3(n_blk), dim3(1024), wlds, st, bases, pos0, n, k, pre, plo, phi, nb_bits, (const u32*)rows, (u64*)out, 0, valid);
 			return;
 		}
-		hipLaunchKernelGGL(k_xpart<3>, dim3(n_blk), dim3(XT_THREADS), 3 * lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
+		YK_LAUNCH(k_xpart<3>, dim3(n_blk), dim3(XT_THREADS), 3 * lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
 		launch_part_scan(rows, n_blk, nb_bits, partial, bstart, st, true);
-		hipLaunchKernelGGL(k_xpart_wcs<true>, dim3(n_blk), dim3(1024), wlds, st,
+		YK_LAUNCH(k_xpart_wcs<true>, dim3(n_blk), dim3(1024), wlds, st,
 		                   bases, pos0, n, k, pre, plo, phi, nb_bits, (const u32*)rows, (u64*)out, 0, valid);
 		return;
 	}
-	hipLaunchKernelGGL(k_xpart<0>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
+	YK_LAUNCH(k_xpart<0>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
 	launch_part_scan(rows, n_blk, nb_bits, partial, bstart, st);
 	const int wc = 3;                                             /* write-combining scatters for both record kinds (the plain ones serve prefixes beyond 10 bits) */
 	static DevOnce attr;
@@ -84,16 +84,16 @@ void yk_launch_xpart(const uint8_t *bases, int64_t pos0, int64_t n, int64_t t_su
 		if (hash_only && (wcs2 || hash_only == 3) && k < 32) {   /* hash_only == 3: bare hashes with the range tag (the caller checked k and nb_bits) */                         /* the round-stable variant needs 7 slots per stack only: two workgroups per CU */
 			static DevOnce attr4;
 			if (!attr4) { hipFuncSetAttribute((const void*)k_xpart_wcs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096); attr4 = true; }
-			hipLaunchKernelGGL(k_xpart_wcs<false>, dim3(n_blk), dim3(1024), (wc_lds_bytes<8, XW_CAP_S, false>(1 << nb_bits, 1024)), st,
+			YK_LAUNCH(k_xpart_wcs<false>, dim3(n_blk), dim3(1024), (wc_lds_bytes<8, XW_CAP_S, false>(1 << nb_bits, 1024)), st,
 			                   bases, pos0, n, k, pre, plo, phi, nb_bits, (const u32*)rows, (u64*)out, hash_only == 3, valid);
 		}
-		else if (hash_only) hipLaunchKernelGGL(k_xpart_wc<2>, dim3(n_blk), dim3(XW_NT), (wc_lds_bytes<8, XW_CAP_H, false>(1 << nb_bits, XW_NT)), st,
+		else if (hash_only) YK_LAUNCH(k_xpart_wc<2>, dim3(n_blk), dim3(XW_NT), (wc_lds_bytes<8, XW_CAP_H, false>(1 << nb_bits, XW_NT)), st,
 		                                  bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, (const u32*)rows, (const u64*)bstart, (void*)out, valid);
-		else hipLaunchKernelGGL(k_xpart_wc<1>, dim3(n_blk), dim3(XW_NT), (wc_lds_bytes<4, XW_CAP_T, true>(1 << nb_bits, XW_NT)), st,
+		else YK_LAUNCH(k_xpart_wc<1>, dim3(n_blk), dim3(XW_NT), (wc_lds_bytes<4, XW_CAP_T, true>(1 << nb_bits, XW_NT)), st,
 		                        bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, (const u32*)rows, (const u64*)bstart, (void*)out, valid);
 	}
-	else if (hash_only) hipLaunchKernelGGL(k_xpart<2>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
-	else hipLaunchKernelGGL(k_xpart<1>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
+	else if (hash_only) YK_LAUNCH(k_xpart<2>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
+	else YK_LAUNCH(k_xpart<1>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
 }
 
 int yk_part_groups(void) { return PS_G; }
@@ -106,9 +106,9 @@ void yk_launch_rpart(const u64 *in_hash, const u32 *in_t, int64_t n, int pre, in
 	if (n <= 0) return;
 	const int n_blk = yk_rpart_blocks(n);
 	const size_t lds = sizeof(u32) << nb_bits;
-	hipLaunchKernelGGL(k_rpart<0>, dim3(n_blk), dim3(256), lds, st, in_hash, in_t, n, pre, plo, phi, nb_bits, rows, out);
+	YK_LAUNCH(k_rpart<0>, dim3(n_blk), dim3(256), lds, st, in_hash, in_t, n, pre, plo, phi, nb_bits, rows, out);
 	launch_part_scan(rows, n_blk, nb_bits, partial, bstart, st);
-	hipLaunchKernelGGL(k_rpart<1>, dim3(n_blk), dim3(256), lds, st, in_hash, in_t, n, pre, plo, phi, nb_bits, rows, out);
+	YK_LAUNCH(k_rpart<1>, dim3(n_blk), dim3(256), lds, st, in_hash, in_t, n, pre, plo, phi, nb_bits, rows, out);
 }
 
 void yk_replay_prof(u64 *out8) { (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(d_rp_prof), 64); u64 z[8] = {0}; (void)hipMemcpyToSymbol(HIP_SYMBOL(d_rp_prof), z, 64); }
@@ -129,25 +129,25 @@ int yk_bad_hash_seen(hipStream_t st)
 
 void yk_launch_acc_init(AccSlot *s, u64 n, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_acc_init, dim3(grid_for(n)), dim3(256), 0, st, s, n);
+	YK_LAUNCH(k_acc_init, dim3(grid_for(n)), dim3(256), 0, st, s, n);
 }
 
 void yk_launch_acc_insert(const Rec *rec, int64_t n, u64 t0, AccTab tab, ImgView img,
                           int img_nonempty, int bloom_mode, u64 *newlist, u64 *counters, hipStream_t st)
 {
 	if (n <= 0) return;
-	hipLaunchKernelGGL(k_acc_insert, dim3(grid_for((u64)n)), dim3(256), 0, st, rec, n, t0, tab, img, img_nonempty, bloom_mode, newlist, counters);
+	YK_LAUNCH(k_acc_insert, dim3(grid_for((u64)n)), dim3(256), 0, st, rec, n, t0, tab, img, img_nonempty, bloom_mode, newlist, counters);
 }
 
 void yk_launch_acc_rehash(AccTab oldt, AccTab newt, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_acc_rehash, dim3(grid_for(oldt.mask + 1)), dim3(256), 0, st, oldt, newt);
+	YK_LAUNCH(k_acc_rehash, dim3(grid_for(oldt.mask + 1)), dim3(256), 0, st, oldt, newt);
 }
 
 void yk_launch_img_count(const Rec *rec, int64_t n, ImgView img, hipStream_t st)
 {
 	if (n <= 0) return;
-	hipLaunchKernelGGL(k_img_count, dim3(grid_for((u64)n)), dim3(256), 0, st, rec, n, img);
+	YK_LAUNCH(k_img_count, dim3(grid_for((u64)n)), dim3(256), 0, st, rec, n, img);
 }
 
 /* LDS needed by k_img_count_lds for a sub-table of `cap` slots holding `count` keys */
@@ -161,97 +161,97 @@ int yk_launch_img_count_lds(const void *rec, int hash_only, const u64 *bstart, I
 		    hipFuncSetAttribute((const void*)k_img_count_lds<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess) { (void)hipGetLastError(); return -1; }
 		attr = true;
 	}
-	if (hash_only) hipLaunchKernelGGL(k_img_count_lds<1>, dim3(phi - plo), dim3(1024), lds, st, (const u64*)rec, bstart, img, plo, compact, stride);
-	else hipLaunchKernelGGL(k_img_count_lds<2>, dim3(phi - plo), dim3(1024), lds, st, (const u64*)rec, bstart, img, plo, compact, stride);
+	if (hash_only) YK_LAUNCH(k_img_count_lds<1>, dim3(phi - plo), dim3(1024), lds, st, (const u64*)rec, bstart, img, plo, compact, stride);
+	else YK_LAUNCH(k_img_count_lds<2>, dim3(phi - plo), dim3(1024), lds, st, (const u64*)rec, bstart, img, plo, compact, stride);
 	return 0;
 }
 
 void yk_launch_img_count_h(const u64 *hash, int64_t n, ImgView img, hipStream_t st)
 {
 	if (n <= 0) return;
-	hipLaunchKernelGGL(k_img_count_h, dim3(grid_for((u64)n)), dim3(256), 0, st, hash, n, img);
+	YK_LAUNCH(k_img_count_h, dim3(grid_for((u64)n)), dim3(256), 0, st, hash, n, img);
 }
 
-void yk_launch_img_inc(ImgView img, u64 hash, u64 *out2, hipStream_t st) { hipLaunchKernelGGL(k_img_inc, dim3(1), dim3(1), 0, st, img, hash, out2); }
+void yk_launch_img_inc(ImgView img, u64 hash, u64 *out2, hipStream_t st) { YK_LAUNCH(k_img_inc, dim3(1), dim3(1), 0, st, img, hash, out2); }
 
 void yk_launch_img_fold(ImgView img, u64 n_slots, hipStream_t st)
 {
-	if (n_slots) hipLaunchKernelGGL(k_img_fold, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots);
+	if (n_slots) YK_LAUNCH(k_img_fold, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots);
 }
 
 void yk_launch_img_clear(ImgView img, u64 n_slots, hipStream_t st)
 {
-	if (n_slots) hipLaunchKernelGGL(k_img_clear, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots);
+	if (n_slots) YK_LAUNCH(k_img_clear, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots);
 }
 
 void yk_launch_img_hist(ImgView img, u64 n_slots, u64 *hist, hipStream_t st)
 {
-	if (n_slots) hipLaunchKernelGGL(k_img_hist, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots, (unsigned long long*)hist);
+	if (n_slots) YK_LAUNCH(k_img_hist, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots, (unsigned long long*)hist);
 }
 
 void yk_launch_img_setcnt(ImgView img, u64 n_slots, u32 cnt, hipStream_t st)
 {
-	if (n_slots) hipLaunchKernelGGL(k_img_setcnt, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots, cnt);
+	if (n_slots) YK_LAUNCH(k_img_setcnt, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots, cnt);
 }
 
 void yk_launch_lastput(const Rec *rec, int64_t n, u64 t0, u64 t_from, AccTab tab, ImgView img,
                        int img_nonempty, int bloom_mode, const u32 *only_missing, u64 *lp_batch, hipStream_t st)
 {
 	if (n <= 0) return;
-	hipLaunchKernelGGL(k_lastput, dim3(grid_for((u64)n)), dim3(256), 0, st, rec, n, t0, t_from, tab, img, img_nonempty, bloom_mode, only_missing, lp_batch);
+	YK_LAUNCH(k_lastput, dim3(grid_for((u64)n)), dim3(256), 0, st, rec, n, t0, t_from, tab, img, img_nonempty, bloom_mode, only_missing, lp_batch);
 }
 
 void yk_launch_lastput_merge(u64 *lastput, const u64 *lp_batch, u32 *missing, u32 *n_missing, int P, int plo, int phi, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_lastput_merge, dim3((P + 255) / 256), dim3(256), 0, st, lastput, lp_batch, missing, n_missing, P, plo, phi);
+	YK_LAUNCH(k_lastput_merge, dim3((P + 255) / 256), dim3(256), 0, st, lastput, lp_batch, missing, n_missing, P, plo, phi);
 }
 
 void yk_launch_bf_test(AccTab tab, const u64 *newlist, u64 n_new, BloomView bf, u64 *miss, hipStream_t st)
 {
-	if (n_new) hipLaunchKernelGGL(k_bf_test, dim3(grid_for(n_new)), dim3(256), 0, st, tab, newlist, n_new, bf, miss);
+	if (n_new) YK_LAUNCH(k_bf_test, dim3(grid_for(n_new)), dim3(256), 0, st, tab, newlist, n_new, bf, miss);
 }
 
 void yk_launch_bf_set(AccTab tab, const u64 *newlist, u64 n_new, BloomView bf, const u64 *miss,
                       u32 *multi, int multi_bits, u64 *counters, hipStream_t st)
 {
-	if (n_new) hipLaunchKernelGGL(k_bf_set, dim3(grid_for(n_new)), dim3(256), 0, st, tab, newlist, n_new, bf, miss, multi, multi_bits, counters);
+	if (n_new) YK_LAUNCH(k_bf_set, dim3(grid_for(n_new)), dim3(256), 0, st, tab, newlist, n_new, bf, miss, multi, multi_bits, counters);
 }
 
 void yk_launch_bf_check(AccTab tab, const u64 *newlist, u64 n_new, BloomView bf, const u64 *miss,
                         const u32 *multi, int multi_bits, u64 *cand, u64 *counters, hipStream_t st)
 {
-	if (n_new) hipLaunchKernelGGL(k_bf_check, dim3(grid_for(n_new)), dim3(256), 0, st, tab, newlist, n_new, bf, miss, multi, multi_bits, cand, counters);
+	if (n_new) YK_LAUNCH(k_bf_check, dim3(grid_for(n_new)), dim3(256), 0, st, tab, newlist, n_new, bf, miss, multi, multi_bits, cand, counters);
 }
 
 void yk_launch_bf_mapfill(AccTab tab, const u64 *newlist, u64 n_new, BloomView bf, const u64 *miss,
                           const u32 *multi, int multi_bits, u64 *map, int map_bits, hipStream_t st)
 {
-	if (n_new) hipLaunchKernelGGL(k_bf_mapfill, dim3(grid_for(n_new)), dim3(256), 0, st, tab, newlist, n_new, bf, miss, multi, multi_bits, map, map_bits);
+	if (n_new) YK_LAUNCH(k_bf_mapfill, dim3(grid_for(n_new)), dim3(256), 0, st, tab, newlist, n_new, bf, miss, multi, multi_bits, map, map_bits);
 }
 
 void yk_launch_bf_resolve(AccTab tab, const u64 *newlist, const u64 *cand, u64 n_cand, BloomView bf,
                           const u64 *miss, const u64 *map, int map_bits, hipStream_t st)
 {
-	if (n_cand) hipLaunchKernelGGL(k_bf_resolve, dim3(grid_for(n_cand)), dim3(256), 0, st, tab, newlist, cand, n_cand, bf, miss, map, map_bits);
+	if (n_cand) YK_LAUNCH(k_bf_resolve, dim3(grid_for(n_cand)), dim3(256), 0, st, tab, newlist, cand, n_cand, bf, miss, map, map_bits);
 }
 
 void yk_launch_select_count(AccTab tab, int bloom_mode, int P, u32 *seg_cnt, hipStream_t st)
 {
 	(void)P;
-	hipLaunchKernelGGL(k_select_count, dim3((unsigned)((tab.mask + SEL_CHUNK) / SEL_CHUNK)), dim3(256), 0, st, tab, bloom_mode, seg_cnt);
+	YK_LAUNCH(k_select_count, dim3((unsigned)((tab.mask + SEL_CHUNK) / SEL_CHUNK)), dim3(256), 0, st, tab, bloom_mode, seg_cnt);
 }
 
 void yk_launch_select_scatter(AccTab tab, int bloom_mode, int P, const u64 *seg_off, u32 *seg_cur,
                               u64 *rec_kc, u64 *rec_t, hipStream_t st)
 {
 	(void)P;
-	hipLaunchKernelGGL(k_select_scatter, dim3((unsigned)((tab.mask + SEL_CHUNK) / SEL_CHUNK)), dim3(256), 0, st, tab, bloom_mode, seg_off, seg_cur, rec_kc, rec_t);
+	YK_LAUNCH(k_select_scatter, dim3((unsigned)((tab.mask + SEL_CHUNK) / SEL_CHUNK)), dim3(256), 0, st, tab, bloom_mode, seg_off, seg_cur, rec_kc, rec_t);
 }
 
 void yk_launch_seg_sort_pass(const u64 *seg_off, int P, const u64 *src_kc, const u64 *src_t,
                              u64 *dst_kc, u64 *dst_t, int shift, hipStream_t st)
 {
-	hipLaunchKernelGGL((k_seg_sort_pass<8, 256>), dim3(P), dim3(256), 0, st, seg_off, (const u32*)0, src_kc, src_t, dst_kc, dst_t, shift);
+	YK_LAUNCH((k_seg_sort_pass<8, 256>), dim3(P), dim3(256), 0, st, seg_off, (const u32*)0, src_kc, src_t, dst_kc, dst_t, shift);
 }
 
 void yk_launch_replay(const ReplayTask *tasks, int n_tasks, int n_threads, const u64 *old_keys, const u32 *old_used,
@@ -262,7 +262,7 @@ void yk_launch_replay(const ReplayTask *tasks, int n_tasks, int n_threads, const
 	static DevOnce attr;
 	if (!attr) { hipFuncSetAttribute((const void*)k_replay, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); attr = true; }
 	if (lds_words < 2 * RP_LDS_WORDS) lds_words = 2 * RP_LDS_WORDS;
-	hipLaunchKernelGGL(k_replay, dim3(n_tasks), dim3(n_threads), (size_t)lds_words * 4, st, tasks, old_keys, old_used, new_keys, new_used,
+	YK_LAUNCH(k_replay, dim3(n_tasks), dim3(n_threads), (size_t)lds_words * 4, st, tasks, old_keys, old_used, new_keys, new_used,
 	                   scr_used, scr_owner, scr_par, rec_kc, rec_t, lastput, out_bits, out_count, lds_words);
 }
 
@@ -270,27 +270,27 @@ void yk_launch_replay(const ReplayTask *tasks, int n_tasks, int n_threads, const
 int yk_shrink_shares(void) { return SHR_RG; }
 void yk_launch_shrink_count(ImgView img, int P, int cmin, int cmax, int which, ImgView other, u32 *seg_cnt, hipStream_t st, int rng)
 {
-	hipLaunchKernelGGL(k_shrink_count, dim3(P, rng ? SHR_RG : 1), dim3(256), 0, st, img, cmin, cmax, which, other, seg_cnt);
+	YK_LAUNCH(k_shrink_count, dim3(P, rng ? SHR_RG : 1), dim3(256), 0, st, img, cmin, cmax, which, other, seg_cnt);
 }
 
 void yk_launch_shrink_scatter(ImgView img, int P, int cmin, int cmax, int which, ImgView other, const u64 *seg_off, u64 *rec_kc, hipStream_t st, const u32 *rng_cnt)
 {
-	hipLaunchKernelGGL(k_shrink_scatter, dim3(P, rng_cnt ? SHR_RG : 1), dim3(256), 0, st, img, cmin, cmax, which, other, seg_off, rec_kc, rng_cnt);
+	YK_LAUNCH(k_shrink_scatter, dim3(P, rng_cnt ? SHR_RG : 1), dim3(256), 0, st, img, cmin, cmax, which, other, seg_off, rec_kc, rng_cnt);
 }
 
 void yk_launch_put_u64(const u64 *pos, const u64 *val, u32 n, u64 *out, hipStream_t st)
 {
-	if (n) hipLaunchKernelGGL(k_put_u64, dim3((n + 255) / 256), dim3(256), 0, st, pos, val, n, out);
+	if (n) YK_LAUNCH(k_put_u64, dim3((n + 255) / 256), dim3(256), 0, st, pos, val, n, out);
 }
 
 void yk_launch_resize(const ResizeTask *tasks, int P, const u64 *old_keys, const u32 *old_used, u64 *new_keys, u32 *new_used, u32 *scr_used, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_resize, dim3(P), dim3(256), 0, st, tasks, old_keys, old_used, new_keys, new_used, scr_used);
+	YK_LAUNCH(k_resize, dim3(P), dim3(256), 0, st, tasks, old_keys, old_used, new_keys, new_used, scr_used);
 }
 
 void yk_launch_keys_to_hashes(const u64 *kc, const u64 *seg_off, int P, int pre, u64 *hash, u32 *t, hipStream_t st, unsigned short *cnt)
 {
-	hipLaunchKernelGGL(k_keys_to_hashes, dim3(P), dim3(256), 0, st, kc, seg_off, pre, hash, t, cnt);
+	YK_LAUNCH(k_keys_to_hashes, dim3(P), dim3(256), 0, st, kc, seg_off, pre, hash, t, cnt);
 }
 
 /* yakamd_ch_sum's count step over a listing of n {hash, count} entries; *missing is raised when a listed key of [plo, phi) is not in the image */
@@ -300,8 +300,8 @@ void yk_launch_img_add_counts(const u64 *hash, const unsigned short *cnt, u64 n,
 	const int tab = img.pre <= 12;
 	const size_t lds = tab ? (size_t)8 << img.pre : 0;
 	const dim3 grid(grid_for(n, AC_THREADS * AC_U)), block(AC_THREADS);
-	if (img.k < 32) hipLaunchKernelGGL(k_img_add_counts<false>, grid, block, lds, st, hash, cnt, n, img, plo, phi, tab, missing);
-	else hipLaunchKernelGGL(k_img_add_counts<true>, grid, block, lds, st, hash, cnt, n, img, plo, phi, tab, missing);
+	if (img.k < 32) YK_LAUNCH(k_img_add_counts<false>, grid, block, lds, st, hash, cnt, n, img, plo, phi, tab, missing);
+	else YK_LAUNCH(k_img_add_counts<true>, grid, block, lds, st, hash, cnt, n, img, plo, phi, tab, missing);
 }
 
 /* one sweep of the sort by insertion time (k_part2<.., TS>): {key, time} pairs in and out, bin = (time >> fp.ssh) mod 2^fp.s2_bits */
@@ -312,12 +312,12 @@ void yk_launch_part2_ts(const Chunk2 *chunks, int n_chunks, const u32 *chunk_fir
 	static DevOnce attr;
 	if (!attr) { hipFuncSetAttribute((const void*)k_part2<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
 	             hipFuncSetAttribute((const void*)k_part2_wc<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); attr = true; }
-	if (n_chunks) hipLaunchKernelGGL((k_part2<0, true>), dim3(n_chunks), dim3(256), lds, st, chunks, fp, rows2, bbase, out);
-	hipLaunchKernelGGL(k_part2_scan, dim3(P), dim3(256), 0, st, chunk_first, bbase, fp.s2_bits, rows2, sbstart, P, 1);
+	if (n_chunks) YK_LAUNCH((k_part2<0, true>), dim3(n_chunks), dim3(256), lds, st, chunks, fp, rows2, bbase, out);
+	YK_LAUNCH(k_part2_scan, dim3(P), dim3(256), 0, st, chunk_first, bbase, fp.s2_bits, rows2, sbstart, P, 1);
 	if (n_chunks && fp.s2_bits <= 13 && fp.s2_bits >= 4) {
 		const size_t l2 = wc_lds_bytes<4, WC_CAP, true>(fp.s2_bits < 11 ? 1 << fp.s2_bits : WC_SEG, WC_NT);
-		hipLaunchKernelGGL((k_part2_wc<true>), dim3(n_chunks), dim3(WC_NT), l2, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, out);
-	} else if (n_chunks) hipLaunchKernelGGL((k_part2<1, true>), dim3(n_chunks), dim3(1024), lds, st, chunks, fp, rows2, bbase, out);
+		YK_LAUNCH((k_part2_wc<true>), dim3(n_chunks), dim3(WC_NT), l2, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, out);
+	} else if (n_chunks) YK_LAUNCH((k_part2<1, true>), dim3(n_chunks), dim3(1024), lds, st, chunks, fp, rows2, bbase, out);
 }
 size_t yk_ts_rank_lds(int ws, u32 *cap_out)
 {
@@ -336,13 +336,13 @@ int yk_launch_ts_rank(const u64 *binstart, const Rec *in, int w, int j, u32 bin_
 	if (lds > 100 * 1024 || (n_bins & ((1u << j) - 1))) return -1;
 	const u32 n_super = n_bins >> j;
 	const u32 grid = std::min<u32>(n_super, 256 * 4 * 16);        /* a few steps per workgroup, handed out as slots free up */
-	if (grid) hipLaunchKernelGGL(k_ts_rank, dim3(grid), dim3(256), lds, st, binstart, in, w, j, bin_lo, n_super, out_kc, out_t, fail, cap);
+	if (grid) YK_LAUNCH(k_ts_rank, dim3(grid), dim3(256), lds, st, binstart, in, w, j, bin_lo, n_super, out_kc, out_t, fail, cap);
 	return 0;
 }
 void yk_launch_kt_split(const Rec *in, u64 n, u64 *out_kc, u64 *out_t, hipStream_t st)
 {
 	const u32 grid = (u32)std::min<u64>((n + 255) / 256, 256 * 8 * 8);
-	if (grid) hipLaunchKernelGGL(k_kt_split, dim3(grid), dim3(256), 0, st, in, n, out_kc, out_t);
+	if (grid) YK_LAUNCH(k_kt_split, dim3(grid), dim3(256), 0, st, in, n, out_kc, out_t);
 }
 
 void yk_launch_part2(const Chunk2 *chunks, int n_chunks, const u32 *chunk_first, const u64 *bbase, FastParams fp, int P,
@@ -352,8 +352,8 @@ void yk_launch_part2(const Chunk2 *chunks, int n_chunks, const u32 *chunk_first,
 	const int nt = 1024;
 	static DevOnce attr;
 	if (!attr) { hipFuncSetAttribute((const void*)k_part2<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); attr = true; }
-	if (n_chunks) hipLaunchKernelGGL((k_part2<0>), dim3(n_chunks), dim3(256), lds, st, chunks, fp, rows2, bbase, out);
-	hipLaunchKernelGGL(k_part2_scan, dim3(P), dim3(256), 0, st, chunk_first, bbase, fp.s2_bits, rows2, sbstart, P, 1);
+	if (n_chunks) YK_LAUNCH((k_part2<0>), dim3(n_chunks), dim3(256), lds, st, chunks, fp, rows2, bbase, out);
+	YK_LAUNCH(k_part2_scan, dim3(P), dim3(256), 0, st, chunk_first, bbase, fp.s2_bits, rows2, sbstart, P, 1);
 	const int wc = (int)yk_knob("YAKAMD_P2_WC", 1);
 	if (n_chunks && wc && fp.rec8_out && fp.s2_bits <= 13 && fp.s2_bits >= 4) {
 		static DevOnce attr8;                                  /* the kernel has 6.5 KB of static LDS besides */
@@ -362,26 +362,26 @@ void yk_launch_part2(const Chunk2 *chunks, int n_chunks, const u32 *chunk_first,
 		if (fp.rec8_in && seg <= 1024 && yk_knob("YAKAMD_P2_CAP7", 1) != 0) {   /* <= 76 KB with the ring: two workgroups per CU */
 			static DevOnce attr7;
 			if (!attr7) { if (hipFuncSetAttribute((const void*)k_part2_wc8<false, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 1024 * 7 * 8 + 1024 * 8 + WC_NT * 4 + 16) != hipSuccess) (void)hipGetLastError(); attr7 = true; }
-			hipLaunchKernelGGL((k_part2_wc8<false, 7>), dim3(n_chunks), dim3(WC_NT), seg * 7 * 8 + seg * 8 + WC_NT * 4 + 16, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, (u64*)out);
+			YK_LAUNCH((k_part2_wc8<false, 7>), dim3(n_chunks), dim3(WC_NT), seg * 7 * 8 + seg * 8 + WC_NT * 4 + 16, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, (u64*)out);
 		}
-		else if (fp.rec8_in) hipLaunchKernelGGL((k_part2_wc8<false>), dim3(n_chunks), dim3(WC_NT), seg * WC8_CAP * 8 + seg * 8 + WC_NT * 4 + 16, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, (u64*)out);
+		else if (fp.rec8_in) YK_LAUNCH((k_part2_wc8<false>), dim3(n_chunks), dim3(WC_NT), seg * WC8_CAP * 8 + seg * 8 + WC_NT * 4 + 16, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, (u64*)out);
 		else {                                                      /* the second sweep of a two-sweep partition: {hash, rank} records in */
 			static DevOnce attr8r;
 			if (!attr8r) { if (hipFuncSetAttribute((const void*)k_part2_wc8r, hipFuncAttributeMaxDynamicSharedMemorySize, WC_SEG * WC8_CAP * 8 + WC_SEG * 8 + WC_NT * 4 + 16) != hipSuccess) (void)hipGetLastError(); attr8r = true; }
-			hipLaunchKernelGGL(k_part2_wc8r, dim3(n_chunks), dim3(WC_NT), seg * WC8_CAP * 8 + seg * 8 + WC_NT * 4 + 16, st, chunks, fp, (const u32*)rows2, bbase, (u64*)out);
+			YK_LAUNCH(k_part2_wc8r, dim3(n_chunks), dim3(WC_NT), seg * WC8_CAP * 8 + seg * 8 + WC_NT * 4 + 16, st, chunks, fp, (const u32*)rows2, bbase, (u64*)out);
 		}
 	} else if (n_chunks && wc && fp.rec8_in && fp.s2_bits <= 13 && fp.s2_bits >= 4) {
 		/* tagged records in, {hash, rank} records out (the first sweep of a two-sweep partition; ranks beyond their field): the ring kernel with 16-byte stacks */
 		static DevOnce attr16;
 		if (!attr16) { if (hipFuncSetAttribute((const void*)k_part2_wc8<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192) != hipSuccess) (void)hipGetLastError(); attr16 = true; }
 		const size_t l2 = wc_lds_bytes<4, WC_CAP, true>(fp.s2_bits < 11 ? 1 << fp.s2_bits : WC_SEG, WC_NT);
-		hipLaunchKernelGGL((k_part2_wc8<true>), dim3(n_chunks), dim3(WC_NT), l2, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, (u64*)out);
+		YK_LAUNCH((k_part2_wc8<true>), dim3(n_chunks), dim3(WC_NT), l2, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, (u64*)out);
 	} else if (n_chunks && wc && fp.s2_bits <= 13 && fp.s2_bits >= 4) {
 		static DevOnce attr2;
 		if (!attr2) { hipFuncSetAttribute((const void*)k_part2_wc<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); attr2 = true; }
 		const size_t l2 = wc_lds_bytes<4, WC_CAP, true>(fp.s2_bits < 11 ? 1 << fp.s2_bits : WC_SEG, WC_NT);
-		hipLaunchKernelGGL((k_part2_wc<false>), dim3(n_chunks), dim3(WC_NT), l2, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, out);
-	} else if (n_chunks) hipLaunchKernelGGL((k_part2<1>), dim3(n_chunks), dim3(nt), lds, st, chunks, fp, rows2, bbase, out);
+		YK_LAUNCH((k_part2_wc<false>), dim3(n_chunks), dim3(WC_NT), l2, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, out);
+	} else if (n_chunks) YK_LAUNCH((k_part2<1>), dim3(n_chunks), dim3(nt), lds, st, chunks, fp, rows2, bbase, out);
 }
 
 int yk_rng_log(void)                      /* log2 slots per range; the env knob lets tests split small tables */
@@ -397,9 +397,9 @@ void yk_launch_hpart2(const Chunk2 *chunks, int n_chunks, const u32 *chunk_first
 	const int S2 = 1 << rb;
 	static DevOnce attr;
 	if (!attr) { hipFuncSetAttribute((const void*)k_hpart2<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); attr = true; }
-	if (n_chunks) hipLaunchKernelGGL(k_hpart2<0>, dim3(n_chunks), dim3(WC_NT), sizeof(u32) * S2, st, chunks, img, rb, yk_rng_log(), rows2, (const u64*)sbstart, out);
-	hipLaunchKernelGGL(k_part2_scan, dim3(P), dim3(256), 0, st, chunk_first, bbase, rb, rows2, sbstart, P, 0);
-	if (n_chunks) hipLaunchKernelGGL(k_hpart2<1>, dim3(n_chunks), dim3(WC_NT), (wc_lds_bytes<8, XW_CAP_H, false>(S2, WC_NT)), st,
+	if (n_chunks) YK_LAUNCH(k_hpart2<0>, dim3(n_chunks), dim3(WC_NT), sizeof(u32) * S2, st, chunks, img, rb, yk_rng_log(), rows2, (const u64*)sbstart, out);
+	YK_LAUNCH(k_part2_scan, dim3(P), dim3(256), 0, st, chunk_first, bbase, rb, rows2, sbstart, P, 0);
+	if (n_chunks) YK_LAUNCH(k_hpart2<1>, dim3(n_chunks), dim3(WC_NT), (wc_lds_bytes<8, XW_CAP_H, false>(S2, WC_NT)), st,
 	                                 chunks, img, rb, yk_rng_log(), rows2, (const u64*)sbstart, out);
 }
 
@@ -414,8 +414,8 @@ int yk_launch_img_count_rng(const u64 *rec, int cross, const u64 *sbstart, ImgVi
 	}
 	const size_t lds = (size_t)((max_len + 31) / 32) * 4 + (size_t)(max_len + 1) / 2 * 4 + 16;
 	const dim3 grid((unsigned)(phi - plo) << rb), blk(1024);
-	if (cross) hipLaunchKernelGGL(k_img_count_rng<1>, grid, blk, lds, st, rec, sbstart, img, plo, rb, yk_rng_log(), list, list_n, list_cap);
-	else hipLaunchKernelGGL(k_img_count_rng<0>, grid, blk, lds, st, rec, sbstart, img, plo, rb, yk_rng_log(), list, list_n, list_cap);
+	if (cross) YK_LAUNCH(k_img_count_rng<1>, grid, blk, lds, st, rec, sbstart, img, plo, rb, yk_rng_log(), list, list_n, list_cap);
+	else YK_LAUNCH(k_img_count_rng<0>, grid, blk, lds, st, rec, sbstart, img, plo, rb, yk_rng_log(), list, list_n, list_cap);
 	return 0;
 }
 
@@ -423,7 +423,7 @@ void yk_launch_lds_count_ovf(FastParams fp, const u64 *sbstart, const Rec *rec,
                              u32 *bloom32, ImgView img, LcOut O, const u32 *ovf_list, u32 n_ovf, const u64 *scr_off,
                              u64 *scr, hipStream_t st)
 {
-	if (n_ovf) hipLaunchKernelGGL(k_lds_count_ovf, dim3(n_ovf), dim3(256), 0, st, fp, sbstart, rec, bloom32, img,
+	if (n_ovf) YK_LAUNCH(k_lds_count_ovf, dim3(n_ovf), dim3(256), 0, st, fp, sbstart, rec, bloom32, img,
 	                              O, ovf_list, scr_off, scr);
 }
 
@@ -440,7 +440,7 @@ int yk_launch_img_count_own(const void *rec, int hash_only, int cross, int ytag,
 	}
 	const int n_p = phi - plo;
 	const dim3 grid((unsigned)((n_p + 7) / 8 * 8) << rb), blk(1024);
-#define YK_OWN(Wv, Cv) hipLaunchKernelGGL((k_img_count_own<Wv, Cv>), grid, blk, lds, st, (const u64*)rec, bstart, img, plo, n_p, rb, rng_log, kmax, list, list_n, list_cap, ytag)
+#define YK_OWN(Wv, Cv) YK_LAUNCH((k_img_count_own<Wv, Cv>), grid, blk, lds, st, (const u64*)rec, bstart, img, plo, n_p, rb, rng_log, kmax, list, list_n, list_cap, ytag)
 	if (hash_only) { if (cross) YK_OWN(1, 1); else YK_OWN(1, 0); }
 	else { if (cross) YK_OWN(2, 1); else YK_OWN(2, 0); }
 #undef YK_OWN
@@ -451,12 +451,12 @@ int yk_launch_img_count_own(const void *rec, int hash_only, int cross, int ytag,
 void yk_r2_binit(const R2Tab *tabs, const R2Act *acts, int P, u32 bmax, u32 *OCC, u32 *USED, hipStream_t st)
 {
 	const u64 W = (2ull << bmax) / 32 + 1;                        /* bitmap words of the largest new table */
-	hipLaunchKernelGGL(k_r2_binit, dim3((unsigned)std::min<u64>((W + 1023) / 1024, 256), P), dim3(256), 0, st, tabs, acts, OCC, USED);
+	YK_LAUNCH(k_r2_binit, dim3((unsigned)std::min<u64>((W + 1023) / 1024, 256), P), dim3(256), 0, st, tabs, acts, OCC, USED);
 }
 void yk_r2_dsmall(const R2Tab *tabs, const R2Act *acts, int P, u64 *K0, u64 *K1, u32 *TAG, u32 *OCC, u32 *USED, u32 *Fcur, u32 *Gcur, u32 *fail, hipStream_t st)
 {
 	const int defer = 1;                                          /* (0: the prefix lane follows every chain to its end -- the older, slower rule) */
-	hipLaunchKernelGGL(k_r2_dsmall, dim3(P), dim3(256), 0, st, tabs, acts, K0, K1, TAG, OCC, USED, Fcur, Gcur, fail, (u32)yk_r2_small_f(), defer);
+	YK_LAUNCH(k_r2_dsmall, dim3(P), dim3(256), 0, st, tabs, acts, K0, K1, TAG, OCC, USED, Fcur, Gcur, fail, (u32)yk_r2_small_f(), defer);
 }
 int yk_r2_small_f(void)                                            /* YAKAMD_R2_SMALL_F: test / tuning knob, a power of two in [16, 4096] */
 {
@@ -477,7 +477,7 @@ int yk_r2_double(const R2Tab *tabs, const R2Act *acts, int P, int n_dbl, u64 *K0
 	static const bool prof = getenv("YAKAMD_VERBOSE") && atoi(getenv("YAKAMD_VERBOSE")) > 1;
 	if (prof && !d_prof) { hipMalloc((void**)&d_prof, 16 * 8); }
 	if (prof) hipMemsetAsync(d_prof, 0, 16 * 8, st);
-#define YK_DBL(NWv, PRv, ILv) hipLaunchKernelGGL((k_r2_double<NWv, PRv, ILv>), dim3(P), dim3(64 * NWv), 0, st, tabs, acts, K0, K1, TAG, (const u32*)OCC, USED, (const u32*)Fin, Fout, fail, d_prof)
+#define YK_DBL(NWv, PRv, ILv) YK_LAUNCH((k_r2_double<NWv, PRv, ILv>), dim3(P), dim3(64 * NWv), 0, st, tabs, acts, K0, K1, TAG, (const u32*)OCC, USED, (const u32*)Fin, Fout, fail, d_prof)
 #define YK_DBL_IL(NWv, PRv) do { if (il == 1) YK_DBL(NWv, PRv, 1); else if (il == 4) YK_DBL(NWv, PRv, 4); else YK_DBL(NWv, PRv, 2); } while (0)
 	if (nw >= 16) { if (prof) YK_DBL(16, true, 1); else YK_DBL(16, false, 1); }
 	else if (nw == 5) { if (prof) YK_DBL(5, true, 1); else YK_DBL_IL(5, false); }
@@ -505,30 +505,30 @@ void yk_r2_place(const R2Tab *tabs, const R2Act *acts, int P, int p0, int np, u3
 	const u32 nseg = bmax > SL ? 1u << (bmax - SL) : 1, L = bmax > SL ? 1u << SL : 1u << bmax;
 	hipMemsetAsync(spill_n, 0, 4, st);
 	if (nseg > 1 && G > 1 && pcnt) {                              /* few sub-tables place: G workgroups each */
-		hipLaunchKernelGGL(k_r2_ppart_cnt, dim3(G, P), dim3(1024), 0, st, tabs, acts, kc, pcnt, SL);
-		hipLaunchKernelGGL(k_r2_ppart_scan, dim3(P), dim3(1024), 0, st, acts, pcnt, seg_start, SL, (u32)G);
-		hipLaunchKernelGGL(k_r2_ppart_scat, dim3(G, P), dim3(1024), 0, st, tabs, acts, kc, pk, pr, (const u32*)pcnt, SL);
-	} else if (nseg > 1) hipLaunchKernelGGL(k_r2_ppart, dim3(P), dim3(1024), 0, st, tabs, acts, kc, pk, pr, seg_start, SL);
+		YK_LAUNCH(k_r2_ppart_cnt, dim3(G, P), dim3(1024), 0, st, tabs, acts, kc, pcnt, SL);
+		YK_LAUNCH(k_r2_ppart_scan, dim3(P), dim3(1024), 0, st, acts, pcnt, seg_start, SL, (u32)G);
+		YK_LAUNCH(k_r2_ppart_scat, dim3(G, P), dim3(1024), 0, st, tabs, acts, kc, pk, pr, (const u32*)pcnt, SL);
+	} else if (nseg > 1) YK_LAUNCH(k_r2_ppart, dim3(P), dim3(1024), 0, st, tabs, acts, kc, pk, pr, seg_start, SL);
 	const int pt = 1024;
-	hipLaunchKernelGGL(k_r2_place, dim3(nseg, np), dim3(pt), (size_t)L * 4 + (pt / 64) * 512, st, tabs, acts, K0, K1, kc, (const u64*)pk, (const u32*)pr, (const u32*)seg_start, head, spill, spill_n, spill_cap, fail, SL, HD, img_u, (u32)p0, USED);
+	YK_LAUNCH(k_r2_place, dim3(nseg, np), dim3(pt), (size_t)L * 4 + (pt / 64) * 512, st, tabs, acts, K0, K1, kc, (const u64*)pk, (const u32*)pr, (const u32*)seg_start, head, spill, spill_n, spill_cap, fail, SL, HD, img_u, (u32)p0, USED);
 	if (nseg > 1) {
-		hipLaunchKernelGGL(k_r2_spill, dim3(64), dim3(256), 0, st, acts, (const u64*)spill, (const u32*)spill_n, spill_cap, head, fail, HD);
-			hipLaunchKernelGGL(k_r2_headfill, dim3(nseg, np), dim3(256), 0, st, tabs, acts, K0, K1, kc, (const u32*)head, SL, HD, img_u, (u32)p0);
+		YK_LAUNCH(k_r2_spill, dim3(64), dim3(256), 0, st, acts, (const u64*)spill, (const u32*)spill_n, spill_cap, head, fail, HD);
+			YK_LAUNCH(k_r2_headfill, dim3(nseg, np), dim3(256), 0, st, tabs, acts, K0, K1, kc, (const u32*)head, SL, HD, img_u, (u32)p0);
 		}
 }
 void yk_r2_load(const R2Tab *tabs, const R2Load *ld, int P, u32 bmax, const u64 *src1, const u64 *src2, u64 *K0, u64 *K1, u32 *USED, hipStream_t st)
 {
 	const u64 n = 1ull << bmax;
-	hipLaunchKernelGGL(k_r2_load, dim3((unsigned)std::min<u64>((n + 1023) / 1024, 4096), P), dim3(256), 0, st, tabs, ld, src1, src2, K0, K1, USED);
+	YK_LAUNCH(k_r2_load, dim3((unsigned)std::min<u64>((n + 1023) / 1024, 4096), P), dim3(256), 0, st, tabs, ld, src1, src2, K0, K1, USED);
 }
 void yk_r2_trail(const u64 *lastput, const u64 *rec_t, const u64 *rec_off, const u32 *m, int P, u32 *out, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_r2_trail, dim3((P + 255) / 256), dim3(256), 0, st, lastput, rec_t, rec_off, m, P, out);
+	YK_LAUNCH(k_r2_trail, dim3((P + 255) / 256), dim3(256), 0, st, lastput, rec_t, rec_off, m, P, out);
 }
 void yk_r2_publish(const R2Tab *tabs, const R2Pub *pub, int P, u32 bmax, const u64 *K0, const u64 *K1, u64 *nk, u32 *nu, hipStream_t st)
 {
 	const u64 n = 1ull << bmax;
-	hipLaunchKernelGGL(k_r2_publish, dim3((unsigned)std::min<u64>((n + 1023) / 1024, 4096), P), dim3(256), 0, st, tabs, pub, K0, K1, nk, nu);
+	YK_LAUNCH(k_r2_publish, dim3((unsigned)std::min<u64>((n + 1023) / 1024, 4096), P), dim3(256), 0, st, tabs, pub, K0, K1, nk, nu);
 }
 
 int yk_lc2_ok(FastParams fp)
@@ -553,7 +553,7 @@ void yk_launch_lc2(FastParams fp, const u64 *sbstart, const Rec *rec, u32 *bloom
 	const int wgs = (int)yk_knob("YAKAMD_LC2_WGS", 256 * 5 * 64);
 	const unsigned grid = n_sb < (unsigned)wgs ? n_sb : (unsigned)wgs;
 	if (grid) {
-#define YK_LC2X(B, I, Pf, R8, S, C) hipLaunchKernelGGL((k_lc2<B, I, Pf, R8, S, C>), dim3(grid), dim3(256), 0, st, fp, sbstart, rec, bloom32, img, O, counters, ovf_list, n_sb)
+#define YK_LC2X(B, I, Pf, R8, S, C) YK_LAUNCH((k_lc2<B, I, Pf, R8, S, C>), dim3(grid), dim3(256), 0, st, fp, sbstart, rec, bloom32, img, O, counters, ovf_list, n_sb)
 #define YK_LC2(B, I, Pf) do { if constexpr (!B) { if (cap11) { if (fp.rec8_out) YK_LC2X(false, I, Pf, true, false, 11); else YK_LC2X(false, I, Pf, false, false, 11); } \
                                                   else if (fp.rec8_out) YK_LC2X(false, I, Pf, true, false, 10); else YK_LC2X(false, I, Pf, false, false, 10); } \
                               else { if (fp.rec8_out) YK_LC2X(true, I, Pf, true, true, 10); else YK_LC2X(true, I, Pf, false, true, 10); } } while (0)
@@ -563,7 +563,7 @@ void yk_launch_lc2(FastParams fp, const u64 *sbstart, const Rec *rec, u32 *bloom
 		const int v = (fp.bloom_mode ? 4 : 0) | (fp.img_nonempty ? 2 : 0) | ((fp.dbg & 128) ? 1 : 0);
 		if (nostage) {
 			if (fp.dbg & 128) YK_LC2X(true, false, true, true, false, 10);
-			else if (yk_knob("YAKAMD_LC2_W6", 1)) hipLaunchKernelGGL((k_lc2<true, false, false, true, false, 10, 6>), dim3(grid), dim3(256), 0, st, fp, sbstart, rec, bloom32, img, O, counters, ovf_list, n_sb);
+			else if (yk_knob("YAKAMD_LC2_W6", 1)) YK_LAUNCH((k_lc2<true, false, false, true, false, 10, 6>), dim3(grid), dim3(256), 0, st, fp, sbstart, rec, bloom32, img, O, counters, ovf_list, n_sb);
 			else YK_LC2X(true, false, false, true, false, 10);
 		}
 		else switch (v) {
@@ -592,37 +592,37 @@ void yk_launch_lc2(FastParams fp, const u64 *sbstart, const Rec *rec, u32 *bloom
 
 void yk_launch_lc_sum(const u32 *nsel, int s2_bits, int plo, int phi, u32 *seg_cnt, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_lc_sum, dim3(phi - plo), dim3(256), 0, st, nsel, s2_bits, plo, seg_cnt);
+	YK_LAUNCH(k_lc_sum, dim3(phi - plo), dim3(256), 0, st, nsel, s2_bits, plo, seg_cnt);
 }
 
 void yk_launch_bf_rebuild(FastParams fp, const u64 *sbstart, const Rec *rec, u32 *bloom32, hipStream_t st)
 {
 	const u32 n_sb = (u32)(fp.phi - fp.plo) << fp.s2_bits;
 	const u32 grid = std::min<u32>(n_sb, 256 * 8 * 16);
-	if (grid) hipLaunchKernelGGL(k_bf_rebuild, dim3(grid), dim3(256), 0, st, fp, sbstart, rec, bloom32, n_sb);
+	if (grid) YK_LAUNCH(k_bf_rebuild, dim3(grid), dim3(256), 0, st, fp, sbstart, rec, bloom32, n_sb);
 }
 void yk_launch_lc_sum3(LcOut O, int s2_bits, int plo, int phi, u64 t_pass0, u32 *seg_cnt, u64 *lastput, u32 *ndist_p, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_lc_sum3, dim3(phi - plo), dim3(256), 0, st, O, s2_bits, plo, t_pass0, seg_cnt, lastput, ndist_p);
+	YK_LAUNCH(k_lc_sum3, dim3(phi - plo), dim3(256), 0, st, O, s2_bits, plo, t_pass0, seg_cnt, lastput, ndist_p);
 }
 void yk_launch_lc_gather(LcOut O, const u64 *sbstart, const u64 *key_off, int s2_bits, int plo, int phi, u64 *out_kc, u64 *out_T, Rec *out_kt, u32 *out_c2, hipStream_t st)
 {
 	const u32 n_sb = (u32)(phi - plo) << s2_bits;
 	const u32 grid = (u32)std::min<u64>(((u64)n_sb + 255) / 256, 256 * 8 * 16);
-	if (grid) hipLaunchKernelGGL(k_lc_gather, dim3(grid), dim3(256), 0, st, O, sbstart, key_off, (u32)plo << s2_bits, n_sb, out_kc, out_T, out_kt, out_c2);
+	if (grid) YK_LAUNCH(k_lc_gather, dim3(grid), dim3(256), 0, st, O, sbstart, key_off, (u32)plo << s2_bits, n_sb, out_kc, out_T, out_kt, out_c2);
 }
 void yk_launch_lc_compact(LcOut O, const u64 *sbstart, int s2_bits, int plo, int phi, u64 t_pass0, const u64 *seg_base,
                           u64 *out_kc, u64 *out_T, u64 *lastput, u32 *ndist_p, Rec *out_kt, u32 *out_c2, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_lc_compact, dim3(phi - plo), dim3(256), 0, st, O, sbstart, s2_bits, plo, t_pass0, seg_base, out_kc, out_T, lastput, ndist_p, out_kt, out_c2);
+	YK_LAUNCH(k_lc_compact, dim3(phi - plo), dim3(256), 0, st, O, sbstart, s2_bits, plo, t_pass0, seg_base, out_kc, out_T, lastput, ndist_p, out_kt, out_c2);
 }
 
 void yk_launch_seg_sort_pass2(const u64 *seg_base, const u32 *seg_cnt, int P, const u64 *src_kc, const u64 *src_t,
                               u64 *dst_kc, u64 *dst_t, int shift, hipStream_t st, int big)
 {
 	/* long segments (an assembly: ~1 M keys per sub-table): 1024 threads per sub-table */
-	if (big) hipLaunchKernelGGL((k_seg_sort_pass<8, 1024>), dim3(P), dim3(1024), 0, st, seg_base, seg_cnt, src_kc, src_t, dst_kc, dst_t, shift);
-	else hipLaunchKernelGGL((k_seg_sort_pass<8, 256>), dim3(P), dim3(256), 0, st, seg_base, seg_cnt, src_kc, src_t, dst_kc, dst_t, shift);
+	if (big) YK_LAUNCH((k_seg_sort_pass<8, 1024>), dim3(P), dim3(1024), 0, st, seg_base, seg_cnt, src_kc, src_t, dst_kc, dst_t, shift);
+	else YK_LAUNCH((k_seg_sort_pass<8, 256>), dim3(P), dim3(256), 0, st, seg_base, seg_cnt, src_kc, src_t, dst_kc, dst_t, shift);
 }
 void yk_launch_cnt2(FastParams fp, const u64 *sbstart, const Rec *rec, const u64 *key_off, const u64 *key_kc, const u64 *seg_base, u32 *key_cnt, ImgView img, u64 n_keys, u32 *used_delta, hipStream_t st)
 {
@@ -632,24 +632,19 @@ void yk_launch_cnt2(FastParams fp, const u64 *sbstart, const Rec *rec, const u64
 	const int wgs = (int)yk_knob("YAKAMD_CNT2_WGS", 256 * 1024);
 	const int small_max = (int)yk_knob("YAKAMD_CNT2_SMALL", 128);   /* mean keys per sub-bucket up to which the small LDS table is used (a fuller sub-bucket falls back to table lookups: exact, slow) */
 	const dim3 grid(std::min<u32>(n_sb, (u32)std::max(1, wgs)));
-	if (n_sb && small_max >= 0 && n_keys / n_sb <= (u64)small_max) hipLaunchKernelGGL((k_cnt2<512, 320>), grid, dim3(256), 0, st, fp, sbstart, rec, key_off, key_kc, img, n_sb, key_cnt, used_delta);
-	else hipLaunchKernelGGL((k_cnt2<2048, 1280>), grid, dim3(256), 0, st, fp, sbstart, rec, key_off, key_kc, img, n_sb, key_cnt, used_delta);
+	if (n_sb && small_max >= 0 && n_keys / n_sb <= (u64)small_max) YK_LAUNCH((k_cnt2<512, 320>), grid, dim3(256), 0, st, fp, sbstart, rec, key_off, key_kc, img, n_sb, key_cnt, used_delta);
+	else YK_LAUNCH((k_cnt2<2048, 1280>), grid, dim3(256), 0, st, fp, sbstart, rec, key_off, key_kc, img, n_sb, key_cnt, used_delta);
 	yk_launch_cnt2_apply(fp, key_kc, key_cnt, seg_base, img, st);
 }
 void yk_launch_cnt2_apply(FastParams fp, const u64 *key_kc, const u32 *key_cnt, const u64 *seg_base, ImgView img, hipStream_t st)
 {
 	const int n_p = fp.phi - fp.plo;
 	const int per = std::max(1, 8192 / std::max(1, n_p));                  /* ~8 K workgroups in all */
-	hipLaunchKernelGGL(k_cnt2_apply, dim3(per, n_p), dim3(256), 0, st, key_kc, key_cnt, seg_base, fp.plo, fp.pre, img);
+	YK_LAUNCH(k_cnt2_apply, dim3(per, n_p), dim3(256), 0, st, key_kc, key_cnt, seg_base, fp.plo, fp.pre, img);
 }
 void yk_launch_nsel_scan(const u32 *nsel, int s2_bits, int plo, int phi, int P, const u64 *seg_base, u64 *key_off, hipStream_t st)
 {
-	hipLaunchKernelGGL(k_nsel_scan, dim3(P), dim3(256), 0, st, nsel, s2_bits, plo, phi, P, seg_base, key_off);
-}
-
-void yk_launch_fill_u64(u64 *p, u64 v, u64 n, hipStream_t st)
-{
-	if (n) hipLaunchKernelGGL(k_fill_u64, dim3(grid_for(n)), dim3(256), 0, st, p, v, n);
+	YK_LAUNCH(k_nsel_scan, dim3(P), dim3(256), 0, st, nsel, s2_bits, plo, phi, P, seg_base, key_off);
 }
 
 /* yak inspect's join (kern_inspect.inc): one persistent grid over the n keys, as many workgroups as the LDS lets share a CU (the 64 KiB corner
@@ -676,9 +671,9 @@ int yk_launch_inspect(const u64 *keys, const u64 *off, u64 n, int n_sub, int sub
 			hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
 		attr = true;
 	}
-	if (!has_b) hipLaunchKernelGGL((k_inspect<false, false>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
-	else if (lng) hipLaunchKernelGGL((k_inspect<true, true>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
-	else hipLaunchKernelGGL((k_inspect<true, false>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
+	if (!has_b) YK_LAUNCH((k_inspect<false, false>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
+	else if (lng) YK_LAUNCH((k_inspect<true, true>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
+	else YK_LAUNCH((k_inspect<true, false>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -690,19 +685,19 @@ void yk_launch_dp_short(DpArgs a, u64 g0, u32 n_win, u32 T, void *out, u32 *long
 {
 	if (n_win == 0) return;
 	const u64 want = ((u64)n_win + DP_THREADS / WAVE - 1) / (DP_THREADS / WAVE);
-	hipLaunchKernelGGL(k_dp_short, dim3((unsigned)std::min<u64>(want, 65536)), dim3(DP_THREADS), 0, st, a, g0, n_win, T, (DpOut*)out, long_list, tile_base,
+	YK_LAUNCH(k_dp_short, dim3((unsigned)std::min<u64>(want, 65536)), dim3(DP_THREADS), 0, st, a, g0, n_win, T, (DpOut*)out, long_list, tile_base,
 	                   long_cap, (unsigned long long*)counter);
 }
 void yk_launch_dp_long(DpArgs a, u64 g0, const u32 *long_list, const u64 *tile_base, u32 slot0, u32 n_slots, u64 tile0, u64 n_tiles, u64 *hist, hipStream_t st)
 {
-	if (n_tiles) hipLaunchKernelGGL(k_dp_long, dim3((unsigned)n_tiles), dim3(DP_THREADS), 0, st, a, g0, long_list, tile_base, slot0, n_slots, tile0,
+	if (n_tiles) YK_LAUNCH(k_dp_long, dim3((unsigned)n_tiles), dim3(DP_THREADS), 0, st, a, g0, long_list, tile_base, slot0, n_slots, tile0,
 	                                (unsigned long long*)hist);
 }
 void yk_launch_dp_finish(const u64 *hist, const u32 *long_list, u32 slot0, u32 n_slots, void *out, hipStream_t st)
 {
 	if (n_slots == 0) return;
 	const u32 want = (n_slots + DP_THREADS / WAVE - 1) / (DP_THREADS / WAVE);
-	hipLaunchKernelGGL(k_dp_finish, dim3(std::min<u32>(want, 65536)), dim3(DP_THREADS), 0, st, (const unsigned long long*)hist, long_list, slot0, n_slots, (DpOut*)out);
+	YK_LAUNCH(k_dp_finish, dim3(std::min<u32>(want, 65536)), dim3(DP_THREADS), 0, st, (const unsigned long long*)hist, long_list, slot0, n_slots, (DpOut*)out);
 }
 
 /* `yak-amd hetmers` (kern_hetmer.inc): one persistent grid over the n staged keys of sub-tables [sub_lo, sub_lo + n_sub), probing the whole image.
@@ -733,9 +728,9 @@ int yk_launch_hetmer(int mode, const u64 *keys, const u64 *off, u64 n, int n_sub
 			if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) return -1;
 		attr = true;
 	}
-	if (mode == 0) hipLaunchKernelGGL((k_hetmer<HM_TALLY>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
-	else if (mode == 1) hipLaunchKernelGGL((k_hetmer<HM_COUNT>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
-	else hipLaunchKernelGGL((k_hetmer<HM_WRITE>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
+	if (mode == 0) YK_LAUNCH((k_hetmer<HM_TALLY>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
+	else if (mode == 1) YK_LAUNCH((k_hetmer<HM_COUNT>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
+	else YK_LAUNCH((k_hetmer<HM_WRITE>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -753,7 +748,7 @@ int yk_launch_graph(int what, int inflight, int grid_want, const u64 *tile0, con
 	a.t_lo = t_lo; a.t_hi = t_hi; a.n_slots = n_slots; a.P = P; a.k = img.k; a.min_cnt = min_cnt;
 	a.tab = img.pre <= 12;
 	if (what == 1) {
-		hipLaunchKernelGGL(k_graph_rank, dim3((unsigned)P), dim3(256), 0, st, a, img);
+		YK_LAUNCH(k_graph_rank, dim3((unsigned)P), dim3(256), 0, st, a, img);
 		return hipGetLastError() == hipSuccess ? 0 : -1;
 	}
 	if (t_hi == t_lo) return 0;
@@ -761,10 +756,10 @@ int yk_launch_graph(int what, int inflight, int grid_want, const u64 *tile0, con
 	int dev = 0, n_cu = 0;
 	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
 	const u64 grid = std::max<u64>(std::min<u64>(grid_want > 0 ? (u64)grid_want : (u64)n_cu * 4, t_hi - t_lo), 1);
-	if (what == 0 && inflight == 8) hipLaunchKernelGGL((k_graph_edges<8>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
-	else if (what == 0) hipLaunchKernelGGL((k_graph_edges<4>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
-	else if (what == 2) hipLaunchKernelGGL((k_graph_link<GR_COUNT>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
-	else hipLaunchKernelGGL((k_graph_link<GR_EMIT>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
+	if (what == 0 && inflight == 8) YK_LAUNCH((k_graph_edges<8>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
+	else if (what == 0) YK_LAUNCH((k_graph_edges<4>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
+	else if (what == 2) YK_LAUNCH((k_graph_link<GR_COUNT>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
+	else YK_LAUNCH((k_graph_link<GR_EMIT>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -776,22 +771,22 @@ void yk_launch_hpc_count(const void *in, const u32 *valid, int64_t n, u32 *tcnt,
 {
 	const int64_t nt = yk_hpc_tiles(valid != 0, n);
 	if (nt <= 0) return;
-	if (valid) hipLaunchKernelGGL(k_hpc_count<HpPacked>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpPacked{ (const u32*)in, valid }, n, tcnt);
-	else hipLaunchKernelGGL(k_hpc_count<HpAscii>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpAscii{ (const uint8_t*)in }, n, tcnt);
+	if (valid) YK_LAUNCH(k_hpc_count<HpPacked>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpPacked{ (const u32*)in, valid }, n, tcnt);
+	else YK_LAUNCH(k_hpc_count<HpAscii>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpAscii{ (const uint8_t*)in }, n, tcnt);
 }
 void yk_launch_hpc_scatter(const void *in, const u32 *valid, int64_t n, const u64 *toff, uint8_t *out, hipStream_t st)
 {
 	const int64_t nt = yk_hpc_tiles(valid != 0, n);
 	if (nt <= 0) return;
-	if (valid) hipLaunchKernelGGL(k_hpc_scatter<HpPacked>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpPacked{ (const u32*)in, valid }, n, toff, nt, out);
-	else hipLaunchKernelGGL(k_hpc_scatter<HpAscii>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpAscii{ (const uint8_t*)in }, n, toff, nt, out);
+	if (valid) YK_LAUNCH(k_hpc_scatter<HpPacked>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpPacked{ (const u32*)in, valid }, n, toff, nt, out);
+	else YK_LAUNCH(k_hpc_scatter<HpAscii>, dim3((unsigned)nt), dim3(HP_THREADS), 0, st, HpAscii{ (const uint8_t*)in }, n, toff, nt, out);
 }
 /* one wave per sequence; toff = the scan of the ASCII form's tiles */
 void yk_launch_hpc_remap(const uint8_t *a, int64_t n, const u64 *toff, const u64 *off, const u32 *len, int64_t n_seq, u64 *off_out, u32 *len_out, hipStream_t st)
 {
 	if (n_seq <= 0) return;
 	const int64_t nb = (n_seq + HP_THREADS / WAVE - 1) / (HP_THREADS / WAVE);
-	hipLaunchKernelGGL(k_hpc_remap, dim3((unsigned)nb), dim3(HP_THREADS), 0, st, HpAscii{ a }, n, toff, off, len, n_seq, off_out, len_out);
+	YK_LAUNCH(k_hpc_remap, dim3((unsigned)nb), dim3(HP_THREADS), 0, st, HpAscii{ a }, n, toff, off, len, n_seq, off_out, len_out);
 }
 
 } /* extern "C" */

@@ -160,7 +160,7 @@ int yk_launch_kmers(const u64 *img, const u64 *off, u64 n, int n_sub, int sub_lo
 {
 	if (n == 0) return 0;
 	const u64 grid = std::min<u64>((n + PR_THREADS - 1) / PR_THREADS, 1u << 20);
-	hipLaunchKernelGGL(k_kmers, dim3((unsigned)grid), dim3(PR_THREADS), 0, st, pr_args(img, off, n, n_sub, sub_lo, k, pre), x, c);
+	YK_LAUNCH(k_kmers, dim3((unsigned)grid), dim3(PR_THREADS), 0, st, pr_args(img, off, n, n_sub, sub_lo, k, pre), x, c);
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -168,7 +168,7 @@ int yk_launch_print_sizes(const u64 *img, const u64 *off, u64 n, int n_sub, int 
 {
 	if (n == 0) return 0;
 	if (yk_print_tiles(n) >> 31) return -1;
-	hipLaunchKernelGGL(k_print_sizes, dim3((unsigned)yk_print_tiles(n)), dim3(PR_THREADS), 0, st, pr_args(img, off, n, n_sub, 0, k, 0), tile_bytes);
+	YK_LAUNCH(k_print_sizes, dim3((unsigned)yk_print_tiles(n)), dim3(PR_THREADS), 0, st, pr_args(img, off, n, n_sub, 0, k, 0), tile_bytes);
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -179,8 +179,8 @@ int yk_launch_print(const u64 *img, const u64 *off, u64 n, int n_sub, int sub_lo
 	if (k < 1 || k > 31 || (yk_print_tiles(n) >> 31)) return -1;
 	const PrArgs a = pr_args(img, off, n, n_sub, sub_lo, k, pre);
 	const size_t lds = (16 + (size_t)PR_TILE * (k + (with_counts ? 6 : 1)) + 15) & ~(size_t)15;   /* at most 37.9 KB (+ 4 KB of offsets with counts) */
-	if (with_counts) hipLaunchKernelGGL((k_print<true>), dim3((unsigned)yk_print_tiles(n)), dim3(PR_THREADS), lds, st, a, tile_off, text);
-	else hipLaunchKernelGGL((k_print<false>), dim3((unsigned)yk_print_tiles(n)), dim3(PR_THREADS), lds, st, a, tile_off, text);
+	if (with_counts) YK_LAUNCH((k_print<true>), dim3((unsigned)yk_print_tiles(n)), dim3(PR_THREADS), lds, st, a, tile_off, text);
+	else YK_LAUNCH((k_print<false>), dim3((unsigned)yk_print_tiles(n)), dim3(PR_THREADS), lds, st, a, tile_off, text);
 	return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

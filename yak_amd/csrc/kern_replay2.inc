@@ -1182,10 +1182,4 @@ void k_put_u64(const u64 *pos, const u64 *val, u32 n, u64 *out)
 	if (i < n) out[pos[i]] = val[i];
 }
 
-__global__ __launch_bounds__(256)
-void k_fill_u64(u64 *p, u64 v, u64 n)
-{
-	const u64 stride = (u64)gridDim.x * blockDim.x;
-	for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) p[i] = v;
-}
 

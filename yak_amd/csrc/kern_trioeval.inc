@@ -192,48 +192,44 @@ void k_te_seq(const uint4 *__restrict__ list, const u64 *__restrict__ n_list, in
 int64_t yk_te_tiles(int64_t n) { return (n + TE_TILE - 1) / TE_TILE; }
 int64_t yk_te_keep_blocks(int64_t n_runs) { return (n_runs + TE_THREADS * TE_ITEMS - 1) / (TE_THREADS * TE_ITEMS); }
 
-template <typename M>
-static void te_runs(const uint8_t *flag, int64_t n, u32 *tcnt, const u64 *toff, u64 *st, u64 *en, int scatter, hipStream_t s)
+/* (macros, not templates: the launch tally names an instantiation as its launch site writes it) */
+#define YK_TE_RUNS(M) do { \
+		if (scatter) YK_LAUNCH((k_te_runs<true, M>), dim3((unsigned)nt), dim3(TE_THREADS), 0, s, flag, n, nt, tcnt, toff, st, en); \
+		else YK_LAUNCH((k_te_runs<false, M>), dim3((unsigned)nt), dim3(TE_THREADS), 0, s, flag, n, nt, tcnt, toff, st, en); \
+	} while (0)
+void yk_launch_te_runs(const uint8_t *flag, int64_t n, u32 *tcnt, const u64 *toff, u64 *st, u64 *en, int scatter, hipStream_t s, int low)
 {
 	const int64_t nt = yk_te_tiles(n);
 	if (nt <= 0) return;
-	if (scatter) hipLaunchKernelGGL((k_te_runs<true, M>), dim3((unsigned)nt), dim3(TE_THREADS), 0, s, flag, n, nt, tcnt, toff, st, en);
-	else hipLaunchKernelGGL((k_te_runs<false, M>), dim3((unsigned)nt), dim3(TE_THREADS), 0, s, flag, n, nt, tcnt, toff, st, en);
+	if (low) YK_TE_RUNS(TeMapLow);
+	else YK_TE_RUNS(TeMapTrio);
 }
-
-void yk_launch_te_runs(const uint8_t *flag, int64_t n, u32 *tcnt, const u64 *toff, u64 *st, u64 *en, int scatter, hipStream_t s, int low)
-{
-	if (low) te_runs<TeMapLow>(flag, n, tcnt, toff, st, en, scatter, s);
-	else te_runs<TeMapTrio>(flag, n, tcnt, toff, st, en, scatter, s);
-}
+#undef YK_TE_RUNS
 
 void yk_launch_te_scan(const u32 *cnt, int64_t m, int n_arrays, u64 *off, hipStream_t s)
 {
-	hipLaunchKernelGGL(k_te_scan, dim3((unsigned)n_arrays), dim3(1024), 0, s, cnt, m, off);
+	YK_LAUNCH(k_te_scan, dim3((unsigned)n_arrays), dim3(1024), 0, s, cnt, m, off);
 }
 
-template <typename M>
-static void te_keep(const u64 *st, const u64 *en, const uint8_t *flag, int64_t n_runs, int min_n, u32 *kcnt, const u64 *koff,
-                    const u64 *seq_off, int64_t n_seq, void *list, int scatter, hipStream_t s)
-{
-	const int64_t nb = yk_te_keep_blocks(n_runs);
-	if (nb <= 0) return;
-	if (scatter) hipLaunchKernelGGL((k_te_keep<true, M>), dim3((unsigned)nb), dim3(TE_THREADS), 0, s, st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, (uint4*)list);
-	else hipLaunchKernelGGL((k_te_keep<false, M>), dim3((unsigned)nb), dim3(TE_THREADS), 0, s, st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, (uint4*)list);
-}
-
+#define YK_TE_KEEP(M) do { \
+		if (scatter) YK_LAUNCH((k_te_keep<true, M>), dim3((unsigned)nb), dim3(TE_THREADS), 0, s, st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, (uint4*)list); \
+		else YK_LAUNCH((k_te_keep<false, M>), dim3((unsigned)nb), dim3(TE_THREADS), 0, s, st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, (uint4*)list); \
+	} while (0)
 void yk_launch_te_keep(const u64 *st, const u64 *en, const uint8_t *flag, int64_t n_runs, int min_n, u32 *kcnt, const u64 *koff,
                        const u64 *seq_off, int64_t n_seq, void *list, int scatter, hipStream_t s, int low)
 {
-	if (low) te_keep<TeMapLow>(st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, list, scatter, s);
-	else te_keep<TeMapTrio>(st, en, flag, n_runs, min_n, kcnt, koff, seq_off, n_seq, list, scatter, s);
+	const int64_t nb = yk_te_keep_blocks(n_runs);
+	if (nb <= 0) return;
+	if (low) YK_TE_KEEP(TeMapLow);
+	else YK_TE_KEEP(TeMapTrio);
 }
+#undef YK_TE_KEEP
 
 void yk_launch_te_seq(const void *list, const u64 *n_list, int64_t n_max, int k, int *cnt6, hipStream_t s)
 {
 	const int64_t nb = yk_te_keep_blocks(n_max);
 	if (nb <= 0) return;
-	hipLaunchKernelGGL(k_te_seq, dim3((unsigned)nb), dim3(TE_THREADS), 0, s, (const uint4*)list, n_list, k, cnt6);
+	YK_LAUNCH(k_te_seq, dim3((unsigned)nb), dim3(TE_THREADS), 0, s, (const uint4*)list, n_list, k, cnt6);
 }
 
 /* cnt[4 j ..] += n_k, n_sexchr, n_sex1, n_sex2 of record j (sexchr.c:57-65: flag > 0, == 1, == 2 over the positions where a k-mer ends); a position
@@ -313,5 +309,5 @@ void yk_launch_sc_reduce(const uint8_t *flag, int64_t n, const u64 *seq_off, con
 {
 	const int64_t nt = yk_te_tiles(n), nb = (nt + SC_ITERS - 1) / SC_ITERS;
 	if (nt <= 0 || n_seq <= 0) return;
-	hipLaunchKernelGGL(k_sc_reduce, dim3((unsigned)nb), dim3(TE_THREADS), 0, s, flag, n, seq_off, seq_len, n_seq, (unsigned long long*)cnt);
+	YK_LAUNCH(k_sc_reduce, dim3((unsigned)nb), dim3(TE_THREADS), 0, s, flag, n, seq_off, seq_len, n_seq, (unsigned long long*)cnt);
 }

@@ -19,6 +19,7 @@
  * shared; separate device compilation would need relocatable device code for them).
  */
 #include "yk_device.h"
+#include "tally.h"
 #include <algorithm>
 #include <type_traits>
 

@@ -213,10 +213,10 @@ static int r2_publish_commit(Replay2 &s)
 	HIPCK(hipStreamSynchronize(c->st));
 	if (h_fail) {
 		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] streaming replay refused (code %u): falling back to k_replay\n", h_fail);
-		++g_r2_refused;
+		++g_r2_refused; yk_event(YKE_R2_REFUSED);
 		return 1;
 	}
-	++g_r2_used;
+	++g_r2_used; yk_event(YKE_R2_USED);
 	for (int p = 0; p < P; ++p) {
 		c->h_bits[p] = pl.large[p] ? pl.bitsF[p] : s.ob[p];
 		c->h_count[p] = pl.large[p] ? pl.cntF[p] : s.oc[p];
