@@ -1,15 +1,17 @@
 # Build of the MI355X k-mer counting engine (gfx950 only) and its test infrastructure.
-#   make            -> yak_amd/libyak_amd.so (HIP kernels + C ABI), yak_amd/yak-amd (CLI),
+#   make            -> yak_amd/libyak_amd.so (HIP kernels + C ABI), yak_amd/libyak_amd_walk.so (the unitig walk on the GPU, a layer
+#                      above it), yak_amd/yak-amd (CLI),
 #                      tools/ (synthetic reads), oracle/ (CPU checker; + oracle/_ref if the
 #                      reference sources are present)
 HIPCC   ?= /opt/rocm/bin/hipcc
 ARCH    ?= gfx950
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -Wall -Wno-unused-result -Wno-unused-value
 CSRC    = yak_amd/csrc
+WALK    = yak_amd/walk
 
 all: lib cli tools oracle
 
-lib: yak_amd/libyak_amd.so
+lib: yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so
 cli: yak_amd/yak-amd
 
 yak_amd/kernels.o: $(CSRC)/kernels.hip $(wildcard $(CSRC)/kern_*.inc) $(CSRC)/yk_device.h $(CSRC)/replay_plan.h $(CSRC)/tally.h
@@ -46,8 +48,17 @@ yak_amd/yak_print.o: $(CSRC)/yak_print.cpp $(HOSTDEPS)
 yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/tally.o yak_amd/pool.o yak_amd/engine.o yak_amd/layout.o yak_amd/lookup_dev.o yak_amd/yak_hetmer.o yak_amd/yak_graph.o yak_amd/yak_hpc.o yak_amd/yak_api.o yak_amd/yak_reader.o yak_amd/yak_multi.o yak_amd/yak_lookup.o yak_amd/yak_inspect.o yak_amd/yak_print.o $(CSRC)/libyak_amd.map
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(CSRC)/libyak_amd.map -o $@ $(filter %.o,$^) -lz
 
-yak_amd/yak-amd: $(CSRC)/main.c include/yak.h include/yak_amd.h yak_amd/libyak_amd.so
-	gcc -O2 -Wall -Iinclude $(CSRC)/main.c -o $@ -Lyak_amd -lyak_amd -Wl,-rpath,'$$ORIGIN' -lz
+# the device walk of `yak-amd unitigs -g`: its own kernels and its own launch tally (tally.cpp a second time), public calls
+# of libyak_amd.so only
+yak_amd/walk.o: $(WALK)/walk.hip $(WALK)/uwalk_step.h $(WALK)/uwalk_host.h $(CSRC)/tally.h include/yak.h include/yak_amd.h include/yak_amd_walk.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+yak_amd/walk_tally.o: $(CSRC)/tally.cpp $(CSRC)/tally.h include/yak_amd.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+yak_amd/libyak_amd_walk.so: yak_amd/walk.o yak_amd/walk_tally.o yak_amd/libyak_amd.so $(WALK)/libyak_amd_walk.map
+	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(WALK)/libyak_amd_walk.map -o $@ $(filter %.o,$^) -Lyak_amd -lyak_amd -Wl,-rpath,'$$ORIGIN'
+
+yak_amd/yak-amd: $(CSRC)/main.c include/yak.h include/yak_amd.h include/yak_amd_walk.h yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so
+	gcc -O2 -Wall -Iinclude $(CSRC)/main.c -o $@ -Lyak_amd -lyak_amd_walk -lyak_amd -Wl,-rpath,'$$ORIGIN' -lz
 
 tools:
 	$(MAKE) -C tools
@@ -55,7 +66,7 @@ oracle: lib
 	$(MAKE) -C oracle all ref
 
 clean:
-	rm -f yak_amd/*.o yak_amd/libyak_amd.so yak_amd/yak-amd
+	rm -f yak_amd/*.o yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so yak_amd/yak-amd
 	$(MAKE) -C tools clean
 	$(MAKE) -C oracle clean
 .PHONY: all lib cli tools oracle clean
