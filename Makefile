@@ -14,11 +14,11 @@ all: lib cli tools oracle
 lib: yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so
 cli: yak_amd/yak-amd
 
-yak_amd/kernels.o: $(CSRC)/kernels.hip $(wildcard $(CSRC)/kern_*.inc) $(CSRC)/yk_device.h $(CSRC)/replay_plan.h $(CSRC)/tally.h
+yak_amd/kernels.o: $(CSRC)/kernels.hip $(wildcard $(CSRC)/kern_*.inc) $(CSRC)/yk_device.h $(CSRC)/replay_plan.h $(CSRC)/seg_sort_tile.h $(CSRC)/tally.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/tally.o: $(CSRC)/tally.cpp $(CSRC)/tally.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/engine.o: $(CSRC)/engine.cpp $(CSRC)/engine_int.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
+yak_amd/engine.o: $(CSRC)/engine.cpp $(CSRC)/seg_sort_tile.h $(CSRC)/engine_int.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 yak_amd/layout.o: $(CSRC)/layout.cpp $(CSRC)/engine_int.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/yk_device.h $(CSRC)/replay_plan.h include/yak.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@

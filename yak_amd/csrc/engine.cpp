@@ -25,6 +25,7 @@
 #include <chrono>
 #include <atomic>
 #include "engine_int.h"
+#include "seg_sort_tile.h"
 
 static thread_local char g_err[512] = "";
 
@@ -1510,11 +1511,14 @@ static int slice_sort(yakamd_ctx *c, Slice &s)
 	}
 	s.kt.reset();
 	if (!sorted) {
-		if (s.kc[1].alloc(n_sel) || s.tt[1].alloc(n_sel)) return -1;
+		/* the first pass counts every digit's histogram in its one sweep over the times, the later ones take theirs from dig_hist */
+		const int n_dig = sst_n_digits(s.tbits);
+		DevBuf<u32> dig_hist;
+		if (s.kc[1].alloc(n_sel) || s.tt[1].alloc(n_sel) || (n_dig > 1 && dig_hist.alloc((size_t)P * n_dig * SST_NBIN))) return -1;
 		EvTimer tm(c->st);
 		const int sort_big = n_sel / (u64)std::max(1, c->phi - c->plo) >= 30000;
 		for (int shift = 0; shift < s.tbits; shift += 8) {
-			yk_launch_seg_sort_pass2(s.segbase, s.segcur, P, s.kc[s.cur], s.tt[s.cur], s.kc[s.cur ^ 1], s.tt[s.cur ^ 1], shift, c->st, sort_big);
+			yk_launch_seg_sort_pass2(s.segbase, s.segcur, P, s.kc[s.cur], s.tt[s.cur], s.kc[s.cur ^ 1], s.tt[s.cur ^ 1], shift, dig_hist, n_dig, c->st, sort_big);
 			s.cur ^= 1;
 		}
 		c->st_cur.ms_sort += tm.stop();
@@ -1608,9 +1612,11 @@ static int64_t pass_end_body(yakamd_ctx *c)
 			dfree(c->acc.s);                              /* the accumulator is no longer needed */
 			{
 				EvTimer tm(c->st);
-				const int tbits = std::max(1, ceil_log2_u64(c->t_end + 1));
+				const int tbits = std::max(1, ceil_log2_u64(c->t_end + 1)), n_dig = sst_n_digits(tbits);
+				DevBuf<u32> dig_hist;                          /* every digit's histogram, counted by the first pass */
+				if (n_dig > 1 && dig_hist.alloc((size_t)P * n_dig * SST_NBIN)) return -1;
 				for (int shift = 0; shift < tbits; shift += 8) {
-					yk_launch_seg_sort_pass(d_segoff, P, kc[cur], tt[cur], kc[cur ^ 1], tt[cur ^ 1], shift, c->st);
+					yk_launch_seg_sort_pass(d_segoff, P, kc[cur], tt[cur], kc[cur ^ 1], tt[cur ^ 1], shift, dig_hist, n_dig, c->st);
 					cur ^= 1;
 				}
 				c->st_cur.ms_sort += tm.stop();

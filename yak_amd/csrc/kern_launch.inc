@@ -249,9 +249,9 @@ void yk_launch_select_scatter(AccTab tab, int bloom_mode, int P, const u64 *seg_
 }
 
 void yk_launch_seg_sort_pass(const u64 *seg_off, int P, const u64 *src_kc, const u64 *src_t,
-                             u64 *dst_kc, u64 *dst_t, int shift, hipStream_t st)
+                             u64 *dst_kc, u64 *dst_t, int shift, u32 *dig_hist, int n_dig, hipStream_t st)
 {
-	YK_LAUNCH((k_seg_sort_pass<8, 256>), dim3(P), dim3(256), 0, st, seg_off, (const u32*)0, src_kc, src_t, dst_kc, dst_t, shift);
+	YK_LAUNCH((k_seg_sort_pass<8, 256>), dim3(P), dim3(256), 0, st, seg_off, (const u32*)0, src_kc, src_t, dst_kc, dst_t, shift, dig_hist, n_dig);
 }
 
 void yk_launch_replay(const ReplayTask *tasks, int n_tasks, int n_threads, const u64 *old_keys, const u32 *old_used,
@@ -618,11 +618,11 @@ void yk_launch_lc_compact(LcOut O, const u64 *sbstart, int s2_bits, int plo, int
 }
 
 void yk_launch_seg_sort_pass2(const u64 *seg_base, const u32 *seg_cnt, int P, const u64 *src_kc, const u64 *src_t,
-                              u64 *dst_kc, u64 *dst_t, int shift, hipStream_t st, int big)
+                              u64 *dst_kc, u64 *dst_t, int shift, u32 *dig_hist, int n_dig, hipStream_t st, int big)
 {
 	/* long segments (an assembly: ~1 M keys per sub-table): 1024 threads per sub-table */
-	if (big) YK_LAUNCH((k_seg_sort_pass<8, 1024>), dim3(P), dim3(1024), 0, st, seg_base, seg_cnt, src_kc, src_t, dst_kc, dst_t, shift);
-	else YK_LAUNCH((k_seg_sort_pass<8, 256>), dim3(P), dim3(256), 0, st, seg_base, seg_cnt, src_kc, src_t, dst_kc, dst_t, shift);
+	if (big) YK_LAUNCH((k_seg_sort_pass<8, 1024>), dim3(P), dim3(1024), 0, st, seg_base, seg_cnt, src_kc, src_t, dst_kc, dst_t, shift, dig_hist, n_dig);
+	else YK_LAUNCH((k_seg_sort_pass<8, 256>), dim3(P), dim3(256), 0, st, seg_base, seg_cnt, src_kc, src_t, dst_kc, dst_t, shift, dig_hist, n_dig);
 }
 void yk_launch_cnt2(FastParams fp, const u64 *sbstart, const Rec *rec, const u64 *key_off, const u64 *key_kc, const u64 *seg_base, u32 *key_cnt, ImgView img, u64 n_keys, u32 *used_delta, hipStream_t st)
 {

@@ -3,27 +3,53 @@
  * per sub-table stable LSD radix sort pass (8-bit digit of T), one workgroup per sub-table.
  * Stable ranking: the tile is split wave-major, each wave ranks its 64 elements per round with
  * eight ballots (peers with an equal digit), per-wave digit counters live in LDS.
+ * The tile is then laid out by digit in an LDS copy and stored in index order: consecutive lanes
+ * write consecutive elements of one digit's run (seg_sort_tile.h has the arithmetic).
  * ------------------------------------------------------------------------------------------ */
-#define SS_E 8
 template <int BITS, int NT>   /* digit width; threads per workgroup (256, or 1024 for long segments: four times the loads in flight per sub-table).
-                               * 8 bits: a tile of NT x 8 keys leaves >= 8 neighbours per digit, i.e. 64-byte runs in the output; 11-bit digits (two passes for 22-bit
-                               * ranks, the first one fused with the gather of the fragments) were measured and lost: one key per digit and tile means lone 8-byte
-                               * stores, and the saved pass does not pay for them */
-__global__ __launch_bounds__(NT)
+                               * 8 bits: a tile of 2048 or 4096 keys leaves >= 8 neighbours per digit, i.e. runs of 64 bytes and more that whole groups of lanes write;
+                               * 11-bit digits (two passes for 22-bit ranks, the first one fused with the gather of the fragments) were measured and lost: one key per
+                               * digit and tile means lone 8-byte stores, and the saved pass does not pay for them.
+                               * dig_hist: 256 counters per digit of T and sub-table (sst_hist_row).  The pass with shift 0 counts all n_dig digits in its one
+                               * sweep over the times and leaves them there, the later ones take theirs from it (a histogram does not depend on the order).
+                               * Without it every pass sweeps for its own digit */
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 1024 ? 8 : 4)))   /* two workgroups of 1024 per CU (<= 64 VGPRs), four of 256 (eight keys per thread: ~100 VGPRs) */
 void k_seg_sort_pass(const u64 *__restrict__ seg_off, const u32 *__restrict__ seg_len, const u64 *__restrict__ src_kc, const u64 *__restrict__ src_t,
-                     u64 *__restrict__ dst_kc, u64 *__restrict__ dst_t, int shift)
+                     u64 *__restrict__ dst_kc, u64 *__restrict__ dst_t, int shift, u32 *__restrict__ dig_hist, int n_dig)
 {
-	constexpr int NBIN = 1 << BITS, NWV = NT / 64;
+	constexpr int NBIN = 1 << BITS, NWV = NT / 64, SS_E = sst_per_thread(NT), TILE = sst_tile(NT);
 	static_assert(NBIN == 256, "the scans below give four digits to each lane of one wave");
-	__shared__ u32 s_hist[NBIN];
+	static_assert(NBIN == SST_NBIN && NT >= NBIN, "one thread per digit");
+	__shared__ u32 s_hist[NBIN];                                /* where the digit's next element goes in the segment */
+	__shared__ u32 s_start[NBIN];                               /* the tile's count of the digit, then where its run starts in the tile */
+	__shared__ u32 s_base[NBIN];                                /* sst_base: s_hist - s_start */
 	__shared__ u32 s_wc[NWV][NBIN];
+	__shared__ u64 s_stage[TILE];                               /* the tile by digit: its times, then its keys */
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-	const u64 a = seg_off[blockIdx.x], len = seg_len ? (u64)seg_len[blockIdx.x] : seg_off[blockIdx.x + 1] - a;
+	const u64 a = seg_off[blockIdx.x];
+	const u32 len = seg_len ? seg_len[blockIdx.x] : (u32)(seg_off[blockIdx.x + 1] - a);   /* (offsets inside a segment are 32-bit throughout) */
 	if (len == 0) return;
 	if (len == 1) { if (tid == 0) { dst_kc[a] = src_kc[a]; dst_t[a] = src_t[a]; } return; }
-	for (int q = tid; q < NBIN; q += NT) s_hist[q] = 0;
-	__syncthreads();
-	for (u64 i = tid; i < len; i += NT) atomicAdd(&s_hist[(src_t[a + i] >> shift) & (NBIN - 1)], 1u);
+	if (dig_hist && shift > 0) {
+		for (int q = tid; q < NBIN; q += NT) s_hist[q] = dig_hist[sst_hist_row(blockIdx.x, n_dig, shift / BITS) + q];
+	} else if (dig_hist && n_dig > 1) {                         /* (n_dig <= SST_MAX_DIGITS: the rows of the later digits borrow the stage) */
+		static_assert(sizeof(s_stage) >= (SST_MAX_DIGITS - 1) * NBIN * sizeof(u32), "rows for the digits behind the first");
+		u32 *rows = (u32*)s_stage;
+		for (int q = tid; q < NBIN; q += NT) s_hist[q] = 0;
+		for (int q = tid; q < (n_dig - 1) * NBIN; q += NT) rows[q] = 0;
+		__syncthreads();
+		for (u32 i = tid; i < len; i += NT) {
+			const u64 t = src_t[a + i];
+			atomicAdd(&s_hist[sst_digit(t, 0)], 1u);
+			for (int j = 1; j < n_dig; ++j) atomicAdd(&rows[(j - 1) * NBIN + sst_digit(t, j * BITS)], 1u);
+		}
+		__syncthreads();
+		for (int q = tid; q < (n_dig - 1) * NBIN; q += NT) dig_hist[sst_hist_row(blockIdx.x, n_dig, 1) + q] = rows[q];
+	} else {
+		for (int q = tid; q < NBIN; q += NT) s_hist[q] = 0;
+		__syncthreads();
+		for (u32 i = tid; i < len; i += NT) atomicAdd(&s_hist[sst_digit(src_t[a + i], shift)], 1u);
+	}
 	__syncthreads();
 	if (tid < 64) {                                              /* exclusive scan of the 256 digit counts by one wave */
 		u32 v[4], t = 0;
@@ -33,19 +59,19 @@ void k_seg_sort_pass(const u64 *__restrict__ seg_off, const u32 *__restrict__ se
 		u32 e = incl - t;
 		for (int q = 0; q < 4; ++q) { s_hist[4 * tid + q] = e; e += v[q]; }
 	}
-	__syncthreads();
-	for (u64 tile = 0; tile < len; tile += (u64)NT * SS_E) {
-		for (int w = 0; w < NWV; ++w) for (int q = tid; q < NBIN; q += NT) s_wc[w][q] = 0;
-		__syncthreads();
+	for (u32 tile = 0; tile < len; tile += TILE) {
+		const u32 n_tile = std::min<u32>(TILE, len - tile);
+		for (int q = tid; q < NWV * NBIN; q += NT) (&s_wc[0][0])[q] = 0;
+		__syncthreads();                                         /* (and the scan above, and the stores of the tile before) */
 		u64 et[SS_E], ek[SS_E];
 		u32 erk[SS_E];
 #pragma unroll
 		for (int r = 0; r < SS_E; ++r) {
-			const u64 idx = tile + (u64)wave * (64 * SS_E) + r * 64 + lane;
+			const u32 idx = (u32)sst_src_index(tile, wave, r, lane, SS_E);
 			const bool valid = idx < len;
-			u64 t = 0, kc = 0;
-			if (valid) { t = src_t[a + idx]; kc = src_kc[a + idx]; }
-			const u32 d = (u32)(t >> shift) & (NBIN - 1);
+			u64 t = 0;
+			if (valid) t = src_t[a + idx];
+			const u32 d = sst_digit(t, shift);
 			u64 peers = __ballot(valid);
 #pragma unroll
 			for (int b = 0; b < BITS; ++b) {
@@ -56,24 +82,57 @@ void k_seg_sort_pass(const u64 *__restrict__ seg_off, const u32 *__restrict__ se
 			const int leader = valid ? __ffsll((long long)peers) - 1 : lane;
 			if (valid && lane == leader) { old = s_wc[wave][d]; s_wc[wave][d] = old + __popcll(peers); }
 			old = __shfl(old, leader);
-			et[r] = t; ek[r] = kc;
-			erk[r] = valid ? (d << 24 | (old + __popcll(peers & lanemask_lt()))) : 0xffffffffu;
+			et[r] = t;
+			erk[r] = valid ? (d << 24 | (old + __builtin_amdgcn_mbcnt_hi((u32)(peers >> 32), __builtin_amdgcn_mbcnt_lo((u32)peers, 0u)))) : 0xffffffffu;   /* + the peers in lower lanes */
 		}
+#pragma unroll
+		for (int r = 0; r < SS_E; ++r)                           /* the keys are not needed before the copy is laid out: their loads run under the scans */
+			if (erk[r] != 0xffffffffu) ek[r] = src_kc[a + (u32)sst_src_index(tile, wave, r, lane, SS_E)];
 		__syncthreads();
-		if (tid < NBIN) {	/* digit `tid`: turn per-wave counts into start offsets, advance the running offset */
-			u32 run = s_hist[tid];
-			for (int w = 0; w < NWV; ++w) { const u32 c = s_wc[w][tid]; s_wc[w][tid] = run; run += c; }
-			s_hist[tid] = run;
+		if (tid < NBIN) s_start[tid] = sst_wave_prefix(&s_wc[0][0], NWV, tid);
+		__syncthreads();
+		if (tid < 64) {                                          /* the digits' runs inside the tile: exclusive scan of the tile's counts; the running offsets move on */
+			u32 v[4], t = 0;
+			for (int q = 0; q < 4; ++q) { v[q] = s_start[4 * tid + q]; t += v[q]; }
+			u32 incl = t;
+#pragma nounroll                                            /* (unrolled, the six source lanes are kept in registers across the whole tile loop) */
+			for (int o = 1; o < 64; o <<= 1) { const u32 x = __shfl_up(incl, o); if (lane >= o) incl += x; }
+			u32 e = incl - t;
+			for (int q = 0; q < 4; ++q) {
+				const u32 run = s_hist[4 * tid + q];
+				s_start[4 * tid + q] = e; s_base[4 * tid + q] = sst_base(run, e); s_hist[4 * tid + q] = run + v[q];
+				e += v[q];
+			}
 		}
 		__syncthreads();
 #pragma unroll
 		for (int r = 0; r < SS_E; ++r) {
 			if (erk[r] != 0xffffffffu) {
-				const u64 d = a + s_wc[wave][erk[r] >> 24] + (erk[r] & 0xffffff);
-				dst_kc[d] = ek[r]; dst_t[d] = et[r];
+				const u32 d = erk[r] >> 24;
+				erk[r] = sst_lds_pos(s_start[d], s_wc[wave][d], erk[r] & 0xffffff);
+				s_stage[erk[r]] = et[r];
 			}
 		}
 		__syncthreads();
+		u32 g[SS_E];                                             /* where the copy's element r x NT + tid goes in the segment */
+#pragma unroll
+		for (int r = 0; r < SS_E; ++r) {
+			const u32 i = r * NT + tid;
+			if (i < n_tile) {
+				const u64 t = s_stage[i];
+				g[r] = (u32)(sst_global(a, s_base[sst_digit(t, shift)], i) - a);
+				dst_t[a + g[r]] = t;
+			}
+		}
+		__syncthreads();
+#pragma unroll
+		for (int r = 0; r < SS_E; ++r) if (erk[r] != 0xffffffffu) s_stage[erk[r]] = ek[r];
+		__syncthreads();
+#pragma unroll
+		for (int r = 0; r < SS_E; ++r) {
+			const u32 i = r * NT + tid;
+			if (i < n_tile) dst_kc[a + g[r]] = s_stage[i];
+		}
 	}
 }
 

@@ -20,6 +20,7 @@
  */
 #include "yk_device.h"
 #include "tally.h"
+#include "seg_sort_tile.h"
 #include <algorithm>
 #include <type_traits>
 

@@ -186,7 +186,7 @@ void yk_launch_select_count(AccTab tab, int bloom_mode, int P, u32 *seg_cnt, hip
 void yk_launch_select_scatter(AccTab tab, int bloom_mode, int P, const u64 *seg_off, u32 *seg_cur,
                               u64 *rec_kc, u64 *rec_t, hipStream_t st);
 void yk_launch_seg_sort_pass(const u64 *seg_off, int P, const u64 *src_kc, const u64 *src_t,
-                             u64 *dst_kc, u64 *dst_t, int shift, hipStream_t st);
+                             u64 *dst_kc, u64 *dst_t, int shift, u32 *dig_hist, int n_dig, hipStream_t st);
 void yk_launch_replay(const ReplayTask *tasks, int n_tasks, int n_threads, const u64 *old_keys, const u32 *old_used,
                       u64 *new_keys, u32 *new_used, u32 *scr_used, u32 *scr_owner, u64 *scr_par,
                       const u64 *rec_kc, const u64 *rec_t, const u64 *lastput,
@@ -299,7 +299,7 @@ void yk_launch_cnt2(FastParams fp, const u64 *sbstart, const Rec *rec, const u64
 void yk_launch_cnt2_apply(FastParams fp, const u64 *key_kc, const u32 *key_cnt, const u64 *seg_base, ImgView img, hipStream_t st);
 void yk_launch_nsel_scan(const u32 *nsel, int s2_bits, int plo, int phi, int P, const u64 *seg_base, u64 *key_off, hipStream_t st);
 void yk_launch_seg_sort_pass2(const u64 *seg_base, const u32 *seg_cnt, int P, const u64 *src_kc, const u64 *src_t,
-                              u64 *dst_kc, u64 *dst_t, int shift, hipStream_t st, int big);
+                              u64 *dst_kc, u64 *dst_t, int shift, u32 *dig_hist, int n_dig, hipStream_t st, int big);
 #ifdef __cplusplus
 }
 #endif
