@@ -93,7 +93,7 @@ R2_SEGMENTED = ["k_r2_place", "k_r2_spill", "k_r2_headfill", "k_r2_publish"]   #
 # (up to 9) with -b28 only; without a switch s2 = 1 / 1 / 2 / 1, below the write-combining scatters' 4 bits (k_part2<1>).  Tagged 8-byte records in
 # and out (k < 32, np_max < 2^(12 + s2)).
 EVERY_INSERT_PATH = {
-    # engine.cpp pass_begin: c->fast = ... YAKAMD_FAST != 0 -> consume_records' create_new branch; pass_end_body's accumulator branch
+    # engine_pass.cpp pass_begin: c->fast = ... YAKAMD_FAST != 0 -> consume_records' create_new branch; pass_end_body's accumulator branch
     "general_path": E(["k_acc_init", "k_bf_check", "k_bf_mapfill", "k_bf_resolve", "k_acc_insert", "k_select_count", "k_select_scatter", SORT256, "k_bf_test", "k_bf_set", "k_lastput", "k_xpart_wc<1>"], FAST_ONLY, slices="==0", fast_abandoned="==0"),
     # slice_plan: s2 = 0; with a filter nb - 9 - s2 > 7, so yk_lc2_ok refuses and slice_count sends every sub-bucket on (h_cnt[YKC_NOVF2] = n_all)
     "lds_overflow_to_global": E(["k_lds_count_ovf", P2_PLAIN], [WC8_7, WC8_8], lc2_passed_on=">0", ovf_groups=">0", ovf_more_groups="==0"),   # -b28: nb - 9 - 0 = 9 > 7

@@ -1,4 +1,4 @@
-/* engine.h -- internal interface between pool.cpp, engine.cpp, lookup_dev.cpp and the yak.h surface (yak_api.cpp, yak_reader.cpp, yak_multi.cpp) */
+/* engine.h -- internal interface between pool.cpp, the engine (engine_ctx.cpp, engine_pass.cpp, engine_slice.cpp, engine_table.cpp), lookup_dev.cpp and the yak.h surface (yak_api.cpp, yak_reader.cpp, yak_multi.cpp) */
 #ifndef YK_ENGINE_H
 #define YK_ENGINE_H
 #include <vector>

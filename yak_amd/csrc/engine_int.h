@@ -1,6 +1,7 @@
-/* engine_int.h -- what the engine's own translation units (engine.cpp: passes; layout.cpp: exact slot layout; lookup_dev.cpp: the device-level
- * exports of the lookup commands) share and nobody else sees:
- * the context of a table, the device-buffer helpers on top of the pool, the error macro. */
+/* engine_int.h -- what the engine's own translation units (engine_ctx.cpp: the context; engine_pass.cpp: passes and feeds; engine_slice.cpp: the
+ * count of a slice; engine_table.cpp: whole-table operations; layout.cpp: exact slot layout; lookup_dev.cpp: the device-level exports of the lookup
+ * commands) share and nobody else sees: the context of a table with the buffers it owns (dev_buf.h), the error macro, and the few functions that
+ * cross between those files. */
 #ifndef YK_ENGINE_INT_H
 #define YK_ENGINE_INT_H
 #include <stdio.h>
@@ -12,16 +13,16 @@
 #include <string>
 #include <mutex>
 #include <algorithm>
+#include <memory>
 #include "yk_device.h"
 #include "tally.h"
 #include "engine.h"
+#include "dev_buf.h"
 
 #define fail(...) yk_set_error(__VA_ARGS__)                  /* this thread's yakamd_last_error() text + a line on stderr; -1 */
 #define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail("%s:%d: %s -> %s", __FILE__, __LINE__, #x, hipGetErrorString(e_)); } while (0)
 
 static inline double now_ms() { return yk_now_ms(); }
-static inline void *pool_alloc(size_t bytes, bool plain = false) { return yk_pool_alloc(bytes, plain); }
-static inline void pool_free(void *p) { yk_pool_free(p); }
 
 static inline int64_t env_i64(const char *name, int64_t dflt) { return yk_knob(name, dflt); }
 
@@ -36,91 +37,97 @@ static inline u32 kh_bits_for(u32 want)
 	return lg > 2 ? lg : 2;
 }
 
+/* engine_ctx.cpp: streams and events are kept and handed out again (creating one costs a runtime call) */
+hipStream_t yk_stream_get(int dev);
+void yk_stream_put(int dev, hipStream_t x);
+hipEvent_t yk_ev_get();
+void yk_ev_put(hipEvent_t e);
 
-template <class T> static int dmalloc(T **p, size_t n)
-{
-	if (n == 0) n = 1;
-	*p = (T*)pool_alloc(n * sizeof(T));
-	if (!*p) return fail("device allocation of %zu bytes failed", n * sizeof(T));
-	return 0;
-}
-template <class T> static void dfree(T *&p) { if (p) { pool_free((void*)p); p = 0; } }
-
-/* one pool allocation owned by a scope: freed by its destructor or by reset(); release() hands the pointer to whoever frees it next */
-template <class T> class DevBuf {
-	T *p_ = 0;
-public:
-	DevBuf() = default;
-	explicit DevBuf(T *p) : p_(p) {}
-	DevBuf(DevBuf &&o) : p_(o.release()) {}
-	DevBuf &operator=(DevBuf &&o) { if (this != &o) { reset(); p_ = o.release(); } return *this; }   /* (and no copies) */
-	~DevBuf() { reset(); }
-	int alloc(size_t n) { reset(); return dmalloc(&p_, n); }
-	void reset() { dfree(p_); }
-	T *release() { T *p = p_; p_ = 0; return p; }
-	T *get() const { return p_; }
-	operator T *() const { return p_; }
+struct EvTimer {
+	hipEvent_t a, b; hipStream_t st;
+	EvTimer(hipStream_t s) : st(s) { a = yk_ev_get(); b = yk_ev_get(); hipEventRecord(a, st); }
+	double stop() { float ms = 0; hipEventRecord(b, st); hipEventSynchronize(b); hipEventElapsedTime(&ms, a, b); return ms; }
+	~EvTimer() { yk_ev_put(a); yk_ev_put(b); }
 };
 
+/* the stream of a context, handed back to the cache when the context goes */
+struct CtxStream {
+	hipStream_t s = 0; int dev = 0;
+	operator hipStream_t() const { return s; }
+	~CtxStream() { if (s) yk_stream_put(dev, s); }
+};
+struct HostFree { void operator()(void *p) const { (void)hipHostFree(p); } };
+struct CFree { void operator()(void *p) const { free(p); } };
+struct yak_ht_t;
+
+/* fast path: a level-1 partitioned batch kept until the slice is counted.  d_rec views the records: the batch's own buffer, or the caller's */
+struct Kept { DevBuf<Rec> own; Rec *d_rec = 0; u64 n = 0; u64 t0 = 0, span = 0; std::vector<u64> bstart; int fmt = 0; };   /* fmt 1: tagged 8-byte records (yk_device.h YK_R8_*) */
+
+/* what a pass holds and pass_free gives back */
+struct PassBufs {
+	std::vector<Kept> kept; u64 kept_bytes = 0;
+	AccTab acc = {}; DevBuf<AccSlot> acc_mem; u64 acc_count = 0;   /* the accumulator as the kernels see it, and its storage */
+	DevVec<Rec> rec;
+	DevVec<uint8_t> hpc;               /* a table in homopolymer-compressed space compacts every feed of bases into this buffer */
+	DevVec<u64> newlist, miss, cand;   /* the bloom gate's lists, grown together (new_reserve) */
+};
+
+/* level-1 records of the last create_new pass, kept for a count pass over the SAME input (yakamd_retain_input / yakamd_count_retained):
+ * the second pass of the bloom protocol (reference main.c:53-57) then neither reads nor hashes the input again */
+struct Retained { DevBuf<Rec> rec; u64 n = 0; std::vector<u64> bstart; };
+/* ... or, when the whole pass was one slice into an empty table, its level-2 records (grouped by sub-bucket) + the keys every sub-bucket put
+ * into the table: the count pass then owns each key's counter in LDS (k_cnt2) -- or, with kc2, takes every key's count as k_lc2 found it
+ * (the same records: min(instances, 1023) per key, in kkc's order) and only applies them */
+struct Ret2 { DevBuf<Rec> r2; DevBuf<u64> sbstart, koff, kkc, segbase; DevBuf<u32> kc2; FastParams fp = {}; u64 n_total = 0, n_keys = 0; bool valid = false; };
+/* what retained_drop gives back */
+struct RetainedInput { std::vector<Retained> l1; u64 l1_bytes = 0; Ret2 l2; };
+
 struct yakamd_ctx {
-	int k, pre, P, n_hash, bf_shift, nb;
-	bool has_bloom;
-	int dev, plo, phi;
-	hipStream_t st;
+	CtxStream st;                      /* declared first, so handed back last: behind the frees of every buffer below */
+	int k = 0, pre = 0, P = 0, n_hash = 0, bf_shift = 0, nb = 0;
+	bool has_bloom = false;
+	int dev = 0, plo = 0, phi = 0;
 
 	/* table image */
-	u32 *d_bits, *d_used, *d_delta;
-	u64 *d_off, *d_keys;
-	u64 n_slots;                       /* arena size (multiple of 32) */
+	DevBuf<u32> d_bits, d_used, d_delta;
+	DevBuf<u64> d_off, d_keys;
+	u64 n_slots = 0;                   /* arena size (multiple of 32) */
 	std::vector<u32> h_bits, h_count;
 	std::vector<u64> h_off;
-	u64 img_keys_total;                /* sum of counts */
+	u64 img_keys_total = 0;            /* sum of counts */
 
 	/* bloom */
-	u32 *d_bf; size_t bf_words;
-	bool bf_virgin;                    /* allocated but never written: logically all zero */
-	bool bf_deferred;                  /* the last pass left its bits in LDS only (FastParams.bf_nowb): the filter is whatever k_bf_rebuild makes of the retained records (ret2) */
-	u32 *d_multi; int multi_bits;
+	DevBuf<u32> d_bf; size_t bf_words = 0;
+	bool bf_virgin = false;            /* allocated but never written: logically all zero */
+	bool bf_deferred = false;          /* the last pass left its bits in LDS only (FastParams.bf_nowb): the filter is whatever k_bf_rebuild makes of the retained records (ret.l2) */
+	DevBuf<u32> d_multi; int multi_bits = 0;
 
 	/* running pass */
-	bool delta_dirty;                  /* the running pass left pending counts in d_delta (k_img_fold at its end) */
-	bool in_pass; int create_new; bool bloom_mode; bool gate_off; int or_mode;   /* gate_off: puts of a merge never consult the filter */
-	AccTab acc; u64 acc_count;
-	u64 *d_counters, *d_lastput, *d_lpbatch;
-	u32 *d_missing, *d_nmissing;
-	Rec *d_rec; int64_t rec_cap;
-	u64 *d_newlist, *d_miss, *d_cand; int64_t new_cap;
-	uint8_t *d_stage; int64_t stage_cap;
-	bool hpc;                          /* the table lives in homopolymer-compressed space (yakamd_ch_set_hpc): every feed of bases is compacted first */
-	uint8_t *d_hpc; int64_t hpc_cap;   /* ... into this buffer, kept for the pass */
-	u32 *d_rows; u64 *d_partial, *d_bstart; int rows_blk; int nb_bits;
-	/* fast path: level-1 partitioned batches kept until pass_end */
-	struct Kept { Rec *d_rec; u64 n; u64 t0, span; std::vector<u64> bstart; bool owned; int fmt; };   /* fmt 1: tagged 8-byte records (yk_device.h YK_R8_*) */
-	std::vector<Kept> kept;
-	bool fast; u64 kept_bytes, fast_budget; u64 t_pass0; bool t_pass0_set; u64 keys_at_begin;
-	double ms_part2, ms_lds;
-	u64 t_end;
-	u64 list_t;                        /* running stream time of yak_ch_insert_list calls */
-	yakamd_stats_t st_cur, st_last;
+	bool delta_dirty = false;          /* the running pass left pending counts in d_delta (k_img_fold at its end) */
+	bool in_pass = false; int create_new = 0; bool bloom_mode = false; bool gate_off = false; int or_mode = 0;   /* gate_off: puts of a merge never consult the filter */
+	PassBufs pass;
+	DevBuf<u64> d_counters, d_lastput, d_lpbatch;
+	DevBuf<u32> d_missing, d_nmissing;
+	DevVec<uint8_t> stage;             /* the staging buffer of the host feeds */
+	bool hpc = false;                  /* the table lives in homopolymer-compressed space (yakamd_ch_set_hpc): every feed of bases is compacted first */
+	DevVec<u32> rows; DevBuf<u64> d_partial, d_bstart; int nb_bits = 0;   /* the level-1 partition's scratch; rows holds NB x blocks */
+	bool fast = false; u64 fast_budget = 0; u64 t_pass0 = 0; bool t_pass0_set = false; u64 keys_at_begin = 0;
+	double ms_part2 = 0, ms_lds = 0;
+	u64 t_end = 0;
+	u64 list_t = 0;                    /* running stream time of yak_ch_insert_list calls */
+	yakamd_stats_t st_cur = {}, st_last = {};
 
-	/* level-1 records of the last create_new pass, kept for a count pass over the SAME input (yakamd_retain_input / yakamd_count_retained):
-	 * the second pass of the bloom protocol (reference main.c:53-57) then neither reads nor hashes the input again */
-	struct Retained { u64 *d_rec; u64 n; std::vector<u64> bstart; };
-	std::vector<Retained> retained; bool retain_on, retain_broken; u64 retained_bytes;
-	/* ... or, when the whole pass was one slice into an empty table, its level-2 records (grouped by sub-bucket) + the keys every sub-bucket put
-	 * into the table: the count pass then owns each key's counter in LDS (k_cnt2) -- or, with d_kc2, takes every key's count as k_lc2 found it
-	 * (the same records: min(instances, 1023) per key, in d_kkc's order) and only applies them */
-	struct Ret2 { Rec *d_r2; u64 *d_sbstart, *d_koff, *d_kkc, *d_segbase; u32 *d_kc2; FastParams fp; u64 n_total, n_keys; bool valid; } ret2;
-	int n_slices;                      /* slices of the running pass counted so far (fast_flush_slice) */
-	u64 src_id[5]; bool src_set;       /* identity of the file the retained records came from + its sequence count (yak_count) */
+	RetainedInput ret; bool retain_on = false, retain_broken = false;
+	int n_slices = 0;                  /* slices of the running pass counted so far (fast_flush_slice) */
+	u64 src_id[5] = {}; bool src_set = false;   /* identity of the file the retained records came from + its sequence count (yak_count) */
 
 	std::mutex api_mu;                 /* serialises whole-table entry points that callers may reach from several threads (yak_ch_insert_list) */
-	void *d_scratch; size_t scratch_bytes;
+	DevVec<uint8_t> scratch;
 
 	/* host mirror */
-	bool host_valid;
-	u64 *hm_keys; u32 *hm_used; u64 hm_slots;
-	struct yak_ht_t *hts;
+	bool host_valid = false;
+	std::unique_ptr<u64[], HostFree> hm_keys; std::unique_ptr<u32[], HostFree> hm_used; u64 hm_slots = 0;
+	std::unique_ptr<yak_ht_t[], CFree> hts;
 };
 
 struct yak_ch_ext { yak_ch_t pub; yakamd_ctx *ctx; u32 magic; int n_sub; yak_ch_t **sub; };   /* n_sub > 1: a table sharded over several GPUs (yak_api.cpp) */
@@ -144,6 +151,41 @@ static inline ImgView img_view(yakamd_ctx *c)
 int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_rec_kc, const u64 *d_rec_t,
                   const u64 *d_lastput, const std::vector<u32> *init_bits, bool from_empty, const std::vector<u64> *rec_off = 0);
 /* layout.cpp: the new image replaces the context's -- `keys` / `used`, an arena of tot slots, sub-table p at new_off[p] with c->h_bits[p] / c->h_count[p] */
-int yk_image_commit(yakamd_ctx *c, u64 *keys, u32 *used, u64 tot, const std::vector<u64> &new_off);
+int yk_image_commit(yakamd_ctx *c, DevBuf<u64> &&keys, DevBuf<u32> &&used, u64 tot, const std::vector<u64> &new_off);
 void yk_replay_counters(u32 *used, u32 *refused);            /* debug: replays done by the streaming kernels / handed back to k_replay */
+
+/* a chunk table of the level-2 partition kernels: work items of at most a given number of records, each inside one bucket, grouped by bucket
+ * (first[q]: bucket q's first item, first[n_buckets]: their number); the last item of a bucket has spare = 1 */
+struct ChunkTable {
+	std::vector<Chunk2> h;
+	std::vector<u32> first;
+	DevBuf<Chunk2> d; DevBuf<u32> d_first;
+	int upload(hipStream_t st)                                   /* (the host tables must outlive the copies: the caller synchronises) */
+	{
+		if (d.alloc(h.size()) || d_first.alloc(first.size())) return -1;
+		HIPCK(hipMemcpyAsync(d, h.data(), h.size() * sizeof(Chunk2), hipMemcpyHostToDevice, st));
+		HIPCK(hipMemcpyAsync(d_first, first.data(), first.size() * 4, hipMemcpyHostToDevice, st));
+		return 0;
+	}
+	void reset() { d.reset(); d_first.reset(); }
+};
+/* engine_slice.cpp: the runs [start[q], start[q + 1]) of buckets q < n_buckets, records of `stride` bytes from `base`, cut into items of at most `len` records */
+void chunk_runs(ChunkTable &t, const void *base, size_t stride, const u64 *start, size_t n_buckets, u64 len);
+
+/* the time of an insert kernel (timed by tm) into the pass's statistics */
+static inline double insert_ms(yakamd_ctx *c, EvTimer &tm) { const double ms = tm.stop(); c->st_cur.ms_insert += ms; c->st_cur.ms_dominant_kernel += ms; c->st_cur.n_dominant_launches += 1; return ms; }
+
+/* engine_ctx.cpp */
+BloomView bloom_view(yakamd_ctx *c);
+int bloom_materialise(yakamd_ctx *c);                       /* give a never-written bloom array its zeros */
+int delta_ensure(yakamd_ctx *c);                            /* the per-slot pending increments exist from here to the end of the pass */
+void retained_drop(yakamd_ctx *c);
+void pass_free(yakamd_ctx *c);
+/* engine_pass.cpp: records [0, n_rec) of d_rec (times = t0 + position, all within [batch_lo, batch_hi)) -> table */
+int consume_records(yakamd_ctx *c, const Rec *d_rec, int64_t n_rec, u64 t0, u64 batch_lo, u64 batch_hi, const u64 *d_bstart = 0, int hash_only = 0, int ytag = 0);
+/* engine_slice.cpp: the exclusive-ownership path of a create pass */
+int fast_admit(yakamd_ctx *c, u64 t, u64 n_pos, u64 n_cap, Rec **out, Rec *borrowed = 0, int fmt = 0);
+int fast_keep(yakamd_ctx *c, u64 n_rec);
+int fast_abandon(yakamd_ctx *c);
+int fast_finish(yakamd_ctx *c, bool last = false);
 #endif

@@ -994,7 +994,7 @@ void k_bf_rebuild(FastParams fp, const u64 *__restrict__ sbstart, const Rec *__r
  * first records in flight, as in k_lc2.  A sub-bucket with more keys than the LDS set takes (other tiers of the insert kernel) looks every
  * instance up in the image with device atomics.  k_img_fold saturates the counts afterwards.
  * k_lc2 owned the same sub-buckets of the same records and had these counts in LDS already: it hands them out (LcOut.c2), and the count pass
- * is then k_cnt2_apply alone.  k_cnt2 stays for a pass 1 that did not keep them (engine.cpp: YAKAMD_CNT2_FUSED=0).
+ * is then k_cnt2_apply alone.  k_cnt2 stays for a pass 1 that did not keep them (engine_slice.cpp: YAKAMD_CNT2_FUSED=0).
  * ------------------------------------------------------------------------------------------ */
 /* C2_CAP slots for up to C2_FULL keys: 2048 / 1280 hold whatever k_lc2 lets through (28 KB of LDS, six workgroups per CU); reads with
  * coverage put a few dozen keys into a sub-bucket, and 512 / 320 (7 KB) lets the CU's wave slots, eight workgroups, be the limit */
@@ -1010,7 +1010,7 @@ void k_cnt2(FastParams fp, const u64 *__restrict__ sbstart, const Rec *__restric
 	const u32 sb0 = (u32)fp.plo << fp.s2_bits;
 	for (u32 i = tid; i < C2_CAP; i += 256) { s_K[i] = YK_EMPTY; s_C[i] = 0; }
 	auto home = [&](u64 x) -> u32 { return (((u32)x ^ (u32)(x >> 32)) * 0x9E3779B9u) >> 20 & (C2_CAP - 1); };   /* one quarter-rate multiply instead of the three of a 64-bit product */
-	/* 8-byte records only (the retained level-2 records always are: engine.cpp keep2).  The NEXT sub-bucket's first 768 records and first 256 keys
+	/* 8-byte records only (the retained level-2 records always are: engine_slice.cpp keep2).  The NEXT sub-bucket's first 768 records and first 256 keys
 	 * (a sub-bucket of reads holds a few dozen) are requested at the top of an iteration and taken over at its end: a whole iteration to arrive */
 	const u64 *rec8 = (const u64*)rec;
 	u32 it = blockIdx.x;

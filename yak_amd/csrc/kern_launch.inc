@@ -538,7 +538,7 @@ int yk_lc2_ok(FastParams fp)
 	if (fp.bloom_mode) { const int lb = fp.nb - 9 - fp.s2_bits; if (lb < 0 || lb > (fp.bf_nowb ? 8 : 7)) return 0; }   /* a staged range holds 128 blocks; without a stage (bf_nowb) the table gives a block >= 4 home slots */
 	return 1;
 }
-int yk_lc2_per_sb(int bloom_mode)       /* mean records per sub-bucket the counting kernel is built for (engine.cpp sizes the level-2 partition by it) */
+int yk_lc2_per_sb(int bloom_mode)       /* mean records per sub-bucket the counting kernel is built for (engine_slice.cpp sizes the level-2 partition by it) */
 {
 	if (bloom_mode) return 1800;
 	return yk_knob("YAKAMD_LC2", 1) != 0 && yk_knob("YAKAMD_LC2_CAPB", 11) >= 11 ? 1200 : 600;
@@ -557,8 +557,8 @@ void yk_launch_lc2(FastParams fp, const u64 *sbstart, const Rec *rec, u32 *bloom
 #define YK_LC2(B, I, Pf) do { if constexpr (!B) { if (cap11) { if (fp.rec8_out) YK_LC2X(false, I, Pf, true, false, 11); else YK_LC2X(false, I, Pf, false, false, 11); } \
                                                   else if (fp.rec8_out) YK_LC2X(false, I, Pf, true, false, 10); else YK_LC2X(false, I, Pf, false, false, 10); } \
                               else { if (fp.rec8_out) YK_LC2X(true, I, Pf, true, true, 10); else YK_LC2X(true, I, Pf, false, true, 10); } } while (0)
-		const bool cap11 = yk_lc2_per_sb(0) == 1200;                  /* no filter: the 2048-slot table (engine.cpp made the sub-buckets for it) */
-		/* an untouched filter whose bits nobody reads (engine.cpp: one-slice pass into an empty table, records kept): no stage in LDS */
+		const bool cap11 = yk_lc2_per_sb(0) == 1200;                  /* no filter: the 2048-slot table (engine_slice.cpp made the sub-buckets for it) */
+		/* an untouched filter whose bits nobody reads (engine_slice.cpp: one-slice pass into an empty table, records kept): no stage in LDS */
 		const bool nostage = fp.bloom_mode && fp.bf_nowb && fp.bf_virgin && !fp.img_nonempty && fp.rec8_out && yk_knob("YAKAMD_LC2_NOSTAGE", 1) != 0;
 		const int v = (fp.bloom_mode ? 4 : 0) | (fp.img_nonempty ? 2 : 0) | ((fp.dbg & 128) ? 1 : 0);
 		if (nostage) {

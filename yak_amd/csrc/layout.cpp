@@ -1,7 +1,7 @@
 /*
  * layout.cpp -- the exact-layout stage of a pass: the streaming replay of large sub-tables (kern_replay2.inc) as a sequence of stages over the host
  * plan of replay_plan.h (capacities after the new keys, khashl.h:197-221; the doubling / placement schedule; the arenas), and the one-workgroup-per-table
- * replay of small tables (k_replay).  Cut out of engine.cpp in round 6.
+ * replay of small tables (k_replay).  Cut out of the engine's passes (now engine_pass.cpp, engine_slice.cpp) in round 6.
  */
 #include "engine_int.h"
 
@@ -24,10 +24,10 @@ static void legacy_replay_launch(yakamd_ctx *c, const std::vector<ReplayTask> &t
 	yk_launch_replay(d_tasks, P, n_thr, c->d_keys, c->d_used, nk, nu, su, so, sp, d_rec_kc, d_rec_t, d_lastput, d_ob, d_oc, lds_words, c->st);
 }
 
-int yk_image_commit(yakamd_ctx *c, u64 *keys, u32 *used, u64 tot, const std::vector<u64> &new_off)
+int yk_image_commit(yakamd_ctx *c, DevBuf<u64> &&keys, DevBuf<u32> &&used, u64 tot, const std::vector<u64> &new_off)
 {
-	dfree(c->d_keys); dfree(c->d_used); dfree(c->d_delta);
-	c->d_keys = keys; c->d_used = used; c->n_slots = tot;
+	c->d_keys = std::move(keys); c->d_used = std::move(used); c->d_delta.reset();   /* (each frees the old image's first) */
+	c->n_slots = tot;
 	c->h_off = new_off;
 	HIPCK(hipMemcpyAsync(c->d_bits, c->h_bits.data(), c->P * 4, hipMemcpyHostToDevice, c->st));
 	HIPCK(hipMemcpyAsync(c->d_off, c->h_off.data(), c->P * 8, hipMemcpyHostToDevice, c->st));
@@ -221,8 +221,8 @@ static int r2_publish_commit(Replay2 &s)
 		c->h_bits[p] = pl.large[p] ? pl.bitsF[p] : s.ob[p];
 		c->h_count[p] = pl.large[p] ? pl.cntF[p] : s.oc[p];
 	}
-	if (pl.inplace) return yk_image_commit(c, A.release(), s.img_u.release(), pl.tot, pl.new_off);
-	return yk_image_commit(c, s.nk_al.release(), s.nu_al.release(), pl.tot, pl.new_off);
+	if (pl.inplace) return yk_image_commit(c, std::move(A), std::move(s.img_u), pl.tot, pl.new_off);
+	return yk_image_commit(c, std::move(s.nk_al), std::move(s.nu_al), pl.tot, pl.new_off);
 }
 
 /* Layout replay with the large sub-tables on the streaming kernels (kernels.hip "replay2").  A sub-table whose
@@ -275,7 +275,7 @@ int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_rec_kc,
 	HIPCK(hipMemcpyAsync(c->h_bits.data(), d_ob, P * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipMemcpyAsync(c->h_count.data(), d_oc, P * 4, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
-	return yk_image_commit(c, nk.release(), nu.release(), tot, pl.new_off);
+	return yk_image_commit(c, std::move(nk), std::move(nu), tot, pl.new_off);
 }
 
 void yk_replay_counters(u32 *used, u32 *refused) { *used = g_r2_used; *refused = g_r2_refused; }

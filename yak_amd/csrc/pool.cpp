@@ -1,7 +1,7 @@
 /*
  * pool.cpp -- what the engine's translation units share below the counting passes: the wall clock, the run-time settings (public environment
  * names + the test hook) and the device memory pool (superblocks for small buffers, physical chunks behind virtual ranges for large ones).
- * Cut out of engine.cpp in round 6; nothing here knows about tables or passes.
+ * Cut out of the engine (today engine_ctx.cpp and its siblings) in round 6; nothing here knows about tables or passes.
  */
 #include <stdio.h>
 #include <stdlib.h>

@@ -17,13 +17,14 @@ struct yakamd_graph {
 	yakamd_ctx *c;
 	int min_cnt;
 	std::vector<u64> tile0, key0;                                  /* [P + 1]: the tiles / stored keys of the sub-tables before p */
-	u64 *d_dir;                                                    /* tile0, then key0 */
-	uint8_t *d_edges;
-	u32 *d_wrank;
-	u64 *d_tally;
+	DevBuf<u64> d_dir;                                             /* tile0, then key0 */
+	DevBuf<uint8_t> d_edges;
+	DevBuf<u32> d_wrank;
+	DevBuf<u64> d_tally;
 	const u64 *keys_then; u64 slots_then, total_then;              /* the image the scratch describes */
 	yakamd_gstat_t st;
 	double ms_edges, ms_rank, ms_link;
+	~yakamd_graph() { if (c) (void)hipSetDevice(c->dev); }         /* the scratch goes back to the pool of the table's device */
 };
 
 namespace {
@@ -62,12 +63,6 @@ int gr_still(yakamd_graph_t *g, const char *what)
 	return 0;
 }
 
-void gr_free(yakamd_graph_t *g)
-{
-	(void)hipSetDevice(g->c->dev);
-	dfree(g->d_dir); dfree(g->d_edges); dfree(g->d_wrank); dfree(g->d_tally);
-}
-
 int gr_launch(yakamd_graph_t *g, int what, u64 t_lo, u64 t_hi, void *out, u64 out_key0, u64 out_n)
 {
 	yakamd_ctx *c = g->c;
@@ -93,7 +88,7 @@ int gr_build(yakamd_graph_t *g)
 	if (g->key0[P] != c->img_keys_total) return fail("graph: the sub-tables hold %llu keys, the table %llu", (unsigned long long)g->key0[P], (unsigned long long)c->img_keys_total);
 	std::vector<u64> dir(g->tile0);
 	dir.insert(dir.end(), g->key0.begin(), g->key0.end());
-	if (dmalloc(&g->d_dir, dir.size()) || dmalloc(&g->d_edges, (size_t)c->n_slots) || dmalloc(&g->d_wrank, (size_t)(c->n_slots / 32 + 1)) || dmalloc(&g->d_tally, (size_t)32))
+	if (g->d_dir.alloc(dir.size()) || g->d_edges.alloc((size_t)c->n_slots) || g->d_wrank.alloc((size_t)(c->n_slots / 32 + 1)) || g->d_tally.alloc(32))
 		return fail("graph: no device memory for %.1f MB of scratch", c->n_slots * 1.125 / 1e6);
 	HIPCK(hipMemcpyAsync(g->d_dir, dir.data(), dir.size() * 8, hipMemcpyHostToDevice, c->st));
 	HIPCK(hipMemsetAsync(g->d_tally, 0, 32 * 8, c->st));
@@ -136,14 +131,13 @@ extern "C" yakamd_graph_t *yakamd_graph_open(yak_ch_t *h, int min_cnt)
 	if (!g) { fail("graph: no memory"); return 0; }
 	g->h = h; g->c = c; g->min_cnt = min_cnt;
 	g->keys_then = c->d_keys; g->slots_then = c->n_slots; g->total_then = c->img_keys_total;
-	if (gr_build(g) != 0) { gr_free(g); delete g; return 0; }
+	if (gr_build(g) != 0) { delete g; return 0; }
 	return g;
 }
 
 extern "C" void yakamd_graph_close(yakamd_graph_t *g)
 {
 	if (!g) return;
-	gr_free(g);
 	delete g;
 }
 

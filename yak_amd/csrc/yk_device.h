@@ -1,6 +1,6 @@
 /*
  * yk_device.h -- shared declarations between the HIP kernels (kernels.hip) and the host engine
- * (engine.cpp).  Internal; the public surface is include/yak.h + include/yak_amd.h.
+ * (engine_*.cpp).  Internal; the public surface is include/yak.h + include/yak_amd.h.
  */
 #ifndef YK_DEVICE_H
 #define YK_DEVICE_H
@@ -198,7 +198,7 @@ struct ResizeTask { u32 old_bits, new_bits, rehash, pad; u64 old_off, new_off; }
 void yk_launch_resize(const ResizeTask *tasks, int P, const u64 *old_keys, const u32 *old_used, u64 *new_keys, u32 *new_used, u32 *scr_used, hipStream_t st);
 void yk_launch_keys_to_hashes(const u64 *kc, const u64 *seg_off, int P, int pre, u64 *hash, u32 *t, hipStream_t st, unsigned short *cnt = 0);   /* cnt != 0: the keys' counts as well */
 void yk_launch_img_add_counts(const u64 *hash, const unsigned short *cnt, u64 n, ImgView img, int plo, int phi, u32 *missing, hipStream_t st);
-long yk_knob(const char *name, long dflt);                   /* engine.cpp: run-time settings (test switches come through yakamd_test_set only) */
+long yk_knob(const char *name, long dflt);                   /* pool.cpp: run-time settings (test switches come through yakamd_test_set only) */
 void yk_launch_put_u64(const u64 *pos, const u64 *val, u32 n, u64 *out, hipStream_t st);
 
 #ifdef __cplusplus
@@ -251,7 +251,7 @@ struct FastParams {
  * front of the sub-bucket's own record range in kc / T (fragments, gathered by k_lc_compact); per sub-bucket
  * their number, the time (relative to the slice, + 1; 0 = none) of its last put-call, its distinct k-mers.
  * c2 (0 = not wanted): next to every selected key, min(instances of the key in the sub-bucket's records, 1023) -- what a count pass over the
- * same records adds to it (engine.cpp keep2: that pass then only applies these, k_cnt2_apply) */
+ * same records adds to it (engine_slice.cpp keep2: that pass then only applies these, k_cnt2_apply) */
 struct LcOut { u64 *kc, *T; u32 *nsel, *lp, *nd; unsigned short *c2; };
 
 #ifdef __cplusplus
