@@ -1,11 +1,13 @@
-/* engine.h -- internal interface between pool.cpp, the engine (engine_ctx.cpp, engine_pass.cpp, engine_slice.cpp, engine_table.cpp), lookup_dev.cpp and the yak.h surface (yak_api.cpp, yak_reader.cpp, yak_multi.cpp) */
+/* engine.h -- internal interface between pool.cpp, the engine (engine_ctx.cpp, engine_pass.cpp, engine_slice.cpp, engine_table.cpp), table_read.cpp,
+ * lookup_dev.cpp and the yak.h surface (yak_api.cpp, yak_reader.cpp, yak_multi.cpp, yak_inspect.cpp, yak_print.cpp) */
 #ifndef YK_ENGINE_H
 #define YK_ENGINE_H
 #include <vector>
 #include "../../include/yak_amd.h"
 #include "yk_device.h"
+#include "table_ranges.h"
 
-/* what a command or export says of a table it cannot read as one image (yak_api.cpp multi_refuse, lookup_dev.cpp lookup_ctx) */
+/* what a command or export says of a table it cannot read as one image (yak_api.cpp multi_refuse, table_read.cpp yk_image_state) */
 #define YK_MSG_SHARDED "not available on a table sharded over prefix ranges"
 
 /* a device buffer kept from one chunk, batch or call to the next and grown when one needs more (yakamd_dev_alloc / yakamd_dev_free are hipMalloc /
@@ -45,7 +47,32 @@ void *yk_pool_get(size_t bytes);
 void *yk_pool_alloc(size_t bytes, bool plain);              /* pool.cpp: a device buffer from the current device's pool (plain: never from the virtual-memory tier); 0 when the device is full */
 void yk_pool_free(void *p);
 double yk_now_ms(void);                                      /* monotonic wall clock */
-int yk_ctx_dump_image_dev(yakamd_ctx *c, int lo, int hi, u64 **d_img, u64 *n_words);   /* the .yak bytes of sub-tables [lo, hi), in pool memory */
+int yk_ctx_dump_image_dev(yakamd_ctx *c, int lo, int hi, u64 **d_img, u64 *n_words);   /* the .yak bytes of sub-tables [lo, hi), in pool memory: StagedRange's to call */
+
+/* ---- table_read.cpp: what the commands that read a resident table's stored keys share ---- */
+/* a run of sub-tables [lo, hi) that one shard of a table owns, and that shard's context */
+struct TablePiece { yakamd_ctx *c; int lo, hi; };
+/* [lo, hi) of `h` cut by owner, in prefix order (a yakamd_set_shard table: the part of [lo, hi) it owns); false after a message that starts with
+ * `what`: not an engine table, a range outside the table, a shard in an open pass */
+bool yk_table_pieces(const yak_ch_t *h, int lo, int hi, const char *what, std::vector<TablePiece> *out);
+/* the range rule (table_ranges.h) over the sizes of sub-tables [lo, hi) of one context */
+std::vector<TableRange> yk_ctx_ranges(yakamd_ctx *c, int lo, int hi, int64_t budget, bool keep_empty);
+/* the owner of one staged range: the .yak body of sub-tables [lo, hi) of a context (pool memory of its device; per sub-table the {capacity, size}
+ * word, then the stored keys in ascending slot order) and, when asked for, the device copy of the range's key offsets, in a buffer kept from one
+ * range to the next.  One owner serves the contexts of one call; whatever it holds goes back with the context's device selected */
+struct StagedRange {
+	u64 *d_img = 0;
+	u64 n_words = 0;
+	GrowBuf d_off;                                               /* (which makes the owner one that is not copied) */
+	~StagedRange() { drop(); }
+	/* the image of [lo, hi) in place of the one held; off != 0: those offsets (hi - lo + 1 of them) beside it, after the check that the image holds
+	 * off->back() keys -- else "<what>: the table changed while it was <verb>".  0, or -1 after a message */
+	int stage(yakamd_ctx *c, int lo, int hi, const std::vector<u64> *off = 0, const char *what = 0, const char *verb = 0);
+	void drop();                                                 /* the image goes back to the pool; the offsets' buffer stays */
+	const u64 *off() const { return (const u64*)d_off.p; }
+private:
+	int dev = -1;
+};
 void yk_ctx_gate(yakamd_ctx *c, bool on);
 void yk_ctx_or_mode(yakamd_ctx *c, int mode);   /* 0 counting; 1 flag loads; 2 saved-count loads (yk_device.h FastParams.or_mode) */
 void yk_ctx_lock(yakamd_ctx *c);

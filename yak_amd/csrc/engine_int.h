@@ -1,6 +1,7 @@
 /* engine_int.h -- what the engine's own translation units (engine_ctx.cpp: the context; engine_pass.cpp: passes and feeds; engine_slice.cpp: the
- * count of a slice; engine_table.cpp: whole-table operations; layout.cpp: exact slot layout; lookup_dev.cpp: the device-level exports of the lookup
- * commands) share and nobody else sees: the context of a table with the buffers it owns (dev_buf.h), the error macro, and the few functions that
+ * count of a slice; engine_table.cpp: whole-table operations; layout.cpp: exact slot layout; table_read.cpp: the staged ranges, owner cut and
+ * refusals of the commands that read a table's stored keys; lookup_dev.cpp: the device-level exports of the lookup commands; yak_hetmer.cpp and
+ * yak_graph.cpp: hetmers and unitigs) share and nobody else sees: the context of a table with the buffers it owns (dev_buf.h), the error macro, and the few functions that
  * cross between those files. */
 #ifndef YK_ENGINE_INT_H
 #define YK_ENGINE_INT_H
@@ -146,6 +147,28 @@ static inline ImgView img_view(yakamd_ctx *c)
 	v.pre = c->pre; v.k = c->k;
 	return v;
 }
+
+/* table_read.cpp: how a table stands to a command that reads it as one image.  c: its context, the first shard's of a table spread over several
+ * GPUs (which has none of its own), 0 if `h` is no engine table; sharded: it cannot be read as one image -- several GPUs' tables, or a
+ * yakamd_set_shard range; in_pass: a shard of it is in an open pass */
+struct ImageState { yakamd_ctx *c; bool sharded, in_pass; };
+ImageState yk_image_state(const yak_ch_t *h);
+/* the context a command that probes the whole image of a table of odd k < 32 for its keys at min_cnt or above works on (hetmers, the graph), or 0
+ * after fail(): every refusal, in the order of include/yak_amd.h, before any device work.  no_gpu / even_k: the command's own ends of those two texts */
+yakamd_ctx *yk_whole_image_ctx(const yak_ch_t *h, int min_cnt, const char *what, const char *no_gpu, const char *even_k);
+
+/* the text a command writes: to `fn`, or to stdout for NULL and "-".  A file is closed when the owner goes; finish() tells whether all of it got out */
+struct OutFile {
+	FILE *f = 0;
+	const char *name = "-";
+	bool own = false;
+	OutFile() = default;
+	OutFile(const OutFile&) = delete;
+	OutFile &operator=(const OutFile&) = delete;
+	~OutFile() { if (own && f) fclose(f); }
+	bool open(const char *fn) { own = fn && strcmp(fn, "-") != 0; if (own) name = fn; f = own ? fopen(fn, "wb") : stdout; return f != 0; }
+	bool finish() { bool ok = fflush(f) == 0 && !ferror(f); if (own) { ok = fclose(f) == 0 && ok; f = 0; } return ok; }
+};
 
 /* layout.cpp: the exact khashl slot layout (khashl.h:152-221) of `m[p]` new keys per sub-table, sorted by insertion time, on top of the table image */
 int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_rec_kc, const u64 *d_rec_t,

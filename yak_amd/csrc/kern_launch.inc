@@ -647,6 +647,12 @@ void yk_launch_nsel_scan(const u32 *nsel, int s2_bits, int plo, int phi, int P, 
 	YK_LAUNCH(k_nsel_scan, dim3(P), dim3(256), 0, st, nsel, s2_bits, plo, phi, P, seg_base, key_off);
 }
 
+static int cu_count()                                             /* the compute units of the current device, for the persistent grids below; 256 if it does not tell */
+{
+	int dev = 0, n_cu = 0;
+	return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n_cu >= 1 ? n_cu : 256;
+}
+
 /* yak inspect's join (kern_inspect.inc): one persistent grid over the n keys, as many workgroups as the LDS lets share a CU (the 64 KiB corner
  * histogram, B's sub-table directory and A's offsets: 80 KiB at pre 10, two per CU), never fewer than n / 2^31 (a corner bin is a u32) */
 int yk_launch_inspect(const u64 *keys, const u64 *off, u64 n, int n_sub, int sub_lo, int hdr, int pre_a, int has_b, ImgView img, int blo, int bhi,
@@ -659,8 +665,7 @@ int yk_launch_inspect(const u64 *keys, const u64 *off, u64 n, int n_sub, int sub
 	a.tab_b = has_b && img.pre <= 12;
 	a.tab_a = n_sub <= 4096;
 	const size_t lds = IN_CORNER_BYTES + (a.tab_b ? (size_t)8 << img.pre : 0) + (a.tab_a ? (size_t)8 * n_sub : 0);
-	int dev = 0, n_cu = 0;
-	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
+	const int n_cu = cu_count();
 	const u64 per_cu = std::max<u64>(1, std::min<u64>(4, (u64)(160 * 1024) / lds));
 	const u64 steps = (n + IN_THREADS * IN_U - 1) / (IN_THREADS * IN_U);
 	const u64 grid = std::max<u64>(std::min<u64>((u64)n_cu * per_cu, steps), (n >> 31) + 1);
@@ -716,8 +721,7 @@ int yk_launch_hetmer(int mode, const u64 *keys, const u64 *off, u64 n, int n_sub
 	a.tab = img.pre <= 12;
 	a.tab_off = n_sub <= 4096;
 	const size_t lds = (mode == 0 ? HM_CORNER_BYTES : 0) + (a.tab ? (size_t)8 << img.pre : 0) + (a.tab_off ? (size_t)8 * n_sub : 0);
-	int dev = 0, n_cu = 0;
-	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
+	const int n_cu = cu_count();
 	const u64 per_cu = std::max<u64>(1, std::min<u64>(4, (u64)(160 * 1024) / (lds + (mode == 0 ? 0 : HM_CORNER_BYTES))));
 	const u64 grid = std::max<u64>(std::min<u64>((u64)n_cu * per_cu, yk_hetmer_tiles(n)), (n >> 31) + 1);
 	static DevOnce attr;
@@ -753,8 +757,7 @@ int yk_launch_graph(int what, int inflight, int grid_want, const u64 *tile0, con
 	}
 	if (t_hi == t_lo) return 0;
 	const size_t lds = a.tab ? (size_t)8 << img.pre : 0;
-	int dev = 0, n_cu = 0;
-	if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n_cu < 1) n_cu = 256;
+	const int n_cu = cu_count();
 	const u64 grid = std::max<u64>(std::min<u64>(grid_want > 0 ? (u64)grid_want : (u64)n_cu * 4, t_hi - t_lo), 1);
 	if (what == 0 && inflight == 8) YK_LAUNCH((k_graph_edges<8>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);
 	else if (what == 0) YK_LAUNCH((k_graph_edges<4>), dim3((unsigned)grid), dim3(GR_THREADS), lds, st, a, img);

@@ -7,13 +7,13 @@
 #include "engine_int.h"
 
 /* ---- the lookups (yak qv, triobin, trioeval, chkerr, sexchr) ---- */
-/* the context a lookup export works on, or 0 after fail().  The kernel reads one whole table image: refused are several GPUs' tables (which have
- * no context of their own) and a yakamd_set_shard range */
+/* the context a lookup export works on, or 0 after fail().  The kernel reads one whole table image: a table that is none (yk_image_state) is
+ * refused first */
 static yakamd_ctx *lookup_ctx(yak_ch_t *h, const char *what, int k_max, const char *k_msg)
 {
-	const yak_ch_ext *e = (const yak_ch_ext*)h;
-	yakamd_ctx *c = ctx_of(h);
-	if ((h && e->magic == EXT_MAGIC && e->n_sub > 1) || (c && (c->plo != 0 || c->phi != c->P))) fail("%s: " YK_MSG_SHARDED, what);
+	const ImageState s = yk_image_state(h);
+	yakamd_ctx *c = s.c;
+	if (s.sharded) fail("%s: " YK_MSG_SHARDED, what);
 	else if (!c) fail("not an engine table");
 	else if (c->in_pass) fail("lookup during an open pass");
 	else if (c->k < 1 || c->k > k_max) fail("%s: %s", what, k_msg);

@@ -449,7 +449,7 @@ yak_knt_t *yak_ch_getseq(const yak_ch_t *h, int w, uint32_t *n) /* reference hta
 
 /* ---- .yak serialisation (reference htab.c:373-394): header, then per sub-table capacity, size and
  * the keys in ascending slot order.  Every shard puts the bytes of its own sub-tables together on its device
- * (yk_ctx_dump_image_dev); they come back in one copy (yakamd_dump_mem), or go to the file in 8 MiB pieces through a
+ * (StagedRange); they come back in one copy (yakamd_dump_mem), or go to the file in 8 MiB pieces through a
  * few page-locked buffers that writer threads pwrite() while the next pieces are on the bus (yak_ch_dump) ---- */
 struct DumpSink {
 	uint8_t *mem; int fd;                                      /* one of the two */
@@ -521,13 +521,9 @@ static int64_t dump_through(yak_ch_t *h, DumpSink *sink, bool size_only)
 		yak_ch_t *hs = YK_MULTI(e) ? e->sub[r] : h;
 		const int lo = YK_MULTI(e) ? (int)(((int64_t)r << h->pre) / n_sub) : 0, hi = YK_MULTI(e) ? (int)(((int64_t)(r + 1) << h->pre) / n_sub) : P;
 		yakamd_ctx *c = ((yak_ch_ext*)hs)->ctx;
-		u64 *d_img = 0, n_words = 0;
-		if (yk_ctx_dump_image_dev(c, lo, hi, &d_img, &n_words) != 0) return -1;
-		const bool ok = sink->put(yk_ctx_device(c), yk_ctx_stream(c), (const uint8_t*)d_img, (size_t)n_words * 8, off);
-		(void)hipSetDevice(yk_ctx_device(c));
-		yk_pool_release(d_img);
-		if (!ok) return -1;
-		off += (size_t)n_words * 8;
+		StagedRange s;                                               /* (the image goes back when the shard is written) */
+		if (s.stage(c, lo, hi) != 0 || !sink->put(yk_ctx_device(c), yk_ctx_stream(c), (const uint8_t*)s.d_img, (size_t)s.n_words * 8, off)) return -1;
+		off += (size_t)s.n_words * 8;
 	}
 	return off == sz ? (int64_t)sz : -1;
 }
@@ -572,13 +568,10 @@ int64_t yakamd_dump_range_mem(yak_ch_t *h, int lo, int hi, uint8_t **out)
 		owner_range(r, &a, &b);
 		if (a >= b) continue;
 		yakamd_ctx *c = ((yak_ch_ext*)(YK_MULTI(e) ? e->sub[r] : h))->ctx;
-		u64 *d_img = 0, n_words = 0;
-		bool ok = yk_ctx_dump_image_dev(c, a, b, &d_img, &n_words) == 0 && off + (size_t)n_words * 8 <= sz;
-		ok = ok && sink.put(yk_ctx_device(c), yk_ctx_stream(c), (const uint8_t*)d_img, (size_t)n_words * 8, off);
-		(void)hipSetDevice(yk_ctx_device(c));
-		if (d_img) yk_pool_release(d_img);
-		if (!ok) { free(sink.mem); return -1; }
-		off += (size_t)n_words * 8;
+		StagedRange s;
+		if (s.stage(c, a, b) != 0 || off + (size_t)s.n_words * 8 > sz
+		    || !sink.put(yk_ctx_device(c), yk_ctx_stream(c), (const uint8_t*)s.d_img, (size_t)s.n_words * 8, off)) { free(sink.mem); return -1; }
+		off += (size_t)s.n_words * 8;
 	}
 	if (off != sz) { free(sink.mem); return -1; }
 	*out = sink.mem;

@@ -29,28 +29,8 @@ struct yakamd_graph {
 
 namespace {
 
-const int NC = YAK_N_COUNTS;
 const int64_t GR_BATCH_DEFAULT = (int64_t)1 << 24;
 double g_unitigs_ms[4];                                           /* the last yakamd_unitigs call: graph, records, walk, text */
-
-/* the context a graph call works on, or 0 after fail(): every refusal, in the order of include/yak_amd.h, before any device work */
-yakamd_ctx *gr_ctx(const yak_ch_t *h, int min_cnt, const char *what)
-{
-	const yak_ch_ext *e = (const yak_ch_ext*)h;
-	if (yakamd_device_count() < 1) { fail("%s: no gfx950 GPU visible: the graph has no CPU fallback", what); return 0; }
-	const bool multi = h && e->magic == EXT_MAGIC && e->n_sub > 1;  /* spread over several GPUs' tables: no context of its own */
-	yakamd_ctx *c = multi ? ctx_of(e->sub[0]) : ctx_of(h);
-	bool in_pass = c && c->in_pass;
-	for (int r = 1; multi && c && r < e->n_sub; ++r) { yakamd_ctx *s = ctx_of(e->sub[r]); in_pass = in_pass || (s && s->in_pass); }
-	if (!c) fail("%s: not an engine table", what);
-	else if (!(h->k & 1)) fail("%s: k = %d is even: an even k-mer can be its own reverse complement, and a side's edges would not be distinct", what, h->k);
-	else if (h->k >= 32) fail("%s: k = %d: k must be below 32 (a stored key inverts to its k-mer for k below 32 only, reference htab.c:359)", what, h->k);
-	else if (min_cnt < 1 || min_cnt > NC - 1) fail("%s: min_cnt %d is outside [1, %d]", what, min_cnt, NC - 1);
-	else if (in_pass) fail("%s during an open pass", what);
-	else if (multi || c->plo != 0 || c->phi != c->P) fail("%s: " YK_MSG_SHARDED, what);
-	else return c;
-	return 0;
-}
 
 /* a later call on an open graph: the pass and the image are looked at again */
 int gr_still(yakamd_graph_t *g, const char *what)
@@ -125,7 +105,8 @@ int64_t gr_batch(int64_t dflt)
 
 extern "C" yakamd_graph_t *yakamd_graph_open(yak_ch_t *h, int min_cnt)
 {
-	yakamd_ctx *c = gr_ctx(h, min_cnt, "graph");
+	yakamd_ctx *c = yk_whole_image_ctx(h, min_cnt, "graph", "the graph has no CPU fallback",
+	                                   "an even k-mer can be its own reverse complement, and a side's edges would not be distinct");
 	if (!c) return 0;
 	yakamd_graph_t *g = new (std::nothrow) yakamd_graph_t();
 	if (!g) { fail("graph: no memory"); return 0; }
@@ -200,18 +181,12 @@ extern "C" int yakamd_unitigs(const yakamd_ugopt_t *opt, const yak_ch_t *ch, con
 	catch (const std::bad_alloc&) { return fail("yakamd_unitigs: the records of %llu stored keys do not fit the host's memory (32 bytes each)", (unsigned long long)n_key); }
 	const int64_t batch = gr_batch(opt->batch_keys);
 	GrowBuf d_rec;
-	int n_ranges = 0;
-	for (int lo = 0; lo < P; ) {
-		int hi = lo + 1;
-		while (hi < P && g->key0[hi + 1] - g->key0[lo] <= (u64)batch) ++hi;
-		const u64 n = g->key0[hi] - g->key0[lo];
-		if (n) {
-			if (!d_rec.fit(n * sizeof(ug_node_t))) return fail("yakamd_unitigs: no device memory for %llu records", (unsigned long long)n);
-			if (yakamd_graph_nodes_dev(g, lo, hi, d_rec.p, (int64_t)n) != (int64_t)n) return -1;
-			if (yakamd_memcpy_d2h(nodes.data() + g->key0[lo], d_rec.p, n * sizeof(ug_node_t)) != 0) return -1;
-			++n_ranges;
-		}
-		lo = hi;
+	const std::vector<TableRange> ranges = yk_ctx_ranges(c, 0, P, batch, false);   /* (those that hold keys) */
+	for (const TableRange &r : ranges) {
+		const u64 n = r.n();
+		if (!d_rec.fit(n * sizeof(ug_node_t))) return fail("yakamd_unitigs: no device memory for %llu records", (unsigned long long)n);
+		if (yakamd_graph_nodes_dev(g, r.lo, r.hi, d_rec.p, (int64_t)n) != (int64_t)n) return -1;
+		if (yakamd_memcpy_d2h(nodes.data() + g->key0[r.lo], d_rec.p, n * sizeof(ug_node_t)) != 0) return -1;
 	}
 	d_rec.drop();
 	const double t1 = now_ms();
@@ -221,10 +196,9 @@ extern "C" int yakamd_unitigs(const yakamd_ugopt_t *opt, const yak_ch_t *ch, con
 		if (ug_walk(nodes.data(), n_key, k, (uint32_t)opt->min_cnt, opt->n_threads, &res, &err) != 0) return fail("yakamd_unitigs: %s", err.c_str());
 	} catch (const std::bad_alloc&) { return fail("yakamd_unitigs: the unitigs of %llu stored keys do not fit the host's memory", (unsigned long long)n_key); }
 	const double t2 = now_ms();
-	const bool to_stdout = !out_fn || strcmp(out_fn, "-") == 0;
-	FILE *out = to_stdout ? stdout : fopen(out_fn, "wb");
-	if (!out) return fail("yakamd_unitigs: cannot write '%s'", out_fn);
-	struct Closer { FILE *f; bool own; ~Closer() { if (own && f) fclose(f); } } closer{ out, !to_stdout };
+	OutFile of;
+	if (!of.open(out_fn)) return fail("yakamd_unitigs: cannot write '%s'", out_fn);
+	FILE *out = of.f;
 	bool ok = true;
 	if (opt->stats_only) {
 		const yakamd_gstat_t &s = g->st;
@@ -235,11 +209,9 @@ extern "C" int yakamd_unitigs(const yakamd_ugopt_t *opt, const yak_ch_t *ch, con
 				if (s.deg[l][r]) fprintf(out, "D\t%d\t%d\t%llu\n", l, r, (unsigned long long)s.deg[l][r]);
 		fputs(ug_stat_line(res).c_str(), out);
 	} else ok = ug_fasta(res, [out](const std::string &t) { return fwrite(t.data(), 1, t.size(), out) == t.size(); });
-	ok = fflush(out) == 0 && !ferror(out) && ok;
-	if (!to_stdout) { ok = fclose(out) == 0 && ok; closer.f = 0; }
-	if (!ok) return fail("yakamd_unitigs: cannot write '%s'", to_stdout ? "-" : out_fn);
+	if (!of.finish() || !ok) return fail("yakamd_unitigs: cannot write '%s'", of.name);
 	g_unitigs_ms[0] = t0 - t_open; g_unitigs_ms[1] = t1 - t0; g_unitigs_ms[2] = t2 - t1; g_unitigs_ms[3] = now_ms() - t2;
 	if (getenv("YAKAMD_VERBOSE"))
-		fprintf(stderr, "[yak_amd] unitigs: %d ranges of records in %.1f ms, the host walk %.1f ms, the text %.1f ms\n", n_ranges, t1 - t0, t2 - t1, now_ms() - t2);
+		fprintf(stderr, "[yak_amd] unitigs: %zu ranges of records in %.1f ms, the host walk %.1f ms, the text %.1f ms\n", ranges.size(), t1 - t0, t2 - t1, now_ms() - t2);
 	return 0;
 }

@@ -13,23 +13,10 @@ namespace {
 const int NC = YAK_N_COUNTS;
 const int64_t HM_BATCH_DEFAULT = (int64_t)1 << 24;
 
-/* the context a het-mer call works on, or 0 after fail(): every refusal, in the order of include/yak_amd.h, before any device work */
+/* the context a het-mer call works on, or 0 after a refusal (yk_whole_image_ctx) */
 yakamd_ctx *hm_ctx(const yak_ch_t *h, int min_cnt, const char *what)
 {
-	const yak_ch_ext *e = (const yak_ch_ext*)h;
-	if (yakamd_device_count() < 1) { fail("%s: no gfx950 GPU visible: the het-mer join has no CPU fallback", what); return 0; }
-	const bool multi = h && e->magic == EXT_MAGIC && e->n_sub > 1;  /* spread over several GPUs' tables: no context of its own */
-	yakamd_ctx *c = multi ? ctx_of(e->sub[0]) : ctx_of(h);
-	bool in_pass = c && c->in_pass;
-	for (int r = 1; multi && c && r < e->n_sub; ++r) { yakamd_ctx *s = ctx_of(e->sub[r]); in_pass = in_pass || (s && s->in_pass); }
-	if (!c) fail("%s: not an engine table", what);
-	else if (!(h->k & 1)) fail("%s: k = %d is even: a k-mer of even length has no middle base", what, h->k);
-	else if (h->k >= 32) fail("%s: k = %d: k must be below 32 (a stored key inverts to its k-mer for k below 32 only, reference htab.c:359)", what, h->k);
-	else if (min_cnt < 1 || min_cnt > NC - 1) fail("%s: min_cnt %d is outside [1, %d]", what, min_cnt, NC - 1);
-	else if (in_pass) fail("%s during an open pass", what);
-	else if (multi || c->plo != 0 || c->phi != c->P) fail("%s: " YK_MSG_SHARDED, what);
-	else return c;
-	return 0;
+	return yk_whole_image_ctx(h, min_cnt, what, "the het-mer join has no CPU fallback", "a k-mer of even length has no middle base");
 }
 
 int64_t hm_batch(int64_t dflt)
@@ -38,56 +25,19 @@ int64_t hm_batch(int64_t dflt)
 	return b < 1 ? 1 : b;
 }
 
-/* a range of whole sub-tables [lo, hi) and the offsets of their keys: as many sub-tables as `batch` keys allow, one at the least */
-struct Range { int lo, hi; std::vector<u64> off; u64 n() const { return off.back(); } };
-
-std::vector<Range> hm_ranges(yakamd_ctx *c, int64_t batch)
-{
-	std::vector<Range> out;
-	Range r;
-	r.lo = 0; r.off.assign(1, 0);
-	for (int p = 0; p < c->P; ++p) {
-		const u64 size = c->h_count[p];
-		if (p > r.lo && r.n() + size > (u64)batch) {
-			r.hi = p;
-			if (r.n()) out.push_back(r);
-			r.lo = p; r.off.assign(1, 0);
-		}
-		r.off.push_back(r.n() + size);
-	}
-	r.hi = c->P;
-	if (r.n()) out.push_back(r);
-	return out;
-}
-
-/* one range on the device: the .yak body of its sub-tables and their key offsets */
-struct Staged {
-	u64 *d_img = 0;
-	GrowBuf *d_off;
-	explicit Staged(GrowBuf *off) : d_off(off) {}
-	Staged(const Staged&) = delete;
-	Staged &operator=(const Staged&) = delete;
-	~Staged() { if (d_img) yk_pool_release(d_img); }
-	int stage(yakamd_ctx *c, const Range &r)
-	{
-		u64 n_words = 0;
-		if (yk_ctx_dump_image_dev(c, r.lo, r.hi, &d_img, &n_words) != 0) return -1;
-		if (n_words != r.n() + (u64)(r.hi - r.lo)) return fail("hetmers: the table changed while it was read");
-		if (!d_off->fit(r.off.size() * 8) || yakamd_memcpy_h2d(d_off->p, r.off.data(), r.off.size() * 8) != 0)
-			return fail("hetmers: no device memory for %zu offsets", r.off.size());
-		return 0;
-	}
-};
+/* a range of the table that holds keys, at most hm_batch() of them (table_ranges.h), staged with its offsets */
+typedef TableRange Range;
+int hm_stage(StagedRange &s, yakamd_ctx *c, const Range &r) { return s.stage(c, r.lo, r.hi, &r.off, "hetmers", "read"); }
 
 /* the scratch of the pair list: the tiles' pair counts and their scan */
 struct PairScratch {
 	GrowBuf cnt, off;
 	/* the pairs each tile of the staged range reports, scanned; *total = their number.  Returns when it is known */
-	int count(yakamd_ctx *c, const Range &r, const Staged &s, int min_cnt, hipStream_t st, u64 *total)
+	int count(yakamd_ctx *c, const Range &r, const StagedRange &s, int min_cnt, hipStream_t st, u64 *total)
 	{
 		const u64 nt = yk_hetmer_tiles(r.n());
 		if (!cnt.fit(nt * 4) || !off.fit((nt + 1) * 8)) return fail("hetmers: no device memory for %llu tile counts", (unsigned long long)nt);
-		if (yk_launch_hetmer(1, s.d_img, (const u64*)s.d_off->p, r.n(), r.hi - r.lo, r.lo, min_cnt, img_view(c), 0, 0, (u32*)cnt.p, 0, 0, st))
+		if (yk_launch_hetmer(1, s.d_img, s.off(), r.n(), r.hi - r.lo, r.lo, min_cnt, img_view(c), 0, 0, (u32*)cnt.p, 0, 0, st))
 			return fail("hetmers: the pair count did not launch");
 		yk_launch_te_scan((const u32*)cnt.p, (int64_t)nt, 1, (u64*)off.p, st);
 		HIPCK(hipGetLastError());
@@ -96,9 +46,9 @@ struct PairScratch {
 		return 0;
 	}
 	/* after count(): the records into d_list[0 .. total).  Asynchronous on st */
-	int write(yakamd_ctx *c, const Range &r, const Staged &s, int min_cnt, void *d_list, hipStream_t st)
+	int write(yakamd_ctx *c, const Range &r, const StagedRange &s, int min_cnt, void *d_list, hipStream_t st)
 	{
-		if (yk_launch_hetmer(2, s.d_img, (const u64*)s.d_off->p, r.n(), r.hi - r.lo, r.lo, min_cnt, img_view(c), 0, 0, 0, (const u64*)off.p, d_list, st))
+		if (yk_launch_hetmer(2, s.d_img, s.off(), r.n(), r.hi - r.lo, r.lo, min_cnt, img_view(c), 0, 0, 0, (const u64*)off.p, d_list, st))
 			return fail("hetmers: the pair list did not launch");
 		return 0;
 	}
@@ -115,13 +65,12 @@ extern "C" int yakamd_hetmers_dev(yak_ch_t *h, int min_cnt, uint64_t *d_joint, u
 	if (!d_joint || !d_group || ((uintptr_t)d_joint & 7) != 0 || ((uintptr_t)d_group & 7) != 0) return fail("hetmers: the histogram and the group counts must be 8-byte aligned device arrays");
 	HIPCK(hipSetDevice(c->dev));
 	const hipStream_t st = (hipStream_t)stream;
-	GrowBuf d_off;
-	for (const Range &r : hm_ranges(c, hm_batch(HM_BATCH_DEFAULT))) {
-		Staged s(&d_off);
-		if (s.stage(c, r)) return -1;
-		if (yk_launch_hetmer(0, s.d_img, (const u64*)d_off.p, r.n(), r.hi - r.lo, r.lo, min_cnt, img_view(c), (u64*)d_joint, (u64*)d_group, 0, 0, 0, st))
+	StagedRange s;
+	for (const Range &r : yk_ctx_ranges(c, 0, c->P, hm_batch(HM_BATCH_DEFAULT), false)) {
+		if (hm_stage(s, c, r)) return -1;
+		if (yk_launch_hetmer(0, s.d_img, s.off(), r.n(), r.hi - r.lo, r.lo, min_cnt, img_view(c), (u64*)d_joint, (u64*)d_group, 0, 0, 0, st))
 			return fail("hetmers: the join did not launch");
-		HIPCK(hipStreamSynchronize(st));                             /* the staged keys are released with `s` */
+		HIPCK(hipStreamSynchronize(st));                             /* the staged keys go when the next range is staged, or with `s` */
 	}
 	return 0;
 }
@@ -132,24 +81,22 @@ extern "C" int64_t yakamd_hetmer_pairs_dev(yak_ch_t *h, int min_cnt, void *d_pai
 	if (!c) return -1;
 	if (d_pairs && ((uintptr_t)d_pairs & 7) != 0) return fail("hetmer pairs: the records must be 8-byte aligned");
 	HIPCK(hipSetDevice(c->dev));
-	const std::vector<Range> ranges = hm_ranges(c, hm_batch(HM_BATCH_DEFAULT));
-	GrowBuf d_off;
+	const std::vector<Range> ranges = yk_ctx_ranges(c, 0, c->P, hm_batch(HM_BATCH_DEFAULT), false);
+	StagedRange s;
 	PairScratch ps;
 	/* the number first: nothing is written before it is known to fit */
 	std::vector<u64> tot(ranges.size(), 0);
 	u64 n = 0;
 	for (size_t i = 0; i < ranges.size(); ++i) {
-		Staged s(&d_off);
-		if (s.stage(c, ranges[i]) || ps.count(c, ranges[i], s, min_cnt, c->st, &tot[i])) return -1;
+		if (hm_stage(s, c, ranges[i]) || ps.count(c, ranges[i], s, min_cnt, c->st, &tot[i])) return -1;
 		n += tot[i];
 	}
 	if (!d_pairs || cap < (int64_t)n) return (int64_t)n;
 	u64 at = 0;
 	for (size_t i = 0; i < ranges.size(); ++i) {
 		if (tot[i] == 0) continue;
-		Staged s(&d_off);
 		u64 again = 0;
-		if (s.stage(c, ranges[i]) || ps.count(c, ranges[i], s, min_cnt, c->st, &again)) return -1;
+		if (hm_stage(s, c, ranges[i]) || ps.count(c, ranges[i], s, min_cnt, c->st, &again)) return -1;
 		if (again != tot[i]) return fail("hetmer pairs: the table changed while it was read");
 		if (ps.write(c, ranges[i], s, min_cnt, (yakamd_hetpair_t*)d_pairs + at, c->st)) return -1;
 		HIPCK(hipStreamSynchronize(c->st));
@@ -175,25 +122,24 @@ extern "C" int yakamd_hetmers(const yakamd_hmopt_t *opt, const yak_ch_t *ch, con
 	HIPCK(hipSetDevice(c->dev));
 	const int k = ch->k, min_cnt = opt->min_cnt;
 	const hipStream_t st = c->st;
-	const std::vector<Range> ranges = hm_ranges(c, hm_batch(opt->batch_keys));
-	GrowBuf d_off, d_list, d_tally;
+	const std::vector<Range> ranges = yk_ctx_ranges(c, 0, c->P, hm_batch(opt->batch_keys), false);
+	GrowBuf d_list, d_tally;
+	StagedRange s;
 	PairScratch ps;
 	const size_t tally_bytes = (size_t)NC * NC * 8 + 64;            /* J, then the five group counts */
 	if (!d_tally.fit(tally_bytes)) return fail("yakamd_hetmers: no device memory for the histogram");
 	HIPCK(hipMemsetAsync(d_tally.p, 0, tally_bytes, st));
 	u64 *d_joint = (u64*)d_tally.p, *d_group = d_joint + (size_t)NC * NC;
-	const bool to_stdout = !out_fn || strcmp(out_fn, "-") == 0;
-	FILE *out = to_stdout ? stdout : fopen(out_fn, "wb");
-	if (!out) return fail("yakamd_hetmers: cannot write '%s'", out_fn);
-	struct Closer { FILE *f; bool own; ~Closer() { if (own && f) fclose(f); } } closer{ out, !to_stdout };
+	OutFile of;
+	if (!of.open(out_fn)) return fail("yakamd_hetmers: cannot write '%s'", out_fn);
+	FILE *out = of.f;
 	fprintf(out, "#hetmers\tk=%d\tmin_cnt=%d\n", k, min_cnt);
 	std::vector<yakamd_hetpair_t> recs;
 	std::string text;
 	u64 n_pairs = 0;
 	for (const Range &r : ranges) {
-		Staged s(&d_off);
-		if (s.stage(c, r)) return -1;
-		if (yk_launch_hetmer(0, s.d_img, (const u64*)d_off.p, r.n(), r.hi - r.lo, r.lo, min_cnt, img_view(c), d_joint, d_group, 0, 0, 0, st))
+		if (hm_stage(s, c, r)) return -1;
+		if (yk_launch_hetmer(0, s.d_img, s.off(), r.n(), r.hi - r.lo, r.lo, min_cnt, img_view(c), d_joint, d_group, 0, 0, 0, st))
 			return fail("yakamd_hetmers: the join did not launch");
 		if (opt->print_pairs) {
 			u64 tot = 0;
@@ -211,7 +157,7 @@ extern "C" int yakamd_hetmers(const yakamd_hmopt_t *opt, const yak_ch_t *ch, con
 					text.append("K\t").append(a, k).append(num, (size_t)snprintf(num, sizeof num, "\t%u\t", p.cx)).append(b, k)
 					    .append(num, (size_t)snprintf(num, sizeof num, "\t%u\n", p.cy));
 				}
-				if (fwrite(text.data(), 1, text.size(), out) != text.size()) return fail("yakamd_hetmers: cannot write '%s'", to_stdout ? "-" : out_fn);
+				if (fwrite(text.data(), 1, text.size(), out) != text.size()) return fail("yakamd_hetmers: cannot write '%s'", of.name);
 				n_pairs += tot;
 			}
 		}
@@ -227,9 +173,7 @@ extern "C" int yakamd_hetmers(const yakamd_hmopt_t *opt, const yak_ch_t *ch, con
 		for (int hi = 0; hi < NC; ++hi)
 			if (J[(size_t)lo * NC + hi]) { sum += J[(size_t)lo * NC + hi]; fprintf(out, "P\t%d\t%d\t%llu\n", lo, hi, (unsigned long long)J[(size_t)lo * NC + hi]); }
 	if (opt->print_pairs && sum != n_pairs) return fail("yakamd_hetmers: %llu pairs listed, %llu counted", (unsigned long long)n_pairs, (unsigned long long)sum);
-	bool ok = fflush(out) == 0 && !ferror(out);
-	if (!to_stdout) { ok = fclose(out) == 0 && ok; closer.f = 0; }
-	if (!ok) return fail("yakamd_hetmers: cannot write '%s'", to_stdout ? "-" : out_fn);
+	if (!of.finish()) return fail("yakamd_hetmers: cannot write '%s'", of.name);
 	if (getenv("YAKAMD_VERBOSE"))
 		fprintf(stderr, "[yak_amd] hetmers: %zu ranges of keys, %llu pairs\n", ranges.size(), (unsigned long long)sum);
 	return 0;

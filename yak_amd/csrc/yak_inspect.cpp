@@ -219,8 +219,8 @@ int yakamd_inspect(const yakamd_inopt_t *opt, const char *fn1, const char *fn2, 
 	return ok ? 0 : -1;
 }
 
-/* the join of yakamd_inspect on resident tables: A's keys in dump order come from its device-side .yak body (yk_ctx_dump_image_dev), one
- * rank's sub-tables at a time, headers left in place */
+/* the join of yakamd_inspect on resident tables: A's keys in dump order come from its device-side .yak body (StagedRange), one rank's
+ * sub-tables at a time, headers left in place */
 int yakamd_inspect_tables(const yak_ch_t *a, const yak_ch_t *b, int ref_probe, int64_t *joint)
 {
 	std::vector<yakamd_ctx*> ea, eb;
@@ -235,30 +235,16 @@ int yakamd_inspect_tables(const yak_ch_t *a, const yak_ch_t *b, int ref_probe, i
 		return -1;
 	}
 	if (hipSetDevice(yk_ctx_device(ea[0])) != hipSuccess) { yk_set_error("inspect: cannot select device %d", yk_ctx_device(ea[0])); return -1; }
-	const yak_ch_ext *e = (const yak_ch_ext*)a;
-	const int n_rank = YK_MULTI(e) ? e->n_sub : 1;
 	uint64_t *d_joint = (uint64_t*)yakamd_dev_alloc((size_t)NC * NC * 8);
 	std::vector<int64_t> J((size_t)NC * NC, 0);
-	bool ok = d_joint && yakamd_memcpy_h2d(d_joint, J.data(), J.size() * 8) == 0;
-	GrowBuf d_off;
-	for (int r = 0; ok && r < n_rank; ++r) {
-		yak_ch_t *s = YK_MULTI(e) ? e->sub[r] : (yak_ch_t*)a;
-		yakamd_ctx *c = ea[r];
-		int lo = 0, hi = 0;
-		yk_ctx_range(c, &lo, &hi);
-		std::vector<uint64_t> off(1, 0);
-		for (int p = lo; p < hi; ++p) {
-			uint32_t cap = 0, size = 0;
-			yakamd_subtable(s, p, &cap, &size);
-			off.push_back(off.back() + size);
-		}
-		if (off.back() == 0) continue;
-		u64 *d_img = 0, n_words = 0;
-		ok = yk_ctx_dump_image_dev(c, lo, hi, &d_img, &n_words) == 0 && d_off.fit(off.size() * 8)
-		     && yakamd_memcpy_h2d(d_off.p, off.data(), off.size() * 8) == 0
-		     && yakamd_inspect_dev((yak_ch_t*)b, a->k, a->pre, lo, hi, d_img, (int64_t)off.back(), (const uint64_t*)d_off.p, 1, ref_probe, d_joint, 0) == 0;
-		yk_pool_release(d_img);
-	}
+	std::vector<TablePiece> pcs;
+	bool ok = d_joint && yakamd_memcpy_h2d(d_joint, J.data(), J.size() * 8) == 0 && yk_table_pieces(a, 0, 1 << a->pre, "inspect", &pcs);
+	StagedRange s;
+	for (size_t i = 0; ok && i < pcs.size(); ++i)
+		for (const TableRange &r : yk_ctx_ranges(pcs[i].c, pcs[i].lo, pcs[i].hi, INT64_MAX, false))   /* the piece as one range, if it holds keys */
+			ok = ok && s.stage(pcs[i].c, r.lo, r.hi, &r.off, "inspect", "read") == 0
+			     && yakamd_inspect_dev((yak_ch_t*)b, a->k, a->pre, r.lo, r.hi, s.d_img, (int64_t)r.n(), (const uint64_t*)s.off(), 1, ref_probe, d_joint, 0) == 0;
+	s.drop();
 	ok = ok && yakamd_memcpy_d2h(J.data(), d_joint, J.size() * 8) == 0;
 	yakamd_dev_free(d_joint);
 	if (!ok) { fprintf(stderr, "[E::%s] %s\n", __func__, yakamd_last_error()); return -1; }

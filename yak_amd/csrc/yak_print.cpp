@@ -10,28 +10,14 @@
 
 namespace {
 
-/* a run of sub-tables [lo, hi) that one shard of a table owns */
-struct Piece { yak_ch_t *s; yakamd_ctx *c; int lo, hi; };
+typedef TablePiece Piece;
 
-/* [lo, hi) of `h` cut by owner, in prefix order; false after a message */
+/* [lo, hi) of `h` cut by owner (yk_table_pieces), after print's own refusal: a stored key inverts to its k-mer for k below 32 only */
 bool pieces_of(const yak_ch_t *h, int lo, int hi, const char *what, std::vector<Piece> *out)
 {
 	const yak_ch_ext *e = (const yak_ch_ext*)h;
-	out->clear();
-	if (!h || e->magic != EXT_MAGIC) { yk_set_error("%s: not an engine table", what); return false; }
-	if (h->k < 1 || h->k >= 32) { yk_set_error("%s: k = %d: k-mers can be listed for k below 32 only (reference htab.c:359)", what, h->k); return false; }
-	if (lo < 0 || hi < lo || hi > 1 << h->pre) { yk_set_error("%s: sub-tables [%d, %d) of %d", what, lo, hi, 1 << h->pre); return false; }
-	const int n_sh = YK_MULTI(e) ? e->n_sub : 1;
-	for (int r = 0; r < n_sh; ++r) {
-		yak_ch_t *s = YK_MULTI(e) ? e->sub[r] : (yak_ch_t*)h;
-		std::vector<yakamd_ctx*> eng;
-		if (yk_inspect_engines(s, &eng)) return false;               /* (an engine table, out of a pass) */
-		int a = 0, b = 0;
-		yk_ctx_range(eng[0], &a, &b);
-		a = std::max(a, lo); b = std::min(b, hi);
-		if (a < b) out->push_back(Piece{ s, eng[0], a, b });
-	}
-	return true;
+	if (h && e->magic == EXT_MAGIC && (h->k < 1 || h->k >= 32)) { yk_set_error("%s: k = %d: k-mers can be listed for k below 32 only (reference htab.c:359)", what, h->k); return false; }
+	return yk_table_pieces(h, lo, hi, what, out);
 }
 
 /* the caller's arrays are on one device: so must the shards be whose kernels write them */
@@ -42,58 +28,28 @@ bool on_one_device(const std::vector<Piece> &pcs, const char *what)
 	return true;
 }
 
-/* one piece on its device: the .yak body of its sub-tables and the key offsets of kern_print.inc */
+/* one range of sub-tables of one shard: its sizes, its staged keys with the key offsets of kern_print.inc, and the scratch of the text's tile
+ * sizes.  The device buffers are kept from one range to the next (of one device: PrintDev) */
 struct Staged {
-	Piece pc;
-	std::vector<u64> off;                                          /* [n_sub + 1] */
-	u64 *d_img = 0, *d_off = 0, *d_toff = 0;
-	u32 *d_tcnt = 0;
+	yakamd_ctx *c = 0;
+	TableRange r;
+	StagedRange img;
+	GrowBuf tcnt, toff;                                            /* with counts: the tiles' bytes and their scan */
 	u64 n = 0, bytes = 0;
-	Staged() = default;
-	Staged(const Staged&) = delete;
-	Staged &operator=(const Staged&) = delete;
-	~Staged() { drop(); }
-	void drop()
-	{
-		if (!d_img && !d_off && !d_toff && !d_tcnt) return;
-		(void)hipSetDevice(yk_ctx_device(pc.c));
-		if (d_img) yk_pool_release(d_img);
-		yakamd_dev_free(d_off); yakamd_dev_free(d_toff); yakamd_dev_free(d_tcnt);
-		d_img = d_off = d_toff = 0; d_tcnt = 0;
-	}
-	void count(const Piece &p)                                     /* the sizes alone: no device work */
-	{
-		pc = p;
-		off.assign(1, 0);
-		for (int w = p.lo; w < p.hi; ++w) {
-			uint32_t cap = 0, size = 0;
-			yakamd_subtable(p.s, w, &cap, &size);
-			off.push_back(off.back() + size);
-		}
-		n = off.back();
-	}
-	bool stage()
-	{
-		if (n == 0) return true;
-		u64 n_words = 0;
-		if (yk_ctx_dump_image_dev(pc.c, pc.lo, pc.hi, &d_img, &n_words) != 0) return false;
-		if (n_words != n + (u64)(pc.hi - pc.lo)) { yk_set_error("print: the table changed while it was listed"); return false; }
-		d_off = (u64*)yakamd_dev_alloc(off.size() * 8);
-		if (!d_off || yakamd_memcpy_h2d(d_off, off.data(), off.size() * 8) != 0) { yk_set_error("print: no device memory for %zu offsets", off.size()); return false; }
-		return true;
-	}
+	void count(yakamd_ctx *c_, const TableRange &r_) { c = c_; r = r_; n = r.n(); }   /* the sizes alone: no device work */
+	void count(const Piece &p) { count(p.c, yk_ctx_ranges(p.c, p.lo, p.hi, INT64_MAX, true)[0]); }   /* a whole piece as one range */
+	bool stage() { return n == 0 || img.stage(c, r.lo, r.hi, &r.off, "print", "listed") == 0; }
+	void drop() { img.drop(); }
 	/* the bytes of the text: computed (without counts), or the scan of the tiles' sizes read back */
 	bool measure(int k, int with_counts)
 	{
 		if (!with_counts || n == 0) { bytes = n * (u64)(k + 1); return true; }
 		const u64 nt = yk_print_tiles(n);
-		const hipStream_t st = yk_ctx_stream(pc.c);
-		d_tcnt = (u32*)yakamd_dev_alloc(nt * 4);
-		d_toff = (u64*)yakamd_dev_alloc((nt + 1) * 8);
-		if (!d_tcnt || !d_toff) { yk_set_error("print: no device memory for %llu tile offsets", (unsigned long long)nt); return false; }
-		if (yk_launch_print_sizes(d_img, d_off, n, pc.hi - pc.lo, k, d_tcnt, st) != 0) { yk_set_error("print: the size kernel did not launch"); return false; }
-		yk_launch_te_scan(d_tcnt, (int64_t)nt, 1, d_toff, st);
-		if (hipMemcpyAsync(&bytes, d_toff + nt, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+		const hipStream_t st = yk_ctx_stream(c);
+		if (!tcnt.fit(nt * 4) || !toff.fit((nt + 1) * 8)) { yk_set_error("print: no device memory for %llu tile offsets", (unsigned long long)nt); return false; }
+		if (yk_launch_print_sizes(img.d_img, img.off(), n, r.hi - r.lo, k, (u32*)tcnt.p, st) != 0) { yk_set_error("print: the size kernel did not launch"); return false; }
+		yk_launch_te_scan((const u32*)tcnt.p, (int64_t)nt, 1, (u64*)toff.p, st);
+		if (hipMemcpyAsync(&bytes, (const u64*)toff.p + nt, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
 			yk_set_error("print: sizes: %s", hipGetErrorString(hipGetLastError()));
 			return false;
 		}
@@ -102,8 +58,8 @@ struct Staged {
 	bool format(int k, int pre, int with_counts, uint8_t *d_text)  /* returns when the text is there */
 	{
 		if (n == 0) return true;
-		const hipStream_t st = yk_ctx_stream(pc.c);
-		if (yk_launch_print(d_img, d_off, n, pc.hi - pc.lo, pc.lo, k, pre, with_counts, d_toff, d_text, st) != 0 || hipStreamSynchronize(st) != hipSuccess) {
+		const hipStream_t st = yk_ctx_stream(c);
+		if (yk_launch_print(img.d_img, img.off(), n, r.hi - r.lo, r.lo, k, pre, with_counts, with_counts ? (const u64*)toff.p : 0, d_text, st) != 0 || hipStreamSynchronize(st) != hipSuccess) {
 			yk_set_error("print: the listing kernel failed: %s", hipGetErrorString(hipGetLastError()));
 			return false;
 		}
@@ -111,10 +67,11 @@ struct Staged {
 	}
 };
 
-/* what one device lends to yakamd_print(): two text buffers, a copy stream, two pinned pieces */
+/* what one device lends to yakamd_print(): the staging of its ranges, two text buffers, a copy stream, two pinned pieces */
 struct PrintDev {
 	enum { CH = 8 << 20 };
 	int dev = -1;
+	Staged s;
 	uint8_t *d_text[2] = { 0, 0 };
 	void *pin[2] = { 0, 0 };
 	hipStream_t st = 0;
@@ -177,8 +134,8 @@ extern "C" int64_t yakamd_kmers_dev(yak_ch_t *h, int sub_lo, int sub_hi, void *d
 	for (Staged &s : st) {
 		if (s.n == 0) continue;
 		if (!s.stage()) return -1;
-		const hipStream_t q = yk_ctx_stream(s.pc.c);
-		if (yk_launch_kmers(s.d_img, s.d_off, s.n, s.pc.hi - s.pc.lo, s.pc.lo, h->k, h->pre, (u64*)d_x_u64 + at, (unsigned short*)d_c_u16 + at, q) != 0
+		const hipStream_t q = yk_ctx_stream(s.c);
+		if (yk_launch_kmers(s.img.d_img, s.img.off(), s.n, s.r.hi - s.r.lo, s.r.lo, h->k, h->pre, (u64*)d_x_u64 + at, (unsigned short*)d_c_u16 + at, q) != 0
 		    || hipStreamSynchronize(q) != hipSuccess) return yk_set_error("kmers: the listing kernel failed: %s", hipGetErrorString(hipGetLastError()));
 		at += s.n;
 		s.drop();
@@ -225,21 +182,12 @@ extern "C" int yakamd_print(const yakamd_propt_t *opt, const yak_ch_t *ch, const
 	const int k = ch->k, pre = ch->pre, with_counts = opt->with_counts != 0;
 	const u64 line_max = (u64)k + (with_counts ? 6 : 1);
 	const u64 room = (u64)std::max<int64_t>(opt->batch_bytes, 1) / line_max;   /* keys per range */
-	/* the ranges: as many whole sub-tables of one shard as `room` keys allow, one at the least */
-	std::vector<Piece> ranges;
+	/* the ranges: as many whole sub-tables of one shard as `room` keys allow, one at the least (table_ranges.h) */
+	struct ShardRange { yakamd_ctx *c; TableRange r; };
+	std::vector<ShardRange> ranges;
 	u64 most = 0;
-	for (const Piece &p : pcs) {
-		int lo = p.lo;
-		u64 n = 0;
-		for (int w = p.lo; w < p.hi; ++w) {
-			uint32_t cap = 0, size = 0;
-			yakamd_subtable(p.s, w, &cap, &size);
-			if (w > lo && n + size > room) { ranges.push_back(Piece{ p.s, p.c, lo, w }); most = std::max(most, n); lo = w; n = 0; }
-			n += size;
-		}
-		ranges.push_back(Piece{ p.s, p.c, lo, p.hi });
-		most = std::max(most, n);
-	}
+	for (const Piece &p : pcs)
+		for (const TableRange &r : yk_ctx_ranges(p.c, p.lo, p.hi, (int64_t)room, true)) { ranges.push_back(ShardRange{ p.c, r }); most = std::max(most, r.n()); }
 	const bool to_stdout = !out_fn || strcmp(out_fn, "-") == 0;
 	if (to_stdout) fflush(stdout);
 	const int fd = to_stdout ? STDOUT_FILENO : ::open(out_fn, O_WRONLY | O_CREAT | O_TRUNC, 0666);
@@ -252,12 +200,12 @@ extern "C" int yakamd_print(const yakamd_propt_t *opt, const yak_ch_t *ch, const
 	double t_fmt = 0;
 	int turn = 0;                                                  /* ranges that had text: they alternate between the two buffers */
 	for (size_t r = 0; ok && r < ranges.size(); ++r) {
-		Staged s;
-		s.count(ranges[r]);
-		if (s.n == 0) continue;
-		const int dev = yk_ctx_device(s.pc.c);
+		if (ranges[r].r.n() == 0) continue;
+		const int dev = yk_ctx_device(ranges[r].c);
 		if (!devs.count(dev) && !devs[dev].open(dev, (size_t)(most * line_max + 16))) { ok = false; yk_set_error("print: no device memory for two text buffers of %llu bytes", (unsigned long long)(most * line_max)); break; }
 		PrintDev &pd = devs[dev];
+		Staged &s = pd.s;
+		s.count(ranges[r].c, ranges[r].r);
 		const double a = yk_realtime();
 		/* this buffer was drained by the writer before the last one, joined before the last range was handed over */
 		uint8_t *d_text = pd.d_text[turn++ & 1];
