@@ -298,6 +298,7 @@ int yk_ctx_sync_host(yakamd_ctx *c, yak_ch_t *h)
 	std::lock_guard<std::mutex> lk(mu);
 	if (c->host_valid) return 0;
 	HIPCK(hipSetDevice(c->dev));
+	if (yk_image_settle(c)) return -1;
 	++g_host_syncs;
 	if (c->hm_slots < c->n_slots) {
 		c->hm_keys.reset(); c->hm_used.reset(); c->hm_slots = 0;

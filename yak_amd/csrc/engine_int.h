@@ -13,6 +13,7 @@
 #include <map>
 #include <string>
 #include <mutex>
+#include <atomic>
 #include <algorithm>
 #include <memory>
 #include "yk_device.h"
@@ -79,7 +80,12 @@ struct Retained { DevBuf<Rec> rec; u64 n = 0; std::vector<u64> bstart; };
 /* ... or, when the whole pass was one slice into an empty table, its level-2 records (grouped by sub-bucket) + the keys every sub-bucket put
  * into the table: the count pass then owns each key's counter in LDS (k_cnt2) -- or, with kc2, takes every key's count as k_lc2 found it
  * (the same records: min(instances, 1023) per key, in kkc's order) and only applies them */
-struct Ret2 { DevBuf<Rec> r2; DevBuf<u64> sbstart, koff, kkc, segbase; DevBuf<u32> kc2; FastParams fp = {}; u64 n_total = 0, n_keys = 0; bool valid = false; };
+struct Ret2 {
+	DevBuf<Rec> r2; DevBuf<u64> sbstart, koff, kkc, segbase; DevBuf<u32> kc2; FastParams fp = {}; u64 n_total = 0, n_keys = 0; bool valid = false;
+	/* kkc lists every key of the image exactly once, each with the count the image holds for it (fast_finish: the pass began on an empty image, ended
+	 * in one slice and kept kc2), and nothing has touched keys or counts since -- yak_ch_clear apart (yk_image_touched) */
+	bool whole_image = false;
+};
 /* what retained_drop gives back */
 struct RetainedInput { std::vector<Retained> l1; u64 l1_bytes = 0; Ret2 l2; };
 
@@ -96,6 +102,7 @@ struct yakamd_ctx {
 	std::vector<u32> h_bits, h_count;
 	std::vector<u64> h_off;
 	u64 img_keys_total = 0;            /* sum of counts */
+	std::atomic<bool> clear_pending{false};   /* yak_ch_clear was asked for and k_img_clear has not run yet: the next reader or writer of the image launches it (img_view; readers may be several threads) */
 
 	/* bloom */
 	DevBuf<u32> d_bf; size_t bf_words = 0;
@@ -140,12 +147,24 @@ static inline yakamd_ctx *ctx_of(const yak_ch_t *h)
 	return (h && e->magic == EXT_MAGIC) ? e->ctx : 0;
 }
 
-static inline ImgView img_view(yakamd_ctx *c)
+/* engine_table.cpp: a pending yak_ch_clear becomes real (k_img_clear on the table's stream, waited for).  Whatever reads or writes the image's keys goes
+ * through here first: img_view below, and the few places that take c->d_keys themselves (layout.cpp, the host mirror, the khashl resizes) */
+int yk_image_settle(yakamd_ctx *c);
+/* keys or counts of the image change by something other than yak_ch_clear: the retained key list no longer stands for the image */
+static inline void yk_image_touched(yakamd_ctx *c) { c->ret.l2.whole_image = false; }
+
+/* the image as it is, a pending clear left pending: for the one caller that folds the clear into its own sweep (yakamd_count_retained) */
+static inline ImgView img_view_pending(yakamd_ctx *c)
 {
 	ImgView v;
 	v.bits = c->d_bits; v.off = c->d_off; v.keys = c->d_keys; v.used = c->d_used; v.delta = c->d_delta;
 	v.pre = c->pre; v.k = c->k;
 	return v;
+}
+static inline ImgView img_view(yakamd_ctx *c)
+{
+	if (c->clear_pending) (void)yk_image_settle(c);          /* (a launch that fails shows in the caller's own checks of the stream) */
+	return img_view_pending(c);
 }
 
 /* table_read.cpp: how a table stands to a command that reads it as one image.  c: its context, the first shard's of a table spread over several

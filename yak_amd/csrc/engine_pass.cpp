@@ -248,6 +248,7 @@ int consume_records(yakamd_ctx *c, const Rec *d_rec, int64_t n_rec, u64 t0, u64 
 	if (batch_hi > c->t_end) c->t_end = batch_hi;
 	if (!c->create_new) {
 		c->delta_dirty = true;
+		yk_image_touched(c);
 		EvTimer tm(c->st);
 		/* records grouped by sub-table and every sub-table small enough for LDS rank counters:
 		 * exclusive-ownership counting, no global atomics */
@@ -547,6 +548,7 @@ extern "C" int yakamd_count_hashes_dev(yak_ch_t *h, const void *d_hash_u64, int6
 	HIPCK(hipSetDevice(c->dev));
 	if (n <= 0) return 0;
 	c->delta_dirty = true;
+	yk_image_touched(c);
 	EvTimer tm(c->st);
 	yk_launch_img_count_h((const u64*)d_hash_u64, n, img_view(c), c->st);
 	insert_ms(c, tm);
@@ -584,14 +586,25 @@ extern "C" int yakamd_count_retained(yak_ch_t *h)
 	HIPCK(hipSetDevice(c->dev));
 	const Ret2 &l2 = c->ret.l2;
 	if (l2.valid && !c->retain_broken && l2.kc2) {
-		/* k_lc2 counted every instance of every key it selected while it owned the sub-bucket: all that is left is to add those counts */
+		/* k_lc2 counted every instance of every key it selected while it owned the sub-bucket: all that is left is to add those counts.
+		 * Behind a yak_ch_clear that has not run yet, on a key list that is the whole image as the pass before left it (Ret2.whole_image), "clear, then
+		 * add c2" needs no probe per key: that pass counted every instance but the first, which the filter took, so c2 == min(c1 + 1, 1023) for every
+		 * key but the few the filter let through at once (k_lc2: fpk).  One sweep raises every count by one (k_img_clear's bump) and takes the pending
+		 * clear's place; k_cnt2_apply reads its lists and probes only the keys whose c2 is something else.  YAKAMD_PASS2_BUMP=0 (a test switch):
+		 * clear, then add */
+		const bool bump = c->clear_pending && l2.whole_image && env_i64("YAKAMD_PASS2_BUMP", 1) != 0;
+		const ImgView img = bump ? img_view_pending(c) : img_view(c);
 		EvTimer tm(c->st);
-		yk_launch_cnt2_apply(l2.fp, l2.kkc, l2.kc2, l2.segbase, img_view(c), c->st);
+		if (bump) {
+			c->clear_pending = false;
+			yk_launch_img_clear(img, c->n_slots, c->st, 1);
+		}
+		yk_launch_cnt2_apply(l2.fp, l2.kkc, l2.kc2, l2.segbase, img, c->st, bump);
 		const double ms = insert_ms(c, tm);
 		const bool bad = hipGetLastError() != hipSuccess;
 		c->st_cur.n_instances += (int64_t)l2.n_total;
 		c->st_cur.pass2_path = 1; yk_event(YKE_PASS2_FUSED);
-		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] count pass: the counts of the pass before applied (%llu keys, %.2f ms)\n", (unsigned long long)l2.n_keys, ms);
+		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] count pass: the counts of the pass before applied (%llu keys, %.2f ms%s)\n", (unsigned long long)l2.n_keys, ms, bump ? "; with the pending clear, in one sweep" : "");
 		retained_drop(c);
 		return bad ? fail("applying the counts of the pass before failed") : 0;
 	}

@@ -475,6 +475,12 @@ int fast_finish(yakamd_ctx *c, bool last)
 		c->st_cur.ms_replay += tm.stop();
 	}
 	s.lap(c, "exact layout");
+	/* the retained key list is the image: the pass began on an empty one and this is its only slice (keep2 says both; no k_lc2 instance met a table),
+	 * it kept the counts of the count pass, and every listed key went in once -- the count pass may then raise all counts in one sweep
+	 * (yakamd_count_retained).  The mark falls with the first change of keys or counts that is not a clear (yk_image_touched: the layout just above too) */
+	Ret2 &l2 = c->ret.l2;
+	l2.whole_image = s.keep2 && l2.valid && l2.kc2 && last && c->n_slices == 0 && c->keys_at_begin == 0 && !s.fp.img_nonempty && !c->retain_broken &&
+	                 l2.n_keys == c->img_keys_total;
 	return 0;
 }
 

@@ -20,16 +20,33 @@ int yk_ctx_setcnt(yakamd_ctx *c, int cnt)
 	yk_launch_img_setcnt(img_view(c), c->n_slots, (u32)cnt & 1023u, c->st);
 	HIPCK(hipStreamSynchronize(c->st));
 	c->host_valid = false;
+	yk_image_touched(c);
 	return 0;
 }
 
+/* The clear is only noted: k_img_clear runs when something next reads or writes the image (img_view -> yk_image_settle), on the same stream and so
+ * in the same order as if it had run here.  The count pass over the input of the pass before is the one caller that takes the note over instead
+ * (yakamd_count_retained: clear and count in one sweep).  The precedent is the filter k_lc2 does not write back (bf_deferred) */
 int yk_ctx_clear(yakamd_ctx *c)
 {
-	HIPCK(hipSetDevice(c->dev));
-	yk_launch_img_clear(img_view(c), c->n_slots, c->st);
-	HIPCK(hipStreamSynchronize(c->st));
+	c->clear_pending = true;
 	c->host_valid = false;
 	return 0;
+}
+
+int yk_image_settle(yakamd_ctx *c)
+{
+	static std::mutex mu;                                      /* readers on several threads (lookups): the first one clears, the others wait for it */
+	std::lock_guard<std::mutex> lk(mu);
+	if (!c->clear_pending) return 0;
+	int cur = c->dev;                                          /* (the image of another table of a command -- subtract, isec -- may live on another device) */
+	(void)hipGetDevice(&cur);
+	if (cur != c->dev) HIPCK(hipSetDevice(c->dev));
+	yk_launch_img_clear(img_view_pending(c), c->n_slots, c->st);
+	const hipError_t e = hipStreamSynchronize(c->st);          /* as yak_ch_clear always did: readers on other streams see the zeros */
+	c->clear_pending = false;
+	if (cur != c->dev) (void)hipSetDevice(cur);
+	return e == hipSuccess ? 0 : fail("clear: %s", hipGetErrorString(e));
 }
 
 /* reference htab.c:180-208 */
@@ -77,6 +94,7 @@ int yk_ctx_isec(yakamd_ctx *c, yakamd_ctx *other, u64 *tot) { return rebuild(c, 
 static int resize_tables(yakamd_ctx *c, const std::vector<u32> &new_bits)
 {
 	HIPCK(hipSetDevice(c->dev));
+	if (yk_image_settle(c)) return -1;
 	const int P = c->P;
 	std::vector<ResizeTask> tasks(P);
 	std::vector<u64> new_off(P);
@@ -180,6 +198,7 @@ int yk_ctx_add_counts(yakamd_ctx *c, const u64 *d_hash, const unsigned short *d_
 	u32 missing = 0;
 	if (d_missing.alloc(1)) return -1;
 	HIPCK(hipMemsetAsync(d_missing, 0, 4, c->st));
+	yk_image_touched(c);
 	yk_launch_img_add_counts(d_hash, d_cnt, n, img_view(c), c->plo, c->phi, d_missing, c->st);
 	HIPCK(hipGetLastError());
 	HIPCK(hipMemcpyAsync(&missing, d_missing, 4, hipMemcpyDeviceToHost, c->st));
@@ -247,6 +266,7 @@ int yk_ctx_inc(yakamd_ctx *c, u64 hash, int *count)
 	if (c->in_pass) return fail("yak_ch_inc during an open pass");
 	HIPCK(hipSetDevice(c->dev));
 	u64 out[2];
+	yk_image_touched(c);
 	yk_launch_img_inc(img_view(c), hash, c->d_counters, c->st);
 	HIPCK(hipMemcpyAsync(out, c->d_counters, 16, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));

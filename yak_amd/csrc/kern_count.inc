@@ -1078,15 +1078,22 @@ void k_cnt2(FastParams fp, const u64 *__restrict__ sbstart, const Rec *__restric
 	}
 }
 
-/* counts of k_cnt2 -> table image: key i of sub-table p (the list is grouped by sub-table: seg_base) */
+/* counts of k_cnt2 -> table image: key i of sub-table p (the list is grouped by sub-table: seg_base).
+ * fix: the image's counts have been raised by one already (k_img_clear's bump) from the counts c1 the pass before left, which the list still holds
+ * (key_kc[i] & 1023).  That is the key's count key_cnt[i] wherever the pass before counted every instance but the first -- every key but the few
+ * whose first instance the filter let through (k_lc2: fpk) -- so a key is skipped when key_cnt[i] == min(c1 + 1, 1023), and only the others are
+ * probed and get key_cnt[i] as their count */
 __global__ __launch_bounds__(256)
-void k_cnt2_apply(const u64 *__restrict__ key_kc, const u32 *__restrict__ key_cnt, const u64 *__restrict__ seg_base, int plo, int pre, ImgView img)
+void k_cnt2_apply(const u64 *__restrict__ key_kc, const u32 *__restrict__ key_cnt, const u64 *__restrict__ seg_base, int plo, int pre, ImgView img, int fix)
 {
 	const u32 p = (u32)plo + blockIdx.y;
 	const u64 a = seg_base[p], b = seg_base[p + 1];
 	for (u64 i = a + (u64)blockIdx.x * 256 + threadIdx.x; i < b; i += (u64)gridDim.x * 256) {
 		const u32 c = key_cnt[i];
-		if (!c) continue;
+		if (fix) {
+			const u32 c1 = (u32)key_kc[i] & 1023u;
+			if (c == (c1 < 1023u ? c1 + 1 : 1023u)) continue;
+		} else if (!c) continue;
 		/* the probe reads the key array alone: the image keeps every unused slot at YK_EMPTY, which no 2k < 64-bit key equals (as k_lookup; this
 		 * path only exists for k < 32) -- the `used` bitmap would be a second random read per step of the probe */
 		const u64 kid = key_kc[i] >> 10;
@@ -1100,7 +1107,7 @@ void k_cnt2_apply(const u64 *__restrict__ key_kc, const u32 *__restrict__ key_cn
 			const u64 kc = keys[s];
 			if (kc == YK_EMPTY) break;
 			if (kc >> 10 == kid) {                                            /* a key occurs once in the list: nobody else touches its slot -- the count goes in at once, saturated (htab.c:73-74) */
-				const u64 n = (kc & 1023) + c;
+				const u64 n = fix ? c : (kc & 1023) + c;
 				yk_global_rw(u64, img.keys)[img.off[p] + s] = (kc & ~1023ull) | (n > 1023 ? 1023 : n);
 				break;
 			}

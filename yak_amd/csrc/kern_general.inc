@@ -274,12 +274,17 @@ void k_img_setcnt(ImgView img, u64 n_slots, u32 cnt)
 		if (img.used[i >> 5] >> (i & 31) & 1) img.keys[i] = (img.keys[i] & ~1023ull) | cnt;
 }
 
+/* bump: instead of 0 the count of a stored key becomes min(count + 1, 1023) -- the clear and the count pass over the input of the pass before in
+ * one sweep (engine_pass.cpp yakamd_count_retained: that pass counts every instance, the pass before counted all but the first) */
 __global__ __launch_bounds__(256)
-void k_img_clear(ImgView img, u64 n_slots)                   /* reference htab.c:116-125 */
+void k_img_clear(ImgView img, u64 n_slots, int bump)         /* reference htab.c:116-125 */
 {
 	const u64 stride = (u64)gridDim.x * blockDim.x;
 	for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n_slots; i += stride)
-		if (img.used[i >> 5] >> (i & 31) & 1) img.keys[i] &= ~1023ull;
+		if (img.used[i >> 5] >> (i & 31) & 1) {
+			const u64 kc = img.keys[i];
+			img.keys[i] = !bump ? kc & ~1023ull : (kc & 1023) < 1023 ? kc + 1 : kc;
+		}
 }
 
 /* yakamd_ch_sum, second step: entry i of a listing of ANOTHER table's keys -- hash[i] the key's full hash, cnt[i] its count c1 >= 1 there -- is

@@ -179,9 +179,9 @@ void yk_launch_img_fold(ImgView img, u64 n_slots, hipStream_t st)
 	if (n_slots) YK_LAUNCH(k_img_fold, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots);
 }
 
-void yk_launch_img_clear(ImgView img, u64 n_slots, hipStream_t st)
+void yk_launch_img_clear(ImgView img, u64 n_slots, hipStream_t st, int bump)
 {
-	if (n_slots) YK_LAUNCH(k_img_clear, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots);
+	if (n_slots) YK_LAUNCH(k_img_clear, dim3(grid_for(n_slots)), dim3(256), 0, st, img, n_slots, bump);
 }
 
 void yk_launch_img_hist(ImgView img, u64 n_slots, u64 *hist, hipStream_t st)
@@ -636,11 +636,11 @@ void yk_launch_cnt2(FastParams fp, const u64 *sbstart, const Rec *rec, const u64
 	else YK_LAUNCH((k_cnt2<2048, 1280>), grid, dim3(256), 0, st, fp, sbstart, rec, key_off, key_kc, img, n_sb, key_cnt, used_delta);
 	yk_launch_cnt2_apply(fp, key_kc, key_cnt, seg_base, img, st);
 }
-void yk_launch_cnt2_apply(FastParams fp, const u64 *key_kc, const u32 *key_cnt, const u64 *seg_base, ImgView img, hipStream_t st)
+void yk_launch_cnt2_apply(FastParams fp, const u64 *key_kc, const u32 *key_cnt, const u64 *seg_base, ImgView img, hipStream_t st, int fix)
 {
 	const int n_p = fp.phi - fp.plo;
 	const int per = std::max(1, 8192 / std::max(1, n_p));                  /* ~8 K workgroups in all */
-	YK_LAUNCH(k_cnt2_apply, dim3(per, n_p), dim3(256), 0, st, key_kc, key_cnt, seg_base, fp.plo, fp.pre, img);
+	YK_LAUNCH(k_cnt2_apply, dim3(per, n_p), dim3(256), 0, st, key_kc, key_cnt, seg_base, fp.plo, fp.pre, img, fix);
 }
 void yk_launch_nsel_scan(const u32 *nsel, int s2_bits, int plo, int phi, int P, const u64 *seg_base, u64 *key_off, hipStream_t st)
 {

@@ -27,6 +27,7 @@ static void legacy_replay_launch(yakamd_ctx *c, const std::vector<ReplayTask> &t
 int yk_image_commit(yakamd_ctx *c, DevBuf<u64> &&keys, DevBuf<u32> &&used, u64 tot, const std::vector<u64> &new_off)
 {
 	c->d_keys = std::move(keys); c->d_used = std::move(used); c->d_delta.reset();   /* (each frees the old image's first) */
+	yk_image_touched(c);
 	c->n_slots = tot;
 	c->h_off = new_off;
 	HIPCK(hipMemcpyAsync(c->d_bits, c->h_bits.data(), c->P * 4, hipMemcpyHostToDevice, c->st));
@@ -249,6 +250,7 @@ int yk_run_replay(yakamd_ctx *c, const std::vector<u32> &m, const u64 *d_rec_kc,
                   const u64 *d_lastput, const std::vector<u32> *init_bits, bool from_empty, const std::vector<u64> *rec_off)
 {
 	const int P = c->P;
+	if (yk_image_settle(c)) return -1;                           /* k_replay and k_r2_load read the old image's keys as they are (c->d_keys) */
 	const ReplayIn in = { P, c->h_bits.data(), c->h_count.data(), c->h_off.data(), m.data(), init_bits ? init_bits->data() : 0, rec_off ? rec_off->data() : 0, from_empty, d_lastput != 0 };
 	{
 		const int r2 = run_replay_v2(c, in, d_rec_kc, d_rec_t, d_lastput);

@@ -167,7 +167,7 @@ void yk_launch_img_inc(ImgView img, u64 hash, u64 *out2, hipStream_t st);
 void yk_launch_img_fold(ImgView img, u64 n_slots, hipStream_t st);
 void yk_launch_img_hist(ImgView img, u64 n_slots, u64 *hist, hipStream_t st);
 void yk_launch_img_setcnt(ImgView img, u64 n_slots, u32 cnt, hipStream_t st);
-void yk_launch_img_clear(ImgView img, u64 n_slots, hipStream_t st);
+void yk_launch_img_clear(ImgView img, u64 n_slots, hipStream_t st, int bump = 0);   /* bump: every count + 1, saturating, instead of 0 */
 void yk_launch_lastput(const Rec *rec, int64_t n, u64 t0, u64 t_from, AccTab tab, ImgView img,
                        int img_nonempty, int bloom_mode, const u32 *only_missing, u64 *lp_batch, hipStream_t st);
 void yk_launch_lastput_merge(u64 *lastput, const u64 *lp_batch, u32 *missing, u32 *n_missing, int P, int plo, int phi, hipStream_t st);
@@ -296,7 +296,7 @@ void yk_launch_bf_rebuild(FastParams fp, const u64 *sbstart, const Rec *rec, u32
 void yk_launch_lc_sum3(LcOut O, int s2_bits, int plo, int phi, u64 t_pass0, u32 *seg_cnt, u64 *lastput, u32 *ndist_p, hipStream_t st);
 void yk_launch_lc_gather(LcOut O, const u64 *sbstart, const u64 *key_off, int s2_bits, int plo, int phi, u64 *out_kc, u64 *out_T, Rec *out_kt, u32 *out_c2, hipStream_t st);
 void yk_launch_cnt2(FastParams fp, const u64 *sbstart, const Rec *rec, const u64 *key_off, const u64 *key_kc, const u64 *seg_base, u32 *key_cnt, ImgView img, u64 n_keys, u32 *used_delta, hipStream_t st);
-void yk_launch_cnt2_apply(FastParams fp, const u64 *key_kc, const u32 *key_cnt, const u64 *seg_base, ImgView img, hipStream_t st);
+void yk_launch_cnt2_apply(FastParams fp, const u64 *key_kc, const u32 *key_cnt, const u64 *seg_base, ImgView img, hipStream_t st, int fix = 0);   /* fix: behind k_img_clear's bump */
 void yk_launch_nsel_scan(const u32 *nsel, int s2_bits, int plo, int phi, int P, const u64 *seg_base, u64 *key_off, hipStream_t st);
 void yk_launch_seg_sort_pass2(const u64 *seg_base, const u32 *seg_cnt, int P, const u64 *src_kc, const u64 *src_t,
                               u64 *dst_kc, u64 *dst_t, int shift, u32 *dig_hist, int n_dig, hipStream_t st, int big);
