@@ -1,11 +1,14 @@
 """The N > 1 path of bench.py on ONE device: two ranks (torch.distributed.run, gloo instead of RCCL so
 that both may use GPU 0) shard the prefixes, exchange their k-mers and count; the job's result must
 equal the single-rank run on the same logical input (rank 0's reads followed by rank 1's)."""
+import ctypes as C
+import gzip
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -80,3 +83,80 @@ def test_bench_n_gpus_with_a_slot_per_rank_runs_the_exchange(knobs, exchange):
     cb = r["cpu_baseline"]
     assert cb["kind"] in ("reference", "port") and cb["value"] > 0 and cb["cores"] >= 1
     assert "traffic" in r["roofline"] and r["roofline"]["traffic_source"]
+
+
+# ---- yak_count()'s own multi-rank driver over the three kinds of input ----
+def count_protocol(ya, fn, bf, count=None):
+    """`yak count -b<bf>` on `fn` through yak_count() (reference main.c:53-61) -> the .yak bytes"""
+    L = ya.lib()
+    count = count or L.yak_count
+    o = ya.CoptT(); L.yak_copt_init(C.byref(o)); o.k, o.bf_shift = 31, bf
+    h = count(fn.encode(), C.byref(o), None)
+    assert h, ya._err()
+    t = ya.Table(ptr=h)
+    try:
+        if bf:
+            t.destroy_bf(); t.clear()
+            assert count(fn.encode(), C.byref(o), t.h), ya._err()
+            t.shrink(2, 1023)
+        return t.dump_bytes()
+    finally:
+        t.close()
+
+
+@pytest.fixture(scope="module")
+def three_ways(synth, oracle, tmp_path_factory):
+    """8000 reads of 150 bases around one record of 200 000 (longer than a chunk of 65536), about 1.4 MB: above the parallel reader's floor of 1 MiB.
+    The same FASTA plain and gzipped, a named pipe to send it through, and what the oracle and ONE rank make of it (both protocols)"""
+    import yak_amd as ya
+    assert ya.lib().yakamd_device_count() >= 1
+    d = tmp_path_factory.mktemp("three_ways")
+    recs = synth(8000, g=60000, s=77).split(b"\n")[:-1]
+    long_rec = np.frombuffer(b"ACGT", np.uint8)[np.random.default_rng(5).integers(0, 4, 200000)].tobytes()
+    recs = recs[:4000] + [long_rec] + recs[4000:]
+    img = b"".join(r + b"\n" for r in recs)
+    plain = str(d / "reads.fa")
+    with open(plain, "wb") as f:
+        for i, r in enumerate(recs):
+            f.write(b">r%d\n%s\n" % (i, r))
+    assert os.path.getsize(plain) > (1 << 20)
+    gz = str(d / "reads.fa.gz")
+    with open(plain, "rb") as f, gzip.open(gz, "wb", compresslevel=1) as g:
+        g.write(f.read())
+    fifo = str(d / "fifo")
+    os.mkfifo(fifo)
+    want = {}
+    for bf in (0, 24):
+        want[bf] = oracle.count_protocol_mem(img, k=31, bf_shift=bf)[0]
+        assert count_protocol(ya, plain, bf) == want[bf]                  # one rank
+    return dict(ya=ya, plain=plain, gz=gz, fifo=fifo, want=want)
+
+
+@pytest.mark.parametrize("bf", [0, 24], ids=["no_filter", "b24_two_passes"])
+@pytest.mark.parametrize("kind", ["plain", "gz", "pipe"])
+def test_yak_count_over_two_ranks_takes_every_kind_of_input(kind, bf, three_ways, knob, capfd):
+    """yak_count() with YAKAMD_GPUS=2, every rank a slot of its own and the grouped send / recv served by the in-process rig: some ten rounds of two
+    chunks of 65536 bases per pass, the long record cut inside -- from the parallel parser (plain), the parallel inflater (gz) and the streaming
+    reader (a named pipe).  The sharded table's .yak bytes equal the oracle's, which the fixture has held ONE rank to as well"""
+    ya, w = three_ways["ya"], three_ways
+    knob("YAKAMD_GPUS", 2); knob("YAKAMD_MGPU_CHUNK", 65536)
+    knob("YAKAMD_MGPU_SLOT_PER_RANK", 1); knob("YAKAMD_MGPU_LOOPBACK", 1)
+    if kind == "pipe":
+        def count(_, o, h):
+            p = subprocess.Popen(["sh", "-c", 'cat "$0" > "$1"', w["plain"], w["fifo"]])   # the writer's open waits in the child for the reader
+            try:
+                return ya.lib().yak_count(w["fifo"].encode(), o, h)
+            finally:
+                p.wait(timeout=600)
+        got = count_protocol(ya, w["fifo"], bf, count)
+    elif kind == "gz":
+        ya.gz_tune(100000, 0, -1)                                        # the parallel inflater takes a file this small, in several chunks
+        try:
+            got = count_protocol(ya, w["gz"], bf)
+        finally:
+            ya.gz_tune(1 << 20, 4 << 20, 64 << 20)
+    else:
+        got = count_protocol(ya, w["plain"], bf)
+    assert ya.lib().yakamd_last_sweeps() == 2
+    assert capfd.readouterr().err.count("(2 GPUs, grouped send / recv served by the in-process test rig)") == (2 if bf else 1)   # every pass went over the rig
+    assert got == w["want"][bf]

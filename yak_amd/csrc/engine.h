@@ -1,5 +1,5 @@
 /* engine.h -- internal interface between pool.cpp, the engine (engine_ctx.cpp, engine_pass.cpp, engine_slice.cpp, engine_table.cpp), table_read.cpp,
- * lookup_dev.cpp and the yak.h surface (yak_api.cpp, yak_reader.cpp, yak_multi.cpp, yak_inspect.cpp, yak_print.cpp) */
+ * lookup_dev.cpp and the yak.h surface (yak_api.cpp, yak_count.cpp, yak_reader.cpp, yak_multi.cpp, yak_inspect.cpp, yak_print.cpp) */
 #ifndef YK_ENGINE_H
 #define YK_ENGINE_H
 #include <vector>
@@ -42,7 +42,6 @@ int  yk_ctx_add_counts(yakamd_ctx *c, const u64 *d_hash, const unsigned short *d
 int  yk_ctx_in_pass(yakamd_ctx *c);
 void yk_pool_release(void *p);
 int yk_set_error(const char *fmt, ...);                      /* this thread's yakamd_last_error() text (+ a line on stderr); returns -1 */
-int64_t yk_knob(const char *name, int64_t dflt);             /* a run-time setting: the test hook's value, else (public names only) the environment's, else dflt */
 void *yk_pool_get(size_t bytes);
 void *yk_pool_alloc(size_t bytes, bool plain);              /* pool.cpp: a device buffer from the current device's pool (plain: never from the virtual-memory tier); 0 when the device is full */
 void yk_pool_free(void *p);

@@ -534,7 +534,7 @@ int fast_admit(yakamd_ctx *c, u64 t, u64 n_pos, u64 n_cap, Rec **out, Rec *borro
 		if (kept_n + n_cap > (u64)(c->phi - c->plo) * (u64)env_i64("YAKAMD_SLICE_SB", env_i64("YAKAMD_P3_MIN", 13) < 18 ? (int64_t)1 << 18 : 8192) * per_sb) fits = false;
 	}
 	if (!c->pass.kept.empty() && c->pass.kept.back().fmt != fmt) fits = false;   /* tagged records carry ranks, Rec records stream positions: never in one slice */
-	/* (a chunk that continues a sequence cut by the caller starts k - 1 positions before the end of the previous one, yak_api.cpp take_piece:
+	/* (a chunk that continues a sequence cut by the caller starts k - 1 positions before the end of the previous one, yak_multi.cpp take_piece:
 	 * its first k - 1 positions complete no k-mer, so it is still "behind" everything kept) */
 	if (!fits && !c->pass.kept.empty() && t + (u64)(c->k - 1) >= c->t_end && (fmt != 0 || n_pos < 0xfffffff0ull) && cost <= c->fast_budget && !c->pass.acc.s) {
 		/* the kept batches are a complete prefix of the stream: count them now, exactly as if the pass

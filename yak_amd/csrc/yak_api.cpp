@@ -2,9 +2,11 @@
  * yak_api.cpp -- the drop-in C surface (include/yak.h) on top of the HBM-resident engine.
  *
  * Every function keeps the reference's name, argument meaning, return convention and messages
- * (reference file:line cited per function).  Host work here is orchestration only: parsing the
- * input file, staging bases, writing the .yak file from the host mirror.  All counting, bloom
- * gating, table layout, clearing and shrinking run in the HIP kernels of kernels.hip.
+ * (reference file:line cited per function): the table's life cycle, insert_list, the operations on
+ * two tables (subtract / isec, merge / sum), dump and restore.  Host work here is orchestration only;
+ * all counting, bloom gating, table layout, clearing and shrinking run in the HIP kernels of
+ * kernels.hip.  yak_count() is in yak_count.cpp, the input reader in yak_reader.cpp, qv's solver in
+ * yak_qv_solve.cpp.
  */
 #include "yak_host.h"
 #include <unistd.h>
@@ -498,85 +500,55 @@ bool DumpSink::put(int dev, hipStream_t st, const uint8_t *d_src, size_t bytes, 
 	return good;
 }
 
-/* the whole .yak image through `sink`; its size, or -1 */
-static int64_t dump_through(yak_ch_t *h, DumpSink *sink, bool size_only)
+/* the bytes of sub-tables [lo, hi) -- {capacity, size, keys in slot order} each -- through `sink`, behind the 16-byte header when `head` is set (the whole
+ * table then: the .yak image), every shard staging the part it owns; their number, or -1.  sink == 0: the number alone */
+static int64_t dump_through(yak_ch_t *h, int lo, int hi, bool head, DumpSink *sink)
 {
 	yak_ch_ext *e = (yak_ch_ext*)h;
 	const int P = 1 << h->pre, n_sub = YK_MULTI(e) ? e->n_sub : 1;
-	size_t sz = 16 + (size_t)8 * P;
+	if (lo < 0 || hi > P || lo >= hi) return -1;
+	struct Part { yak_ch_t *hs; int a, b; };
+	std::vector<Part> part;
+	size_t sz = (head ? 16 : 0) + (size_t)8 * (hi - lo), off = 0;
 	uint32_t cap, cnt;
 	for (int r = 0; r < n_sub; ++r) {
-		yak_ch_t *hs = YK_MULTI(e) ? e->sub[r] : h;
-		const int lo = YK_MULTI(e) ? (int)(((int64_t)r << h->pre) / n_sub) : 0, hi = YK_MULTI(e) ? (int)(((int64_t)(r + 1) << h->pre) / n_sub) : P;
-		for (int p = lo; p < hi; ++p) { if (yakamd_subtable(hs, p, &cap, &cnt) != 0) return -1; sz += (size_t)8 * cnt; }
+		const Part pt = { YK_MULTI(e) ? e->sub[r] : h, std::max(lo, (int)(((int64_t)r << h->pre) / n_sub)), std::min(hi, (int)(((int64_t)(r + 1) << h->pre) / n_sub)) };
+		for (int p = pt.a; p < pt.b; ++p) { if (yakamd_subtable(pt.hs, p, &cap, &cnt) != 0) return -1; sz += (size_t)8 * cnt; }
+		if (pt.a < pt.b) part.push_back(pt);
 	}
-	if (size_only) return (int64_t)sz;
-	uint8_t head[16];
-	const uint32_t t[3] = { (uint32_t)h->k, (uint32_t)h->pre, YAK_COUNTER_BITS };
-	memcpy(head, YAK_MAGIC, 4); memcpy(head + 4, t, 12);
-	if (sink->mem) memcpy(sink->mem, head, 16);
-	else if (::pwrite(sink->fd, head, 16, 0) != 16) return -1;
-	size_t off = 16;
-	for (int r = 0; r < n_sub; ++r) {
-		yak_ch_t *hs = YK_MULTI(e) ? e->sub[r] : h;
-		const int lo = YK_MULTI(e) ? (int)(((int64_t)r << h->pre) / n_sub) : 0, hi = YK_MULTI(e) ? (int)(((int64_t)(r + 1) << h->pre) / n_sub) : P;
-		yakamd_ctx *c = ((yak_ch_ext*)hs)->ctx;
+	if (!sink) return (int64_t)sz;
+	if (head) {
+		uint8_t hd[16];
+		const uint32_t t[3] = { (uint32_t)h->k, (uint32_t)h->pre, YAK_COUNTER_BITS };
+		memcpy(hd, YAK_MAGIC, 4); memcpy(hd + 4, t, 12);
+		if (sink->mem) memcpy(sink->mem, hd, 16);
+		else if (::pwrite(sink->fd, hd, 16, 0) != 16) return -1;
+		off = 16;
+	}
+	for (const Part &pt : part) {
+		yakamd_ctx *c = ((yak_ch_ext*)pt.hs)->ctx;
 		StagedRange s;                                               /* (the image goes back when the shard is written) */
-		if (s.stage(c, lo, hi) != 0 || !sink->put(yk_ctx_device(c), yk_ctx_stream(c), (const uint8_t*)s.d_img, (size_t)s.n_words * 8, off)) return -1;
+		if (s.stage(c, pt.a, pt.b) != 0 || off + (size_t)s.n_words * 8 > sz || !sink->put(yk_ctx_device(c), yk_ctx_stream(c), (const uint8_t*)s.d_img, (size_t)s.n_words * 8, off)) return -1;
 		off += (size_t)s.n_words * 8;
 	}
 	return off == sz ? (int64_t)sz : -1;
 }
 
-int64_t yakamd_dump_mem(yak_ch_t *h, uint8_t **out)
+/* to memory: the whole image (yakamd_dump_mem), or the bytes of sub-tables [lo, hi) alone, no header: what one rank of a prefix-sharded job owns of
+ * the .yak file (tests and bench.py compare a rank's share with the oracle's without serialising the whole table) */
+static int64_t dump_to_mem(yak_ch_t *h, int lo, int hi, bool head, uint8_t **out)
 {
 	*out = 0;
-	const int64_t sz = dump_through(h, 0, true);
+	const int64_t sz = dump_through(h, lo, hi, head, 0);
 	if (sz < 0) return -1;
 	DumpSink sink; sink.mem = (uint8_t*)malloc((size_t)sz); sink.fd = -1;
 	if (!sink.mem) return -1;
-	if (dump_through(h, &sink, false) != sz) { free(sink.mem); return -1; }
+	if (dump_through(h, lo, hi, head, &sink) != sz) { free(sink.mem); return -1; }
 	*out = sink.mem;
 	return sz;
 }
-
-/* the bytes of sub-tables [lo, hi) alone -- {capacity, size, keys in slot order} each, no header: what one rank of a prefix-sharded job owns of
- * the .yak file (tests and bench.py compare a rank's share with the oracle's without serialising the whole table) */
-int64_t yakamd_dump_range_mem(yak_ch_t *h, int lo, int hi, uint8_t **out)
-{
-	*out = 0;
-	yak_ch_ext *e = (yak_ch_ext*)h;
-	const int P = 1 << h->pre, n_sub = YK_MULTI(e) ? e->n_sub : 1;
-	if (lo < 0 || hi > P || lo >= hi) return -1;
-	size_t sz = (size_t)8 * (hi - lo);
-	uint32_t cap, cnt;
-	auto owner_range = [&](int r, int *a, int *b) {
-		*a = YK_MULTI(e) ? (int)(((int64_t)r << h->pre) / n_sub) : 0; *b = YK_MULTI(e) ? (int)(((int64_t)(r + 1) << h->pre) / n_sub) : P;
-		*a = std::max(*a, lo); *b = std::min(*b, hi);
-	};
-	for (int r = 0; r < n_sub; ++r) {
-		int a, b;
-		owner_range(r, &a, &b);
-		yak_ch_t *hs = YK_MULTI(e) ? e->sub[r] : h;
-		for (int p = a; p < b; ++p) { if (yakamd_subtable(hs, p, &cap, &cnt) != 0) return -1; sz += (size_t)8 * cnt; }
-	}
-	DumpSink sink; sink.mem = (uint8_t*)malloc(sz); sink.fd = -1;
-	if (!sink.mem) return -1;
-	size_t off = 0;
-	for (int r = 0; r < n_sub; ++r) {
-		int a, b;
-		owner_range(r, &a, &b);
-		if (a >= b) continue;
-		yakamd_ctx *c = ((yak_ch_ext*)(YK_MULTI(e) ? e->sub[r] : h))->ctx;
-		StagedRange s;
-		if (s.stage(c, a, b) != 0 || off + (size_t)s.n_words * 8 > sz
-		    || !sink.put(yk_ctx_device(c), yk_ctx_stream(c), (const uint8_t*)s.d_img, (size_t)s.n_words * 8, off)) { free(sink.mem); return -1; }
-		off += (size_t)s.n_words * 8;
-	}
-	if (off != sz) { free(sink.mem); return -1; }
-	*out = sink.mem;
-	return (int64_t)sz;
-}
+int64_t yakamd_dump_mem(yak_ch_t *h, uint8_t **out) { return dump_to_mem(h, 0, 1 << h->pre, true, out); }
+int64_t yakamd_dump_range_mem(yak_ch_t *h, int lo, int hi, uint8_t **out) { return dump_to_mem(h, lo, hi, false, out); }
 
 int yak_ch_dump(const yak_ch_t *h, const char *fn)
 {
@@ -598,7 +570,7 @@ int yak_ch_dump(const yak_ch_t *h, const char *fn)
 		 * instead of being given back and asked for again (0.05 s instead of 0.12 s for 420 MB) */
 		sink.fd = ::open(fn, O_WRONLY | O_CREAT, 0666);
 		if (sink.fd < 0) return -1;
-		const int64_t sz = dump_through((yak_ch_t*)h, &sink, false);
+		const int64_t sz = dump_through((yak_ch_t*)h, 0, 1 << h->pre, true, &sink);
 		const bool cut = sz >= 0 && ::ftruncate(sink.fd, (off_t)sz) == 0;
 		if (sz < 0) (void)::ftruncate(sink.fd, 0);                  /* a dump that failed midway leaves an empty file, not a header in front of old bytes (fopen "wb", htab.c:377, never keeps any) */
 		if (::close(sink.fd) != 0 || !cut) return -1;
@@ -729,402 +701,4 @@ yak_ch_t *yak_ch_restore_core(yak_ch_t *ch0, const char *fn, int mode, ...)
 
 yak_ch_t *yak_ch_restore(const char *fn) { return yak_ch_restore_core(0, fn, YAK_LOAD_ALL); }   /* reference htab.c:478 */
 
-/* hpc: a new table is marked as living in homopolymer-compressed space before its first feed (yakamd_count_hpc); an existing table's own mark governs */
-static yak_ch_t *count_file(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, bool hpc);
-yak_ch_t *yak_count(const char *fn, const yak_copt_t *opt, yak_ch_t *h0) { return count_file(fn, opt, h0, false); }
-yak_ch_t *yakamd_count_hpc(const char *fn, const yak_copt_t *opt, yak_ch_t *h0)
-{
-	if (h0 && !yakamd_ch_hpc(h0)) {
-		yk_set_error("yakamd_count_hpc: the table is not marked as homopolymer-compressed (yakamd_ch_set_hpc); its keys were chosen in uncompressed space");
-		return 0;
-	}
-	return count_file(fn, opt, h0, true);
-}
-
-static yak_ch_t *count_file(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, bool hpc)
-{
-	{
-		std::vector<int> dev;
-		const int N = h0 ? ((yak_ch_ext*)h0)->n_sub : multi_gpus(opt, &dev, fn);
-		if (N > 1) {
-			if (h0) { dev.clear(); for (int r = 0; r < N; ++r) dev.push_back(yk_ctx_device(((yak_ch_ext*)((yak_ch_ext*)h0)->sub[r])->ctx)); }
-			return yak_count_multi(fn, opt, h0, N, dev, hpc);
-		}
-	}
-	/* the file's identity: the filtered protocol counts the same file twice (main.c:53-57); the first call then keeps its hashed k-mers on
-	 * the device (yakamd_retain_input) and the second counts those instead of parsing, copying and hashing the file again */
-	uint64_t sid[4] = { 0, 0, 0, 0 };
-	bool have_sid = false;
-	{
-		struct stat sb;
-		if (fn && strcmp(fn, "-") != 0 && stat(fn, &sb) == 0 && S_ISREG(sb.st_mode) && !yk_knob("YAKAMD_NO_RETAIN", 0)) {
-			sid[0] = (uint64_t)sb.st_dev; sid[1] = (uint64_t)sb.st_ino; sid[2] = (uint64_t)sb.st_size;
-			sid[3] = (uint64_t)sb.st_mtim.tv_sec * 1000000000ull + (uint64_t)sb.st_mtim.tv_nsec;
-			have_sid = true;
-		}
-	}
-	bool pass_open = false;
-	if (h0) {
-		assert(h0->k == opt->k && h0->pre == opt->pre);         /* count.c:157 */
-		int64_t n_seq_kept = 0;
-		if (have_sid && yk_ctx_same_source(((yak_ch_ext*)h0)->ctx, sid, &n_seq_kept)) {
-			yk_realtime();
-			if (yakamd_pass_begin(h0, 0) != 0) return 0;
-			const int r = yakamd_count_retained(h0);
-			if (r < 0) { yakamd_pass_end(h0); return 0; }
-			if (r == 0) {
-				const int64_t n_ins = yakamd_pass_end(h0);
-				if (n_ins < 0) return 0;
-				h0->tot += (uint64_t)n_ins;
-				fprintf(stderr, "[M::%s::%.3f*%.2f] %ld sequences in total (the k-mers of the first pass over this file, kept on the device); %ld distinct k-mers in the hash table\n", "yak_count",
-				        yk_realtime(), yk_cputime() / (yk_realtime() + 1e-9), (long)n_seq_kept, (long)h0->tot);
-				return h0;
-			}
-			pass_open = true;                                     /* nothing usable was kept: the pass goes on with the file */
-		}
-	}
-	FxReader fx;
-	if (!fx.open_file(fn)) { if (pass_open) yakamd_pass_end(h0); return 0; }   /* count.c:152 */
-	yak_ch_t *h = h0;
-	const int create_new = h0 ? 0 : 1;
-	yk_realtime();
-	/* a plain regular file is mapped and parsed by several threads; anything else (gzip, a pipe) streams through the reader */
-	const int n_thr = parse_threads(opt->n_thread);
-	ByteSource psrc; int psrc_fd = -1;
-	int64_t par_size = parallel_source(fn, fx, n_thr, 1 << 20, &psrc, &psrc_fd) ? psrc.size : -1;   /* plain or block-gzipped regular file */
-	pgz::Reader *gz_p = new pgz::Reader;
-	pgz::Reader &gz = *gz_p;
-	struct GzDrop { pgz::Reader *p; ~GzDrop() { pgz::Reader *q = p; yk_reap_later([q]() { delete q; }); } } gz_drop{ gz_p };   /* (its buffers go back to the system behind the caller's back) */
-	const bool use_gz = par_size < 0 && gz_source(fn, fx, n_thr, &gz);   /* an ordinary gzip file */
-	if (use_gz) par_size = 0;
-	int ok = 0;
-	auto open_table = [&]() {                                /* a new table: runtime start-up, the filter's 2^bf_shift bits, the pass */
-		if (!h0) h = yak_ch_init(opt->k, opt->pre, opt->bf_n_hash, opt->bf_shift);
-		if (!h0 && h && hpc) yakamd_ch_set_hpc(h, 1);
-		if (!h0 && h && have_sid && opt->bf_shift > opt->pre) yakamd_retain_input(h, 1);   /* a filtered count: a second pass over this file is to be expected */
-		ok = h != 0 && (pass_open || yakamd_pass_begin(h, create_new) == 0);
-	};
-	std::thread opener;                                      /* ... happen while the first window of the file is being parsed */
-	if (par_size >= 0 && !h0) opener = std::thread(open_table); else open_table();
-	if (!opener.joinable() && h == 0) { if (psrc_fd >= 0) ::close(psrc_fd); fx.close_file(); return 0; }
-	std::vector<char> chunk;
-	if (par_size < 0) chunk.reserve((size_t)std::min<int64_t>(opt->chunk_size + (opt->chunk_size >> 3) + 65536, (int64_t)1 << 31));
-	uint64_t t0 = 0;
-	int64_t l, sum_len = 0, n_seq = 0, n_seq_tot = 0;
-	if (par_size >= 0) {
-		const bool pack = !yk_knob("YAKAMD_NO_HOST_PACK", 0);          /* the stream crosses the bus at 0.375 B per base, packed by the threads that parsed it */
-		psrc.pack = pack;
-		double t_sink = 0, t_open_wait = 0;
-		g_t_parse_windows.store(0, std::memory_order_relaxed);
-		const ImgSink sink = [&](const char *img, size_t img_n, int64_t ns, const WinPack *packed) {
-			const double ts0 = yk_realtime();
-			if (opener.joinable()) { opener.join(); t_open_wait = yk_realtime() - ts0; }
-			if (!ok) return false;
-			bool good = img_n == 0 || (pack ? yakamd_feed_packed_pieces_host(h, (int)packed->n_words.size(), packed->codes.data(), packed->valid.data(), packed->n_words.data(), t0)
-			                                : yakamd_feed_bases_host(h, img, (int64_t)img_n, t0)) == 0;
-			t_sink += yk_realtime() - ts0;
-			t0 += img_n; n_seq_tot += ns;
-			fprintf(stderr, "[M::%s::%.3f*%.2f] processed %ld sequences\n", "yak_count", yk_realtime(), yk_cputime() / (yk_realtime() + 1e-9), (long)ns);
-			return good;
-		};
-		const double tp0 = yk_realtime();
-		const bool parsed = use_gz ? parse_gz(&gz, opt->k, n_thr, sink, pack) : parse_parallel(&psrc, opt->k, n_thr, sink);
-		if (getenv("YAKAMD_VERBOSE")) fprintf(stderr, "[yak_amd] reader: %.3f s from the first window to the last piece fed; the windows took %.3f s to parse (the first %.3f s), the feeds %.3f s (%.3f s of it waiting for the new table)\n",
-		                                      yk_realtime() - tp0, g_t_parse_windows.load(), g_t_first_window.load(), t_sink, t_open_wait);
-		if (opener.joinable()) opener.join();
-		if (h == 0) { if (psrc_fd >= 0) ::close(psrc_fd); fx.close_file(); return 0; }
-		ok = ok && parsed;
-	}
-	auto flush = [&]() {
-		if (!chunk.empty() && ok) ok = yakamd_feed_bases_host(h, chunk.data(), (int64_t)chunk.size(), t0) == 0;
-		t0 += chunk.size();
-		n_seq_tot += n_seq;
-		fprintf(stderr, "[M::%s::%.3f*%.2f] processed %ld sequences\n", "yak_count", yk_realtime(), yk_cputime() / (yk_realtime() + 1e-9), (long)n_seq);
-		chunk.clear(); sum_len = 0; n_seq = 0;
-	};
-	while (ok && par_size < 0) {                             /* count.c:93 */
-		if ((l = fx.fast(chunk, opt->k)) == FxReader::NOT_FAST) {
-			if ((l = fx.next()) < 0) break;
-			if (l >= opt->k) { chunk.insert(chunk.end(), fx.seq.begin(), fx.seq.end()); chunk.push_back('\n'); }   /* a non-ACGT byte ends the read (count.c:41) */
-		}
-		if (l < opt->k) continue;                            /* count.c:95 */
-		sum_len += l; ++n_seq;
-		if (sum_len >= opt->chunk_size || chunk.size() > ((size_t)1 << 31)) flush();   /* count.c:106 */
-	}
-	if (n_seq) flush();
-	if (ok) {
-		const int64_t n_ins = yakamd_pass_end(h);
-		if (n_ins < 0) ok = 0; else h->tot += (uint64_t)n_ins;   /* count.c:138 */
-		if (ok && create_new && have_sid && yakamd_retained_instances(h) > 0) yk_ctx_set_source(((yak_ch_ext*)h)->ctx, sid, n_seq_tot);
-	}
-	fprintf(stderr, "[M::%s::%.3f*%.2f] %ld sequences in total; %ld distinct k-mers in the hash table\n", "yak_count",
-	        yk_realtime(), yk_cputime() / (yk_realtime() + 1e-9), (long)n_seq_tot, (long)h->tot);
-	if (getenv("YAKAMD_VERBOSE") && h) { (void)hipSetDevice(yk_ctx_device(((yak_ch_ext*)h)->ctx)); yk_pool_report("the pass"); }
-	if (psrc_fd >= 0) ::close(psrc_fd);
-	fx.close_file();
-	if (!ok) { if (!h0) yak_ch_destroy(h); return 0; }
-	return h;
-}
-
-/* reference count.c:168-193: clear the counts, then count the k-mers of fn that are in the table --
- * one count-existing pass on the device (sequences shorter than k have no k-mer either way) */
-void yak_recount(const char *fn, yak_ch_t *h)
-{
-	yak_copt_t o;
-	yak_copt_init(&o);
-	o.k = h->k; o.pre = h->pre;
-	/* count.c:172-173: an unreadable file leaves the table untouched.  (Asked, not tried: opening and closing a named pipe -- `yak recount <(zcat ...)` --
-	 * would take the stream away from the count behind it) */
-	if (fn != 0 && strcmp(fn, "-") != 0 && access(fn, R_OK) != 0) return;
-	yak_ch_clear(h, 1);
-	if (yak_count(fn, &o, h) == 0) fprintf(stderr, "[E::yak_recount] %s\n", yakamd_last_error());
-}
-
-/* host-only hook for tests: the base image yak_count() would hand to the device for `fn` (sequences
- * of at least min_len bases, each followed by '\n'); caller frees *out with free().  -1 if unreadable. */
-int64_t yakamd_host_image(const char *fn, int min_len, int use_fast_path, char **out)
-{
-	FxReader fx;
-	if (!fx.open_file(fn)) return -1;
-	std::vector<char> img;
-	int64_t l;
-	const double t_ = yk_realtime();
-	const int n_thr = use_fast_path ? parse_threads(1) : 1;    /* tests set YAKAMD_PARSE_THREADS */
-	{
-		ByteSource psrc; int psrc_fd = -1;
-		pgz::Reader gz;
-		const bool plain = parallel_source(fn, fx, n_thr, 0, &psrc, &psrc_fd);
-		if (plain || gz_source(fn, fx, n_thr, &gz)) {
-			size_t total = 0;
-			const bool keep = !(use_fast_path & 2);                   /* (2: the image is only measured, for timing the reader) */
-			const ImgSink sink = [&](const char *part, size_t part_n, int64_t, const WinPack*) { total += part_n; if (keep) img.insert(img.end(), part, part + part_n); return true; };
-			if (plain) parse_parallel(&psrc, min_len, n_thr, sink);
-			else if (!parse_gz(&gz, min_len, n_thr, sink)) { fx.close_file(); return -1; }
-			if (getenv("YAKAMD_VERBOSE")) fprintf(stderr, "[yak_amd] host_image: %.3f s, %d threads, %zu bytes%s\n", yk_realtime() - t_, n_thr, total, psrc.bgzf ? " (BGZF blocks inflated by the parser threads)" : "");
-			if (psrc_fd >= 0) ::close(psrc_fd);
-			fx.close_file();
-			*out = (char*)malloc(img.size() + 1);
-			memcpy(*out, img.data(), img.size());
-			return (int64_t)img.size();
-		}
-	}
-	for (;;) {
-		if (!use_fast_path || (l = fx.fast(img, min_len)) == FxReader::NOT_FAST) {
-			if ((l = fx.next()) < 0) break;
-			if (l >= min_len) { img.insert(img.end(), fx.seq.begin(), fx.seq.end()); img.push_back('\n'); }
-		}
-	}
-	if (getenv("YAKAMD_VERBOSE")) fprintf(stderr, "[yak_amd] host_image: %.3f s in the reader loop\n", yk_realtime() - t_);
-	fx.close_file();
-	*out = (char*)malloc(img.size() + 1);
-	memcpy(*out, img.data(), img.size());
-	return (int64_t)img.size();
-}
-
-/* host-only hook for tests: what yak_count() hands to the device when its parser threads pack (one packed image per window), unpacked again --
- * 'A' 'C' 'G' 'T' for a base, '\n' for a position that is none (N, a record's end, the positions that pad a segment to a multiple of 32) */
-int64_t yakamd_host_image_packed(const char *fn, int min_len, char **out)
-{
-	FxReader fx;
-	*out = 0;
-	if (!fx.open_file(fn)) return -1;
-	const int n_thr = parse_threads(1);
-	std::vector<char> img;
-	ByteSource psrc; int psrc_fd = -1;
-	pgz::Reader gz;
-	const ImgSink sink = [&](const char*, size_t, int64_t, const WinPack *wp) {
-		for (size_t p = 0; p < wp->n_words.size(); ++p) {
-			const uint32_t *codes = (const uint32_t*)wp->codes[p], *valid = (const uint32_t*)wp->valid[p];
-			for (size_t j = 0; j < (size_t)wp->n_words[p] * 32; ++j) img.push_back((valid[j >> 5] >> (j & 31) & 1) ? "ACGT"[codes[j >> 4] >> (2 * (j & 15)) & 3] : '\n');
-		}
-		return true;
-	};
-	bool ok = true;
-	if (parallel_source(fn, fx, n_thr, 0, &psrc, &psrc_fd)) { psrc.pack = true; ok = parse_parallel(&psrc, min_len, n_thr, sink); }
-	else if (gz_source(fn, fx, n_thr, &gz)) ok = parse_gz(&gz, min_len, n_thr, sink, true);
-	else ok = false;
-	if (psrc_fd >= 0) ::close(psrc_fd);
-	fx.close_file();
-	if (!ok) return -1;
-	*out = (char*)malloc(img.size() + 1);
-	memcpy(*out, img.data(), img.size());
-	return (int64_t)img.size();
-}
-
-/* host-only hooks for tests of the gzip reader: its chunk size, the smallest file it takes and the room in front of a batch (0 / < 0: as is); the whole inflated stream of
- * `fn` through the batch interface, every batch handing a tail back as the parser does (-1: not a file the reader takes; -2: it failed) */
-void yakamd_gz_tune(int64_t chunk_bytes, int64_t min_file_bytes, int64_t front_bytes)
-{
-	if (chunk_bytes > 0) pgz::tune().chunk = (size_t)chunk_bytes;
-	if (min_file_bytes >= 0) pgz::tune().min_size = (size_t)min_file_bytes;
-	if (front_bytes >= 0) pgz::tune().front = (size_t)front_bytes;
-}
-int64_t yakamd_gz_inflate(const char *fn, int n_threads, char **out)
-{
-	pgz::Reader z;
-	*out = 0;
-	pgz::tune().no_simd = yk_knob("YAKAMD_NO_AVX2", 0) != 0;
-	if (!z.open(fn, n_threads, true)) return -1;
-	std::vector<char> all;
-	size_t keep = 0;
-	for (bool last = false; !last; ) {
-		uint8_t *p = 0; size_t n = 0;
-		if (!z.next(keep, &p, &n, &last)) { yk_set_error("%s", z.why.c_str()); return -2; }
-		keep = last ? n : n - std::min<size_t>(n, (all.size() * 7 + 13) % 5000);
-		all.insert(all.end(), (const char*)p, (const char*)p + keep);
-	}
-	*out = (char*)malloc(all.size() + 1);
-	memcpy(*out, all.data(), all.size());
-	return (int64_t)all.size();
-}
-
-/* n x n linear system a x = b by Gauss-Jordan elimination with full pivoting (the solver the
- * reference links as 6gjdn.c); the solution replaces b.  false if the matrix is singular. */
-static bool solve_full_pivot(double *a, double *b, int n)
-{
-	std::vector<int> col_of(n);
-	for (int k = 0; k < n; ++k) {
-		int pr = k, pc = k;
-		double big = 0.0;
-		for (int i = k; i < n; ++i)
-			for (int j = k; j < n; ++j)
-				if (fabs(a[i * n + j]) > big) { big = fabs(a[i * n + j]); pr = i; pc = j; }
-		if (big + 1.0 == 1.0) return false;
-		col_of[k] = pc;
-		if (pc != k) for (int i = 0; i < n; ++i) std::swap(a[i * n + k], a[i * n + pc]);
-		if (pr != k) { for (int j = k; j < n; ++j) std::swap(a[k * n + j], a[pr * n + j]); std::swap(b[k], b[pr]); }
-		const double piv = a[k * n + k];
-		for (int j = k + 1; j < n; ++j) a[k * n + j] /= piv;
-		b[k] /= piv;
-		for (int j = k + 1; j < n; ++j)
-			for (int i = 0; i < n; ++i)
-				if (i != k) a[i * n + j] -= a[i * n + k] * a[k * n + j];
-		for (int i = 0; i < n; ++i)
-			if (i != k) b[i] -= a[i * n + k] * b[k];
-	}
-	for (int k = n - 1; k >= 0; --k)                          /* undo the column exchanges */
-		if (col_of[k] != k) std::swap(b[k], b[col_of[k]]);
-	return true;
-}
-
-/* yak_qv_solve (reference qv.c:146-244): host arithmetic on two 1024-bin histograms -- in_table[c] = stored k-mers
- * that occur c times in the short reads, in_seqs[c] = k-mers of the assembly found with count c.  The statistics are
- * the reference's (raw QV from the share of absent k-mers; coverage at the histogram peak; bounds on the false-positive
- * rate of "absent"; corrected counts between the trough and the peak; successive ratios fitted by a parabola and
- * extrapolated to count 0; adjusted QV) and the printed digits must equal the reference's, so every floating-point
- * expression keeps the reference's operand order and association (sums run over ascending k, powers are built by
- * repeated multiplication).  That is the only thing shared with qv.c: the stages below are this file's own cut. */
 } /* extern "C" */
-namespace {
-struct QvShape { int peak = -1, trough = -1; };
-
-/* the mode of in_seqs over counts [2, 1023) and the lowest point in front of it */
-QvShape qv_shape(const int64_t *in_seqs)
-{
-	QvShape s;
-	int32_t top = 0;
-	for (int c = 2; c < YAK_N_COUNTS - 1; ++c) if (top < in_seqs[c]) { top = (int32_t)in_seqs[c]; s.peak = c; }
-	int32_t low = top;
-	for (int c = 2; c < s.peak; ++c) if (low > in_seqs[c]) { low = (int32_t)in_seqs[c]; s.trough = c; }
-	return s;
-}
-
-/* brackets the false-positive rate from the counts below the peak and clamps the caller's estimate into them */
-double qv_fpr_bounds(const int64_t *in_table, const int64_t *in_seqs, const QvShape &s, double fpr, yak_qstat_t *qs)
-{
-	qs->fpr_upper = 1.0;
-	for (int c = 2; c < s.peak; ++c) {
-		const double e = in_seqs[c] / (qs->cov * in_table[c]);
-		if (qs->fpr_upper > e) qs->fpr_upper = e;
-	}
-	if (fpr > qs->fpr_upper) fpr = qs->fpr_upper * 0.5;
-	qs->fpr_lower = 0.0;
-	if (s.trough > 2 && in_table[2] > in_table[s.trough]) {
-		const double e = (in_seqs[2] - in_seqs[s.trough]) / (qs->cov * (in_table[2] - in_table[s.trough]));
-		if (qs->fpr_lower < e) qs->fpr_lower = e;
-	}
-	if (fpr < qs->fpr_lower) fpr = qs->fpr_lower;
-	if (qs->fpr_lower >= qs->fpr_upper)
-		fprintf(stderr, "Warning: the FPR upper bound is smaller than the lower bound. Trust the lower bound.\n");
-	return fpr;
-}
-
-/* least-squares polynomial of degree DEG through (x[k], y[k]), k < n, by the normal equations: coef[i] multiplies x^i.
- * pw[m][k] = x[k]^m by repeated multiplication; entry (i, j) of the matrix is the sum over k of pw[i + j][k] */
-template <int DEG>
-bool fit_polynomial(const double *x, const double *y, int n, double *coef)
-{
-	std::vector<double> pw((size_t)(2 * DEG + 1) * n);
-	for (int k = 0; k < n; ++k) {
-		double t = 1.0;
-		for (int m = 0; m <= 2 * DEG; ++m) { pw[(size_t)m * n + k] = t; t *= x[k]; }
-	}
-	double M[(DEG + 1) * (DEG + 1)];
-	for (int i = 0; i <= DEG; ++i) {
-		for (int j = 0; j <= i; ++j) {
-			double acc = 0.0;
-			for (int k = 0; k < n; ++k) acc += pw[(size_t)(i + j) * n + k];
-			M[i * (DEG + 1) + j] = M[j * (DEG + 1) + i] = acc;
-		}
-		double acc = 0.0;
-		for (int k = 0; k < n; ++k) acc += pw[(size_t)i * n + k] * y[k];
-		coef[i] = acc;
-	}
-	return solve_full_pivot(M, coef, DEG + 1);
-}
-
-template <int DEG> double eval_polynomial(const double *coef, double at)
-{
-	double r = 0.0, t = 1.0;
-	for (int i = 0; i <= DEG; ++i) { r += coef[i] * t; t *= at; }
-	return r;
-}
-} // namespace
-
-extern "C" int yak_qv_solve(const int64_t *in_table, const int64_t *in_seqs, int kmer, double fpr, yak_qstat_t *qs)
-{
-	constexpr int DEG = 2, MAX_FIT = 8;
-	const double db_per_ln = 4.3429448190325175;             /* 10 / ln 10 */
-	memset(qs, 0, sizeof(*qs));
-	for (int c = 0; c < YAK_N_COUNTS; ++c) { qs->tot += in_seqs[c]; qs->adj_cnt[c] = (double)in_seqs[c]; }
-	qs->err = (double)in_seqs[0];
-	qs->qv = -1.0;
-	qs->qv_raw = (qs->tot > 0 && qs->tot > in_seqs[0]) ? -db_per_ln * log(log((double)qs->tot / (qs->tot - in_seqs[0])) / kmer) : -1.0;
-
-	const QvShape s = qv_shape(in_seqs);
-	if (s.peak < 0) return -1;                               /* nothing beyond count 1 */
-	qs->cov = (double)in_seqs[s.peak] / in_table[s.peak];
-	fpr = qv_fpr_bounds(in_table, in_seqs, s, fpr, qs);
-
-	const int n_fit = std::min(MAX_FIT, s.peak - s.trough + 1);
-	if (s.peak <= 4 || n_fit < 3) return -1;                 /* not high-coverage data: no adjustment */
-
-	for (int c = s.peak - 1; c >= s.trough; --c) {           /* take the expected false "present" calls out */
-		const double wrong = (in_table[c] - in_seqs[c] / qs->cov) / (1.0 - fpr);
-		qs->adj_cnt[c] = in_seqs[c] - wrong * qs->cov * fpr;
-		if (qs->adj_cnt[c] < 0.0) qs->adj_cnt[c] = 0.0;
-	}
-
-	double at[MAX_FIT], ratio[MAX_FIT], coef[DEG + 1];
-	for (int k = 0; k < n_fit; ++k) { at[k] = s.trough + k; ratio[k] = qs->adj_cnt[s.trough + k + 1] / qs->adj_cnt[s.trough + k]; }
-	if (!fit_polynomial<DEG>(at, ratio, n_fit, coef)) fprintf(stderr, "ERROR: fail\n");
-	for (int c = s.trough - 1; c >= 0; --c) {                /* below the trough: divide down by the fitted ratio, at least 1.01 */
-		double r = eval_polynomial<DEG>(coef, c);
-		if (r < 1.01) r = 1.01;
-		qs->adj_cnt[c] = qs->adj_cnt[c + 1] / r;
-	}
-
-	double adj_sum = 0.0;
-	for (int c = 0; c < YAK_N_COUNTS; ++c) adj_sum += qs->adj_cnt[c];
-	if (adj_sum <= (double)qs->tot) {
-		qs->err = qs->tot - adj_sum;
-		qs->qv = -db_per_ln * log(log(qs->tot / adj_sum) / kmer);
-	} else {
-		fprintf(stderr, "WARNING: failed to estimate the calibrated QV\n");
-		qs->err = 0;
-		qs->qv = qs->qv_raw;
-	}
-	return 0;
-}
-
-

@@ -1,7 +1,7 @@
 /*
- * yak_host.h -- internal: what the host translation units of the library share (yak_api.cpp: the yak.h surface, dump / restore, qv's solver;
- * yak_reader.cpp: the FASTA / FASTQ reader, its parallel parser and packer, the gzip hooks; yak_multi.cpp: several GPUs behind yak_count();
- * yak_lookup.cpp: the lookup-only commands qv and triobin).
+ * yak_host.h -- internal: what the host translation units of the library share (yak_api.cpp: the yak.h life cycle, merge / sum, dump / restore;
+ * yak_count.cpp: yak_count() on one device; yak_reader.cpp: the FASTA / FASTQ reader, its parallel parser and packer, the input front end (SeqInput),
+ * the reader's and the gzip hooks; yak_multi.cpp: several GPUs behind yak_count(); yak_lookup.cpp: the lookup-only commands, qv and triobin first).
  */
 #ifndef YAK_HOST_H
 #define YAK_HOST_H
@@ -195,6 +195,15 @@ struct FxReader {
 		last = c;
 		return true;
 	}
+	/* the next record's marker, name and the rest of its header line (kseq.h:192-203); false at EOF */
+	bool begin_record() {
+		int d;
+		if (!seek_marker()) return false;
+		seq.clear(); name.clear(); qlen = 0; qlast = 0;
+		if (until(false, 3, &d) < 0) return false;
+		if (d != '\n') until(true, 0, 0);
+		return true;
+	}
 	int64_t marker_pos() const { return pos0 + (last != 0 ? beg - 1 : end); }   /* file offset of the marker `last` was read from (positional mode) */
 	bool fill() {
 		if (beg < end) return true;
@@ -348,15 +357,8 @@ struct FxReader {
 			if (l >= min_len) { out.insert(out.end(), seq.begin(), seq.end()); out.push_back('\n'); }
 			return l;
 		}
-		int c, d;
-		if (last == 0) {
-			while ((c = getc()) != -1 && c != '>' && c != '@') {}
-			if (c == -1) return -1;
-			last = c;
-		}
-		seq.clear(); name.clear(); qlen = 0; qlast = 0;
-		if (until(false, 3, &d) < 0) return -1;
-		if (d != '\n') until(true, 0, 0);
+		int c;
+		if (!begin_record()) return -1;
 		const size_t at0 = out.size();
 		int64_t bulked = 0;
 		while ((c = getc()) != -1 && c != '>' && c != '+' && c != '@') {
@@ -402,15 +404,8 @@ struct FxReader {
 		return ret;
 	}
 	int64_t next() {
-		int c, d;
-		if (last == 0) {
-			while ((c = getc()) != -1 && c != '>' && c != '@') {}
-			if (c == -1) return -1;
-			last = c;
-		}
-		seq.clear(); name.clear(); qlen = 0; qlast = 0;
-		if (until(false, 3, &d) < 0) return -1;
-		if (d != '\n') until(true, 0, 0);
+		int c;
+		if (!begin_record()) return -1;
 		while ((c = getc()) != -1 && c != '>' && c != '+' && c != '@') {
 			if (c == '\n') continue;
 			seq.push_back((char)c);
@@ -435,10 +430,32 @@ extern std::atomic<double> g_t_parse_windows, g_t_first_window;   /* YAKAMD_VERB
  * at exit() or dlclose() -- and not on a detached one, which could still be inside free() while the process tears down or the code is unmapped */
 void yk_reap_later(std::function<void()> f);
 int parse_threads(int n_thread);
-bool parallel_source(const char *fn, const FxReader &fx, int n_thr, int64_t min_size, ByteSource *src, int *own_fd);
-bool parse_parallel(const ByteSource *fd, int min_len, int n_thr, const ImgSink &sink, int64_t *stopped_at = 0, bool *stream_ended = 0);
-bool gz_source(const char *fn, const FxReader &fx, int n_thr, pgz::Reader *z);
-bool parse_gz(pgz::Reader *z, int min_len, int n_thr, const ImgSink &sink, bool pack = false);
+/* when the streaming reader closes a piece: once the lengths of its sequences sum to sum_len, or its image is longer than `bytes` */
+struct PieceEnd { int64_t sum_len; size_t bytes; };
+/* The one owner of an open sequence file: the record reader, the parallel parser's byte source with the descriptor it may have opened, the parallel
+ * inflater.  open() settles what the file is -- PARALLEL: a plain or block-gzipped regular file of more than min_parallel_size bytes, parsed window by
+ * window on n_thr > 1 threads; GZ: an ordinary gzip file the parallel inflater takes; STREAM: everything else (a pipe, stdin, a small file, n_thr == 1),
+ * read record by record through `fx`.  The destructor closes what was opened; the inflater's buffers go back on another thread (yk_reap_later) */
+struct SeqInput {
+	enum Kind { STREAM, PARALLEL, GZ };
+	FxReader fx;
+	ByteSource src;
+	Kind kind = STREAM;
+	int n_thr = 1;
+	SeqInput() {}
+	SeqInput(const SeqInput&) = delete; SeqInput &operator=(const SeqInput&) = delete;
+	~SeqInput();
+	bool open(const char *fn, int n_thr, int64_t min_parallel_size);   /* false: `fn` cannot be opened */
+	/* PARALLEL and GZ: sink(image, bytes, sequences, packed pieces) for consecutive pieces of the sequences of at least min_len bases, in order; pack:
+	 * the parser threads pack what they parsed and the sink gets the pieces of a whole window, no ASCII image.  false if the sink or the inflater failed */
+	bool run(int min_len, bool pack, const ImgSink &sink);
+	/* any kind, through `fx` from where it stands: the same pieces, each closed by `end` (the last one by the end of the input; none without a sequence).
+	 * fast: FxReader::fast() may take the records it can.  reserve: room the piece's image starts with.  false if the sink failed */
+	bool stream(int min_len, bool fast, PieceEnd end, size_t reserve, const ImgSink &sink);
+private:
+	int own_fd = -1;
+	pgz::Reader *gz = 0;
+};
 
 /* 1 (and a message naming `what`) on a table sharded over prefix ranges (yak_api.cpp) */
 extern "C" int multi_refuse(const yak_ch_t *h, const char *what);

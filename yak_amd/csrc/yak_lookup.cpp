@@ -162,9 +162,11 @@ void yak_qv(const yak_qopt_t *opt, const char *fn, const yak_ch_t *ch, int64_t *
 	yak_ch_t *h = (yak_ch_t*)ch;
 	if (ch->k >= 32) { fprintf(stderr, "[E::yak_qv] k must be below 32\n"); return; }   /* qv.c:44 asserts */
 	if (multi_refuse(ch, __func__)) return;                      /* the lookup kernel reads one table image: restore the .yak file for qv */
-	FxReader fx;
-	if (!fx.open_file(fn)) return;
 	const bool want_names = opt->print_each || opt->print_err_kmer;
+	/* without -p / -E nothing of a record but its bases is needed: a plain, block-gzipped or gzip file then goes through the parallel reader
+	 * (every record's sequence + '\n', in order: qv.c:45 skips the short ones later); with them the records are read one by one */
+	SeqInput in;
+	if (!in.open(fn, want_names ? 1 : parse_threads(opt->n_threads), 1 << 20)) return;
 	const size_t max_bytes = (size_t)1 << 31;
 	uint64_t *d_hist = (uint64_t*)yakamd_dev_alloc(n_cnt * 8);
 	std::vector<uint64_t> zero(n_cnt, 0);
@@ -227,14 +229,8 @@ void yak_qv(const yak_qopt_t *opt, const char *fn, const yak_ch_t *ch, int64_t *
 		fprintf(stderr, "[M::%s] processed %ld sequences\n", "yak_qv", (long)ns);
 		chunk.clear();
 	};
-	/* without -p / -E nothing of a record but its bases is needed: a plain, block-gzipped or gzip file then goes through the parallel reader
-	 * (every record's sequence + '\n', in order: qv.c:45 skips the short ones later) */
-	const int n_thr = parse_threads(opt->n_threads);
-	ByteSource psrc; int psrc_fd = -1;
-	pgz::Reader *gz_p = new pgz::Reader;
-	struct GzDrop { pgz::Reader *p; ~GzDrop() { pgz::Reader *q = p; yk_reap_later([q]() { delete q; }); } } gz_drop{ gz_p };
-	bool parallel = false;
-	if (ok && !want_names) {
+	const bool parallel = ok && in.kind != SeqInput::STREAM;
+	if (parallel) {
 		const ImgSink sink = [&](const char *img, size_t n, int64_t, const WinPack*) {
 			const size_t base = chunk.img.size();
 			for (const char *p = img, *e = img + n; p < e; ) {
@@ -248,12 +244,10 @@ void yak_qv(const yak_qopt_t *opt, const char *fn, const yak_ch_t *ch, int64_t *
 			if (chunk.full(opt->chunk_size, max_bytes)) flush();
 			return ok;
 		};
-		if (parallel_source(fn, fx, n_thr, 1 << 20, &psrc, &psrc_fd)) { parallel = true; ok = parse_parallel(&psrc, 0, n_thr, sink) && ok; }
-		else if (gz_source(fn, fx, n_thr, gz_p)) { parallel = true; ok = parse_gz(gz_p, 0, n_thr, sink) && ok; }
-		if (psrc_fd >= 0) ::close(psrc_fd);
+		ok = in.run(0, false, sink) && ok;
 	}
 	for (bool more = !parallel; ok && more; ) {
-		more = read_chunk(fx, opt->chunk_size, max_bytes, want_names, &chunk);
+		more = read_chunk(in.fx, opt->chunk_size, max_bytes, want_names, &chunk);
 		flush();
 	}
 	if (ok) flush();                                             /* the parallel reader's last chunk */
@@ -262,7 +256,6 @@ void yak_qv(const yak_qopt_t *opt, const char *fn, const yak_ch_t *ch, int64_t *
 	if (ok) for (int i = 0; i < n_cnt; ++i) cnt[i] = (int64_t)hh[i];
 	else fprintf(stderr, "[E::yak_qv] %s\n", yakamd_last_error());
 	yakamd_dev_free(d_hist);
-	fx.close_file();
 }
 
 /* reference triobin.c:153-160 */

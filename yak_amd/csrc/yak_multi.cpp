@@ -4,6 +4,7 @@
  */
 #include "yak_host.h"
 #include "hpc_host.h"
+#include "round_plan.h"
 
 /* ------------------------------------------------------------------------------------------
  * Several GPUs behind yak_count() (replaces the kt_for over prefixes, count.c:129-143).
@@ -154,6 +155,12 @@ struct MultiJob {
  * smaller N needs (an earlier job obtained it) keeps the smaller N. */
 static int g_last_sweeps = 1;
 extern "C" int yakamd_last_sweeps(void) { return g_last_sweeps; }   /* ranks (= sweeps on one device) of this process's last yak_count() */
+/* the device of a job that names none: YAKAMD_DEVICE, else LOCAL_RANK, else 0, within the nd devices there are */
+static int default_device(int nd)
+{
+	const char *dv = getenv("YAKAMD_DEVICE"), *lr = getenv("LOCAL_RANK");
+	return (dv ? atoi(dv) : lr ? atoi(lr) : 0) % nd;
+}
 int auto_sweeps(const yak_copt_t *opt, const char *fn)
 {
 	if (fn == 0 || strcmp(fn, "-") == 0 || opt->bf_shift > opt->pre) return 1;
@@ -178,7 +185,7 @@ int auto_sweeps(const yak_copt_t *opt, const char *fn)
 	auto peak = [&](int n) { return bases * (14.0 + 56.0 / n); };
 	if (cold > 0 && peak(N) > cold) {
 		int nd = 0, d = 0;
-		if (hipGetDeviceCount(&nd) == hipSuccess && nd > 0) { const char *dv = getenv("YAKAMD_DEVICE"), *lr = getenv("LOCAL_RANK"); d = (dv ? atoi(dv) : lr ? atoi(lr) : 0) % nd; }
+		if (hipGetDeviceCount(&nd) == hipSuccess && nd > 0) d = default_device(nd);
 		if ((double)yk_pool_held_bytes(d) < peak(N))            /* the process does not own that memory yet */
 			while (N < 16 && P % (2 * N) == 0 && peak(N) > cold) N <<= 1;
 	}
@@ -194,8 +201,7 @@ int multi_gpus(const yak_copt_t *opt, std::vector<int> *dev, const char *fn)
 		if (S <= 1) return 1;
 		int nd = 0;
 		if (hipGetDeviceCount(&nd) != hipSuccess || nd < 1) return 1;
-		const char *dv = getenv("YAKAMD_DEVICE"), *lr = getenv("LOCAL_RANK");
-		const int d = (dv ? atoi(dv) : lr ? atoi(lr) : 0) % nd;
+		const int d = default_device(nd);
 		dev->assign(S, d);
 		fprintf(stderr, "[M::yak_count] %s: no filter and a large plain file: counting in %d sweeps over prefix ranges on device %d (YAKAMD_GPUS / YAKAMD_AUTO_SWEEP_GB / YAKAMD_COLD_GB change that)\n", fn, S, d);
 		g_last_sweeps = S;
@@ -302,8 +308,7 @@ static void multi_close(MultiJob *J)
 struct RoundPlan {
 	bool tagged; int W;                                         /* 8-byte tagged records; words per record */
 	std::vector<int64_t> fill; std::vector<uint64_t> t0;
-	std::vector<std::vector<uint64_t> > bst;                    /* [slot][P + 1]: where the records of prefix p start in the slot's send buffer */
-	std::vector<std::vector<uint64_t> > roff;                   /* [rank][slot]: where owner d's slice of chunk s lies in its slot's receive buffer (records) */
+	ExchangePlan X;                                             /* round_plan.h: X.bst is the partition's to fill, the rest round_exchange builds from it */
 	std::string why; std::mutex why_mu;
 	void note() { std::lock_guard<std::mutex> lk(why_mu); if (why.empty()) why = yakamd_last_error(); }   /* called on the thread that failed (the text is per thread) */
 };
@@ -322,7 +327,7 @@ static bool round_partition(MultiJob *J, int x, int k, int pre, int create_new, 
 	const int P = J->P, S = J->S;
 	R->W = create_new && !R->tagged ? 2 : 1;                    /* {hash, position}, or one word (tagged record / bare hash) */
 	for (int s = 0; s < S; ++s) if (R->fill[s] * R->W > J->send_words) { fprintf(stderr, "[E::yak_count] a chunk of %lld positions does not fit the send buffer (%lld words): 16-byte records were not planned for\n", (long long)R->fill[s], (long long)J->send_words); return false; }
-	R->bst.assign(S, std::vector<uint64_t>(P + 1, 0));
+	R->X.bst.assign(S, std::vector<uint64_t>(P + 1, 0));
 	std::vector<char> ok(S, 1);
 	std::vector<std::thread> th;
 	for (int s = 0; s < S; ++s) th.emplace_back([&, s]() {
@@ -336,9 +341,9 @@ static bool round_partition(MultiJob *J, int x, int k, int pre, int create_new, 
 			if (nb < 0) { if (!J->d_hpc[s]) yk_set_error("out of device memory for the compacted chunk"); ok[s] = 0; R->note(); return; }
 			base = J->d_hpc[s];
 		}
-		const int64_t n = R->tagged ? yakamd_partition_tagged_dev(k, pre, base, nb, J->d_send[x][s], R->bst[s].data())
-		                : create_new ? yakamd_partition_dev(k, pre, base, nb, J->d_send[x][s], R->bst[s].data())
-		                             : yakamd_partition_hashes_dev(k, pre, base, nb, J->d_send[x][s], R->bst[s].data());
+		const int64_t n = R->tagged ? yakamd_partition_tagged_dev(k, pre, base, nb, J->d_send[x][s], R->X.bst[s].data())
+		                : create_new ? yakamd_partition_dev(k, pre, base, nb, J->d_send[x][s], R->X.bst[s].data())
+		                             : yakamd_partition_hashes_dev(k, pre, base, nb, J->d_send[x][s], R->X.bst[s].data());
 		if (n < 0) { ok[s] = 0; R->note(); }
 	});
 	for (auto &t : th) t.join();
@@ -346,45 +351,31 @@ static bool round_partition(MultiJob *J, int x, int k, int pre, int create_new, 
 	return true;
 }
 
-/* the slices of every chunk go to the slots of the ranks that own their prefixes.  Receive layout of a slot: for each rank it hosts (rank order), the
- * slices of the other slots' chunks (slot order) */
+/* the slices of every chunk go to the slots of the ranks that own their prefixes, as the round's plan lists them (round_plan.h) */
 static bool round_exchange(MultiJob *J, int x, RoundPlan *R)
 {
-	const int N = J->N, P = J->P, S = J->S, W = R->W;
-	const std::vector<std::vector<uint64_t> > &bst = R->bst;
-	R->roff.assign(N, std::vector<uint64_t>(S, 0));
-	std::vector<uint64_t> used(S, 0);
-	for (int d = 0; d < N; ++d) {
-		const int lo = d * (P / N), hi = (d + 1) * (P / N), sd = J->slot_of[d];
-		for (int s = 0; s < S; ++s) { if (s == sd) continue; R->roff[d][s] = used[sd]; used[sd] += bst[s][hi] - bst[s][lo]; }
-	}
-	for (int s = 0; s < S; ++s) if ((int64_t)(used[s] * W) > J->recv_words) { fprintf(stderr, "[E::yak_count] device %d would receive %llu records in one round: prefixes too unevenly filled for YAKAMD_MGPU_CHUNK\n", J->sdev[s], (unsigned long long)used[s]); return false; }
+	const int S = J->S;
+	ExchangePlan &X = R->X;
+	X.build(J->N, J->P, S, J->slot_of, R->W);
+	for (int s = 0; s < S; ++s) if ((int64_t)(X.recv[s] * R->W) > J->recv_words) { fprintf(stderr, "[E::yak_count] device %d would receive %llu records in one round: prefixes too unevenly filled for YAKAMD_MGPU_CHUNK\n", J->sdev[s], (unsigned long long)X.recv[s]); return false; }
 	if (S <= 1) return true;
 	bool ok = true;
 	auto peer_copies = [&]() {
-		for (int s = 0; s < S; ++s)
-			for (int d = 0; d < N; ++d) {
-				const int lo = d * (P / N), hi = (d + 1) * (P / N), sd = J->slot_of[d];
-				const uint64_t cnt = (bst[s][hi] - bst[s][lo]) * W;
-				if (cnt == 0 || s == sd) continue;
-				hipSetDevice(J->sdev[sd]);
-				if (hipMemcpyPeerAsync(J->d_recv[x][sd] + R->roff[d][s] * W, J->sdev[sd], J->d_send[x][s] + bst[s][lo] * W, J->sdev[s], cnt * 8, J->st[sd]) != hipSuccess) ok = false;
-			}
+		for (const RoundXfer &t : X.xfer) {
+			hipSetDevice(J->sdev[t.dst]);
+			if (hipMemcpyPeerAsync(J->d_recv[x][t.dst] + t.recv_off, J->sdev[t.dst], J->d_send[x][t.src] + t.send_off, J->sdev[t.src], t.cnt * 8, J->st[t.dst]) != hipSuccess) ok = false;
+		}
 	};
 	auto wait_streams = [&]() { for (int s = 0; s < S; ++s) { hipSetDevice(J->sdev[s]); if (hipStreamSynchronize(J->st[s]) != hipSuccess) ok = false; } };
 	if (J->use_rccl) {
 		J->R.GroupStart();
-		for (int s = 0; s < S; ++s)
-			for (int d = 0; d < N; ++d) {
-				const int lo = d * (P / N), hi = (d + 1) * (P / N), sd = J->slot_of[d];
-				const uint64_t cnt = (bst[s][hi] - bst[s][lo]) * W;
-				if (cnt == 0 || s == sd) continue;
-				/* (the current device matches the communicator of every call, as the library's own examples do it) */
-				hipSetDevice(J->sdev[s]);
-				if (J->R.Send(J->d_send[x][s] + bst[s][lo] * W, cnt, ncclUint64, sd, J->comm[s], J->st[s]) != ncclSuccess) ok = false;
-				hipSetDevice(J->sdev[sd]);
-				if (J->R.Recv(J->d_recv[x][sd] + R->roff[d][s] * W, cnt, ncclUint64, s, J->comm[sd], J->st[sd]) != ncclSuccess) ok = false;
-			}
+		for (const RoundXfer &t : X.xfer) {
+			/* (the current device matches the communicator of every call, as the library's own examples do it) */
+			hipSetDevice(J->sdev[t.src]);
+			if (J->R.Send(J->d_send[x][t.src] + t.send_off, t.cnt, ncclUint64, t.dst, J->comm[t.src], J->st[t.src]) != ncclSuccess) ok = false;
+			hipSetDevice(J->sdev[t.dst]);
+			if (J->R.Recv(J->d_recv[x][t.dst] + t.recv_off, t.cnt, ncclUint64, t.src, J->comm[t.dst], J->st[t.dst]) != ncclSuccess) ok = false;
+		}
 		if (J->R.GroupEnd() != ncclSuccess) ok = false;
 		wait_streams();
 		if (!ok) {
@@ -410,22 +401,17 @@ static bool round_exchange(MultiJob *J, int x, RoundPlan *R)
 /* every owner takes its slices, in chunk order = stream order; owners that share a slot take turns (a feed may count a whole slice of the pass) */
 static bool round_feed(MultiJob *J, int x, yak_ch_ext *e, int create_new, RoundPlan *R)
 {
-	const int N = J->N, P = J->P, S = J->S, W = R->W;
-	const std::vector<std::vector<uint64_t> > &bst = R->bst;
+	const int N = J->N, S = J->S;
 	std::vector<char> ok(N, 1);
 	std::vector<std::thread> th;
 	for (int sd = 0; sd < S; ++sd) th.emplace_back([&, sd]() { for (int d = 0; d < N; ++d) if (J->slot_of[d] == sd) {
 		hipSetDevice(J->dev[d]);
-		const int lo = d * (P / N), hi = (d + 1) * (P / N);
-		std::vector<uint64_t> ob(P + 1);
-		for (int s = 0; s < S; ++s) {
-			const uint64_t cnt = bst[s][hi] - bst[s][lo];
-			if (cnt == 0) continue;
-			for (int p = 0; p <= P; ++p) { const int q = p < lo ? lo : p > hi ? hi : p; ob[p] = bst[s][q] - bst[s][lo]; }
-			const uint64_t *rec = s == sd ? J->d_send[x][s] + bst[s][lo] * W : J->d_recv[x][sd] + R->roff[d][s] * W;   /* the slice of the slot's own chunk is fed where the partition left it */
-			const int rc = R->tagged ? yakamd_feed_partitioned_tagged_dev(e->sub[d], rec, (int64_t)cnt, ob.data(), R->t0[s], (uint64_t)R->fill[s], 0)
-			             : create_new ? yakamd_feed_partitioned_dev(e->sub[d], rec, (int64_t)cnt, ob.data(), R->t0[s], (uint64_t)R->fill[s])
-			                          : yakamd_count_partitioned_dev(e->sub[d], rec, (int64_t)cnt, ob.data());
+		for (const RoundSlice &f : R->X.feed[d]) {
+			const int s = f.slot;
+			const uint64_t *rec = (f.own ? J->d_send[x][sd] : J->d_recv[x][sd]) + f.off;
+			const int rc = R->tagged ? yakamd_feed_partitioned_tagged_dev(e->sub[d], rec, (int64_t)f.cnt, f.ob.data(), R->t0[s], (uint64_t)R->fill[s], 0)
+			             : create_new ? yakamd_feed_partitioned_dev(e->sub[d], rec, (int64_t)f.cnt, f.ob.data(), R->t0[s], (uint64_t)R->fill[s])
+			                          : yakamd_count_partitioned_dev(e->sub[d], rec, (int64_t)f.cnt, f.ob.data());
 			if (rc != 0) { ok[d] = 0; R->note(); }
 		}
 		if (hipStreamSynchronize(yk_ctx_stream(((yak_ch_ext*)e->sub[d])->ctx)) != hipSuccess) ok[d] = 0;   /* the copies out of this set's buffers are done before the set is filled again */
@@ -445,17 +431,43 @@ static bool multi_round(MultiJob *J, int x, yak_ch_ext *e, int k, int pre, int c
 	return ok;
 }
 
+/* ---- the ends the two drivers share ---- */
+static bool begin_passes(yak_ch_ext *e, int N, int create_new) { bool ok = true; for (int r = 0; r < N && ok; ++r) ok = yakamd_pass_begin(e->sub[r], create_new) == 0; return ok; }
+
+/* every rank finishes its pass: partitions, counting, layout -- side by side; ranks that share a device take turns, so that the scratch of only
+ * one of them is alive at a time (one device posing as N = the pass in N sweeps over prefix ranges: what lets a 5 Gb assembly through 288 GB).
+ * false after a line per failed rank under the caller's tag */
+static bool finish_passes(const MultiJob &J, yak_ch_ext *e, const std::vector<int> &dev, const char *tag)
+{
+	const int N = J.N;
+	std::vector<int64_t> n_ins(N, 0);
+	std::vector<std::thread> th;
+	std::vector<std::string> why(N);                           /* the error text is per thread: bring it back */
+	for (int sd = 0; sd < J.S; ++sd) th.emplace_back([&, sd]() { for (int r = 0; r < N; ++r) if (J.slot_of[r] == sd) { n_ins[r] = yakamd_pass_end(e->sub[r]); if (n_ins[r] < 0) why[r] = yakamd_last_error(); } });
+	for (auto &t : th) t.join();
+	bool ok = true;
+	for (int r = 0; r < N; ++r)
+		if (n_ins[r] < 0) { fprintf(stderr, "[E::%s] rank %d of %d (device %d): %s\n", tag, r, N, dev[r], why[r].c_str()); ok = false; }
+		else e->sub[r]->tot += (uint64_t)n_ins[r];
+	return ok;
+}
+
+/* how the job's slices travelled (yakamd_count_multi_dev's exchange_out), and the words for it */
+static int exchange_kind(const MultiJob &J) { return J.S == 1 ? 0 : J.use_rccl ? (J.loopback ? 3 : 1) : 2; }
+static const char *exchange_label(int kind) { return kind == 0 ? "one device: nothing exchanged" : kind == 1 ? "RCCL exchange" : kind == 3 ? "grouped send / recv served by the in-process test rig" : "peer copies"; }
+
 static yak_ch_t *multi_table_new(const yak_copt_t *opt, int N, const std::vector<int> &dev);
 yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, int N, const std::vector<int> &dev, bool hpc)
 {
-	FxReader fx;
-	if (!fx.open_file(fn)) return 0;
+	SeqInput in;
+	const int n_thr = parse_threads(opt->n_thread);
+	if (!in.open(fn, n_thr, 1 << 20)) return 0;
 	const int P = 1 << opt->pre;
 	yak_ch_t *h = h0;
 	const int create_new = h0 ? 0 : 1;
 	if (h0 == 0) {                                             /* N tables, one per rank, each owning its prefix range */
 		h = multi_table_new(opt, N, dev);
-		if (!h) { fx.close_file(); return 0; }
+		if (!h) return 0;
 		if (hpc) yakamd_ch_set_hpc(h, 1);
 	}
 	yak_ch_ext *e = (yak_ch_ext*)h;
@@ -464,7 +476,7 @@ yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, i
 	bool ok = multi_open(&J, N, P, dev);
 	const int S = J.S;
 	const double t_job0 = yk_realtime();
-	for (int r = 0; r < N && ok; ++r) ok = yakamd_pass_begin(e->sub[r], create_new) == 0;
+	ok = ok && begin_passes(e, N, create_new);
 	/* the reader fills the chunks of set `cur` while a worker thread partitions, exchanges and feeds the set before it */
 	std::vector<int64_t> fill[2] = { std::vector<int64_t>(S, 0), std::vector<int64_t>(S, 0) };
 	std::vector<uint64_t> t0[2] = { std::vector<uint64_t>(S, 0), std::vector<uint64_t>(S, 0) };
@@ -550,25 +562,8 @@ yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, i
 		return ok;
 	};
 	auto take_piece = [&](const char *img, size_t n, int64_t ns, const WinPack*) -> bool { const double t0 = yk_realtime(); const bool r = take_piece_body(img, n, ns); t_sink += yk_realtime() - t0; return r; };
-	const int n_thr = parse_threads(opt->n_thread);
-	ByteSource psrc; int psrc_fd = -1;
-	bool par = parallel_source(fn, fx, n_thr, 1 << 20, &psrc, &psrc_fd);
-	pgz::Reader gz;
-	if (ok && par) ok = parse_parallel(&psrc, opt->k, n_thr, take_piece) && ok;
-	else if (ok && gz_source(fn, fx, n_thr, &gz)) { par = true; ok = parse_gz(&gz, opt->k, n_thr, take_piece) && ok; }
-	else if (ok) {
-		std::vector<char> piece;
-		int64_t l, ns = 0;
-		for (;;) {
-			if ((l = fx.fast(piece, opt->k)) == FxReader::NOT_FAST) {
-				if ((l = fx.next()) < 0) break;
-				if (l >= opt->k) { piece.insert(piece.end(), fx.seq.begin(), fx.seq.end()); piece.push_back('\n'); }
-			}
-			if (l >= opt->k) ++ns;
-			if (piece.size() >= ((size_t)1 << 24)) { if (!take_piece(piece.data(), piece.size(), ns, 0)) break; piece.clear(); ns = 0; }
-		}
-		if (ok && !piece.empty()) take_piece(piece.data(), piece.size(), ns, 0);
-	}
+	if (ok && in.kind != SeqInput::STREAM) ok = in.run(opt->k, false, take_piece) && ok;
+	else if (ok) ok = in.stream(opt->k, true, PieceEnd{ INT64_MAX, ((size_t)1 << 24) - 1 }, 0, take_piece) && ok;   /* pieces of 16 MiB */
 	if (ok) { bool any = false; for (int s = 0; s < S; ++s) any = any || fill[cur][s] > 0; if (any) round(); }
 	wait_worker();
 	const double t_fed = yk_realtime() - t_job0;
@@ -578,17 +573,7 @@ yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, i
 		if (stg[i]) (void)hipHostFree(stg[i]);
 	}
 	multi_close(&J);                                           /* the chunk and exchange buffers go before the passes finish: memory is tightest there */
-	{	/* every rank finishes its pass: partitions, counting, layout -- side by side; ranks that share a device take turns, so that the
-		 * scratch of only one of them is alive at a time (one device posing as N = the pass in N sweeps over prefix ranges: what lets a
-		 * 5 Gb assembly through 288 GB) */
-		std::vector<int64_t> n_ins(N, 0);
-		std::vector<std::thread> th;
-		std::vector<std::string> why(N);                       /* the error text is per thread: bring it back */
-		for (int sd = 0; sd < S; ++sd) th.emplace_back([&, sd]() { for (int r = 0; r < N; ++r) if (J.slot_of[r] == sd) { n_ins[r] = yakamd_pass_end(e->sub[r]); if (n_ins[r] < 0) why[r] = yakamd_last_error(); } });
-		for (auto &t : th) t.join();
-		for (int r = 0; r < N; ++r) if (n_ins[r] < 0) fprintf(stderr, "[E::yak_count] rank %d of %d (device %d): %s\n", r, N, dev[r], why[r].c_str());
-		for (int r = 0; r < N; ++r) { if (n_ins[r] < 0) ok = false; else e->sub[r]->tot += (uint64_t)n_ins[r]; }
-	}
+	if (!finish_passes(J, e, dev, "yak_count")) ok = false;
 	multi_tot(h);
 	if (getenv("YAKAMD_VERBOSE") && atoi(getenv("YAKAMD_VERBOSE")) > 0) {
 		fprintf(stderr, "[yak_amd] %d ranks: input read, dealt and fed by %.3f s (%d parser threads; %.3f s inside the sink that copies the pieces to the devices, %.3f s of it waiting for copies and the round before), the ranks' passes finished by %.3f s\n",
@@ -596,9 +581,7 @@ yak_ch_t *yak_count_multi(const char *fn, const yak_copt_t *opt, yak_ch_t *h0, i
 		for (int s = 0; s < S; ++s) { hipSetDevice(J.sdev[s]); yk_pool_report("the job"); }
 	}
 	fprintf(stderr, "[M::%s::%.3f*%.2f] %ld sequences in total; %ld distinct k-mers in the hash table (%d GPUs, %s)\n", "yak_count",
-	        yk_realtime(), yk_cputime() / (yk_realtime() + 1e-9), (long)n_seq_tot, (long)h->tot, N, S == 1 ? "one device: nothing exchanged" : J.use_rccl ? (J.loopback ? "grouped send / recv served by the in-process test rig" : "RCCL exchange") : "peer copies");
-	if (psrc_fd >= 0) ::close(psrc_fd);
-	fx.close_file();
+	        yk_realtime(), yk_cputime() / (yk_realtime() + 1e-9), (long)n_seq_tot, (long)h->tot, N, exchange_label(exchange_kind(J)));
 	if (!ok) { fprintf(stderr, "[E::yak_count] %s\n", !worker_why.empty() ? worker_why.c_str() : yakamd_last_error()); if (!h0) yak_ch_destroy(h); return 0; }
 	return h;
 }
@@ -664,7 +647,7 @@ extern "C" yak_ch_t *yakamd_count_multi_dev(const yak_copt_t *opt, yak_ch_t *h0,
 	bool ok = multi_open(&J, N, P, dev, cmax, tagged_only || !create_new);
 	const int S = J.S;
 	yk_realtime();
-	for (int r = 0; r < N && ok; ++r) ok = yakamd_pass_begin(e->sub[r], create_new) == 0;
+	ok = ok && begin_passes(e, N, create_new);
 	std::string why;
 	uint64_t t_stream = 0;
 	/* rounds overlapped: while round b is exchanged and fed (this thread), a second thread partitions round b + 1 into the other buffer set, on the
@@ -703,18 +686,10 @@ extern "C" yak_ch_t *yakamd_count_multi_dev(const yak_copt_t *opt, yak_ch_t *h0,
 	}
 	if (part.joinable()) part.join();
 	const double t_rounds = yk_realtime() - t_rounds0;
-	const int exch = S == 1 ? 0 : J.use_rccl ? (J.loopback ? 3 : 1) : 2;
+	const int exch = exchange_kind(J);
 	for (int x = 0; x < 2; ++x) for (int s = 0; s < S; ++s) J.d_base[x][s] = 0;
 	multi_close(&J);
-	{
-		std::vector<int64_t> n_ins(N, 0);
-		std::vector<std::thread> th;
-		std::vector<std::string> whyr(N);
-		for (int sd = 0; sd < S; ++sd) th.emplace_back([&, sd]() { for (int r = 0; r < N; ++r) if (J.slot_of[r] == sd) { n_ins[r] = yakamd_pass_end(e->sub[r]); if (n_ins[r] < 0) whyr[r] = yakamd_last_error(); } });
-		for (auto &t : th) t.join();
-		for (int r = 0; r < N; ++r) if (n_ins[r] < 0) { fprintf(stderr, "[E::yakamd_count_multi_dev] rank %d of %d (device %d): %s\n", r, N, dev[r], whyr[r].c_str()); ok = false; }
-		for (int r = 0; r < N; ++r) if (n_ins[r] >= 0) e->sub[r]->tot += (uint64_t)n_ins[r];
-	}
+	if (!finish_passes(J, e, dev, "yakamd_count_multi_dev")) ok = false;
 	if (N > 1) multi_tot(h);
 	if (yk_knob("YAKAMD_VERBOSE", 0) > 0) {
 		fprintf(stderr, "[yak_amd] %d rounds in %.3f s (%s): partitions %.3f s on their thread; this thread waited %.3f s for them, exchanged for %.3f s, fed for %.3f s; the ranks' passes finished by %.3f s\n",
@@ -723,7 +698,7 @@ extern "C" yak_ch_t *yakamd_count_multi_dev(const yak_copt_t *opt, yak_ch_t *h0,
 	}
 	if (exchange_out) *exchange_out = exch;
 	fprintf(stderr, "[M::%s::%.3f*%.2f] %d rounds of device-resident chunks; %ld distinct k-mers in the hash table (%d ranks, %s)\n", "yakamd_count_multi_dev",
-	        yk_realtime(), yk_cputime() / (yk_realtime() + 1e-9), n_rounds, (long)h->tot, N, exch == 0 ? "one device: nothing exchanged" : exch == 1 ? "RCCL exchange" : exch == 3 ? "grouped send / recv served by the in-process test rig" : "peer copies");
+	        yk_realtime(), yk_cputime() / (yk_realtime() + 1e-9), n_rounds, (long)h->tot, N, exchange_label(exch));
 	if (!ok) { fprintf(stderr, "[E::yakamd_count_multi_dev] %s\n", !why.empty() ? why.c_str() : yakamd_last_error()); if (!h0) yak_ch_destroy(h); return 0; }
 	return h;
 }

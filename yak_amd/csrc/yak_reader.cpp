@@ -223,28 +223,6 @@ static int parse_window(const ByteSource *fd, int64_t size, int64_t pos, int64_t
 	return n_ok;
 }
 
-/* the source the parallel parser can take for `fn`, if any: a plain regular file (fx.fd) or a BGZF file, larger than min_size.
- * *own_fd (>= 0) is a descriptor the caller closes afterwards */
-bool parallel_source(const char *fn, const FxReader &fx, int n_thr, int64_t min_size, ByteSource *src, int *own_fd)
-{
-	*own_fd = -1;
-	if (n_thr <= 1) return false;
-	struct stat sb;
-	if (fx.fd >= 0) {
-		if (fstat(fx.fd, &sb) != 0 || !S_ISREG(sb.st_mode) || sb.st_size <= min_size) return false;
-		src->fd = fx.fd; src->size = sb.st_size; src->bgzf = false;
-		src->map_plain();
-		return true;
-	}
-	if (fn == 0 || strcmp(fn, "-") == 0) return false;
-	if (stat(fn, &sb) != 0 || !S_ISREG(sb.st_mode)) return false;   /* (never open() a FIFO a second time: with its writer gone -- a short input, all of it in the pipe already -- that open blocks for ever) */
-	const int f = ::open(fn, O_RDONLY);
-	if (f < 0) return false;
-	if (!src->index_bgzf(f) || src->size <= min_size) { ::close(f); src->fd = -1; src->bgzf = false; return false; }
-	*own_fd = f;
-	return true;
-}
-
 /* calls sink(image bytes, n_bytes, n_seq) for consecutive pieces of the input, in order; false if sink failed.
  * Two sets of segment buffers: while the sink consumes one window (copy to the device + kernels), the parser
  * threads already work on the next one. */
@@ -268,7 +246,7 @@ std::atomic<double> g_t_parse_windows{0}, g_t_first_window{0};    /* YAKAMD_VERB
 /* A parser thread fills a ring of window sets while the caller's thread hands the finished windows to the sink, in order: two sets for
  * ASCII pieces (the sink copies a window to the device while the next one is parsed), four when the windows are packed -- a new table's
  * first feed waits ~0.25 s for the runtime to come up, time in which the parser gets through 2 GB of file instead of standing still */
-bool parse_parallel(const ByteSource *fd, int min_len, int n_thr, const ImgSink &sink, int64_t *stopped_at, bool *stream_ended)
+static bool parse_parallel(const ByteSource *fd, int min_len, int n_thr, const ImgSink &sink, int64_t *stopped_at = 0, bool *stream_ended = 0)
 {
 	if (stopped_at) *stopped_at = 0;
 	if (stream_ended) *stream_ended = false;
@@ -322,30 +300,145 @@ bool parse_parallel(const ByteSource *fd, int min_len, int n_thr, const ImgSink 
 	return ok;
 }
 
+/* ---- SeqInput (yak_host.h) ---- */
+bool SeqInput::open(const char *fn, int n_thr_, int64_t min_size)
+{
+	if (!fx.open_file(fn)) return false;
+	n_thr = n_thr_;
+	struct stat sb;
+	if (n_thr <= 1 || fn == 0 || strcmp(fn, "-") == 0) return true;
+	if (fx.fd >= 0) {                                             /* the plain bytes of a regular file: mapped */
+		if (fstat(fx.fd, &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size > min_size) { src.fd = fx.fd; src.size = sb.st_size; src.map_plain(); kind = PARALLEL; }
+		return true;
+	}
+	/* (never open() a FIFO a second time: with its writer gone -- a short input, all of it in the pipe already -- that open blocks for ever) */
+	if (stat(fn, &sb) == 0 && S_ISREG(sb.st_mode) && (own_fd = ::open(fn, O_RDONLY)) >= 0) {
+		if (src.index_bgzf(own_fd) && src.size > min_size) { kind = PARALLEL; return true; }
+		::close(own_fd); own_fd = src.fd = -1; src.bgzf = false;
+	}
+	if (yk_knob("YAKAMD_NO_PGZ", 0)) return true;
+	pgz::tune().no_simd = yk_knob("YAKAMD_NO_AVX2", 0) != 0;
+	gz = new pgz::Reader;
+	if (gz->open(fn, n_thr)) kind = GZ;
+	return true;
+}
+
+SeqInput::~SeqInput()
+{
+	if (own_fd >= 0) ::close(own_fd);
+	fx.close_file();
+	if (pgz::Reader *q = gz) yk_reap_later([q]() { delete q; });
+}
+
 /* an ordinary gzip file: batches of it are inflated by several threads (pgz.h) while the batch before is parsed, by the same window
  * parser, from memory; the record a batch ends in is carried to the front of the next one */
-bool gz_source(const char *fn, const FxReader &fx, int n_thr, pgz::Reader *z)
+bool SeqInput::run(int min_len, bool pack, const ImgSink &sink)
 {
-	if (n_thr <= 1 || fx.fd >= 0 || fn == 0 || strcmp(fn, "-") == 0 || yk_knob("YAKAMD_NO_PGZ", 0)) return false;
-	pgz::tune().no_simd = yk_knob("YAKAMD_NO_AVX2", 0) != 0;
-	return z->open(fn, n_thr);
-}
-bool parse_gz(pgz::Reader *z, int min_len, int n_thr, const ImgSink &sink, bool pack)
-{
+	src.pack = pack;
+	if (kind == PARALLEL) return parse_parallel(&src, min_len, n_thr, sink);
 	size_t keep = 0;
 	for (bool last = false; !last; ) {
 		uint8_t *p = 0; size_t n = 0;
-		if (!z->next(keep, &p, &n, &last)) { yk_set_error("%s", z->why.c_str()); return false; }
-		ByteSource src;
-		src.set_memory(p, n, !last);
-		src.pack = pack;
+		if (!gz->next(keep, &p, &n, &last)) { yk_set_error("%s", gz->why.c_str()); return false; }
+		ByteSource batch;
+		batch.set_memory(p, n, !last);
+		batch.pack = pack;
 		int64_t stop = 0; bool ended = false;
-		if (!parse_parallel(&src, min_len, n_thr, sink, &stop, &ended)) return false;
+		if (!parse_parallel(&batch, min_len, n_thr, sink, &stop, &ended)) return false;
 		if (ended) break;                                         /* a truncated record ended the stream (count.c:93) */
 		keep = (size_t)stop;
 	}
 	if (getenv("YAKAMD_VERBOSE")) fprintf(stderr, "[yak_amd] gzip: %d threads inflated %lu chunks from a searched block start (%lu searched starts not used, %.1f MB decoded by the stitch)\n",
-	                                      z->n_thr, (unsigned long)z->n_search_ok, (unsigned long)z->n_search_bad, z->n_gap_bits / 8e6);
+	                                      gz->n_thr, (unsigned long)gz->n_search_ok, (unsigned long)gz->n_search_bad, gz->n_gap_bits / 8e6);
 	return true;
 }
 
+bool SeqInput::stream(int min_len, bool fast, PieceEnd end, size_t reserve, const ImgSink &sink)
+{
+	std::vector<char> piece;
+	piece.reserve(reserve);
+	int64_t l, sum_len = 0, n_seq = 0;
+	for (;;) {                                                    /* count.c:93 */
+		if (!fast || (l = fx.fast(piece, min_len)) == FxReader::NOT_FAST) {
+			if ((l = fx.next()) < 0) break;
+			if (l >= min_len) { piece.insert(piece.end(), fx.seq.begin(), fx.seq.end()); piece.push_back('\n'); }   /* a non-ACGT byte ends the read (count.c:41) */
+		}
+		if (l < min_len) continue;                                /* count.c:95 */
+		sum_len += l; ++n_seq;
+		if (sum_len >= end.sum_len || piece.size() > end.bytes) {
+			if (!sink(piece.data(), piece.size(), n_seq, 0)) return false;
+			piece.clear(); sum_len = 0; n_seq = 0;
+		}
+	}
+	return n_seq == 0 || sink(piece.data(), piece.size(), n_seq, 0);
+}
+
+/* ---- the reader's hooks for tests (include/yak_amd.h); what they return is the caller's to free() ---- */
+static int64_t image_out(const std::vector<char> &img, char **out)
+{
+	*out = (char*)malloc(img.size() + 1);
+	memcpy(*out, img.data(), img.size());
+	return (int64_t)img.size();
+}
+
+/* host-only hook for tests: the base image yak_count() would hand to the device for `fn` (sequences
+ * of at least min_len bases, each followed by '\n'); caller frees *out with free().  -1 if unreadable. */
+extern "C" int64_t yakamd_host_image(const char *fn, int min_len, int use_fast_path, char **out)
+{
+	const double t_ = yk_realtime();
+	SeqInput in;
+	if (!in.open(fn, use_fast_path ? parse_threads(1) : 1, 0)) return -1;   /* tests set YAKAMD_PARSE_THREADS */
+	std::vector<char> img;
+	size_t total = 0;
+	const bool par = in.kind != SeqInput::STREAM, keep = !par || !(use_fast_path & 2);   /* (2: the image of the parallel kinds is only measured, for timing the reader) */
+	const ImgSink sink = [&](const char *part, size_t part_n, int64_t, const WinPack*) { total += part_n; if (keep) img.insert(img.end(), part, part + part_n); return true; };
+	const bool good = par ? in.run(min_len, false, sink) : in.stream(min_len, use_fast_path != 0, PieceEnd{ INT64_MAX, SIZE_MAX }, 0, sink);   /* (one piece: none ever closes) */
+	if (!good) return -1;                                         /* the inflater failed */
+	if (getenv("YAKAMD_VERBOSE") && par) fprintf(stderr, "[yak_amd] host_image: %.3f s, %d threads, %zu bytes%s\n", yk_realtime() - t_, in.n_thr, total, in.src.bgzf ? " (BGZF blocks inflated by the parser threads)" : "");
+	else if (getenv("YAKAMD_VERBOSE")) fprintf(stderr, "[yak_amd] host_image: %.3f s in the reader loop\n", yk_realtime() - t_);
+	return image_out(img, out);
+}
+
+/* host-only hook for tests: what yak_count() hands to the device when its parser threads pack (one packed image per window), unpacked again --
+ * 'A' 'C' 'G' 'T' for a base, '\n' for a position that is none (N, a record's end, the positions that pad a segment to a multiple of 32) */
+extern "C" int64_t yakamd_host_image_packed(const char *fn, int min_len, char **out)
+{
+	*out = 0;
+	SeqInput in;
+	if (!in.open(fn, parse_threads(1), 0)) return -1;
+	std::vector<char> img;
+	const ImgSink sink = [&](const char*, size_t, int64_t, const WinPack *wp) {
+		for (size_t p = 0; p < wp->n_words.size(); ++p) {
+			const uint32_t *codes = (const uint32_t*)wp->codes[p], *valid = (const uint32_t*)wp->valid[p];
+			for (size_t j = 0; j < (size_t)wp->n_words[p] * 32; ++j) img.push_back((valid[j >> 5] >> (j & 31) & 1) ? "ACGT"[codes[j >> 4] >> (2 * (j & 15)) & 3] : '\n');
+		}
+		return true;
+	};
+	if (in.kind == SeqInput::STREAM || !in.run(min_len, true, sink)) return -1;
+	return image_out(img, out);
+}
+
+/* host-only hooks for tests of the gzip reader: its chunk size, the smallest file it takes and the room in front of a batch (0 / < 0: as is); the whole inflated stream of
+ * `fn` through the batch interface, every batch handing a tail back as the parser does (-1: not a file the reader takes; -2: it failed) */
+extern "C" void yakamd_gz_tune(int64_t chunk_bytes, int64_t min_file_bytes, int64_t front_bytes)
+{
+	if (chunk_bytes > 0) pgz::tune().chunk = (size_t)chunk_bytes;
+	if (min_file_bytes >= 0) pgz::tune().min_size = (size_t)min_file_bytes;
+	if (front_bytes >= 0) pgz::tune().front = (size_t)front_bytes;
+}
+extern "C" int64_t yakamd_gz_inflate(const char *fn, int n_threads, char **out)
+{
+	pgz::Reader z;
+	*out = 0;
+	pgz::tune().no_simd = yk_knob("YAKAMD_NO_AVX2", 0) != 0;
+	if (!z.open(fn, n_threads, true)) return -1;
+	std::vector<char> all;
+	size_t keep = 0;
+	for (bool last = false; !last; ) {
+		uint8_t *p = 0; size_t n = 0;
+		if (!z.next(keep, &p, &n, &last)) { yk_set_error("%s", z.why.c_str()); return -2; }
+		keep = last ? n : n - std::min<size_t>(n, (all.size() * 7 + 13) % 5000);
+		all.insert(all.end(), (const char*)p, (const char*)p + keep);
+	}
+	return image_out(all, out);
+}

@@ -198,7 +198,7 @@ struct ResizeTask { u32 old_bits, new_bits, rehash, pad; u64 old_off, new_off; }
 void yk_launch_resize(const ResizeTask *tasks, int P, const u64 *old_keys, const u32 *old_used, u64 *new_keys, u32 *new_used, u32 *scr_used, hipStream_t st);
 void yk_launch_keys_to_hashes(const u64 *kc, const u64 *seg_off, int P, int pre, u64 *hash, u32 *t, hipStream_t st, unsigned short *cnt = 0);   /* cnt != 0: the keys' counts as well */
 void yk_launch_img_add_counts(const u64 *hash, const unsigned short *cnt, u64 n, ImgView img, int plo, int phi, u32 *missing, hipStream_t st);
-long yk_knob(const char *name, long dflt);                   /* pool.cpp: run-time settings (test switches come through yakamd_test_set only) */
+int64_t yk_knob(const char *name, int64_t dflt);             /* pool.cpp: a run-time setting -- the test hook's value (yakamd_test_set), else (public names only) the environment's, else dflt */
 void yk_launch_put_u64(const u64 *pos, const u64 *val, u32 n, u64 *out, hipStream_t st);
 
 #ifdef __cplusplus
