@@ -1,6 +1,7 @@
 # Build of the MI355X k-mer counting engine (gfx950 only) and its test infrastructure.
 #   make            -> yak_amd/libyak_amd.so (HIP kernels + C ABI), yak_amd/libyak_amd_walk.so (the unitig walk on the GPU, a layer
-#                      above it), yak_amd/yak-amd (CLI),
+#                      above it), yak_amd/libyak_amd_gfa.so (the links between the unitigs and the GFA, a layer above both),
+#                      yak_amd/yak-amd (CLI),
 #                      tools/ (synthetic reads), oracle/ (CPU checker; + oracle/_ref if the
 #                      reference sources are present)
 HIPCC   ?= /opt/rocm/bin/hipcc
@@ -8,10 +9,11 @@ ARCH    ?= gfx950
 HIPFLAGS = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Iinclude -Wall -Wno-unused-result -Wno-unused-value
 CSRC    = yak_amd/csrc
 WALK    = yak_amd/walk
+GFA     = yak_amd/gfa
 
 all: lib cli tools oracle
 
-lib: yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so
+lib: yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so yak_amd/libyak_amd_gfa.so
 cli: yak_amd/yak-amd
 
 yak_amd/kernels.o: $(CSRC)/kernels.hip $(wildcard $(CSRC)/kern_*.inc) $(CSRC)/yk_device.h $(CSRC)/replay_plan.h $(CSRC)/seg_sort_tile.h $(CSRC)/tally.h
@@ -35,8 +37,17 @@ yak_amd/walk_tally.o: $(CSRC)/tally.cpp $(CSRC)/tally.h include/yak_amd.h
 yak_amd/libyak_amd_walk.so: yak_amd/walk.o yak_amd/walk_tally.o yak_amd/libyak_amd.so $(WALK)/libyak_amd_walk.map
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(WALK)/libyak_amd_walk.map -o $@ $(filter %.o,$^) -Lyak_amd -lyak_amd -Wl,-rpath,'$$ORIGIN'
 
-yak_amd/yak-amd: $(CSRC)/main.c include/yak.h include/yak_amd.h include/yak_amd_walk.h yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so
-	gcc -O2 -Wall -Iinclude $(CSRC)/main.c -o $@ -Lyak_amd -lyak_amd_walk -lyak_amd -Wl,-rpath,'$$ORIGIN' -lz
+# the links between unitigs of `yak-amd unitigs -G`: its own kernels and its own launch tally (tally.cpp a third time),
+# public calls of the two libraries below it only
+yak_amd/gfa.o: $(GFA)/gfa.hip $(GFA)/gfa_step.h $(GFA)/gfa_text.h $(CSRC)/tally.h include/yak.h include/yak_amd.h include/yak_amd_walk.h include/yak_amd_gfa.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+yak_amd/gfa_tally.o: $(CSRC)/tally.cpp $(CSRC)/tally.h include/yak_amd.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+yak_amd/libyak_amd_gfa.so: yak_amd/gfa.o yak_amd/gfa_tally.o yak_amd/libyak_amd_walk.so yak_amd/libyak_amd.so $(GFA)/libyak_amd_gfa.map
+	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(GFA)/libyak_amd_gfa.map -o $@ $(filter %.o,$^) -Lyak_amd -lyak_amd_walk -lyak_amd -Wl,-rpath,'$$ORIGIN'
+
+yak_amd/yak-amd: $(CSRC)/main.c include/yak.h include/yak_amd.h include/yak_amd_walk.h include/yak_amd_gfa.h yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so yak_amd/libyak_amd_gfa.so
+	gcc -O2 -Wall -Iinclude $(CSRC)/main.c -o $@ -Lyak_amd -lyak_amd_gfa -lyak_amd_walk -lyak_amd -Wl,-rpath,'$$ORIGIN' -lz
 
 tools:
 	$(MAKE) -C tools
@@ -44,7 +55,7 @@ oracle: lib
 	$(MAKE) -C oracle all ref
 
 clean:
-	rm -f yak_amd/*.o yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so yak_amd/yak-amd
+	rm -f yak_amd/*.o yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so yak_amd/libyak_amd_gfa.so yak_amd/yak-amd
 	$(MAKE) -C tools clean
 	$(MAKE) -C oracle clean
 .PHONY: all lib cli tools oracle clean

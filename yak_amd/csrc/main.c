@@ -31,6 +31,7 @@
 #include <stdint.h>
 #include "yak.h"
 #include "yak_amd_walk.h"  /* yakamd_unitigs_dev (unitigs -g) */
+#include "yak_amd_gfa.h"   /* yakamd_unitigs_gfa (unitigs -G) */
 #include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_cover, yakamd_unitigs, yakamd_count_hpc and yakamd_ch_set_hpc */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
@@ -542,12 +543,13 @@ static int cmd_cover(int argc, char **argv)
 
 /* ---- unitigs (not in the reference) ---- */
 /* the de Bruijn graph of a count table's k-mers: its unitigs as FASTA, or with -s its tallies (yakamd_unitigs; with -g yakamd_unitigs_dev of
- * libyak_amd_walk.so, which walks on the GPU as well) */
+ * libyak_amd_walk.so, which walks on the GPU as well; with -G yakamd_unitigs_gfa of libyak_amd_gfa.so: the unitigs and the links between them as
+ * GFA 1, or with -s the tallies and the G line) */
 static int cmd_unitigs(int argc, char **argv)
 {
 	yakamd_ugopt_t o;
 	const char *out = 0;
-	int stats = 0, min_cnt = 1, n_threads = 0, on_gpu = 0;
+	int stats = 0, min_cnt = 1, n_threads = 0, on_gpu = 0, gfa = 0;
 	yakamd_ugopt_init(&o);
 	n_threads = o.n_threads;
 	const struct arg_def defs[] = {
@@ -555,6 +557,7 @@ static int cmd_unitigs(int argc, char **argv)
 		{ 's', ARG_FLAG, &stats, "the tallies of the graph and of its unitigs, not the FASTA" },
 		{ 't', ARG_I32, &n_threads, "threads of the host walk [8]" },
 		{ 'g', ARG_FLAG, &on_gpu, "walk on the GPU too (list ranking over the links); the same text" },
+		{ 'G', ARG_FLAG, &gfa, "GFA 1: the unitigs as segments and the links between them (implies -g); with -s a G line more" },
 		{ 'o', ARG_TEXT, &out, "write the output here; stdout without it" },
 	};
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
@@ -569,7 +572,7 @@ static int cmd_unitigs(int argc, char **argv)
 	o.min_cnt = min_cnt; o.stats_only = stats; o.n_threads = n_threads;
 	yak_ch_t *tab = yak_ch_restore(argv[first]);
 	if (!tab) { fprintf(stderr, "yak-amd unitigs: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
-	const int rc = (on_gpu ? yakamd_unitigs_dev(&o, tab, out) : yakamd_unitigs(&o, tab, out)) == 0 ? 0 : 3;
+	const int rc = (gfa ? yakamd_unitigs_gfa(&o, tab, out) : on_gpu ? yakamd_unitigs_dev(&o, tab, out) : yakamd_unitigs(&o, tab, out)) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
 }
