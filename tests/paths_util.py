@@ -318,6 +318,115 @@ HASHED_RECORDS = {
     "key_owning_ranges_cross_sweep": E(["k_img_count_own<2,0>", "k_img_count_own<2,1>"], ["k_img_count_own<1,*", "k_img_count_lds*"], own_sweeps=">0"),
 }
 
+# ---- test_gpu_adversarial.py ----  clustered tables (tests/adversarial_util.py): one sub-table of chosen home slots, blocks and counts per image
+# The rows, taken from the matrices above.  An entry's key is "<case>.<row>"; its tally is the count without a filter (k = 31) alone, where the
+# put-by-put model speaks for the table: tests/test_adversarial.py derives r2_used / r2_refused of every entry from the model's report and the
+# thresholds of kern_replay2.inc (adversarial_util.refusal_codes), so an entry cannot be fitted to a run
+ADVERSARIAL_ROWS = {
+    "default": dict(),
+    "sb5": dict(YAKAMD_R2_SMALL_BITS="5"), "sb5_seg10": dict(YAKAMD_R2_SMALL_BITS="5", YAKAMD_R2_SEG_LOG="10"),
+    "sb5_prefix1024": dict(YAKAMD_R2_SMALL_F="1024", YAKAMD_R2_SMALL_BITS="5"),
+    "sb5_dbl61": dict(YAKAMD_R2_SMALL_BITS="5", YAKAMD_R2_DBL="61"), "sb5_dbl52": dict(YAKAMD_R2_SMALL_BITS="5", YAKAMD_R2_DBL="52"),
+    "replay2_off": dict(YAKAMD_REPLAY2="0"),
+    "replay_lds_0": dict(YAKAMD_REPLAY_LDS="0"), "replay_lds_1024": dict(YAKAMD_REPLAY_LDS="1024", YAKAMD_REPLAY_THREADS="256"), "replay_lds_8192": dict(YAKAMD_REPLAY_LDS="8192"),
+    "lc2_off": dict(YAKAMD_LC2="0"), "lc2_capb10": dict(YAKAMD_LC2_CAPB="10", YAKAMD_FAST_BUDGET="3000000", YAKAMD_BATCH="65536"),
+    "slices": dict(YAKAMD_FAST_BUDGET="1100000", YAKAMD_BATCH="65536"),
+    "fast_off": dict(YAKAMD_FAST="0"),
+}
+R2_ONE = ["k_replay", "k_r2_trail", "k_r2_load", "k_r2_binit", "k_r2_dsmall", "k_r2_double<16,false,1>", "k_r2_place", "k_r2_publish"]   # yk_r2_double: n_dbl <= 256 -> 16 waves, whatever YAKAMD_R2_DBL says
+R2_ONE_SEG = R2_ONE + R2_SEGMENTED + ["k_r2_ppart_cnt", "k_r2_ppart_scan", "k_r2_ppart_scat"]        # r2_buffers: n_large = 1 -> ppG = 16 workgroups group the keys
+_NOT_LARGE = E(["k_replay"], ["k_r2_*"], r2_used="==0", r2_refused="==0")                            # r2_plan: classify() finds no sub-table beyond 2^SB slots
+_USED, _USED_SEG = E(R2_ONE, [], r2_used=">0", r2_refused="==0"), E(R2_ONE_SEG, ["k_r2_ppart"], r2_used=">0", r2_refused="==0")
+_REFUSED, _REFUSED_SEG = E(R2_ONE, [], r2_used="==0", r2_refused=">0"), E(R2_ONE_SEG, ["k_r2_ppart"], r2_used="==0", r2_refused=">0")   # r2_publish_commit: h_fail -> 1 -> yk_run_replay's k_replay
+_OFF = E(["k_replay"], ["k_r2_*"], r2_used="==0", r2_refused="==0")                                  # run_replay_v2: YAKAMD_REPLAY2 = 0 -> 1
+ADVERSARIAL = {
+    # ---- one sub-table of 16 Ki slots, streamed from 8 Ki on (SB = 13): the last doubling's old table holds the runs the case lays out ----
+    # runs of up to 512 slots: r2_wave_run takes L <= R2_LMAX (kern_replay2.inc:152, :163); 255 and more go to s_big (:577, :621)
+    "run_ladder_plain.default": _USED,
+    "run_ladder_over.default": _REFUSED,             # a run of 513: L > R2_LMAX -> fail = 6 (:163)
+    # the table's last run (100 slots) reaches its end, keys of it go around: wrap = 2 * min(128, 236) + 2 = 258 slots of the new table's start (:157-161)
+    "run_ladder_wrap.default": _USED,
+    # R2_MMAX: hand_over (:576) places the last run in the wave's own LDS up to 192 slots, R = 2 * 192 + 2 + 12 <= 642; 193 goes to wave 0's (s_big)
+    "run_ladder_tail192.default": _USED, "run_ladder_tail193.default": _USED,
+    "long_prefix.default": _REFUSED,                 # slots [0, 4100] used: F0 = 4102 > R2_BASE_MAX -> fail = 1 (:417)
+    # 32 Ki slots, two segments of 16 Ki: a walk may end on slot HEAD - 1 = 2047 of the next head (k_r2_spill :1030); cluster - 2 is the farthest
+    "segment_mid_15_100.default": _USED_SEG, "segment_mid_15_2049.default": _USED_SEG,
+    "segment_mid_15_2050.default": _REFUSED_SEG,     # fail = 5
+    "segment_end_15_600.default": _USED_SEG,         # the last segment's walks go on in segment 0 (k_r2_place :988: (seg + 1) & (nseg - 1))
+    # ---- streamed from 32 slots on (SB = 5); k_r2_dsmall works on the arrays below 2048 slots (:359), its prefix is the whole first run ----
+    "one_home_zero_200.sb5": _USED, "one_home_mid_200.sb5": _USED, "one_home_last_200.sb5": _USED,
+    "one_home_zero_392.sb5": _USED, "one_home_mid_392.sb5": _USED,
+    # the one key of the last run finds the first 258 slots of the new table taken by the 382 keys before it: li >= R -> fail = 7 (:192)
+    "one_home_last_392.sb5": _REFUSED, "one_home_last_1544.sb5": _REFUSED, "lastput_growth.sb5": _REFUSED,
+    "run_ladder_wrap.sb5": _USED, "segment_mid_12_513.sb5": _USED, "segment_end_12_300.sb5": _USED,
+    # segments of 1 Ki slots, HEAD = 512 (kern_launch.inc:498)
+    "segment_mid_12_513.sb5_seg10": _USED_SEG, "segment_mid_12_514.sb5_seg10": _REFUSED_SEG, "segment_end_12_300.sb5_seg10": _USED_SEG,
+    "one_home_mid_392.sb5_seg10": _USED, "segment_mid_15_2049.sb5_seg10": _REFUSED_SEG,
+    # the rounds below YAKAMD_R2_SMALL_F = 1024 run in k_r2_dsmall (r2_small_rounds): r2_run places runs of up to R2_LONG = 8 slots, a wave the longer ones (:84, :309)
+    "run_ladder_plain.sb5_prefix1024": _USED, "one_home_zero_392.sb5_prefix1024": _USED,
+    "run_ladder_over.replay2_off": _OFF, "one_home_last_392.replay2_off": _OFF,
+    # ---- k_replay's rank variants on a table of one cluster (4 Ki slots: not large at SB = 13) ----
+    "one_home_last_1544.replay_lds_0": _NOT_LARGE, "one_home_last_1544.replay_lds_1024": _NOT_LARGE, "one_home_last_1544.replay_lds_8192": _NOT_LARGE,
+    # ---- the LDS counting table: without a filter s2 = 0 (slice_plan: n_total / P is small), the sub-table is one sub-bucket ----
+    # Lc2Cfg::FULL = CAP / 4 * 3 = 1536 distinct keys (kern_count.inc:567, :721); one more is passed on to k_lds_count_ovf
+    "hot_block_9.default": E([LC2_NOFILTER], ["k_lds_count_ovf"], lc2_passed_on="==0"), "hot_block_600.default": E([LC2_NOFILTER], ["k_lds_count_ovf"], lc2_passed_on="==0"),
+    "hot_block_probes_600.default": E([LC2_NOFILTER], ["k_lds_count_ovf"], lc2_passed_on="==0"),
+    "hot_block_1536.default": E(["k_lc2<false,false,false,true,false,11>"], ["k_lds_count_ovf"], lc2_passed_on="==0"),
+    "hot_block_1537.default": E(["k_lds_count_ovf"], [], lc2_passed_on=">0", ovf_groups=">0"),
+    "hot_block_3000.default": E(["k_lds_count_ovf"], [], lc2_passed_on=">0", ovf_groups=">0"),
+    # YAKAMD_LC2_CAPB = 10: 1024 slots, FULL = 768
+    "hot_block_768.lc2_capb10": E(["k_lc2<false,false,false,true,false,10>"], ["k_lds_count_ovf", LC2_NOFILTER], lc2_passed_on="==0"),
+    "hot_block_769.lc2_capb10": E(["k_lds_count_ovf"], [LC2_NOFILTER], lc2_passed_on=">0", ovf_groups=">0"),
+    # one key 2047 ... 70 000 times: more than 2^12 records in a sub-table, so the level-2 records take 16 bytes (slice_plan: np_max)
+    "hot_key.default": E(["k_lc2<false,false,false,false,false,11>"], ["k_lds_count_ovf"], lc2_passed_on="==0"),
+    "hot_key_among_600.default": E(["k_lc2<false,false,false,false,false,11>"], ["k_lds_count_ovf"], lc2_passed_on="==0"),
+    # yk_lc2_ok: YAKAMD_LC2 = 0 -> every sub-bucket to the tiers behind
+    "hot_block_769.lc2_off": E(["k_lds_count_ovf"], ["k_lc2*"], lc2_passed_on=">0"), "hot_block_3000.lc2_off": E(["k_lds_count_ovf"], ["k_lc2*"], lc2_passed_on=">0"),
+    "hot_key_among_600.lc2_off": E(["k_lds_count_ovf"], ["k_lc2*"], lc2_passed_on=">0"),
+    # fast_admit: a batch costs 65536 * 12 bytes, a second one is over the budget -> a slice per batch; the later ones meet the clustered table (I = true)
+    "hot_block_3000.slices": E(["k_lds_count_ovf"], ["k_acc_insert"], early_slices=">0", fast_abandoned="==0"),
+    "run_ladder_wrap.slices": E(["k_r2_dsmall", "k_r2_place"], ["k_acc_insert"], early_slices=">0", fast_abandoned="==0", r2_used=">0", r2_refused="==0"),
+    "long_prefix.slices": E(["k_r2_dsmall"], ["k_acc_insert"], early_slices=">0", fast_abandoned="==0", r2_refused=">0"),
+    # pass_begin: YAKAMD_FAST = 0 -> the accumulator path
+    "hot_block_625.fast_off": E(["k_acc_insert"], FAST_ONLY, slices="==0"), "hot_key.fast_off": E(["k_acc_insert"], FAST_ONLY, slices="==0"),
+    "one_home_last_392.fast_off": E(["k_acc_insert"], FAST_ONLY, slices="==0"),
+    # ---- the cases side by side in sub-tables 500 ... 503 of an ordinary read set: more than 256 sub-tables double in a step, so the doubling's waves
+    # come from YAKAMD_R2_DBL (yk_r2_double).  tests/test_adversarial.py replays the four sub-tables' actual streams through the model: none refuses ----
+    "mixed.default": E(R2_ONE, ["k_r2_double<5,*", "k_r2_double<6,*"], r2_used=">0", r2_refused="==0"),   # (sub-table 502 alone is large: 16 Ki slots)
+    "mixed.sb5": E(["k_r2_dsmall", "k_r2_double<5,false,1>", "k_r2_place"], [], r2_used=">0", r2_refused="==0"),
+    "mixed.sb5_seg10": E(["k_r2_double<5,false,1>", "k_r2_ppart"] + R2_SEGMENTED, [], r2_used=">0", r2_refused="==0"),
+    "mixed.sb5_dbl61": E(["k_r2_double<6,false,1>"], ["k_r2_double<5,*"], r2_used=">0", r2_refused="==0"),
+    "mixed.sb5_dbl52": E(["k_r2_double<5,false,2>"], ["k_r2_double<6,*", "k_r2_double<5,false,1>"], r2_used=">0", r2_refused="==0"),
+}
+# the count with -b22 of the same file (8 blocks per sub-table, s2 = 0: one sub-bucket): the staged instance holds LC2_FULL_BF = 624 distinct keys (kern_count.inc:550)
+ADVERSARIAL_B22 = {
+    "hot_block_624": E([LC2_FILTER], ["k_lds_count_ovf"], lc2_passed_on="==0"),
+    "hot_block_625": E([LC2_FILTER, "k_lds_count_ovf"], [], lc2_passed_on=">0", ovf_groups=">0"),
+}
+# pass 2 on the clustered tables, keyed by the row; every case of test_gpu_adversarial.PASS2_CASES runs under each, with -b22 (k = 31) and -b20 (k = 21), in one tally.
+# `retained`: both passes on one device image with yakamd_retain_input (the protocol of test_second_pass_counts_the_records_the_first_pass_retained);
+# else count_protocol_host, whose count pass feeds the input again (feed_image -> consume_records -> count_own / count_by_ranges / k_img_count_h)
+ADVERSARIAL_PASS2_ROWS = {
+    "fused": dict(retained=1), "cnt2_unfused": dict(retained=1, YAKAMD_CNT2_FUSED="0"), "retain2_off": dict(retained=1, YAKAMD_RETAIN2="0"),
+    "count_atomics": dict(YAKAMD_COUNT_OWN="0", YAKAMD_COUNT_LDS="0", YAKAMD_COUNT_RNG="0"),
+    "ranges_32_slots_no_list": dict(YAKAMD_COUNT_OWN="0", YAKAMD_COUNT_LDS="0", YAKAMD_RNG_LOG="5", YAKAMD_XLIST_CAP="0"),
+    "own_lds": dict(YAKAMD_OWN_LDS="18700", YAKAMD_OWN_MAXRB="12"), "own_lds_no_list": dict(YAKAMD_OWN_LDS="18700", YAKAMD_OWN_MAXRB="12", YAKAMD_XLIST_CAP="0"),
+}
+ADVERSARIAL_PASS2 = {
+    # slice_plan: nowb_plan (one slice into an empty table, fewer than 2^12 records per sub-table: kept) -> yakamd_count_retained's first branch
+    "fused": E(["k_cnt2_apply"], ["k_cnt2<*"], pass2_fused=">0", pass2_none="==0"),
+    "cnt2_unfused": E(["k_cnt2_apply"], [], pass2_recount=">0", pass2_fused="==0"),                    # YAKAMD_CNT2_FUSED = 0: k_cnt2 counts again
+    "retain2_off": E([OWN_H], ["k_cnt2*"], pass2_prefix=">0", pass2_none="==0"),                       # slice_retain: the level-1 records; consume_records
+    # consume_records: count_own, count_lds_bytes and count_by_ranges all refuse -> every instance walks its chain with device atomics
+    "count_atomics": E(["k_img_count_h"], ["k_img_count_own*", "k_img_count_lds*", "k_img_count_rng*", "k_hpart2*"]),
+    # count_by_ranges: ranges of 32 slots; a chain that leaves its range is an exception, and a list of no entries sends them all to the cross sweep
+    "ranges_32_slots_no_list": E([RNG, RNGX], ["k_img_count_own*"], rng_sweeps=">0"),
+    # count_own_plan: 18700 B leave room for ~228 keys (yk_count_own_lds): ranges of 64 slots and fewer; the instances whose key sits beyond their
+    # home slot's range -- all but a few of a cluster's -- go through the list (k_img_count_h), or with no list through the cross sweep
+    "own_lds": E([OWN_H, "k_img_count_h"], [OWN_HX, "k_img_count_rng*", "k_img_count_lds*"], own_sweeps="==0"),
+    "own_lds_no_list": E([OWN_H, OWN_HX], ["k_img_count_rng*"], own_sweeps=">0"),
+}
+
 # test function -> (module, parametrize argument whose ids key the table, table)
 TABLES = {
     "test_every_insert_path_is_exact": ("test_gpu_parity", "env", EVERY_INSERT_PATH),
@@ -331,4 +440,7 @@ TABLES = {
     "test_fused_counts_on_every_gather_and_tier": ("test_gpu_pass2_fused", "env", FUSED_GATHER_AND_TIER),
     "test_inc_and_shrink_between_the_passes": ("test_gpu_pass2_fused", "fused", INC_AND_SHRINK),
     "test_sub_buckets_k_lc2_passes_on": ("test_gpu_pass2_fused", None, SUB_BUCKETS_PASSED_ON),
+    "test_clustered_tables_are_exact": ("test_gpu_adversarial", "case_row", ADVERSARIAL),
+    "test_one_block_at_the_staged_table_bound": ("test_gpu_adversarial", "name", ADVERSARIAL_B22),
+    "test_pass2_on_clustered_tables": ("test_gpu_adversarial", "row", ADVERSARIAL_PASS2),
 }

@@ -483,21 +483,11 @@ def _kmers_of_sub_tables(lo, hi, per_sub, k=31, pre=10, seed=7):
     reverse complement, somewhere else, and are left out"""
     import random
     import numpy as np
-    from tablecmds_util import hash64_inv
-    rnd, mask = random.Random(seed), (1 << 2 * k) - 1
+    from adversarial_util import canonical_kmers, records
+    rnd = random.Random(seed)
     recs = []
     for p in range(lo, hi):
-        xs = np.array([hash64_inv(h << pre | p, mask) for h in rnd.sample(range(1 << (2 * k - pre)), 3 * per_sub)], dtype=np.uint64)
-        rc = np.zeros_like(xs)
-        for j in range(k):
-            rc |= (np.uint64(3) - (xs >> np.uint64(2 * j) & np.uint64(3))) << np.uint64(2 * (k - 1 - j))
-        xs = xs[xs < rc][:per_sub]
-        assert len(xs) == per_sub
-        seq = np.empty((per_sub, k + 1), dtype=np.uint8)
-        for j in range(k):
-            seq[:, j] = np.frombuffer(b"ACGT", dtype=np.uint8)[(xs >> np.uint64(2 * (k - 1 - j)) & np.uint64(3)).astype(np.int64)]
-        seq[:, k] = ord("\n")
-        recs.append(seq)
+        recs.append(records(canonical_kmers([h << pre | p for h in rnd.sample(range(1 << (2 * k - pre)), 3 * per_sub)], k, per_sub), k))
     out = np.concatenate(recs)
     np.random.RandomState(seed).shuffle(out)
     return out.tobytes()

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import paths_util
-from tablecmds_util import hash64_inv
+from adversarial_util import canonical_kmers, records
 
 pytestmark = pytest.mark.gpu
 
@@ -34,20 +34,10 @@ RAN1024 = paths_util.E([paths_util.SORT1024], [paths_util.SORT256, "k_ts_rank"],
 
 def _kmers(lo, sizes, seed=11):
     """records of one canonical k-mer each: sizes[j] distinct ones that hash into sub-table lo + j, shuffled"""
-    rnd, mask = random.Random(seed), (1 << 2 * K) - 1
+    rnd = random.Random(seed)
     recs = []
     for p, per in enumerate(sizes, lo):
-        xs = np.array([hash64_inv(h << PRE | p, mask) for h in rnd.sample(range(1 << (2 * K - PRE)), 3 * per + 16)], dtype=np.uint64)
-        rc = np.zeros_like(xs)
-        for j in range(K):
-            rc |= (np.uint64(3) - (xs >> np.uint64(2 * j) & np.uint64(3))) << np.uint64(2 * (K - 1 - j))
-        xs = xs[xs < rc][:per]                  # (the others would be counted as their reverse complement, somewhere else)
-        assert len(xs) == per
-        seq = np.empty((per, K + 1), dtype=np.uint8)
-        for j in range(K):
-            seq[:, j] = np.frombuffer(b"ACGT", dtype=np.uint8)[(xs >> np.uint64(2 * (K - 1 - j)) & np.uint64(3)).astype(np.int64)]
-        seq[:, K] = ord("\n")
-        recs.append(seq)
+        recs.append(records(canonical_kmers([h << PRE | p for h in rnd.sample(range(1 << (2 * K - PRE)), 3 * per + 16)], K, per), K))
     out = np.concatenate(recs)
     np.random.RandomState(seed).shuffle(out)
     return out.tobytes()

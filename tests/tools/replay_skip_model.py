@@ -13,76 +13,12 @@ keys fails with probability -> 1 as C0 grows (the expected number of differing s
 CAN be skipped is the cost, not the history: tables up to 8 Ki slots replay their whole history inside one workgroup's LDS (k_replay), so the streaming
 stages (k_r2_double / place) only start at 16 Ki slots -- the replay already "starts above the smallest capacities" in the only sense that is exact.
 """
+import os
 import random
 import sys
 
-M32 = 0xFFFFFFFF
-
-
-def h2b(h, bits):
-    return ((h * 2654435769) & M32) >> (32 - bits)
-
-
-class Kh:
-    """khashl set of 32-bit hashes, keys == hashes (what matters to the layout)"""
-    def __init__(self):
-        self.bits, self.count, self.used, self.keys = 0, 0, None, None
-
-    def n_buckets(self):
-        return (1 << self.bits) if self.keys is not None else 0
-
-    def resize(self, new_n):
-        j, x = 0, new_n
-        while x > 1:
-            x >>= 1; j += 1
-        if new_n & (new_n - 1):
-            j += 1
-        nb = max(j, 2)
-        new_n = 1 << nb
-        if self.count > (new_n >> 1) + (new_n >> 2):
-            return
-        new_used = [False] * new_n
-        n = self.n_buckets()
-        if self.keys is None:
-            self.keys, self.used = [None] * new_n, [False] * 0
-        if n < new_n:
-            self.keys = self.keys + [None] * (new_n - n)
-        mask = new_n - 1
-        for j in range(n):
-            if not self.used[j]:
-                continue
-            key = self.keys[j]
-            self.used[j] = False
-            while True:
-                i = h2b(key, nb)
-                while new_used[i]:
-                    i = (i + 1) & mask
-                new_used[i] = True
-                if i < n and self.used[i]:
-                    self.keys[i], key = key, self.keys[i]
-                    self.used[i] = False
-                else:
-                    self.keys[i] = key
-                    break
-        self.used, self.bits = new_used, nb
-
-    def put(self, key):
-        n = self.n_buckets()
-        if self.count >= (n >> 1) + (n >> 2):
-            self.resize(n + 1)
-            n = self.n_buckets()
-        mask = n - 1
-        i = last = h2b(key, self.bits)
-        while self.used[i] and self.keys[i] != key:
-            i = (i + 1) & mask
-            if i == last:
-                break
-        if not self.used[i]:
-            self.keys[i], self.used[i] = key, True
-            self.count += 1
-
-    def layout(self):
-        return [self.keys[i] if self.used[i] else None for i in range(self.n_buckets())]
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from adversarial_util import Kh, h2b          # noqa: E402  the literal put / resize of khashl (the keys here are 32-bit values, their own hashes)
 
 
 def through_history(keys, upto_bits):
