@@ -29,32 +29,24 @@ yak_amd/%.o: $(CSRC)/%.cpp $(ENGDEPS)
 yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/tally.o yak_amd/pool.o yak_amd/engine_ctx.o yak_amd/engine_pass.o yak_amd/engine_slice.o yak_amd/engine_table.o yak_amd/layout.o yak_amd/table_read.o yak_amd/lookup_dev.o yak_amd/yak_hetmer.o yak_amd/yak_graph.o yak_amd/yak_hpc.o yak_amd/yak_api.o yak_amd/yak_count.o yak_amd/yak_qv_solve.o yak_amd/yak_reader.o yak_amd/yak_multi.o yak_amd/yak_lookup.o yak_amd/yak_inspect.o yak_amd/yak_print.o $(CSRC)/libyak_amd.map
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(CSRC)/libyak_amd.map -o $@ $(filter %.o,$^) -lz
 
-# the device walk of `yak-amd unitigs -g`: its own kernels and its own launch tally (tally.cpp a second time), public calls
-# of libyak_amd.so only
-yak_amd/walk.o: $(WALK)/walk.hip $(WALK)/uwalk_step.h $(WALK)/uwalk_host.h $(CSRC)/tally.h include/yak.h include/yak_amd.h include/yak_amd_walk.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/walk_tally.o: $(CSRC)/tally.cpp $(CSRC)/tally.h include/yak_amd.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/libyak_amd_walk.so: yak_amd/walk.o yak_amd/walk_tally.o yak_amd/libyak_amd.so $(WALK)/libyak_amd_walk.map
-	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(WALK)/libyak_amd_walk.map -o $@ $(filter %.o,$^) -Lyak_amd -lyak_amd -Wl,-rpath,'$$ORIGIN'
-
-# the links between unitigs of `yak-amd unitigs -G`: its own kernels and its own launch tally (tally.cpp a third time),
-# public calls of the two libraries below it only
-yak_amd/gfa.o: $(GFA)/gfa.hip $(GFA)/gfa_step.h $(GFA)/gfa_text.h $(CSRC)/tally.h include/yak.h include/yak_amd.h include/yak_amd_walk.h include/yak_amd_gfa.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/gfa_tally.o: $(CSRC)/tally.cpp $(CSRC)/tally.h include/yak_amd.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/libyak_amd_gfa.so: yak_amd/gfa.o yak_amd/gfa_tally.o yak_amd/libyak_amd_walk.so yak_amd/libyak_amd.so $(GFA)/libyak_amd_gfa.map
-	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(GFA)/libyak_amd_gfa.map -o $@ $(filter %.o,$^) -Lyak_amd -lyak_amd_walk -lyak_amd -Wl,-rpath,'$$ORIGIN'
-
-# sequences as paths on the unitig graph, `yak-amd paths`: its own kernels and its own launch tally (tally.cpp a fourth
-# time), public calls of the walk's library and of libyak_amd.so only; gfa_step.h is a header and makes no link dependency
-yak_amd/path.o: $(PATHD)/path.hip $(PATHD)/path_step.h $(PATHD)/path_text.h $(PATHD)/path_reader.h $(GFA)/gfa_step.h $(CSRC)/tally.h include/yak.h include/yak_amd.h include/yak_amd_walk.h include/yak_amd_path.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/path_tally.o: $(CSRC)/tally.cpp $(CSRC)/tally.h include/yak_amd.h
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/libyak_amd_path.so: yak_amd/path.o yak_amd/path_tally.o yak_amd/libyak_amd_walk.so yak_amd/libyak_amd.so $(PATHD)/libyak_amd_path.map
-	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(PATHD)/libyak_amd_path.map -o $@ $(filter %.o,$^) -Lyak_amd -lyak_amd_walk -lyak_amd -Wl,-rpath,'$$ORIGIN' -lz
+# The three layers above libyak_amd.so (DESIGN.md sections 21 to 24): each its own kernels, public calls of the libraries below it only, the shared
+# headers of yak_amd/layer/, and tally.o linked in once more: its table is per library behind the version script.
+#   $(1) the name and its directory under yak_amd/, $(2) its further headers, $(3) the libraries below it in link order, $(4) further link flags
+LAYER     = yak_amd/layer
+LAYERDEPS = $(LAYER)/layer_host.h $(LAYER)/layer_dev.h $(CSRC)/tally.h include/yak.h include/yak_amd.h include/yak_amd_walk.h
+define LAYER_LIB
+yak_amd/$(1).o: yak_amd/$(1)/$(1).hip $(2) $$(LAYERDEPS)
+	$$(HIPCC) $$(HIPFLAGS) -c $$< -o $$@
+yak_amd/libyak_amd_$(1).so: yak_amd/$(1).o yak_amd/tally.o $(3) yak_amd/$(1)/libyak_amd_$(1).map
+	$$(HIPCC) --offload-arch=$$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=yak_amd/$(1)/libyak_amd_$(1).map -o $$@ $$(filter %.o,$$^) -Lyak_amd \
+		$$(patsubst yak_amd/lib%.so,-l%,$$(filter %.so,$$^)) -Wl,-rpath,'$$$$ORIGIN' $(4)
+endef
+# the device walk of `yak-amd unitigs -g`
+$(eval $(call LAYER_LIB,walk,$(WALK)/uwalk_step.h $(WALK)/uwalk_host.h,yak_amd/libyak_amd.so))
+# the links between unitigs of `yak-amd unitigs -G`
+$(eval $(call LAYER_LIB,gfa,$(GFA)/gfa_step.h $(GFA)/gfa_text.h include/yak_amd_gfa.h,yak_amd/libyak_amd_walk.so yak_amd/libyak_amd.so))
+# sequences as paths on the unitig graph, `yak-amd paths`; gfa_step.h is a header and makes no link dependency
+$(eval $(call LAYER_LIB,path,$(PATHD)/path_step.h $(PATHD)/path_text.h $(PATHD)/path_reader.h $(GFA)/gfa_step.h include/yak_amd_path.h,yak_amd/libyak_amd_walk.so yak_amd/libyak_amd.so,-lz))
 
 yak_amd/yak-amd: $(CSRC)/main.c include/yak.h include/yak_amd.h include/yak_amd_walk.h include/yak_amd_gfa.h include/yak_amd_path.h yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so yak_amd/libyak_amd_gfa.so yak_amd/libyak_amd_path.so
 	gcc -O2 -Wall -Iinclude $(CSRC)/main.c -o $@ -Lyak_amd -lyak_amd_path -lyak_amd_gfa -lyak_amd_walk -lyak_amd -Wl,-rpath,'$$ORIGIN' -lz

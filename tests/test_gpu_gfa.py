@@ -3,8 +3,8 @@ CLI's -G and yak_amd.gfa) against the restatements of tests/gfa_util.py (held to
 the kernels by tests/test_gfa.py and tests/test_gfa_model.py), always on the dump of the very table that was walked: the links element by element,
 the tallies, both texts byte for byte; the S lines against the FASTA of `unitigs -g`; the identities against the graph's tallies as the walk keeps
 them.  Tables of every degree, of one unitig without a link, of bubbles across sub-tables, of reads, of cycles, without a node, and of every 7-mer
--- 16 384 oriented ends, more than one tile of the scan, every end full -- also with the end table at its smallest capacity; the size queries, the
-refusals, and a launch of every kernel of the library."""
+-- 16 384 oriented ends, more than one tile of the scan, every end full -- also with the end table at its smallest capacity; of every 9-mer -- as
+many tiles as the scan's workgroup has threads; the size queries, the refusals, and a launch of every kernel of the library."""
 import ctypes as C
 import os
 import random
@@ -61,6 +61,26 @@ def every_7_mer():
     return U.image(["".join("ACGT"[i >> 2 * j & 3] for j in range(7)).encode() for i in range(1 << 14)])
 
 
+def every_9_mer():
+    """a de Bruijn sequence of order 9 over ACGT (the Lyndon words whose length divides 9, in order), its first 8 bases again behind it: 262 152
+    bases in which every 9-mer stands once"""
+    seq, a = [], [0] * 10
+
+    def db(t, p):
+        if t > 9:
+            if 9 % p == 0:
+                seq.extend(a[1:p + 1])
+        else:
+            a[t] = a[t - p]
+            db(t + 1, p)
+            for j in range(a[t - p] + 1, 4):
+                a[t] = j
+                db(t + 1, t)
+    db(1, 1)
+    assert len(seq) == 4 ** 9
+    return U.image([bytes(b"ACGT"[c] for c in seq + seq[:8])])
+
+
 SHAPES = {
     "mixed_k5_p10": lambda synth: mixed_k5(),
     "genome3000_k31_p10": lambda synth: U.image([genome(3000, 31)]),
@@ -69,6 +89,7 @@ SHAPES = {
     "cycles_k31_p10": lambda synth: U.image([genome(3000, 31), b"AC" * 20, genome(500, 5), b"ACG" * 14]),
     "ac8_k5_p10": lambda synth: U.image([b"AC" * 8]),
     "every_k7_p10": lambda synth: every_7_mer(),
+    "every_k9_p10": lambda synth: every_9_mer(),
 }
 
 
@@ -204,6 +225,21 @@ def test_every_7_mer(ya, yw, yg, tabs, tmp_path, monkeypatch):
     monkeypatch.setenv("YAKAMD_GFA_SLOTS", "8191")
     with yw.Walk(tab.t, 1) as w:
         assert yg.lib().yakamd_gfa_open(w.w, 7) is None and b"YAKAMD_GFA_SLOTS = 8191: the end table has 8192 keys" in yg.lib().yakamd_gfa_last_error()
+
+
+def test_every_9_mer(ya, yw, yg, tabs):
+    """131 072 unitigs of one node: 262 144 oriented ends are exactly 256 tiles of 1024, so that each of the 256 threads of k_gfa_tile_scan owns one
+    tile and the clamp of its slice sits on the slice's edge.  Every end has four links, so end e must own the entries 4e .. 4e + 3 of the list: an
+    offset that is wrong at any tile's edge moves them.  (The restatement in Python is not run at this size.)"""
+    tab = tabs("every_k9_p10")
+    with yw.Walk(tab.t, 1) as w, yg.Gfa(w, 9) as g:
+        got = g.stats()
+        arr = g.links()
+    print("stats", got)
+    assert got["n_open"] == 131072
+    assert got["n_link"] == 1048576
+    assert got["end_deg"] == [0, 0, 0, 0, 262144]
+    assert len(arr) == 1048576 and np.array_equal(arr["from"], np.repeat(np.arange(262144, dtype=np.uint64), 4))
 
 
 def test_smallest_capacity_with_chains(ya, yw, yg, tabs, tmp_path, monkeypatch):

@@ -6,7 +6,8 @@ import os
 
 import yak_amd
 import yak_amd.walk
-from yak_amd import ChT, UgoptT
+from yak_amd import ChT, UgoptT, _layer
+from yak_amd._layer import P
 
 GFA_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libyak_amd_gfa.so")
 GFA_H_SYMBOLS = [
@@ -26,39 +27,22 @@ _lib = None
 def lib():
     """Load libyak_amd_gfa.so (once), after the two libraries below it.  Raises if it has not been built: there is no fallback."""
     global _lib
-    if _lib is not None:
-        return _lib
-    yak_amd.walk.lib()
-    if not os.path.exists(GFA_LIB_PATH):
-        raise RuntimeError(f"{GFA_LIB_PATH} is missing: build it with `make lib` (python __graft_entry__.py build)")
-    L = C.CDLL(GFA_LIB_PATH)
-    P = C.POINTER
-    L.yakamd_gfa_open.restype = C.c_void_p; L.yakamd_gfa_open.argtypes = [C.c_void_p, C.c_int]
-    L.yakamd_gfa_stats.restype = C.c_int; L.yakamd_gfa_stats.argtypes = [C.c_void_p, P(GfastatT)]
-    L.yakamd_gfa_links_dev.restype = C.c_int64; L.yakamd_gfa_links_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.yakamd_gfa_close.restype = None; L.yakamd_gfa_close.argtypes = [C.c_void_p]
-    L.yakamd_unitigs_gfa.restype = C.c_int; L.yakamd_unitigs_gfa.argtypes = [P(UgoptT), P(ChT), C.c_char_p]
-    L.yakamd_gfa_ms.restype = None; L.yakamd_gfa_ms.argtypes = [P(C.c_double)]
-    L.yakamd_gfa_last_error.restype = C.c_char_p; L.yakamd_gfa_last_error.argtypes = []
-    L.yakamd_gfa_tally_names.restype = C.c_int; L.yakamd_gfa_tally_names.argtypes = [P(P(C.c_char_p))]
-    L.yakamd_gfa_tally_read.restype = None; L.yakamd_gfa_tally_read.argtypes = [P(C.c_uint64), C.c_int]
-    L.yakamd_gfa_tally_reset.restype = None; L.yakamd_gfa_tally_reset.argtypes = []
-    _lib = L
-    return L
+    if _lib is None:
+        _lib = _layer.load(GFA_LIB_PATH, yak_amd.walk.lib, {
+            **_layer.common("gfa"),
+            "yakamd_gfa_open": (C.c_void_p, [C.c_void_p, C.c_int]), "yakamd_gfa_stats": (C.c_int, [C.c_void_p, P(GfastatT)]),
+            "yakamd_gfa_links_dev": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64]), "yakamd_gfa_close": (None, [C.c_void_p]),
+            "yakamd_unitigs_gfa": (C.c_int, [P(UgoptT), P(ChT), C.c_char_p]), "yakamd_gfa_ms": (None, [P(C.c_double)])})
+    return _lib
 
 
 def _err():
-    return (lib().yakamd_gfa_last_error() or b"").decode()
+    return _layer.last_error(lib(), "gfa")
 
 
 def tally():
     """{kernel instantiation: launches since the last yakamd_gfa_tally_reset} of this library's own kernels"""
-    L = lib()
-    names = C.POINTER(C.c_char_p)()
-    n = L.yakamd_gfa_tally_names(C.byref(names))
-    out = (C.c_uint64 * max(n, 1))()
-    L.yakamd_gfa_tally_read(out, n)
-    return {names[i].decode(): int(out[i]) for i in range(n)}
+    return _layer.tally(lib(), "gfa")
 
 
 class Gfa:

@@ -3,7 +3,8 @@
  * (include/yak_amd_gfa.h).  A layer above libyak_amd_walk.so and libyak_amd.so: it calls their public functions only
  * (yakamd_uwalk_open / _stats / _gstat / _desc_dev / _bases_dev / _close, yakamd_walk_last_error) and owns its device memory
  * (hipMalloc / hipFree).  The per-thread steps are those of gfa_step.h, the texts those of gfa_text.h; every launch goes through YK_LAUNCH of
- * ../csrc/tally.h into this library's own tally (yakamd_gfa_tally_*).
+ * ../csrc/tally.h into this library's own tally (yakamd_gfa_tally_*).  The host scaffolding and the scan are those of ../layer/layer_host.h and
+ * ../layer/layer_dev.h, which the three layers share.
  *
  *   k_gfa_ends         a thread per unitig: W of its two oriented ends into endw[], and for an open unitig the canonical k-mers of its first and
  *                      last node claimed in the end table (64-bit atomicCAS on the key word, the value stored beside it and read by later
@@ -15,27 +16,15 @@
  *   k_gfa_links<EMIT>  the same decision again; an end writes its links at its offset, a 16-byte store each
  * All results are addressed by j, o and b; the tallies are integer sums (max_probe, a measurement, a maximum); all stores are vector stores.
  */
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-#include <new>
-#include <string>
-#include <vector>
 #include "yak.h"
-#include "yak_amd.h"
-#include "yak_amd_walk.h"
 #include "yak_amd_gfa.h"
-#include "../csrc/tally.h"
+#define LAYER_NAME "gfa"
+#include "../layer/layer_host.h"
+#include "../layer/layer_dev.h"
 #include "gfa_step.h"
 #include "gfa_text.h"
 
 static_assert(sizeof(yakamd_udesc_t) == sizeof(gf_desc_t) && sizeof(yakamd_ulink_t) == sizeof(gf_link_t) && sizeof(gf_slot_t) == 16, "the records as declared");
-
-typedef unsigned long long u64;
-typedef ulonglong2 v2;                                            /* 16 bytes: one vector load or store */
 
 namespace {
 
@@ -45,22 +34,6 @@ enum { GF_THREADS = 256, GF_ITEMS = 4, GF_TILE = GF_THREADS * GF_ITEMS, GF_WAVE 
 enum { GFS_DEG = 0, GFS_PROBE = 5, GFS_BAD = 6, GFS_FULL = 7, GFS_DUP = 8, GFS_N = 16 };
 enum GfMode { COUNT = 0, EMIT = 1 };
 
-struct DevCas {
-	__device__ uint64_t operator()(uint64_t *p, uint64_t expected, uint64_t desired) const { return (uint64_t)atomicCAS(reinterpret_cast<u64*>(p), (u64)expected, (u64)desired); }
-};
-
-__device__ inline u64 wave_sum(u64 v)
-{
-#pragma unroll
-	for (int o = GF_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o);
-	return v;                                                      /* lane 0 has the sum */
-}
-__device__ inline u64 wave_max(u64 v)
-{
-#pragma unroll
-	for (int o = GF_WAVE / 2; o > 0; o >>= 1) { const u64 y = __shfl_down(v, o); v = y > v ? y : v; }
-	return v;
-}
 /* what a thread gathered, into stat[]: a wave's sums and its maximum by one atomic each */
 __device__ inline void tally_out(u64 *stat, u64 probe, u64 bad, u64 full, u64 dup)
 {
@@ -134,107 +107,17 @@ void k_gfa_links(const gf_slot_t *__restrict__ slots, u64 cap, const u64 *__rest
 	tally_out(stat, probe, bad, 0, 0);
 }
 
-/* this thread's exclusive prefix of a within the workgroup of GF_THREADS, and the workgroup's sum */
-__device__ inline void block_scan(u64 a, u64 *ea, u64 *ta)
-{
-	__shared__ u64 s_w[GF_THREADS / GF_WAVE];
-	const unsigned lane = threadIdx.x & (GF_WAVE - 1), wave = threadIdx.x / GF_WAVE;
-	u64 ia = a;
-#pragma unroll
-	for (int o = 1; o < GF_WAVE; o <<= 1) {
-		const u64 y = __shfl_up(ia, o);
-		if (lane >= (unsigned)o) ia += y;
-	}
-	if (lane == GF_WAVE - 1) s_w[wave] = ia;
-	__syncthreads();
-	u64 r = ia - a, s = 0;
-#pragma unroll
-	for (unsigned w = 0; w < GF_THREADS / GF_WAVE; ++w) {
-		const u64 v = s_w[w];
-		if (w < wave) r += v;
-		s += v;
-	}
-	__syncthreads();                                               /* the next call writes s_w again */
-	*ea = r; *ta = s;
-}
-
-/* tsum[tile] = the sum of cnt[tile * GF_TILE ..]; one workgroup per tile, a thread GF_ITEMS consecutive entries */
+/* the exclusive scan of cnt[] in place (../layer/layer_dev.h): tiles of GF_TILE, their sums scanned by one workgroup */
 __global__ __launch_bounds__(GF_THREADS)
-void k_gfa_tile_sum(const u64 *__restrict__ cnt, u64 n, u64 *__restrict__ tsum)
-{
-	const u64 i0 = (u64)blockIdx.x * GF_TILE + (u64)threadIdx.x * GF_ITEMS;
-	u64 a = 0, ea, ta;
-#pragma unroll
-	for (int i = 0; i < GF_ITEMS; ++i) if (i0 + i < n) a += cnt[i0 + i];
-	block_scan(a, &ea, &ta);
-	if (threadIdx.x == 0) tsum[blockIdx.x] = ta;
-}
-
-/* the exclusive scan of tsum[0 .. m) in place, its sum in tsum[m]: one workgroup, each thread a contiguous slice */
+void k_gfa_tile_sum(const u64 *__restrict__ cnt, u64 n, u64 *__restrict__ tsum) { tile_sum<GF_THREADS, GF_ITEMS, u64, AddU64>(cnt, n, tsum); }
 __global__ __launch_bounds__(GF_THREADS)
-void k_gfa_tile_scan(u64 *__restrict__ tsum, u64 m)
-{
-	const u64 per = (m + GF_THREADS - 1) / GF_THREADS, lo = (u64)threadIdx.x * per < m ? (u64)threadIdx.x * per : m, hi = lo + per < m ? lo + per : m;
-	u64 a = 0, ea, ta;
-	for (u64 i = lo; i < hi; ++i) a += tsum[i];
-	block_scan(a, &ea, &ta);
-	for (u64 i = lo; i < hi; ++i) { const u64 v = tsum[i]; tsum[i] = ea; ea += v; }
-	if (threadIdx.x == 0) tsum[m] = ta;
-}
-
-/* cnt[] becomes its exclusive scan, tile by tile on top of the scanned tile sums */
+void k_gfa_tile_scan(u64 *__restrict__ tsum, u64 m) { tile_scan<GF_THREADS, u64, AddU64>(tsum, m); }
 __global__ __launch_bounds__(GF_THREADS)
-void k_gfa_scan_apply(u64 *__restrict__ cnt, u64 n, const u64 *__restrict__ tsum)
-{
-	const u64 i0 = (u64)blockIdx.x * GF_TILE + (u64)threadIdx.x * GF_ITEMS;
-	u64 it[GF_ITEMS], a = 0, ea, ta;
-#pragma unroll
-	for (int i = 0; i < GF_ITEMS; ++i) { it[i] = i0 + i < n ? cnt[i0 + i] : 0; a += it[i]; }
-	block_scan(a, &ea, &ta);
-	ea += tsum[blockIdx.x];
-#pragma unroll
-	for (int i = 0; i < GF_ITEMS; ++i) if (i0 + i < n) { cnt[i0 + i] = ea; ea += it[i]; }
-}
+void k_gfa_scan_apply(u64 *__restrict__ cnt, u64 n, const u64 *__restrict__ tsum) { scan_apply<GF_THREADS, GF_ITEMS, u64, AddU64>(cnt, n, tsum); }
 
 /* ---------------- host ---------------- */
 
-thread_local char g_err[512];
 thread_local double g_ms[4];                                       /* of this thread's last call */
-
-int gfail(const char *fmt, ...)
-{
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(g_err, sizeof g_err, fmt, ap);
-	va_end(ap);
-	fprintf(stderr, "[E::yak_amd] %s\n", g_err);
-	return -1;
-}
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return gfail("gfa: %s -> %s", #x, hipGetErrorString(e_)); } while (0)
-
-double now_ms()
-{
-	struct timespec ts;
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return ts.tv_sec * 1e3 + ts.tv_nsec / 1e6;
-}
-
-/* the device of the links for a call, and the caller's current device again after it */
-struct OnDevice {
-	int before = -1;
-	explicit OnDevice(int dev) { if (hipGetDevice(&before) != hipSuccess) before = -1; if (before != dev) (void)hipSetDevice(dev); else before = -1; }
-	~OnDevice() { if (before >= 0) (void)hipSetDevice(before); }
-};
-
-unsigned grid_for(u64 n) { const u64 b = (n + GF_THREADS - 1) / GF_THREADS; return (unsigned)(b < 1 ? 1 : b > 2048 ? 2048 : b); }
-
-/* device memory that frees itself */
-struct GfDevBuf {
-	void *p = 0;
-	~GfDevBuf() { drop(); }
-	void drop() { if (p) (void)hipFree(p); p = 0; }
-	bool get(size_t bytes) { return hipMalloc(&p, bytes < 256 ? 256 : bytes) == hipSuccess; }
-};
 
 }   // namespace
 
@@ -242,7 +125,7 @@ struct yakamd_gfa {
 	int k, dev;
 	yakamd_gfastat_t st;
 	u64 n_bases;
-	GfDevBuf links, desc, bases;                                   /* desc and bases are kept for the text of yakamd_unitigs_gfa only */
+	DevBuf links, desc, bases;                                   /* desc and bases are kept for the text of yakamd_unitigs_gfa only */
 	std::vector<gf_desc_t> h_desc;
 };
 
@@ -251,11 +134,11 @@ namespace {
 /* what yakamd_gfa_open refuses, before any device work */
 int gfa_check(yakamd_uwalk_t *w, int k, yakamd_uwstat_t *us)
 {
-	if (!w) return gfail("gfa: no walk");
-	if (k < 3 || k > 31 || !(k & 1)) return gfail("gfa: k = %d: the links are defined for an odd k in [3, 31]", k);
-	if (yakamd_uwalk_stats(w, us) != 0) { snprintf(g_err, sizeof g_err, "%s", yakamd_walk_last_error()); return -1; }
+	if (!w) return fail("gfa: no walk");
+	if (k < 3 || k > 31 || !(k & 1)) return fail("gfa: k = %d: the links are defined for an odd k in [3, 31]", k);
+	if (yakamd_uwalk_stats(w, us) != 0) return fail_below(yakamd_walk_last_error());
 	if (us->sum_len != us->n_node + (us->n_open + us->n_cycle) * (u64)(k - 1))
-		return gfail("gfa: k = %d does not fit the walk: %llu bases in %llu unitigs of %llu nodes", k, (u64)us->sum_len, (u64)(us->n_open + us->n_cycle), (u64)us->n_node);
+		return fail("gfa: k = %d does not fit the walk: %llu bases in %llu unitigs of %llu nodes", k, (u64)us->sum_len, (u64)(us->n_open + us->n_cycle), (u64)us->n_node);
 	return 0;
 }
 
@@ -271,42 +154,32 @@ int gfa_run(yakamd_gfa *g, yakamd_uwalk_t *w, const yakamd_uwstat_t &us, bool ke
 	double t0 = now_ms();
 
 	/* copies of the walk's results, the descriptors on the host as well: the number of keys comes from them */
-	if (!g->desc.get(n_u * 32) || !g->bases.get(us.sum_len)) return gfail("gfa: no device memory for %llu bytes", n_u * 32 + (u64)us.sum_len);
-	if (yakamd_uwalk_desc_dev(w, g->desc.p, (int64_t)n_u) != (int64_t)n_u || yakamd_uwalk_bases_dev(w, g->bases.p, (int64_t)us.sum_len) != (int64_t)us.sum_len) {
-		snprintf(g_err, sizeof g_err, "%s", yakamd_walk_last_error());
-		return -1;
-	}
-	try { g->h_desc.resize((size_t)n_u); } catch (const std::bad_alloc&) { return gfail("gfa: the descriptors of %llu unitigs do not fit the host's memory", n_u); }
-	HIPCK(hipMemcpy(g->h_desc.data(), g->desc.p, n_u * 32, hipMemcpyDeviceToHost));
+	const int rc = copy_walk(w, n_u, us.sum_len, 1, g->desc, g->bases, g->h_desc);
+	if (rc) return rc < 0 ? -1 : fail("gfa: no device memory for %llu bytes", n_u * 32 + (u64)us.sum_len);
 	u64 n_key = 0, n_open = 0;
 	for (const gf_desc_t &u : g->h_desc) if (!(u.first & 1)) { ++n_open; n_key += u.n_node > 1 ? 2 : 1; }
-	if (n_open != us.n_open) return gfail("gfa: %llu descriptors of open unitigs, the walk states %llu", n_open, (u64)us.n_open);
-	u64 cap = gf_capacity(n_key);
-	const char *sw = getenv("YAKAMD_GFA_SLOTS");
-	if (sw && *sw) {
-		const u64 want = strtoull(sw, 0, 10);
-		if (want < n_key || want < 1 || want > (u64)1 << 40) return gfail("gfa: YAKAMD_GFA_SLOTS = %llu: the end table has %llu keys", want, n_key);
-		for (cap = 1; cap < want; cap <<= 1) {}
-	}
+	if (n_open != us.n_open) return fail("gfa: %llu descriptors of open unitigs, the walk states %llu", n_open, (u64)us.n_open);
+	u64 cap = gf_capacity(n_key), want = 0;
+	if (!slots_from_env("YAKAMD_GFA_SLOTS", n_key, &cap, &want)) return fail("gfa: YAKAMD_GFA_SLOTS = %llu: the end table has %llu keys", want, n_key);
 	st.table_slots = cap;
 	const double t_copy = now_ms();
 
 	const u64 m = (n_end + GF_TILE - 1) / GF_TILE;
-	GfDevBuf slots, endw, cnt, tsum, stat;
+	DevBuf slots, endw, cnt, tsum, stat;
 	if (!slots.get(cap * 16) || !endw.get(n_end * 8) || !cnt.get(n_end * 8) || !tsum.get((m + 1) * 8) || !stat.get(GFS_N * 8))
-		return gfail("gfa: no device memory for %llu bytes", cap * 16 + n_end * 16 + (m + 1) * 8);
+		return fail("gfa: no device memory for %llu bytes", cap * 16 + n_end * 16 + (m + 1) * 8);
 	u64 *d_stat = (u64*)stat.p, *d_cnt = (u64*)cnt.p, *d_tsum = (u64*)tsum.p, h_stat[GFS_N];
 	HIPCK(hipMemset(slots.p, 0xff, cap * 16));                     /* every key GF_EMPTY */
 	HIPCK(hipMemset(d_stat, 0, GFS_N * 8));
 	HIPCK(hipDeviceSynchronize());
 	const double t_table = now_ms();
-	YK_LAUNCH(k_gfa_ends, dim3(grid_for(n_u)), dim3(GF_THREADS), 0, 0, (const gf_desc_t*)g->desc.p, n_u, (const char*)g->bases.p, (u64)us.sum_len, k, (gf_slot_t*)slots.p, cap,
+	YK_LAUNCH(k_gfa_ends, dim3(grid_for(n_u, GF_THREADS)), dim3(GF_THREADS), 0, 0, (const gf_desc_t*)g->desc.p, n_u, (const char*)g->bases.p, (u64)us.sum_len, k, (gf_slot_t*)slots.p, cap,
 	          (u64*)endw.p, d_stat);
 	HIPCK(hipGetLastError());
 	HIPCK(hipMemcpy(h_stat, d_stat, sizeof h_stat, hipMemcpyDeviceToHost));
-	if (h_stat[GFS_FULL]) return gfail("gfa: %llu end nodes met no free slot among the %llu of the end table", h_stat[GFS_FULL], cap);
-	if (h_stat[GFS_BAD]) return gfail("gfa: the descriptors of %llu unitigs do not fit the %llu bases", h_stat[GFS_BAD], (u64)us.sum_len);
-	if (h_stat[GFS_DUP]) return gfail("gfa: %llu end nodes stand in two unitigs", h_stat[GFS_DUP]);
+	if (h_stat[GFS_FULL]) return fail("gfa: %llu end nodes met no free slot among the %llu of the end table", h_stat[GFS_FULL], cap);
+	if (h_stat[GFS_BAD]) return fail("gfa: the descriptors of %llu unitigs do not fit the %llu bases", h_stat[GFS_BAD], (u64)us.sum_len);
+	if (h_stat[GFS_DUP]) return fail("gfa: %llu end nodes stand in two unitigs", h_stat[GFS_DUP]);
 	const double t_ends = now_ms();
 	if (!keep) { g->desc.drop(); g->bases.drop(); std::vector<gf_desc_t>().swap(g->h_desc); }     /* endw[] and the table hold all that the links need */
 	g_ms[0] = now_ms() - t0;
@@ -315,7 +188,7 @@ int gfa_run(yakamd_gfa *g, yakamd_uwalk_t *w, const yakamd_uwstat_t &us, bool ke
 		        t_copy - t0, cap, t_table - t_copy, t_ends - t_table, now_ms() - t_ends);
 	t0 = now_ms();
 
-	YK_LAUNCH(k_gfa_links<COUNT>, dim3(grid_for(n_end)), dim3(GF_THREADS), 0, 0, (const gf_slot_t*)slots.p, cap, (const u64*)endw.p, n_end, k, n_u, d_cnt, (gf_link_t*)0, (u64)0, d_stat);
+	YK_LAUNCH(k_gfa_links<COUNT>, dim3(grid_for(n_end, GF_THREADS)), dim3(GF_THREADS), 0, 0, (const gf_slot_t*)slots.p, cap, (const u64*)endw.p, n_end, k, n_u, d_cnt, (gf_link_t*)0, (u64)0, d_stat);
 	YK_LAUNCH(k_gfa_tile_sum, dim3((unsigned)m), dim3(GF_THREADS), 0, 0, (const u64*)d_cnt, n_end, d_tsum);
 	YK_LAUNCH(k_gfa_tile_scan, dim3(1), dim3(GF_THREADS), 0, 0, d_tsum, m);
 	YK_LAUNCH(k_gfa_scan_apply, dim3((unsigned)m), dim3(GF_THREADS), 0, 0, d_cnt, n_end, (const u64*)d_tsum);
@@ -326,15 +199,15 @@ int gfa_run(yakamd_gfa *g, yakamd_uwalk_t *w, const yakamd_uwstat_t &us, bool ke
 	u64 ends = 0;
 	for (int d = 0; d < 5; ++d) { st.end_deg[d] = h_stat[GFS_DEG + d]; ends += h_stat[GFS_DEG + d]; }
 	if (h_stat[GFS_BAD] || ends != 2 * us.n_open || n_link > 4 * n_end)
-		return gfail("gfa: the end table does not fit the unitigs (%llu values, %llu of %llu ends of open unitigs)", h_stat[GFS_BAD], ends, 2 * (u64)us.n_open);
+		return fail("gfa: the end table does not fit the unitigs (%llu values, %llu of %llu ends of open unitigs)", h_stat[GFS_BAD], ends, 2 * (u64)us.n_open);
 	st.n_link = n_link;
 	g_ms[1] = now_ms() - t0; t0 = now_ms();
 
-	if (!g->links.get(n_link * 16)) return gfail("gfa: no device memory for %llu links", n_link);
-	YK_LAUNCH(k_gfa_links<EMIT>, dim3(grid_for(n_end)), dim3(GF_THREADS), 0, 0, (const gf_slot_t*)slots.p, cap, (const u64*)endw.p, n_end, k, n_u, d_cnt, (gf_link_t*)g->links.p, n_link, d_stat);
+	if (!g->links.get(n_link * 16)) return fail("gfa: no device memory for %llu links", n_link);
+	YK_LAUNCH(k_gfa_links<EMIT>, dim3(grid_for(n_end, GF_THREADS)), dim3(GF_THREADS), 0, 0, (const gf_slot_t*)slots.p, cap, (const u64*)endw.p, n_end, k, n_u, d_cnt, (gf_link_t*)g->links.p, n_link, d_stat);
 	HIPCK(hipGetLastError());
 	HIPCK(hipMemcpy(h_stat, d_stat, sizeof h_stat, hipMemcpyDeviceToHost));
-	if (h_stat[GFS_BAD]) return gfail("gfa: %llu ends have no place in the list of %llu links", h_stat[GFS_BAD], n_link);
+	if (h_stat[GFS_BAD]) return fail("gfa: %llu ends have no place in the list of %llu links", h_stat[GFS_BAD], n_link);
 	st.max_probe = h_stat[GFS_PROBE];
 	g_ms[2] = now_ms() - t0;
 	return 0;
@@ -346,7 +219,7 @@ yakamd_gfa_t *gfa_open(yakamd_uwalk_t *w, int k, bool keep)
 	yakamd_uwstat_t us;
 	if (gfa_check(w, k, &us) != 0) return 0;
 	yakamd_gfa_t *g = new (std::nothrow) yakamd_gfa_t();
-	if (!g) { gfail("gfa: no memory"); return 0; }
+	if (!g) { fail("gfa: no memory"); return 0; }
 	g->k = k; g->dev = 0; g->n_bases = 0;
 	memset(&g->st, 0, sizeof g->st);
 	if (gfa_run(g, w, us, keep) != 0) { delete g; return 0; }
@@ -369,17 +242,17 @@ extern "C" void yakamd_gfa_close(yakamd_gfa_t *g)
 
 extern "C" int yakamd_gfa_stats(yakamd_gfa_t *g, yakamd_gfastat_t *st)
 {
-	if (!g || !st) return gfail("gfa stats: no links, or no place for them");
+	if (!g || !st) return fail("gfa stats: no links, or no place for them");
 	*st = g->st;
 	return 0;
 }
 
 extern "C" int64_t yakamd_gfa_links_dev(yakamd_gfa_t *g, void *d, int64_t cap)
 {
-	if (!g) return gfail("gfa links: no links");
+	if (!g) return fail("gfa links: no links");
 	const u64 n = g->st.n_link;
 	if (!d || cap < (int64_t)n) return (int64_t)n;
-	if (((uintptr_t)d & 15) != 0) return gfail("gfa links: the entries must be 16-byte aligned");
+	if (((uintptr_t)d & 15) != 0) return fail("gfa links: the entries must be 16-byte aligned");
 	if (n == 0) return 0;
 	OnDevice dev(g->dev);
 	HIPCK(hipMemcpy(d, g->links.p, n * 16, hipMemcpyDeviceToDevice));
@@ -389,29 +262,27 @@ extern "C" int64_t yakamd_gfa_links_dev(yakamd_gfa_t *g, void *d, int64_t cap)
 /* the command: the walk, the links, then the text from the tallies or from the descriptors, the bases and the links */
 extern "C" int yakamd_unitigs_gfa(const yakamd_ugopt_t *opt, yak_ch_t *ch, const char *out_fn)
 {
-	if (!opt) return gfail("yakamd_unitigs_gfa: no options");
-	struct Walk { yakamd_uwalk_t *w; ~Walk() { yakamd_uwalk_close(w); } } W{ yakamd_uwalk_open(ch, opt->min_cnt) };
-	if (!W.w) { snprintf(g_err, sizeof g_err, "%s", yakamd_walk_last_error()); return -1; }     /* its message, which it has put on stderr itself */
+	if (!opt) return fail("yakamd_unitigs_gfa: no options");
+	WalkGuard W{ yakamd_uwalk_open(ch, opt->min_cnt) };
+	if (!W.w) return fail_below(yakamd_walk_last_error());
 	struct Gfa { yakamd_gfa_t *g; ~Gfa() { yakamd_gfa_close(g); } } G{ gfa_open(W.w, ch->k, !opt->stats_only) };
 	yakamd_gfa_t *g = G.g;
 	if (!g) return -1;
 	const double t0 = now_ms();
 	yakamd_gstat_t gs;
 	yakamd_uwstat_t us;
-	if (yakamd_uwalk_gstat(W.w, &gs) != 0 || yakamd_uwalk_stats(W.w, &us) != 0) { snprintf(g_err, sizeof g_err, "%s", yakamd_walk_last_error()); return -1; }
+	if (yakamd_uwalk_gstat(W.w, &gs) != 0 || yakamd_uwalk_stats(W.w, &us) != 0) return fail_below(yakamd_walk_last_error());
 	std::string bases;
 	std::vector<gf_link_t> links;
 	if (!opt->stats_only) {
 		try { bases.resize((size_t)g->n_bases); links.resize((size_t)g->st.n_link); }
-		catch (const std::bad_alloc&) { return gfail("yakamd_unitigs_gfa: %llu bases and %llu links do not fit the host's memory", g->n_bases, (u64)g->st.n_link); }
+		catch (const std::bad_alloc&) { return fail("yakamd_unitigs_gfa: %llu bases and %llu links do not fit the host's memory", g->n_bases, (u64)g->st.n_link); }
 		OnDevice dev(g->dev);
 		if (g->n_bases) HIPCK(hipMemcpy(&bases[0], g->bases.p, (size_t)g->n_bases, hipMemcpyDeviceToHost));
 		if (g->st.n_link) HIPCK(hipMemcpy(links.data(), g->links.p, (size_t)g->st.n_link * 16, hipMemcpyDeviceToHost));
 	}
-	const bool to_stdout = !out_fn || strcmp(out_fn, "-") == 0;
-	FILE *out = to_stdout ? stdout : fopen(out_fn, "wb");
-	if (!out) return gfail("yakamd_unitigs_gfa: cannot write '%s'", out_fn);
-	struct Closer { FILE *f; bool own; ~Closer() { if (own && f) fclose(f); } } closer{ out, !to_stdout };
+	OutFile out(out_fn);
+	if (!out.f) return fail("yakamd_unitigs_gfa: cannot write '%s'", out.name);
 	bool ok = true;
 	try {
 		if (opt->stats_only) {
@@ -420,15 +291,12 @@ extern "C" int yakamd_unitigs_gfa(const yakamd_ugopt_t *opt, yak_ch_t *ch, const
 			t.n_key = gs.n_key; t.n_node = gs.n_node; t.n_arc = gs.n_arc; t.n_linked_side = gs.n_linked_side;
 			for (int l = 0; l < 5; ++l) for (int r = 0; r < 5; ++r) t.deg[l][r] = gs.deg[l][r];
 			t.n_open = us.n_open; t.n_cycle = us.n_cycle; t.sum_len = us.sum_len; t.max_len = us.max_len; t.n50 = us.n50;
-			const std::string text = gft_stats(t, g->st.n_link, g->st.end_deg);
-			ok = fwrite(text.data(), 1, text.size(), out) == text.size();
+			ok = out.write(gft_stats(t, g->st.n_link, g->st.end_deg));
 		} else
 			ok = gft_gfa(g->h_desc.data(), g->h_desc.size(), bases.data(), g->n_bases, links.data(), links.size(), g->k,
-			             [out](const std::string &t) { return fwrite(t.data(), 1, t.size(), out) == t.size(); });
-	} catch (const std::bad_alloc&) { return gfail("yakamd_unitigs_gfa: no host memory for the text"); }
-	ok = fflush(out) == 0 && !ferror(out) && ok;
-	if (!to_stdout) { ok = fclose(out) == 0 && ok; closer.f = 0; }
-	if (!ok) return gfail("yakamd_unitigs_gfa: cannot write '%s'", to_stdout ? "-" : out_fn);
+			             [&out](const std::string &t) { return out.write(t); });
+	} catch (const std::bad_alloc&) { return fail("yakamd_unitigs_gfa: no host memory for the text"); }
+	if (!(out.finish() && ok)) return fail("yakamd_unitigs_gfa: cannot write '%s'", out.name);
 	g_ms[3] = now_ms() - t0;
 	if (getenv("YAKAMD_VERBOSE"))
 		fprintf(stderr, "[yak_amd] unitigs -G: %llu links of %llu unitigs: end table (%llu slots, longest probe %llu) %.1f ms, count and scan %.1f ms, emit %.1f ms, text %.1f ms\n",
@@ -436,19 +304,4 @@ extern "C" int yakamd_unitigs_gfa(const yakamd_ugopt_t *opt, yak_ch_t *ch, const
 	return 0;
 }
 
-/* the launch tally of this library: tally.cpp, compiled into it a third time, keeps a table of its own behind the version script; its path events
- * belong to libyak_amd.so and are not listed */
-extern "C" int yakamd_gfa_tally_names(const char *const **names)
-{
-	const char *const *all = 0;
-	const int n = yakamd_tally_names(&all);
-	if (names) *names = all + YKE_N;
-	return n - YKE_N;
-}
-extern "C" void yakamd_gfa_tally_read(uint64_t *out, int n)
-{
-	std::vector<uint64_t> all((size_t)(n > 0 ? n : 0) + YKE_N);
-	yakamd_tally_read(all.data(), (int)all.size());
-	for (int i = 0; i < n; ++i) out[i] = all[(size_t)i + YKE_N];
-}
-extern "C" void yakamd_gfa_tally_reset(void) { yakamd_tally_reset(); }
+LAYER_TALLY_EXPORTS(gfa)

@@ -6,7 +6,8 @@ import os
 
 import yak_amd
 import yak_amd.walk
-from yak_amd import ChT
+from yak_amd import ChT, _layer
+from yak_amd._layer import P
 
 PATH_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libyak_amd_path.so")
 PATH_H_SYMBOLS = [
@@ -33,43 +34,25 @@ _lib = None
 def lib():
     """Load libyak_amd_path.so (once), after the two libraries below it.  Raises if it has not been built: there is no fallback."""
     global _lib
-    if _lib is not None:
-        return _lib
-    yak_amd.walk.lib()
-    if not os.path.exists(PATH_LIB_PATH):
-        raise RuntimeError(f"{PATH_LIB_PATH} is missing: build it with `make lib` (python __graft_entry__.py build)")
-    L = C.CDLL(PATH_LIB_PATH)
-    P = C.POINTER
-    L.yakamd_path_open.restype = C.c_void_p; L.yakamd_path_open.argtypes = [C.c_void_p, C.c_int]
-    L.yakamd_path_stats.restype = C.c_int; L.yakamd_path_stats.argtypes = [C.c_void_p, P(PxstatT)]
-    L.yakamd_path_hits_dev.restype = C.c_int; L.yakamd_path_hits_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.yakamd_path_chain_dev.restype = C.c_int
-    L.yakamd_path_chain_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
-                                        P(C.c_int64)]
-    L.yakamd_path_close.restype = None; L.yakamd_path_close.argtypes = [C.c_void_p]
-    L.yakamd_paths.restype = C.c_int; L.yakamd_paths.argtypes = [P(PpoptT), P(ChT), C.c_char_p, C.c_char_p]
-    L.yakamd_ppopt_init.restype = None; L.yakamd_ppopt_init.argtypes = [P(PpoptT)]
-    L.yakamd_path_ms.restype = None; L.yakamd_path_ms.argtypes = [P(C.c_double)]
-    L.yakamd_path_last_error.restype = C.c_char_p; L.yakamd_path_last_error.argtypes = []
-    L.yakamd_path_tally_names.restype = C.c_int; L.yakamd_path_tally_names.argtypes = [P(P(C.c_char_p))]
-    L.yakamd_path_tally_read.restype = None; L.yakamd_path_tally_read.argtypes = [P(C.c_uint64), C.c_int]
-    L.yakamd_path_tally_reset.restype = None; L.yakamd_path_tally_reset.argtypes = []
-    _lib = L
-    return L
+    if _lib is None:
+        V = C.c_void_p
+        _lib = _layer.load(PATH_LIB_PATH, yak_amd.walk.lib, {
+            **_layer.common("path"),
+            "yakamd_path_open": (V, [V, C.c_int]), "yakamd_path_stats": (C.c_int, [V, P(PxstatT)]),
+            "yakamd_path_hits_dev": (C.c_int, [V, V, C.c_int64, V]),
+            "yakamd_path_chain_dev": (C.c_int, [V, V, C.c_int64, V, V, C.c_int64, V, C.c_int64, V, C.c_int64, V, P(C.c_int64)]),
+            "yakamd_path_close": (None, [V]), "yakamd_paths": (C.c_int, [P(PpoptT), P(ChT), C.c_char_p, C.c_char_p]),
+            "yakamd_ppopt_init": (None, [P(PpoptT)]), "yakamd_path_ms": (None, [P(C.c_double)])})
+    return _lib
 
 
 def _err():
-    return (lib().yakamd_path_last_error() or b"").decode()
+    return _layer.last_error(lib(), "path")
 
 
 def tally():
     """{kernel instantiation: launches since the last yakamd_path_tally_reset} of this library's own kernels"""
-    L = lib()
-    names = C.POINTER(C.c_char_p)()
-    n = L.yakamd_path_tally_names(C.byref(names))
-    out = (C.c_uint64 * max(n, 1))()
-    L.yakamd_path_tally_read(out, n)
-    return {names[i].decode(): int(out[i]) for i in range(n)}
+    return _layer.tally(lib(), "path")
 
 
 def ms():

@@ -3,7 +3,8 @@
  * section 23).  A layer above libyak_amd_walk.so and libyak_amd.so: it calls their public functions only (yakamd_uwalk_open / _stats / _desc_dev /
  * _bases_dev / _close, yakamd_walk_last_error, yakamd_ch_hpc, seq_nt4_table) and owns its device memory (hipMalloc / hipFree).  The per-thread steps
  * are those of path_step.h (with ../gfa/gfa_step.h's k-mers and table), the texts those of path_text.h, the reader that of path_reader.h; every
- * launch goes through YK_LAUNCH of ../csrc/tally.h into this library's own tally (yakamd_path_tally_*).
+ * launch goes through YK_LAUNCH of ../csrc/tally.h into this library's own tally (yakamd_path_tally_*).  The host scaffolding and the workgroup scan
+ * are those of ../layer/layer_host.h and ../layer/layer_dev.h, which the three layers share.
  *
  * A workgroup of 256 threads serves a tile of 1024 positions, a thread 4 consecutive ones.
  *   k_path_index      over the positions of the walk's bases: the tile and k - 1 bytes behind it staged in LDS by 16-byte loads; a thread finds its
@@ -19,20 +20,11 @@
  * Nothing but hit[] (8 bytes a position) and the tile array (64 bytes a tile) is kept between the kernels.  All results are addressed by position
  * and rank; the tallies are integer sums (max_probe, a measurement, a maximum); all stores are vector stores.
  */
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-#include <new>
-#include <string>
-#include <vector>
 #include "yak.h"
-#include "yak_amd.h"
-#include "yak_amd_walk.h"
 #include "yak_amd_path.h"
-#include "../csrc/tally.h"
+#define LAYER_NAME "path"
+#include "../layer/layer_host.h"
+#include "../layer/layer_dev.h"
 #include "path_step.h"
 #include "path_text.h"
 #include "path_reader.h"
@@ -41,8 +33,20 @@ static_assert(sizeof(yakamd_udesc_t) == sizeof(gf_desc_t) && sizeof(yakamd_upath
               sizeof(yakamd_ptally_t) == sizeof(px_tally_t) && sizeof(gf_slot_t) == 16, "the records as declared");
 static_assert(YAKAMD_PATH_NONE == PX_NONE && YAKAMD_PATH_ABSENT == PX_ABSENT && PX_WIN % 16 == 0 && PX_HALO >= 30, "the constants as declared");
 
-typedef unsigned long long u64;
-typedef ulonglong2 v2;                                            /* 16 bytes: one vector load or store */
+static_assert(PX_WAVE == LY_WAVE, "one wave size");
+
+/* px_cnt_t for the workgroup scan of ../layer/layer_dev.h: its shuffle, found beside the type, and its join */
+__device__ inline px_cnt_t scan_shfl_up(const px_cnt_t &a, int o)
+{
+	px_cnt_t y;
+	y.path = __shfl_up((u64)a.path, o); y.step = __shfl_up((u64)a.step, o); y.hit = __shfl_up((u64)a.hit, o); y.kmer = __shfl_up((u64)a.kmer, o);
+	y.seg_flag = __shfl_up((u64)a.seg_flag, o); y.seg_val = __shfl_up((u64)a.seg_val, o);
+	return y;
+}
+struct CntJoin {
+	__device__ static px_cnt_t zero() { px_cnt_t z; px_cnt_zero(&z); return z; }
+	__device__ px_cnt_t operator()(const px_cnt_t &front, const px_cnt_t &own) const { return px_cnt_join(front, own); }
+};
 
 namespace {
 
@@ -50,26 +54,11 @@ namespace {
  * there already; nodes with a byte that is none of ACGT */
 enum { PXS_PROBE = 0, PXS_BAD = 1, PXS_FULL = 2, PXS_DUP = 3, PXS_NONBASE = 4, PXS_N = 8 };
 
-struct DevCas {
-	__device__ uint64_t operator()(uint64_t *p, uint64_t expected, uint64_t desired) const { return (uint64_t)atomicCAS(reinterpret_cast<u64*>(p), (u64)expected, (u64)desired); }
-};
 struct DevLoad16 {
 	const unsigned char *g;
 	__device__ void operator()(int64_t off, unsigned char *dst) const { *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(g + off); }
 };
 
-__device__ inline u64 wave_sum(u64 v)
-{
-#pragma unroll
-	for (int o = PX_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o);
-	return v;                                                      /* lane 0 has the sum */
-}
-__device__ inline u64 wave_max(u64 v)
-{
-#pragma unroll
-	for (int o = PX_WAVE / 2; o > 0; o >>= 1) { const u64 y = __shfl_down(v, o); v = y > v ? y : v; }
-	return v;
-}
 /* what a thread gathered, into stat[]: a wave's sums and its maximum by one atomic each */
 __device__ inline void err_out(u64 *stat, const px_err_t &e)
 {
@@ -136,41 +125,6 @@ __device__ inline void load_hits(const u64 *__restrict__ hit, int64_t n, int64_t
 	if (i0 + 4 < n) h[5] = hit[i0 + 4];
 }
 
-__device__ inline px_cnt_t cnt_shfl_up(const px_cnt_t &a, int o)
-{
-	px_cnt_t y;
-	y.path = __shfl_up((u64)a.path, o); y.step = __shfl_up((u64)a.step, o); y.hit = __shfl_up((u64)a.hit, o); y.kmer = __shfl_up((u64)a.kmer, o);
-	y.seg_flag = __shfl_up((u64)a.seg_flag, o); y.seg_val = __shfl_up((u64)a.seg_val, o);
-	return y;
-}
-/* what the threads in front of this one hold within the workgroup, joined in order, and what the whole workgroup holds */
-__device__ inline void block_scan(const px_cnt_t &own, px_cnt_t *before, px_cnt_t *total)
-{
-	__shared__ px_cnt_t s_w[PX_THREADS / PX_WAVE];
-	const unsigned lane = threadIdx.x & (PX_WAVE - 1), wave = threadIdx.x / PX_WAVE;
-	px_cnt_t inc = own;
-#pragma unroll
-	for (int o = 1; o < PX_WAVE; o <<= 1) {
-		const px_cnt_t y = cnt_shfl_up(inc, o);
-		if (lane >= (unsigned)o) inc = px_cnt_join(y, inc);
-	}
-	if (lane == PX_WAVE - 1) s_w[wave] = inc;
-	px_cnt_t ex = cnt_shfl_up(inc, 1);
-	if (lane == 0) px_cnt_zero(&ex);
-	__syncthreads();
-	px_cnt_t front, all;
-	px_cnt_zero(&front); px_cnt_zero(&all);
-#pragma unroll
-	for (unsigned w = 0; w < PX_THREADS / PX_WAVE; ++w) {
-		const px_cnt_t v = s_w[w];
-		if (w < wave) front = px_cnt_join(front, v);
-		all = px_cnt_join(all, v);
-	}
-	__syncthreads();                                               /* the next call writes s_w again */
-	*before = px_cnt_join(front, ex);
-	*total = all;
-}
-
 __global__ __launch_bounds__(PX_THREADS)
 void k_path_count(const u64 *__restrict__ hit, int64_t n, uint64_t *__restrict__ tile)
 {
@@ -179,7 +133,7 @@ void k_path_count(const u64 *__restrict__ hit, int64_t n, uint64_t *__restrict__
 	load_hits(hit, n, (int64_t)blockIdx.x * PX_TILE + (int64_t)threadIdx.x * PX_ITEMS, h);
 	const px_cnt_t own = px_count_thread(h, fl);
 	px_cnt_t before, total;
-	block_scan(own, &before, &total);
+	block_scan<PX_THREADS, px_cnt_t, CntJoin>(own, &before, &total);
 	if (threadIdx.x == 0) px_tile_put(tile + (u64)blockIdx.x * PXT_WORDS, &total);
 }
 
@@ -190,7 +144,7 @@ void k_path_tile_scan(uint64_t *__restrict__ tile, u64 m)
 	const u64 per = (m + PX_THREADS - 1) / PX_THREADS, lo = (u64)threadIdx.x * per < m ? (u64)threadIdx.x * per : m, hi = lo + per < m ? lo + per : m;
 	const px_cnt_t own = px_tile_join(tile, lo, hi);
 	px_cnt_t before, total;
-	block_scan(own, &before, &total);
+	block_scan<PX_THREADS, px_cnt_t, CntJoin>(own, &before, &total);
 	px_tile_apply(tile, lo, hi, before);
 	if (threadIdx.x == 0) px_tile_put(tile + m * PXT_WORDS, &total);
 }
@@ -204,7 +158,7 @@ void k_path_emit(const u64 *__restrict__ hit, int64_t n, const uint64_t *__restr
 	load_hits(hit, n, i0, h);
 	const px_cnt_t own = px_count_thread(h, fl);
 	px_cnt_t before, total;
-	block_scan(own, &before, &total);
+	block_scan<PX_THREADS, px_cnt_t, CntJoin>(own, &before, &total);
 	before = px_cnt_join(px_tile_get(tile + (u64)blockIdx.x * PXT_WORDS), before);
 	px_err_t e = { 0, 0, 0, 0, 0 };
 #pragma unroll
@@ -236,43 +190,7 @@ void k_path_tally(const uint64_t *__restrict__ hit, u64 n, const uint64_t *__res
 
 /* ---------------- host ---------------- */
 
-thread_local char g_err[512];
 thread_local double g_ms[6];
-
-int pfail(const char *fmt, ...)
-{
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(g_err, sizeof g_err, fmt, ap);
-	va_end(ap);
-	fprintf(stderr, "[E::yak_amd] %s\n", g_err);
-	return -1;
-}
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return pfail("path: %s -> %s", #x, hipGetErrorString(e_)); } while (0)
-
-double now_ms()
-{
-	struct timespec ts;
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return ts.tv_sec * 1e3 + ts.tv_nsec / 1e6;
-}
-
-/* the device of the index for the close, and the caller's current device again after it */
-struct OnDevice {
-	int before = -1;
-	explicit OnDevice(int dev) { if (hipGetDevice(&before) != hipSuccess) before = -1; if (before != dev) (void)hipSetDevice(dev); else before = -1; }
-	~OnDevice() { if (before >= 0) (void)hipSetDevice(before); }
-};
-
-/* device memory that frees itself; need() keeps what is large enough */
-struct PxDevBuf {
-	void *p = 0;
-	size_t have = 0;
-	~PxDevBuf() { drop(); }
-	void drop() { if (p) (void)hipFree(p); p = 0; have = 0; }
-	bool get(size_t bytes) { drop(); have = bytes < 256 ? 256 : bytes; if (hipMalloc(&p, have) != hipSuccess) { p = 0; have = 0; } return p != 0; }
-	bool need(size_t bytes) { return (p && have >= bytes) || get(bytes + bytes / 8); }
-};
 
 const u64 MAX_TILES = 0x7fffffffull;                              /* a grid's first dimension */
 u64 tiles_of(u64 n) { return (n + PX_TILE - 1) / PX_TILE; }
@@ -283,7 +201,7 @@ u64 up16(u64 n) { return (n + 15) & ~(u64)15; }
 struct yakamd_path {
 	int k, dev;
 	yakamd_pxstat_t st;
-	PxDevBuf slots, desc, nt4, stat, tile;
+	DevBuf slots, desc, nt4, stat, tile;
 	std::vector<uint32_t> n_node;                                  /* per unitig, for the text */
 };
 
@@ -292,21 +210,17 @@ namespace {
 /* what yakamd_path_open refuses before any device work; *cap = the slots of the index, *need = its bytes with the copies */
 int path_check(yakamd_uwalk_t *w, int k, yakamd_uwstat_t *us, u64 *cap, u64 *need)
 {
-	if (!w) return pfail("path: no walk");
-	if (k < 3 || k > 31 || !(k & 1)) return pfail("path: k = %d: the paths are defined for an odd k in [3, 31]", k);
-	if (yakamd_uwalk_stats(w, us) != 0) { snprintf(g_err, sizeof g_err, "%s", yakamd_walk_last_error()); return -1; }
+	if (!w) return fail("path: no walk");
+	if (k < 3 || k > 31 || !(k & 1)) return fail("path: k = %d: the paths are defined for an odd k in [3, 31]", k);
+	if (yakamd_uwalk_stats(w, us) != 0) return fail_below(yakamd_walk_last_error());
 	const u64 n_u = us->n_open + us->n_cycle;
 	if (us->sum_len != us->n_node + n_u * (u64)(k - 1))
-		return pfail("path: k = %d does not fit the walk: %llu bases in %llu unitigs of %llu nodes", k, (u64)us->sum_len, n_u, (u64)us->n_node);
+		return fail("path: k = %d does not fit the walk: %llu bases in %llu unitigs of %llu nodes", k, (u64)us->sum_len, n_u, (u64)us->n_node);
 	if (n_u >= (u64)1 << 31 || (n_u && us->max_len - (u64)(k - 1) >= (u64)1 << 31))
-		return pfail("path: %llu unitigs, the longest of %llu nodes: a value of the index holds less than 2^31 of either", n_u, n_u ? (u64)us->max_len - (u64)(k - 1) : 0);
+		return fail("path: %llu unitigs, the longest of %llu nodes: a value of the index holds less than 2^31 of either", n_u, n_u ? (u64)us->max_len - (u64)(k - 1) : 0);
 	*cap = n_u ? gf_capacity(us->n_node) : 0;
-	const char *sw = getenv("YAKAMD_PATH_SLOTS");
-	if (n_u && sw && *sw) {
-		const u64 want = strtoull(sw, 0, 10);
-		if (want < us->n_node || want < 1 || want > (u64)1 << 40) return pfail("path: YAKAMD_PATH_SLOTS = %llu: the index has %llu keys", want, (u64)us->n_node);
-		for (*cap = 1; *cap < want; *cap <<= 1) {}
-	}
+	u64 want = 0;
+	if (n_u && !slots_from_env("YAKAMD_PATH_SLOTS", us->n_node, cap, &want)) return fail("path: YAKAMD_PATH_SLOTS = %llu: the index has %llu keys", want, (u64)us->n_node);
 	*need = *cap * 16 + n_u * 32 + up16(us->sum_len);
 	return 0;
 }
@@ -322,33 +236,29 @@ int path_build(yakamd_path *px, yakamd_uwalk_t *w, const yakamd_uwstat_t &us, u6
 	const char *lim = getenv("YAKAMD_PATH_MAX_BYTES");
 	const u64 limit = lim && *lim ? strtoull(lim, 0, 10) : (u64)free_b;
 	if (need > limit)
-		return pfail("path: %llu bytes of device memory are needed for the index of %llu nodes (%llu slots of 16 bytes, %llu descriptors, %llu bases), %llu are free",
+		return fail("path: %llu bytes of device memory are needed for the index of %llu nodes (%llu slots of 16 bytes, %llu descriptors, %llu bases), %llu are free",
 		             need, (u64)us.n_node, cap, n_u, n_bases, limit);
 	const double t0 = now_ms();
-	if (!px->nt4.get(256) || !px->stat.get(PXS_N * 8)) return pfail("path: no device memory");
+	if (!px->nt4.get(256) || !px->stat.get(PXS_N * 8)) return fail("path: no device memory");
 	HIPCK(hipMemcpy(px->nt4.p, seq_nt4_table, 256, hipMemcpyHostToDevice));
 	HIPCK(hipMemset(px->stat.p, 0, PXS_N * 8));
 	if (n_u == 0) { g_ms[0] = now_ms() - t0; return 0; }
-	if (tiles_of(n_bases) > MAX_TILES) return pfail("path: %llu bases are more than one launch serves", n_bases);
+	if (tiles_of(n_bases) > MAX_TILES) return fail("path: %llu bases are more than one launch serves", n_bases);
 
-	PxDevBuf bases;
-	if (!px->desc.get(n_u * 32) || !bases.get(up16(n_bases)) || !px->slots.get(cap * 16)) return pfail("path: no device memory for %llu bytes", need);
-	if (yakamd_uwalk_desc_dev(w, px->desc.p, (int64_t)n_u) != (int64_t)n_u || yakamd_uwalk_bases_dev(w, bases.p, (int64_t)n_bases) != (int64_t)n_bases) {
-		snprintf(g_err, sizeof g_err, "%s", yakamd_walk_last_error());
-		return -1;
-	}
+	DevBuf bases;
 	/* the descriptors on the host: their nodes for the text, and one look at whether they tile the bases */
 	std::vector<gf_desc_t> h_desc;
-	try { h_desc.resize((size_t)n_u); px->n_node.resize((size_t)n_u); } catch (const std::bad_alloc&) { return pfail("path: the descriptors of %llu unitigs do not fit the host's memory", n_u); }
-	HIPCK(hipMemcpy(h_desc.data(), px->desc.p, n_u * 32, hipMemcpyDeviceToHost));
+	const int rc = px->slots.get(cap * 16) ? copy_walk(w, n_u, n_bases, 16, px->desc, bases, h_desc) : 1;
+	if (rc) return rc < 0 ? -1 : fail("path: no device memory for %llu bytes", need);
+	try { px->n_node.resize((size_t)n_u); } catch (const std::bad_alloc&) { return fail("path: the descriptors of %llu unitigs do not fit the host's memory", n_u); }
 	u64 at = 0, nodes = 0;
 	for (u64 j = 0; j < n_u; ++j) {
 		const gf_desc_t &u = h_desc[(size_t)j];
-		if (u.off != at || !px_desc_fits(&u, n_bases, k)) return pfail("path: the descriptor of unitig %llu does not fit the %llu bases", j, n_bases);
+		if (u.off != at || !px_desc_fits(&u, n_bases, k)) return fail("path: the descriptor of unitig %llu does not fit the %llu bases", j, n_bases);
 		at += u.n_node + (u64)(k - 1); nodes += u.n_node;
 		px->n_node[(size_t)j] = (uint32_t)u.n_node;
 	}
-	if (at != n_bases || nodes != us.n_node) return pfail("path: the descriptors hold %llu nodes in %llu bases, the walk states %llu in %llu", nodes, at, (u64)us.n_node, n_bases);
+	if (at != n_bases || nodes != us.n_node) return fail("path: the descriptors hold %llu nodes in %llu bases, the walk states %llu in %llu", nodes, at, (u64)us.n_node, n_bases);
 
 	u64 *d_stat = (u64*)px->stat.p, h_stat[PXS_N];
 	HIPCK(hipMemset(px->slots.p, 0xff, cap * 16));                 /* every key GF_EMPTY */
@@ -356,10 +266,10 @@ int path_build(yakamd_path *px, yakamd_uwalk_t *w, const yakamd_uwstat_t &us, u6
 	          (gf_slot_t*)px->slots.p, cap, d_stat);
 	HIPCK(hipGetLastError());
 	HIPCK(hipMemcpy(h_stat, d_stat, sizeof h_stat, hipMemcpyDeviceToHost));
-	if (h_stat[PXS_FULL]) return pfail("path: %llu nodes met no free slot among the %llu of the index", h_stat[PXS_FULL], cap);
-	if (h_stat[PXS_BAD]) return pfail("path: the descriptors do not fit the %llu bases at %llu places", n_bases, h_stat[PXS_BAD]);
-	if (h_stat[PXS_NONBASE]) return pfail("path: %llu nodes hold a byte that is none of ACGT", h_stat[PXS_NONBASE]);
-	if (h_stat[PXS_DUP]) return pfail("path: %llu nodes stand in two places of the unitigs", h_stat[PXS_DUP]);
+	if (h_stat[PXS_FULL]) return fail("path: %llu nodes met no free slot among the %llu of the index", h_stat[PXS_FULL], cap);
+	if (h_stat[PXS_BAD]) return fail("path: the descriptors do not fit the %llu bases at %llu places", n_bases, h_stat[PXS_BAD]);
+	if (h_stat[PXS_NONBASE]) return fail("path: %llu nodes hold a byte that is none of ACGT", h_stat[PXS_NONBASE]);
+	if (h_stat[PXS_DUP]) return fail("path: %llu nodes stand in two places of the unitigs", h_stat[PXS_DUP]);
 	px->st.max_probe = h_stat[PXS_PROBE];
 	g_ms[0] = now_ms() - t0;
 	if (getenv("YAKAMD_VERBOSE"))
@@ -376,7 +286,7 @@ int path_after(yakamd_path *px, const char *what)
 	if (h_stat[PXS_PROBE] > px->st.max_probe) px->st.max_probe = h_stat[PXS_PROBE];
 	if (h_stat[PXS_BAD]) {
 		(void)hipMemset(px->stat.p, 0, PXS_N * 8);
-		return pfail("path %s: %llu values do not fit the unitigs, the sequences or the lists", what, h_stat[PXS_BAD]);
+		return fail("path %s: %llu values do not fit the unitigs, the sequences or the lists", what, h_stat[PXS_BAD]);
 	}
 	return 0;
 }
@@ -398,7 +308,7 @@ extern "C" yakamd_path_t *yakamd_path_open(yakamd_uwalk_t *w, int k)
 	u64 cap = 0, need = 0;
 	if (path_check(w, k, &us, &cap, &need) != 0) return 0;
 	yakamd_path_t *px = new (std::nothrow) yakamd_path_t();
-	if (!px) { pfail("path: no memory"); return 0; }
+	if (!px) { fail("path: no memory"); return 0; }
 	px->k = k; px->dev = 0;
 	memset(&px->st, 0, sizeof px->st);
 	if (path_build(px, w, us, cap, need) != 0) { delete px; return 0; }
@@ -414,18 +324,18 @@ extern "C" void yakamd_path_close(yakamd_path_t *px)
 
 extern "C" int yakamd_path_stats(yakamd_path_t *px, yakamd_pxstat_t *st)
 {
-	if (!px || !st) return pfail("path stats: no index, or no place for the numbers");
+	if (!px || !st) return fail("path stats: no index, or no place for the numbers");
 	*st = px->st;
 	return 0;
 }
 
 extern "C" int yakamd_path_hits_dev(yakamd_path_t *px, const void *d_bases, int64_t n_bytes, uint64_t *d_hit)
 {
-	if (!px) return pfail("path hits: no index");
-	if (n_bytes < 0) return pfail("path hits: %lld bytes", (long long)n_bytes);
+	if (!px) return fail("path hits: no index");
+	if (n_bytes < 0) return fail("path hits: %lld bytes", (long long)n_bytes);
 	if (n_bytes == 0) return 0;
-	if (!d_bases || !d_hit || (((uintptr_t)d_bases | (uintptr_t)d_hit) & 15) != 0) return pfail("path hits: the image and the hits must be given and 16-byte aligned");
-	if (tiles_of((u64)n_bytes) > MAX_TILES) return pfail("path hits: %lld bytes are more than one launch serves", (long long)n_bytes);
+	if (!d_bases || !d_hit || (((uintptr_t)d_bases | (uintptr_t)d_hit) & 15) != 0) return fail("path hits: the image and the hits must be given and 16-byte aligned");
+	if (tiles_of((u64)n_bytes) > MAX_TILES) return fail("path hits: %lld bytes are more than one launch serves", (long long)n_bytes);
 	const double t0 = now_ms();
 	YK_LAUNCH(k_path_hits, dim3((unsigned)tiles_of((u64)n_bytes)), dim3(PX_THREADS), 0, 0, (const gf_slot_t*)px->slots.p, (u64)px->st.table_slots, (const unsigned char*)px->nt4.p,
 	          (const unsigned char*)d_bases, n_bytes, px->k, (u64)px->st.n_unitig, (u64*)d_hit, (u64*)px->stat.p);
@@ -437,22 +347,22 @@ extern "C" int yakamd_path_hits_dev(yakamd_path_t *px, const void *d_bases, int6
 extern "C" int yakamd_path_chain_dev(yakamd_path_t *px, const uint64_t *d_hit, int64_t n_bytes, const uint64_t *d_seq_off, const uint32_t *d_seq_len, int64_t n_seq,
                                      yakamd_upath_t *d_paths, int64_t cap_paths, uint64_t *d_steps, int64_t cap_steps, yakamd_ptally_t *d_tally, int64_t n_out[2])
 {
-	if (!px) return pfail("path chain: no index");
-	if (!n_out) return pfail("path chain: no place for the two numbers");
+	if (!px) return fail("path chain: no index");
+	if (!n_out) return fail("path chain: no place for the two numbers");
 	n_out[0] = n_out[1] = 0;
-	if (n_bytes < 0 || n_seq < 0) return pfail("path chain: %lld bytes, %lld sequences", (long long)n_bytes, (long long)n_seq);
-	if (n_seq > 0 && (!d_seq_off || !d_seq_len)) return pfail("path chain: %lld sequences without their offsets and lengths", (long long)n_seq);
+	if (n_bytes < 0 || n_seq < 0) return fail("path chain: %lld bytes, %lld sequences", (long long)n_bytes, (long long)n_seq);
+	if (n_seq > 0 && (!d_seq_off || !d_seq_len)) return fail("path chain: %lld sequences without their offsets and lengths", (long long)n_seq);
 	if ((((uintptr_t)d_hit | (uintptr_t)d_paths | (uintptr_t)d_tally) & 15) != 0 || (((uintptr_t)d_steps | (uintptr_t)d_seq_off) & 7) != 0 || ((uintptr_t)d_seq_len & 3) != 0)
-		return pfail("path chain: the hits, the records and the tallies must be 16-byte aligned, the steps and the offsets 8-byte, the lengths 4-byte");
+		return fail("path chain: the hits, the records and the tallies must be 16-byte aligned, the steps and the offsets 8-byte, the lengths 4-byte");
 	if (n_bytes == 0) {                                            /* no position: no launch */
 		if (d_tally && n_seq > 0) HIPCK(hipMemset(d_tally, 0, (size_t)n_seq * sizeof(yakamd_ptally_t)));
 		return 0;
 	}
-	if (!d_hit) return pfail("path chain: no hits");
-	if (n_seq < 1) return pfail("path chain: %lld bytes in no sequence", (long long)n_bytes);
+	if (!d_hit) return fail("path chain: no hits");
+	if (n_seq < 1) return fail("path chain: %lld bytes in no sequence", (long long)n_bytes);
 	const u64 m = tiles_of((u64)n_bytes);
-	if (m > MAX_TILES) return pfail("path chain: %lld bytes are more than one launch serves", (long long)n_bytes);
-	if (!px->tile.need((size_t)(m + 1) * PXT_WORDS * 8)) return pfail("path chain: no device memory for %llu tiles", m);
+	if (m > MAX_TILES) return fail("path chain: %lld bytes are more than one launch serves", (long long)n_bytes);
+	if (!px->tile.need((size_t)(m + 1) * PXT_WORDS * 8)) return fail("path chain: no device memory for %llu tiles", m);
 	uint64_t *d_tile = (uint64_t*)px->tile.p, tot[PXT_WORDS];
 	double t0 = now_ms();
 	YK_LAUNCH(k_path_count, dim3((unsigned)m), dim3(PX_THREADS), 0, 0, (const u64*)d_hit, n_bytes, d_tile);
@@ -490,7 +400,7 @@ struct Chunk {
 	std::vector<uint32_t> len;
 	void clear() { seqs.clear(); img.clear(); off.clear(); len.clear(); }
 };
-struct ChunkDev { PxDevBuf img, hit, off, len, tally, paths, steps; };
+struct ChunkDev { DevBuf img, hit, off, len, tally, paths, steps; };
 
 /* one chunk through the device; its text behind `text` */
 int run_chunk(yakamd_path *px, const yakamd_ppopt_t &o, Chunk &c, ChunkDev &d, std::string &text, pxt_total_t *tot)
@@ -499,7 +409,7 @@ int run_chunk(yakamd_path *px, const yakamd_ppopt_t &o, Chunk &c, ChunkDev &d, s
 	if (n_seq == 0) return 0;
 	c.img.resize((size_t)up16(n), '\n');
 	if (!d.img.need(c.img.size()) || !d.hit.need(c.img.size() * 8) || !d.off.need(n_seq * 8) || !d.len.need(n_seq * 4) || !d.tally.need(n_seq * 16))
-		return pfail("yakamd_paths: no device memory for a chunk of %zu bytes", n);
+		return fail("yakamd_paths: no device memory for a chunk of %zu bytes", n);
 	double t0 = now_ms();
 	HIPCK(hipMemcpy(d.img.p, c.img.data(), c.img.size(), hipMemcpyHostToDevice));
 	HIPCK(hipMemcpy(d.off.p, c.off.data(), n_seq * 8, hipMemcpyHostToDevice));
@@ -523,11 +433,11 @@ int run_chunk(yakamd_path *px, const yakamd_ppopt_t &o, Chunk &c, ChunkDev &d, s
 		return 0;
 	}
 	if (n_out[0] == 0) return 0;
-	if (!d.paths.need((size_t)n_out[0] * 32) || !d.steps.need((size_t)n_out[1] * 8)) return pfail("yakamd_paths: no device memory for %lld paths of %lld steps", (long long)n_out[0], (long long)n_out[1]);
+	if (!d.paths.need((size_t)n_out[0] * 32) || !d.steps.need((size_t)n_out[1] * 8)) return fail("yakamd_paths: no device memory for %lld paths of %lld steps", (long long)n_out[0], (long long)n_out[1]);
 	int64_t again[2];
 	rc = yakamd_path_chain_dev(px, (const uint64_t*)d.hit.p, (int64_t)n, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)n_seq, (yakamd_upath_t*)d.paths.p, n_out[0],
 	                           (uint64_t*)d.steps.p, n_out[1], 0, again);
-	if (rc != 0) return rc < 0 ? -1 : pfail("yakamd_paths: the writing call counted %lld paths of %lld steps, the counting call %lld of %lld", (long long)again[0], (long long)again[1],
+	if (rc != 0) return rc < 0 ? -1 : fail("yakamd_paths: the writing call counted %lld paths of %lld steps, the counting call %lld of %lld", (long long)again[0], (long long)again[1],
 	                                        (long long)n_out[0], (long long)n_out[1]);
 	paths.resize((size_t)n_out[0]); steps.resize((size_t)n_out[1]);
 	t0 = now_ms();
@@ -535,7 +445,7 @@ int run_chunk(yakamd_path *px, const yakamd_ppopt_t &o, Chunk &c, ChunkDev &d, s
 	HIPCK(hipMemcpy(steps.data(), d.steps.p, steps.size() * 8, hipMemcpyDeviceToHost));
 	g_ms[4] += now_ms() - t0; t0 = now_ms();
 	if (!pxt_gaf(text, c.seqs, paths.data(), paths.size(), steps.data(), steps.size(), px->n_node.data(), px->n_node.size(), px->k, o.min_len))
-		return pfail("yakamd_paths: a path record does not fit its chunk");
+		return fail("yakamd_paths: a path record does not fit its chunk");
 	g_ms[5] += now_ms() - t0;
 	return 0;
 }
@@ -544,23 +454,21 @@ int run_chunk(yakamd_path *px, const yakamd_ppopt_t &o, Chunk &c, ChunkDev &d, s
 
 extern "C" int yakamd_paths(const yakamd_ppopt_t *opt, yak_ch_t *ch, const char *fn, const char *out_fn)
 {
-	if (!opt) return pfail("yakamd_paths: no options");
-	if (opt->min_len < 0) return pfail("yakamd_paths: min_len %d", opt->min_len);
-	if (opt->chunk_size < 1) return pfail("yakamd_paths: chunk_size %lld", (long long)opt->chunk_size);
-	if (!fn) return pfail("yakamd_paths: no sequences");
-	if (ch && yakamd_ch_hpc(ch)) return pfail("yakamd_paths: the table is marked homopolymer-compressed: its unitigs are no sequences to lay others onto");
+	if (!opt) return fail("yakamd_paths: no options");
+	if (opt->min_len < 0) return fail("yakamd_paths: min_len %d", opt->min_len);
+	if (opt->chunk_size < 1) return fail("yakamd_paths: chunk_size %lld", (long long)opt->chunk_size);
+	if (!fn) return fail("yakamd_paths: no sequences");
+	if (ch && yakamd_ch_hpc(ch)) return fail("yakamd_paths: the table is marked homopolymer-compressed: its unitigs are no sequences to lay others onto");
 	PxReader rd;
-	if (ch && !rd.open(fn)) return pfail("yakamd_paths: cannot read '%s'", fn);
-	struct Walk { yakamd_uwalk_t *w; ~Walk() { yakamd_uwalk_close(w); } void close() { yakamd_uwalk_close(w); w = 0; } } W{ yakamd_uwalk_open(ch, opt->min_cnt) };
-	if (!W.w) { snprintf(g_err, sizeof g_err, "%s", yakamd_walk_last_error()); return -1; }     /* its message, which it has put on stderr itself */
+	if (ch && !rd.open(fn)) return fail("yakamd_paths: cannot read '%s'", fn);
+	WalkGuard W{ yakamd_uwalk_open(ch, opt->min_cnt) };
+	if (!W.w) return fail_below(yakamd_walk_last_error());
 	struct Px { yakamd_path_t *p; ~Px() { yakamd_path_close(p); } } P{ yakamd_path_open(W.w, ch->k) };
 	yakamd_path_t *px = P.p;
 	if (!px) return -1;
 	W.close();
-	const bool to_stdout = !out_fn || strcmp(out_fn, "-") == 0;
-	FILE *out = to_stdout ? stdout : fopen(out_fn, "wb");
-	if (!out) return pfail("yakamd_paths: cannot write '%s'", out_fn);
-	struct Closer { FILE *f; bool own; ~Closer() { if (own && f) fclose(f); } } closer{ out, !to_stdout };
+	OutFile out(out_fn);
+	if (!out.f) return fail("yakamd_paths: cannot write '%s'", out.name);
 	bool ok = true;
 	try {
 		Chunk c;
@@ -573,7 +481,7 @@ extern "C" int yakamd_paths(const yakamd_ppopt_t *opt, yak_ch_t *ch, const char 
 		while (more) {
 			more = rd.next(name, seq);
 			if (more) {
-				if (seq.size() >= 0xffffffffull) return pfail("yakamd_paths: sequence '%s' has %zu bases: a length is a 32-bit number", name.c_str(), seq.size());
+				if (seq.size() >= 0xffffffffull) return fail("yakamd_paths: sequence '%s' has %zu bases: a length is a 32-bit number", name.c_str(), seq.size());
 				c.off.push_back(c.img.size());
 				c.len.push_back((uint32_t)seq.size());
 				c.seqs.push_back(pxt_seq_t{ name, seq.size() });
@@ -587,34 +495,17 @@ extern "C" int yakamd_paths(const yakamd_ppopt_t *opt, yak_ch_t *ch, const char 
 			}
 			if (text.size() >= (size_t)1 << 22 || !more) {
 				if (!more && opt->stats_only) pxt_stats_tail(text, tot);
-				ok = fwrite(text.data(), 1, text.size(), out) == text.size() && ok;
+				ok = out.write(text) && ok;
 				text.clear();
 			}
 		}
-		if (rd.failed()) return pfail("yakamd_paths: '%s' is damaged: the inflater gave up", fn);
-	} catch (const std::bad_alloc&) { return pfail("yakamd_paths: no host memory for a chunk"); }
-	ok = fflush(out) == 0 && !ferror(out) && ok;
-	if (!to_stdout) { ok = fclose(out) == 0 && ok; closer.f = 0; }
-	if (!ok) return pfail("yakamd_paths: cannot write '%s'", to_stdout ? "-" : out_fn);
+		if (rd.failed()) return fail("yakamd_paths: '%s' is damaged: the inflater gave up", fn);
+	} catch (const std::bad_alloc&) { return fail("yakamd_paths: no host memory for a chunk"); }
+	if (!(out.finish() && ok)) return fail("yakamd_paths: cannot write '%s'", out.name);
 	if (getenv("YAKAMD_VERBOSE"))
 		fprintf(stderr, "[yak_amd] paths: index %.1f ms, hits %.1f ms, count and scan %.1f ms, emit %.1f ms, copies %.1f ms, text %.1f ms (longest probe %llu)\n", g_ms[0], g_ms[1],
 		        g_ms[2], g_ms[3], g_ms[4], g_ms[5], (u64)px->st.max_probe);
 	return 0;
 }
 
-/* the launch tally of this library: tally.cpp, compiled into it a fourth time, keeps a table of its own behind the version script; its path events
- * belong to libyak_amd.so and are not listed */
-extern "C" int yakamd_path_tally_names(const char *const **names)
-{
-	const char *const *all = 0;
-	const int n = yakamd_tally_names(&all);
-	if (names) *names = all + YKE_N;
-	return n - YKE_N;
-}
-extern "C" void yakamd_path_tally_read(uint64_t *out, int n)
-{
-	std::vector<uint64_t> all((size_t)(n > 0 ? n : 0) + YKE_N);
-	yakamd_tally_read(all.data(), (int)all.size());
-	for (int i = 0; i < n; ++i) out[i] = all[(size_t)i + YKE_N];
-}
-extern "C" void yakamd_path_tally_reset(void) { yakamd_tally_reset(); }
+LAYER_TALLY_EXPORTS(path)

@@ -5,7 +5,8 @@ import ctypes as C
 import os
 
 import yak_amd
-from yak_amd import ChT, GstatT, UgoptT
+from yak_amd import ChT, GstatT, UgoptT, _layer
+from yak_amd._layer import P
 
 WALK_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libyak_amd_walk.so")
 WALK_H_SYMBOLS = [
@@ -26,41 +27,24 @@ _lib = None
 def lib():
     """Load libyak_amd_walk.so (once), after libyak_amd.so.  Raises if it has not been built: there is no fallback to the host walk."""
     global _lib
-    if _lib is not None:
-        return _lib
-    yak_amd.lib()
-    if not os.path.exists(WALK_LIB_PATH):
-        raise RuntimeError(f"{WALK_LIB_PATH} is missing: build it with `make lib` (python __graft_entry__.py build)")
-    L = C.CDLL(WALK_LIB_PATH)
-    P = C.POINTER
-    L.yakamd_uwalk_open.restype = C.c_void_p; L.yakamd_uwalk_open.argtypes = [P(ChT), C.c_int]
-    L.yakamd_uwalk_stats.restype = C.c_int; L.yakamd_uwalk_stats.argtypes = [C.c_void_p, P(UwstatT)]
-    L.yakamd_uwalk_gstat.restype = C.c_int; L.yakamd_uwalk_gstat.argtypes = [C.c_void_p, P(GstatT)]
-    for f in (L.yakamd_uwalk_map_dev, L.yakamd_uwalk_desc_dev, L.yakamd_uwalk_bases_dev):
-        f.restype = C.c_int64; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.yakamd_uwalk_close.restype = None; L.yakamd_uwalk_close.argtypes = [C.c_void_p]
-    L.yakamd_unitigs_dev.restype = C.c_int; L.yakamd_unitigs_dev.argtypes = [P(UgoptT), P(ChT), C.c_char_p]
-    L.yakamd_uwalk_ms.restype = None; L.yakamd_uwalk_ms.argtypes = [P(C.c_double)]
-    L.yakamd_walk_last_error.restype = C.c_char_p; L.yakamd_walk_last_error.argtypes = []
-    L.yakamd_walk_tally_names.restype = C.c_int; L.yakamd_walk_tally_names.argtypes = [P(P(C.c_char_p))]
-    L.yakamd_walk_tally_read.restype = None; L.yakamd_walk_tally_read.argtypes = [P(C.c_uint64), C.c_int]
-    L.yakamd_walk_tally_reset.restype = None; L.yakamd_walk_tally_reset.argtypes = []
-    _lib = L
-    return L
+    if _lib is None:
+        dev = (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int64])
+        _lib = _layer.load(WALK_LIB_PATH, yak_amd.lib, {
+            **_layer.common("walk"),
+            "yakamd_uwalk_open": (C.c_void_p, [P(ChT), C.c_int]), "yakamd_uwalk_stats": (C.c_int, [C.c_void_p, P(UwstatT)]),
+            "yakamd_uwalk_gstat": (C.c_int, [C.c_void_p, P(GstatT)]), "yakamd_uwalk_map_dev": dev, "yakamd_uwalk_desc_dev": dev,
+            "yakamd_uwalk_bases_dev": dev, "yakamd_uwalk_close": (None, [C.c_void_p]), "yakamd_unitigs_dev": (C.c_int, [P(UgoptT), P(ChT), C.c_char_p]),
+            "yakamd_uwalk_ms": (None, [P(C.c_double)])})
+    return _lib
 
 
 def _err():
-    return (lib().yakamd_walk_last_error() or b"").decode()
+    return _layer.last_error(lib(), "walk")
 
 
 def tally():
     """{kernel instantiation: launches since the last yakamd_walk_tally_reset} of this library's own kernels"""
-    L = lib()
-    names = C.POINTER(C.c_char_p)()
-    n = L.yakamd_walk_tally_names(C.byref(names))
-    out = (C.c_uint64 * max(n, 1))()
-    L.yakamd_walk_tally_read(out, n)
-    return {names[i].decode(): int(out[i]) for i in range(n)}
+    return _layer.tally(lib(), "walk")
 
 
 class Walk:

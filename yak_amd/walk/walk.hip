@@ -2,7 +2,8 @@
  * walk.hip -- libyak_amd_walk.so: the unitigs of a count table's de Bruijn graph walked on the GPU (include/yak_amd_walk.h).
  * A layer above libyak_amd.so: it calls its public functions only (yakamd_graph_open / _stats / _nodes_dev / _close, yakamd_last_error) and owns its
  * device memory (hipMalloc / hipFree).  The per-state steps are those of uwalk_step.h, the host's share (cycles, tallies, text) that of uwalk_host.h;
- * every launch goes through YK_LAUNCH of ../csrc/tally.h into this library's own tally (yakamd_walk_tally_*).
+ * every launch goes through YK_LAUNCH of ../csrc/tally.h into this library's own tally (yakamd_walk_tally_*).  The host scaffolding and the scans are
+ * those of ../layer/layer_host.h and ../layer/layer_dev.h, which the three layers share.
  *
  *   k_uw_init          the pair (ptr, dist) of both states of every stored key from its record
  *   k_uw_jump          one doubling round from one pair buffer into the other (never in place: a 16-byte pair is not read atomically), and the
@@ -17,25 +18,15 @@
  *                      the records of the nodes on cycles compacted in listing order for the host, and the host's map entries put in place
  * All results are addressed by listing index or by j; all stores are vector stores, all tallies integer atomics whose order changes no result.
  */
-#include <hip/hip_runtime.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-#include <time.h>
-#include <new>
 #include "yak.h"
-#include "yak_amd.h"
-#include "yak_amd_walk.h"
-#include "../csrc/tally.h"
+#define LAYER_NAME "walk"
+#include "../layer/layer_host.h"
+#include "../layer/layer_dev.h"
 #include "uwalk_step.h"
 #include "uwalk_host.h"
 
 static_assert(sizeof(yakamd_gnode_t) == 32 && sizeof(uw_node_t) == 32, "a graph record is 32 bytes");
 static_assert(sizeof(yakamd_umap_t) == sizeof(uw_map_t) && sizeof(yakamd_udesc_t) == sizeof(uw_desc_t) && sizeof(uw_pair_t) == 16, "the results as declared");
-
-typedef unsigned long long u64;
-typedef ulonglong2 v2;                                            /* 16 bytes: one vector load or store */
 
 namespace {
 
@@ -52,12 +43,6 @@ __device__ inline uw_node_t ld_node(const uw_node_t *p)
 	uw_node_t r;
 	r.x = a.x; r.link[0] = a.y; r.link[1] = b.x; r.count = (uint32_t)b.y; r.edges = (uint32_t)(b.y >> 32);
 	return r;
-}
-__device__ inline u64 wave_sum(u64 v)
-{
-#pragma unroll
-	for (int o = UW_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o);
-	return v;                                                      /* lane 0 has the sum */
 }
 
 __global__ __launch_bounds__(UW_THREADS)
@@ -115,84 +100,13 @@ void k_uw_decide(const uw_pair_t *__restrict__ fin, u64 n, int k, v2 *__restrict
 	}
 }
 
-/* this thread's exclusive prefix of (a, b) within the workgroup of UW_THREADS, and the workgroup's sums */
-__device__ inline void block_scan2(u64 a, u64 b, u64 *ea, u64 *eb, u64 *ta, u64 *tb)
-{
-	__shared__ u64 s_w[2][UW_THREADS / UW_WAVE];
-	const unsigned lane = threadIdx.x & (UW_WAVE - 1), wave = threadIdx.x / UW_WAVE;
-	u64 ia = a, ib = b;
-#pragma unroll
-	for (int o = 1; o < UW_WAVE; o <<= 1) {
-		const u64 ya = __shfl_up(ia, o), yb = __shfl_up(ib, o);
-		if (lane >= (unsigned)o) { ia += ya; ib += yb; }
-	}
-	if (lane == UW_WAVE - 1) { s_w[0][wave] = ia; s_w[1][wave] = ib; }
-	__syncthreads();
-	u64 ra = ia - a, rb = ib - b, sa = 0, sb = 0;
-#pragma unroll
-	for (unsigned w = 0; w < UW_THREADS / UW_WAVE; ++w) {
-		const u64 va = s_w[0][w], vb = s_w[1][w];
-		if (w < wave) { ra += va; rb += vb; }
-		sa += va; sb += vb;
-	}
-	__syncthreads();                                               /* the next call writes s_w again */
-	*ea = ra; *eb = rb; *ta = sa; *tb = sb;
-}
-
-/* tsum[tile] = the sums of sc[tile * UW_TILE ..]; one workgroup per tile, a thread UW_ITEMS consecutive entries */
+/* the exclusive scan of a (u64, u64) array in place (../layer/layer_dev.h): tiles of UW_TILE, their sums scanned by one workgroup of UW_SCAN_THREADS */
 __global__ __launch_bounds__(UW_THREADS)
-void k_uw_tile_sum(const v2 *__restrict__ sc, u64 n, v2 *__restrict__ tsum)
-{
-	const u64 i0 = (u64)blockIdx.x * UW_TILE + (u64)threadIdx.x * UW_ITEMS;
-	u64 a = 0, b = 0, ea, eb, ta, tb;
-#pragma unroll
-	for (int i = 0; i < UW_ITEMS; ++i) if (i0 + i < n) { const v2 v = sc[i0 + i]; a += v.x; b += v.y; }
-	block_scan2(a, b, &ea, &eb, &ta, &tb);
-	if (threadIdx.x == 0) tsum[blockIdx.x] = make_ulonglong2(ta, tb);
-}
-
-/* the exclusive scan of tsum[0 .. m) in place, its sums in tsum[m]: one workgroup, each thread a contiguous slice (as k_te_scan of the library) */
+void k_uw_tile_sum(const v2 *__restrict__ sc, u64 n, v2 *__restrict__ tsum) { tile_sum<UW_THREADS, UW_ITEMS, v2, AddV2>(sc, n, tsum); }
 __global__ __launch_bounds__(UW_SCAN_THREADS)
-void k_uw_tile_scan(v2 *__restrict__ tsum, u64 m)
-{
-	__shared__ u64 s_w[2][UW_SCAN_THREADS / UW_WAVE];
-	const unsigned lane = threadIdx.x & (UW_WAVE - 1), wave = threadIdx.x / UW_WAVE;
-	const u64 per = (m + UW_SCAN_THREADS - 1) / UW_SCAN_THREADS, lo = (u64)threadIdx.x * per, hi = lo + per < m ? lo + per : m;
-	u64 a = 0, b = 0;
-	for (u64 i = lo; i < hi; ++i) { const v2 v = tsum[i]; a += v.x; b += v.y; }
-	u64 ia = a, ib = b;
-#pragma unroll
-	for (int o = 1; o < UW_WAVE; o <<= 1) {
-		const u64 ya = __shfl_up(ia, o), yb = __shfl_up(ib, o);
-		if (lane >= (unsigned)o) { ia += ya; ib += yb; }
-	}
-	if (lane == UW_WAVE - 1) { s_w[0][wave] = ia; s_w[1][wave] = ib; }
-	__syncthreads();
-	u64 ra = ia - a, rb = ib - b, sa = 0, sb = 0;
-	for (unsigned w = 0; w < UW_SCAN_THREADS / UW_WAVE; ++w) {
-		const u64 va = s_w[0][w], vb = s_w[1][w];
-		if (w < wave) { ra += va; rb += vb; }
-		sa += va; sb += vb;
-	}
-	for (u64 i = lo; i < hi; ++i) { const v2 v = tsum[i]; tsum[i] = make_ulonglong2(ra, rb); ra += v.x; rb += v.y; }
-	if (threadIdx.x == 0) tsum[m] = make_ulonglong2(sa, sb);
-}
-
-/* sc[] becomes its exclusive scan, tile by tile on top of the scanned tile sums */
+void k_uw_tile_scan(v2 *__restrict__ tsum, u64 m) { tile_scan<UW_SCAN_THREADS, v2, AddV2>(tsum, m); }
 __global__ __launch_bounds__(UW_THREADS)
-void k_uw_scan_apply(v2 *__restrict__ sc, u64 n, const v2 *__restrict__ tsum)
-{
-	const u64 i0 = (u64)blockIdx.x * UW_TILE + (u64)threadIdx.x * UW_ITEMS;
-	v2 it[UW_ITEMS];
-	u64 a = 0, b = 0, ea, eb, ta, tb;
-#pragma unroll
-	for (int i = 0; i < UW_ITEMS; ++i) { it[i] = i0 + i < n ? sc[i0 + i] : make_ulonglong2(0, 0); a += it[i].x; b += it[i].y; }
-	block_scan2(a, b, &ea, &eb, &ta, &tb);
-	const v2 base = tsum[blockIdx.x];
-	ea += base.x; eb += base.y;
-#pragma unroll
-	for (int i = 0; i < UW_ITEMS; ++i) if (i0 + i < n) { sc[i0 + i] = make_ulonglong2(ea, eb); ea += it[i].x; eb += it[i].y; }
-}
+void k_uw_scan_apply(v2 *__restrict__ sc, u64 n, const v2 *__restrict__ tsum) { scan_apply<UW_THREADS, UW_ITEMS, v2, AddV2>(sc, n, tsum); }
 
 /* the open unitigs: sc[e] = (j, off) of start node e.  A place outside the arrays (inconsistent links) is tallied, not written */
 __global__ __launch_bounds__(UW_THREADS)
@@ -260,35 +174,7 @@ void k_uw_cyc_scatter(const u64 *__restrict__ idx, const v2 *__restrict__ ent, u
 
 /* ---------------- host ---------------- */
 
-thread_local char g_err[512];
 thread_local double g_ms[6];                                       /* of this thread's last call */
-
-int wfail(const char *fmt, ...)
-{
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(g_err, sizeof g_err, fmt, ap);
-	va_end(ap);
-	fprintf(stderr, "[E::yak_amd] %s\n", g_err);
-	return -1;
-}
-#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return wfail("walk: %s -> %s", #x, hipGetErrorString(e_)); } while (0)
-
-double now_ms()
-{
-	struct timespec ts;
-	clock_gettime(CLOCK_MONOTONIC, &ts);
-	return ts.tv_sec * 1e3 + ts.tv_nsec / 1e6;
-}
-
-/* the walk's device for a call, and the caller's current device again after it */
-struct OnDevice {
-	int before = -1;
-	explicit OnDevice(int dev) { if (hipGetDevice(&before) != hipSuccess) before = -1; if (before != dev) (void)hipSetDevice(dev); else before = -1; }
-	~OnDevice() { if (before >= 0) (void)hipSetDevice(before); }
-};
-
-unsigned grid_for(u64 n) { const u64 b = (n + UW_THREADS - 1) / UW_THREADS; return (unsigned)(b < 1 ? 1 : b > 2048 ? 2048 : b); }
 
 /* the exclusive scan of sc[0 .. n) in place; tot = the sums */
 int scan_pairs(v2 *sc, u64 n, v2 *tsum, u64 tot[2])
@@ -304,19 +190,11 @@ int scan_pairs(v2 *sc, u64 n, v2 *tsum, u64 tot[2])
 
 }   // namespace
 
-/* device memory that frees itself */
-struct UwDevBuf {
-	void *p = 0;
-	~UwDevBuf() { drop(); }
-	void drop() { if (p) (void)hipFree(p); p = 0; }
-	bool get(size_t bytes) { return hipMalloc(&p, bytes < 256 ? 256 : bytes) == hipSuccess; }
-};
-
 struct yakamd_uwalk {
 	int k, dev;
 	yakamd_gstat_t gst;
 	yakamd_uwstat_t st;
-	UwDevBuf map, desc, bases;
+	DevBuf map, desc, bases;
 	std::vector<uw_desc_t> h_desc;
 };
 
@@ -352,15 +230,15 @@ int walk_run(yakamd_uwalk *w, yakamd_graph_t **gp, yak_ch_t *h, int min_cnt)
 	const char *lim = getenv("YAKAMD_WALK_MAX_BYTES");
 	const u64 limit = lim && *lim ? strtoull(lim, 0, 10) : (u64)free_b;
 	if (q.work + q.kept > limit)
-		return wfail("walk: %llu bytes of device memory are needed for %llu stored keys (%llu while it runs, %llu kept), %llu are free", q.work + q.kept, n, q.work, q.kept, limit);
+		return fail("walk: %llu bytes of device memory are needed for %llu stored keys (%llu while it runs, %llu kept), %llu are free", q.work + q.kept, n, q.work, q.kept, limit);
 	double t0 = now_ms();
 	if (n == 0) return 0;
-	UwDevBuf rec, pa, pb, idx, tsum, cnt;
+	DevBuf rec, pa, pb, idx, tsum, cnt;
 	if (!rec.get(n * 32) || !pa.get(n * 32) || !pb.get(n * 32) || !idx.get(n * 8) || !tsum.get((q.n_tile + 1) * 16) || !cnt.get((UW_MAX_ROUNDS + UWT_N) * 8)
 	    || !w->map.get(n * 16) || !w->desc.get(q.n_desc * 32) || !w->bases.get(q.n_bases))
-		return wfail("walk: no device memory for %llu bytes", q.work + q.kept);
+		return fail("walk: no device memory for %llu bytes", q.work + q.kept);
 	const double t_alloc = now_ms();
-	if (yakamd_graph_nodes_dev(g, 0, 1 << h->pre, rec.p, (int64_t)n) != (int64_t)n) { snprintf(g_err, sizeof g_err, "%s", yakamd_last_error()); return -1; }
+	if (yakamd_graph_nodes_dev(g, 0, 1 << h->pre, rec.p, (int64_t)n) != (int64_t)n) return fail_below(yakamd_last_error());
 	const double t_rec = now_ms();
 	yakamd_graph_close(g); *gp = 0;                                /* its scratch is not needed any more */
 	g_ms[1] = now_ms() - t0;
@@ -373,10 +251,10 @@ int walk_run(yakamd_uwalk *w, yakamd_graph_t **gp, yak_ch_t *h, int min_cnt)
 	HIPCK(hipMemset(d_cnt, 0, (UW_MAX_ROUNDS + UWT_N) * 8));
 	uw_pair_t *src = (uw_pair_t*)pa.p, *dst = (uw_pair_t*)pb.p;
 	const uw_node_t *d_rec = (const uw_node_t*)rec.p;
-	YK_LAUNCH(k_uw_init, dim3(grid_for(n)), dim3(UW_THREADS), 0, 0, d_rec, n, (uint32_t)min_cnt, src);
+	YK_LAUNCH(k_uw_init, dim3(grid_for(n, UW_THREADS)), dim3(UW_THREADS), 0, 0, d_rec, n, (uint32_t)min_cnt, src);
 	for (;;) {
-		if (st.rounds >= UW_MAX_ROUNDS) return wfail("walk: the ranking did not end in %d rounds", (int)UW_MAX_ROUNDS);
-		YK_LAUNCH(k_uw_jump, dim3(grid_for(2 * n)), dim3(UW_THREADS), 0, 0, (const uw_pair_t*)src, dst, 2 * n, d_cnt + st.rounds);
+		if (st.rounds >= UW_MAX_ROUNDS) return fail("walk: the ranking did not end in %d rounds", (int)UW_MAX_ROUNDS);
+		YK_LAUNCH(k_uw_jump, dim3(grid_for(2 * n, UW_THREADS)), dim3(UW_THREADS), 0, 0, (const uw_pair_t*)src, dst, 2 * n, d_cnt + st.rounds);
 		HIPCK(hipGetLastError());
 		u64 finished = 0;
 		HIPCK(hipMemcpy(&finished, d_cnt + st.rounds, 8, hipMemcpyDeviceToHost));
@@ -390,28 +268,28 @@ int walk_run(yakamd_uwalk *w, yakamd_graph_t **gp, yak_ch_t *h, int min_cnt)
 	const uw_pair_t *fin = src;
 	v2 *dec = (v2*)dst, *sc = dec + n, *d_map = (v2*)w->map.p;
 	uw_desc_t *d_desc = (uw_desc_t*)w->desc.p;
-	YK_LAUNCH(k_uw_decide, dim3(grid_for(n)), dim3(UW_THREADS), 0, 0, fin, n, k, dec, sc, d_tally);
+	YK_LAUNCH(k_uw_decide, dim3(grid_for(n, UW_THREADS)), dim3(UW_THREADS), 0, 0, fin, n, k, dec, sc, d_tally);
 	u64 tot[2], tally[UWT_N];
 	if (scan_pairs(sc, n, (v2*)tsum.p, tot)) return -1;
 	HIPCK(hipMemcpy(tally, d_tally, sizeof tally, hipMemcpyDeviceToHost));
 	st.n_open = tot[0];
 	const u64 open_len = tot[1], nc = tally[UWT_CYCLE];
 	if (tally[UWT_BAD] || st.n_open > q.n_desc || open_len > q.n_bases || nc > n)
-		return wfail("walk: the links of %llu nodes do not lead to an end node each way", tally[UWT_BAD]);
+		return fail("walk: the links of %llu nodes do not lead to an end node each way", tally[UWT_BAD]);
 	HIPCK(hipMemset(d_desc, 0, q.n_desc * 32 < 256 ? 256 : q.n_desc * 32));
-	YK_LAUNCH(k_uw_emit, dim3(grid_for(n)), dim3(UW_THREADS), 0, 0, d_rec, fin, (const v2*)dec, (const v2*)sc, n, k, d_map, d_desc, st.n_open, (char*)w->bases.p, open_len, d_tally);
+	YK_LAUNCH(k_uw_emit, dim3(grid_for(n, UW_THREADS)), dim3(UW_THREADS), 0, 0, d_rec, fin, (const v2*)dec, (const v2*)sc, n, k, d_map, d_desc, st.n_open, (char*)w->bases.p, open_len, d_tally);
 	HIPCK(hipGetLastError());
 	HIPCK(hipMemcpy(tally, d_tally, sizeof tally, hipMemcpyDeviceToHost));
-	if (tally[UWT_BAD]) return wfail("walk: %llu nodes have no place in their unitig", tally[UWT_BAD]);
+	if (tally[UWT_BAD]) return fail("walk: %llu nodes have no place in their unitig", tally[UWT_BAD]);
 
 	/* the cycles: their records alone go to the host, compacted in listing order; the pair buffer that held the final pairs is free now */
 	u64 cyc_len = 0;
 	if (nc) {
 		uw_node_t *d_out = (uw_node_t*)src;
-		YK_LAUNCH(k_uw_cyc_flag, dim3(grid_for(n)), dim3(UW_THREADS), 0, 0, (const v2*)dec, n, sc);
+		YK_LAUNCH(k_uw_cyc_flag, dim3(grid_for(n, UW_THREADS)), dim3(UW_THREADS), 0, 0, (const v2*)dec, n, sc);
 		if (scan_pairs(sc, n, (v2*)tsum.p, tot)) return -1;
-		if (tot[0] != nc) return wfail("walk: %llu nodes on cycles were tallied and %llu found", nc, tot[0]);
-		YK_LAUNCH(k_uw_cyc_gather, dim3(grid_for(n)), dim3(UW_THREADS), 0, 0, d_rec, (const v2*)dec, (const v2*)sc, n, (u64*)idx.p, d_out, nc);
+		if (tot[0] != nc) return fail("walk: %llu nodes on cycles were tallied and %llu found", nc, tot[0]);
+		YK_LAUNCH(k_uw_cyc_gather, dim3(grid_for(n, UW_THREADS)), dim3(UW_THREADS), 0, 0, d_rec, (const v2*)dec, (const v2*)sc, n, (u64*)idx.p, d_out, nc);
 		HIPCK(hipGetLastError());
 		std::vector<uw_node_t> h_rec;
 		std::vector<uint64_t> h_idx;
@@ -422,15 +300,15 @@ int walk_run(yakamd_uwalk *w, yakamd_graph_t **gp, yak_ch_t *h, int min_cnt)
 			HIPCK(hipMemcpy(h_rec.data(), d_out, nc * 32, hipMemcpyDeviceToHost));
 			HIPCK(hipMemcpy(h_idx.data(), idx.p, nc * 8, hipMemcpyDeviceToHost));
 			st.host_nodes = nc;
-			if (uwh_cycles(h_rec.data(), h_idx.data(), nc, k, st.n_open, open_len, &cy, &err) != 0) return wfail("walk: %s", err.c_str());
-		} catch (const std::bad_alloc&) { return wfail("walk: the %llu nodes on cycles do not fit the host's memory", nc); }
+			if (uwh_cycles(h_rec.data(), h_idx.data(), nc, k, st.n_open, open_len, &cy, &err) != 0) return fail("walk: %s", err.c_str());
+		} catch (const std::bad_alloc&) { return fail("walk: the %llu nodes on cycles do not fit the host's memory", nc); }
 		st.n_cycle = cy.desc.size();
 		cyc_len = cy.bases.size();
-		if (st.n_open + st.n_cycle > q.n_desc || open_len + cyc_len > q.n_bases) return wfail("walk: more cycles than the graph's tallies allow");
+		if (st.n_open + st.n_cycle > q.n_desc || open_len + cyc_len > q.n_bases) return fail("walk: more cycles than the graph's tallies allow");
 		HIPCK(hipMemcpy(d_desc + st.n_open, cy.desc.data(), st.n_cycle * 32, hipMemcpyHostToDevice));
 		HIPCK(hipMemcpy((char*)w->bases.p + open_len, cy.bases.data(), cyc_len, hipMemcpyHostToDevice));
 		HIPCK(hipMemcpy(d_out, cy.map.data(), nc * 16, hipMemcpyHostToDevice));
-		YK_LAUNCH(k_uw_cyc_scatter, dim3(grid_for(nc)), dim3(UW_THREADS), 0, 0, (const u64*)idx.p, (const v2*)d_out, nc, n, d_map);
+		YK_LAUNCH(k_uw_cyc_scatter, dim3(grid_for(nc, UW_THREADS)), dim3(UW_THREADS), 0, 0, (const u64*)idx.p, (const v2*)d_out, nc, n, d_map);
 		HIPCK(hipGetLastError());
 	}
 	HIPCK(hipDeviceSynchronize());
@@ -438,19 +316,19 @@ int walk_run(yakamd_uwalk *w, yakamd_graph_t **gp, yak_ch_t *h, int min_cnt)
 
 	/* the descriptors come out for the tallies and the text */
 	const u64 n_u = st.n_open + st.n_cycle;
-	try { w->h_desc.resize((size_t)n_u); } catch (const std::bad_alloc&) { return wfail("walk: the descriptors of %llu unitigs do not fit the host's memory", n_u); }
+	try { w->h_desc.resize((size_t)n_u); } catch (const std::bad_alloc&) { return fail("walk: the descriptors of %llu unitigs do not fit the host's memory", n_u); }
 	if (n_u) HIPCK(hipMemcpy(w->h_desc.data(), d_desc, n_u * 32, hipMemcpyDeviceToHost));
-	try { uwh_lengths(w->h_desc.data(), n_u, k, &st.sum_len, &st.max_len, &st.n50); } catch (const std::bad_alloc&) { return wfail("walk: no host memory for the lengths"); }
-	if (st.sum_len != open_len + cyc_len) return wfail("walk: the descriptors hold %llu bases, the scan %llu", (u64)st.sum_len, open_len + cyc_len);
+	try { uwh_lengths(w->h_desc.data(), n_u, k, &st.sum_len, &st.max_len, &st.n50); } catch (const std::bad_alloc&) { return fail("walk: no host memory for the lengths"); }
+	if (st.sum_len != open_len + cyc_len) return fail("walk: the descriptors hold %llu bases, the scan %llu", (u64)st.sum_len, open_len + cyc_len);
 	g_ms[4] = now_ms() - t0;
 	return 0;
 }
 
 int64_t copy_out(yakamd_uwalk_t *w, const void *src, u64 n, u64 each, void *d, int64_t cap, const char *what)
 {
-	if (!w) return wfail("%s: no walk", what);
+	if (!w) return fail("%s: no walk", what);
 	if (!d || cap < (int64_t)n) return (int64_t)n;
-	if (each > 1 && ((uintptr_t)d & 15) != 0) return wfail("%s: the entries must be 16-byte aligned", what);
+	if (each > 1 && ((uintptr_t)d & 15) != 0) return fail("%s: the entries must be 16-byte aligned", what);
 	if (n == 0) return 0;
 	OnDevice dev(w->dev);
 	HIPCK(hipMemcpy(d, src, n * each, hipMemcpyDeviceToDevice));
@@ -467,13 +345,13 @@ extern "C" yakamd_uwalk_t *yakamd_uwalk_open(yak_ch_t *h, int min_cnt)
 	for (int i = 0; i < 6; ++i) g_ms[i] = 0;
 	const double t0 = now_ms();
 	yakamd_graph_t *g = yakamd_graph_open(h, min_cnt);
-	if (!g) { snprintf(g_err, sizeof g_err, "%s", yakamd_last_error()); return 0; }      /* its message, which it has put on stderr itself */
+	if (!g) { fail_below(yakamd_last_error()); return 0; }
 	struct Graph { yakamd_graph_t *g; ~Graph() { yakamd_graph_close(g); } } G{ g };
 	yakamd_uwalk_t *w = new (std::nothrow) yakamd_uwalk_t();
-	if (!w) { wfail("walk: no memory"); return 0; }
+	if (!w) { fail("walk: no memory"); return 0; }
 	w->k = h->k; w->dev = 0;
 	memset(&w->st, 0, sizeof w->st);
-	if (yakamd_graph_stats(g, &w->gst) != 0) { snprintf(g_err, sizeof g_err, "%s", yakamd_last_error()); delete w; return 0; }
+	if (yakamd_graph_stats(g, &w->gst) != 0) { fail_below(yakamd_last_error()); delete w; return 0; }
 	g_ms[0] = now_ms() - t0;
 	if (walk_run(w, &G.g, h, min_cnt) != 0) { delete w; return 0; }
 	return w;
@@ -488,14 +366,14 @@ extern "C" void yakamd_uwalk_close(yakamd_uwalk_t *w)
 
 extern "C" int yakamd_uwalk_stats(yakamd_uwalk_t *w, yakamd_uwstat_t *st)
 {
-	if (!w || !st) return wfail("walk stats: no walk, or no place for them");
+	if (!w || !st) return fail("walk stats: no walk, or no place for them");
 	*st = w->st;
 	return 0;
 }
 
 extern "C" int yakamd_uwalk_gstat(yakamd_uwalk_t *w, yakamd_gstat_t *st)
 {
-	if (!w || !st) return wfail("walk gstat: no walk, or no place for them");
+	if (!w || !st) return fail("walk gstat: no walk, or no place for them");
 	*st = w->gst;
 	return 0;
 }
@@ -507,23 +385,22 @@ extern "C" int64_t yakamd_uwalk_bases_dev(yakamd_uwalk_t *w, void *d, int64_t ca
 /* the command: the walk, then the text from the descriptors and, for the FASTA, the bases */
 extern "C" int yakamd_unitigs_dev(const yakamd_ugopt_t *opt, yak_ch_t *ch, const char *out_fn)
 {
-	if (!opt) return wfail("yakamd_unitigs_dev: no options");
-	struct Walk { yakamd_uwalk_t *w; ~Walk() { yakamd_uwalk_close(w); } } W{ yakamd_uwalk_open(ch, opt->min_cnt) };
+	if (!opt) return fail("yakamd_unitigs_dev: no options");
+	WalkGuard W{ yakamd_uwalk_open(ch, opt->min_cnt) };
 	yakamd_uwalk_t *w = W.w;
 	if (!w) return -1;
 	const yakamd_uwstat_t &u = w->st;
 	double t0 = now_ms();
 	std::string bases;
 	if (!opt->stats_only && u.sum_len) {
-		try { bases.resize((size_t)u.sum_len); } catch (const std::bad_alloc&) { return wfail("yakamd_unitigs_dev: %llu bases do not fit the host's memory", (u64)u.sum_len); }
+		try { bases.resize((size_t)u.sum_len); } catch (const std::bad_alloc&) { return fail("yakamd_unitigs_dev: %llu bases do not fit the host's memory", (u64)u.sum_len); }
 		OnDevice dev(w->dev);
 		HIPCK(hipMemcpy(&bases[0], w->bases.p, (size_t)u.sum_len, hipMemcpyDeviceToHost));
 	}
 	g_ms[4] += now_ms() - t0; t0 = now_ms();
-	const bool to_stdout = !out_fn || strcmp(out_fn, "-") == 0;
-	FILE *out = to_stdout ? stdout : fopen(out_fn, "wb");
-	if (!out) return wfail("yakamd_unitigs_dev: cannot write '%s'", out_fn);
-	struct Closer { FILE *f; bool own; ~Closer() { if (own && f) fclose(f); } } closer{ out, !to_stdout };
+	OutFile of(out_fn);
+	FILE *out = of.f;
+	if (!out) return fail("yakamd_unitigs_dev: cannot write '%s'", of.name);
 	bool ok = true;
 	if (opt->stats_only) {
 		const yakamd_gstat_t &s = w->gst;
@@ -534,12 +411,10 @@ extern "C" int yakamd_unitigs_dev(const yakamd_ugopt_t *opt, yak_ch_t *ch, const
 				if (s.deg[l][r]) fprintf(out, "D\t%d\t%d\t%llu\n", l, r, (u64)s.deg[l][r]);
 		fputs(uwh_u_line(u.n_open, u.n_cycle, u.sum_len, u.max_len, u.n50).c_str(), out);
 	} else {
-		try { ok = uwh_fasta(w->h_desc.data(), w->h_desc.size(), bases.data(), w->k, [out](const std::string &t) { return fwrite(t.data(), 1, t.size(), out) == t.size(); }); }
-		catch (const std::bad_alloc&) { return wfail("yakamd_unitigs_dev: no host memory for the text"); }
+		try { ok = uwh_fasta(w->h_desc.data(), w->h_desc.size(), bases.data(), w->k, [&of](const std::string &t) { return of.write(t); }); }
+		catch (const std::bad_alloc&) { return fail("yakamd_unitigs_dev: no host memory for the text"); }
 	}
-	ok = fflush(out) == 0 && !ferror(out) && ok;
-	if (!to_stdout) { ok = fclose(out) == 0 && ok; closer.f = 0; }
-	if (!ok) return wfail("yakamd_unitigs_dev: cannot write '%s'", to_stdout ? "-" : out_fn);
+	if (!(of.finish() && ok)) return fail("yakamd_unitigs_dev: cannot write '%s'", of.name);
 	g_ms[5] = now_ms() - t0;
 	if (getenv("YAKAMD_VERBOSE"))
 		fprintf(stderr, "[yak_amd] unitigs -g: graph %.1f ms, records %.1f ms, %llu rounds %.1f ms, numbering and bases %.1f ms, copies out %.1f ms, text %.1f ms\n",
@@ -547,19 +422,4 @@ extern "C" int yakamd_unitigs_dev(const yakamd_ugopt_t *opt, yak_ch_t *ch, const
 	return 0;
 }
 
-/* the launch tally of this library: tally.cpp, compiled into it a second time, keeps a table of its own behind the version script; its path
- * events belong to libyak_amd.so and are not listed */
-extern "C" int yakamd_walk_tally_names(const char *const **names)
-{
-	const char *const *all = 0;
-	const int n = yakamd_tally_names(&all);
-	if (names) *names = all + YKE_N;
-	return n - YKE_N;
-}
-extern "C" void yakamd_walk_tally_read(uint64_t *out, int n)
-{
-	std::vector<uint64_t> all((size_t)(n > 0 ? n : 0) + YKE_N);
-	yakamd_tally_read(all.data(), (int)all.size());
-	for (int i = 0; i < n; ++i) out[i] = all[(size_t)i + YKE_N];
-}
-extern "C" void yakamd_walk_tally_reset(void) { yakamd_tally_reset(); }
+LAYER_TALLY_EXPORTS(walk)
