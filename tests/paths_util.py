@@ -116,9 +116,9 @@ EVERY_INSERT_PATH = {
     # count_by_ranges: xn[1] (list too small) -> the cross sweep
     "range_count_cross_sweep": E([RNG, RNGX], ["k_img_count_own*"], rng_sweeps=">0"),
     "range_count_short_list": E([RNG, RNGX], ["k_img_count_own*"], rng_sweeps=">0"),
-    # consume_records: all three refuse -> !lds_done, hash_only
+    # consume_records: all three refuse -> !lds_done, YK_FMT_HASH
     "count_with_device_atomics": E(["k_img_count_h"], ["k_img_count_own*", "k_img_count_lds*", "k_img_count_rng*", "k_hpart2*"]),
-    # count_lds_bytes > 0 -> yk_launch_img_count_lds, hash_only
+    # count_lds_bytes > 0 -> yk_launch_img_count_lds, YK_FMT_HASH
     "count_lds_rank_kernel": E(["k_img_count_lds<1>"], ["k_img_count_own*", "k_img_count_rng*", "k_img_count_h", "k_img_count_lds<2>"]),
     # count_own_plan: the LDS budget leaves 32-slot ranges (THIN_INPUT: sub-tables of 1024 / 2048 slots; a whole table of up to ~250 keys is cheaper
     # than any range of it, e + e / 8 + 192 keys of room); the list holds every boundary-crossing instance -> count_own's k_img_count_h over it
@@ -131,13 +131,13 @@ EVERY_INSERT_PATH = {
     "three_tier_lds_kernels_crowded": E(["k_lds_count_ovf", WC8_7], ["k_lc2*"], lc2_passed_on=">0"),
     # a grid size only (yk_launch_lc2: wgs): the same instances as without the switch
     "lc2_three_persistent_workgroups": E([LC2_NOFILTER, LC2_FILTER] + DEFAULT_PASS, ["k_lc2<false,false,false,true,false,10>"]),
-    # feed_image: ytag stays 0, hash_only 1: the same kernels as with the tag (an argument of k_xpart_wcs<false> and k_img_count_own)
+    # feed_image: the consumed format stays YK_FMT_HASH, no range tag: the same kernels as with the tag (an argument of k_xpart_wcs<false> and k_img_count_own)
     "pass2_plain_hashes": E(["k_xpart_wcs<false>", OWN_H], [OWN_HX, "k_xpart<2>", "k_xpart_wc<2>"], own_sweeps="==0"),
     "pass2_plain_hashes_cross_sweep": E([OWN_H, OWN_HX], [], own_sweeps=">0"),
     # r2_steps: k_r2_dsmall takes YAKAMD_R2_SMALL_F; only a streaming replay launches it (YAKAMD_R2_SMALL_BITS = 5 makes the 1024-slot sub-tables large)
     "replay_prefix_16": E(["k_r2_dsmall", "k_r2_double<5,false,1>", "k_r2_place"], [], r2_used=">0", r2_refused="==0"),
     "replay_prefix_1024": E(["k_r2_dsmall", "k_r2_double<5,false,1>", "k_r2_place"], [], r2_used=">0", r2_refused="==0"),
-    # feed_image: fmt = 0 -> {hash, position} records; yk_launch_part2's third branch; k_lc2 with R8 = false
+    # feed_image: kept = YK_FMT_POS -> {hash, position} records; yk_launch_part2's third branch; k_lc2 with R8 = false
     "rec16_records": E(["k_xpart_wc<1>", P2_PLAIN, "k_lc2<false,false,false,false,false,11>", "k_lc2<true,false,false,false,true,10>"], ["k_xpart_wcs<true*", WC8_7, WC8_8, WC8_T, LC2_NOFILTER, LC2_FILTER]),
     # slice_plan: rec8_out = 0 -> yk_launch_part2's second branch (tagged in, {hash, rank} out), which wants s2 >= 4 (YAKAMD_S2_BITS = 6)
     "tagged_in_rec16_out": E([WC8_T, "k_lc2<false,false,false,false,false,11>", "k_lc2<true,false,false,false,true,10>"], [WC8_7, WC8_8, WC8_R, LC2_NOFILTER, LC2_FILTER]),
@@ -265,7 +265,7 @@ SECOND_PASS_RETAINED = {
     "subbucket_records_many_batches": E([LC2_NOSTAGE_W6, "k_cnt2_apply"], ["k_cnt2<*", LC2_FILTER], pass2_fused=">0", early_slices="==0"),
     # yk_launch_cnt2 (YAKAMD_CNT2_FUSED = 0: slice_count allocates no lo_c2, yakamd_count_retained's second branch): n_keys / n_sb <= small_max
     "subbucket_records_3_workgroups": E(["k_cnt2<512,320>", "k_cnt2_apply"], ["k_cnt2<2048,1280>"], pass2_recount=">0", pass2_fused="==0"),
-    # slice_retain: YAKAMD_RETAIN2 = 0 -> the level-1 records; yakamd_count_retained's last branch (consume_records, hash_only)
+    # slice_retain: YAKAMD_RETAIN2 = 0 -> the level-1 records; yakamd_count_retained's last branch (consume_records, YK_FMT_TAGGED)
     "prefix_records": E([LC2_FILTER, OWN_H], ["k_cnt2*", LC2_NOSTAGE_W6], pass2_prefix=">0", pass2_none="==0"),
     "prefix_records_many_batches": E([LC2_FILTER, OWN_H], ["k_cnt2*", LC2_NOSTAGE_W6], pass2_prefix=">0", pass2_none="==0"),
     # slice_plan: budget 0 -> nothing kept; yakamd_count_retained returns 1 and the test feeds the input
@@ -308,12 +308,12 @@ SUB_BUCKETS_PASSED_ON = {"": E([LC2_NOSTAGE_W6, "k_lds_count_ovf", "k_cnt2_apply
 # ::test_seg_sort_pass_of_long_segments (test_gpu_parity.py): slice_sort's sort_big = n_sel / (phi - plo) >= 30000
 LONG_SEGMENTS = {"": E([SORT1024], [SORT256, "k_ts_rank"], rank_refused="==0")}
 
-# ---- test_gpu_parity.py::test_count_pass_over_hashed_records ----  consume_records with hash_only = 0: the W = 2 / MODE 2 instances
+# ---- test_gpu_parity.py::test_count_pass_over_hashed_records ----  consume_records with YK_FMT_POS: the W = 2 / MODE 2 instances
 HASHED_RECORDS = {
-    # count_own and count_lds_bytes refuse, count_by_ranges wants hashes alone -> !lds_done, !hash_only
+    # count_own and count_lds_bytes refuse, count_by_ranges wants hashes alone -> !lds_done, YK_FMT_POS
     "device_atomics": E(["k_rpart<0>", "k_rpart<1>", "k_img_count"], ["k_img_count_own*", "k_img_count_lds*", "k_img_count_rng*", "k_img_count_h"]),
     "lds_rank_kernel": E(["k_img_count_lds<2>"], ["k_img_count_own*", "k_img_count_lds<1>", "k_img_count", "k_img_count_h"]),
-    # yk_launch_img_count_own: !hash_only -> W = 2; the crossing instances of the 32-slot ranges go through the list (k_img_count_h)
+    # yk_launch_img_count_own: YK_FMT_POS -> W = 2; the crossing instances of the 32-slot ranges go through the list (k_img_count_h)
     "key_owning_ranges": E(["k_img_count_own<2,0>", "k_img_count_h"], ["k_img_count_own<2,1>", "k_img_count_own<1,*", "k_img_count_lds*"], own_sweeps="==0"),
     "key_owning_ranges_cross_sweep": E(["k_img_count_own<2,0>", "k_img_count_own<2,1>"], ["k_img_count_own<1,*", "k_img_count_lds*"], own_sweeps=">0"),
 }

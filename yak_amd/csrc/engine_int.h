@@ -62,8 +62,8 @@ struct HostFree { void operator()(void *p) const { (void)hipHostFree(p); } };
 struct CFree { void operator()(void *p) const { free(p); } };
 struct yak_ht_t;
 
-/* fast path: a level-1 partitioned batch kept until the slice is counted.  d_rec views the records: the batch's own buffer, or the caller's */
-struct Kept { DevBuf<Rec> own; Rec *d_rec = 0; u64 n = 0; u64 t0 = 0, span = 0; std::vector<u64> bstart; int fmt = 0; };   /* fmt 1: tagged 8-byte records (yk_device.h YK_R8_*) */
+/* fast path: a level-1 partitioned batch kept until the slice is counted.  d_rec views the records, YK_FMT_POS or YK_FMT_TAGGED: the batch's own buffer, or the caller's */
+struct Kept { DevBuf<Rec> own; const void *d_rec = 0; RecFmt fmt = YK_FMT_POS; u64 n = 0; u64 t0 = 0, span = 0; std::vector<u64> bstart; };
 
 /* what a pass holds and pass_free gives back */
 struct PassBufs {
@@ -223,10 +223,10 @@ int bloom_materialise(yakamd_ctx *c);                       /* give a never-writ
 int delta_ensure(yakamd_ctx *c);                            /* the per-slot pending increments exist from here to the end of the pass */
 void retained_drop(yakamd_ctx *c);
 void pass_free(yakamd_ctx *c);
-/* engine_pass.cpp: records [0, n_rec) of d_rec (times = t0 + position, all within [batch_lo, batch_hi)) -> table */
-int consume_records(yakamd_ctx *c, const Rec *d_rec, int64_t n_rec, u64 t0, u64 batch_lo, u64 batch_hi, const u64 *d_bstart = 0, int hash_only = 0, int ytag = 0);
-/* engine_slice.cpp: the exclusive-ownership path of a create pass */
-int fast_admit(yakamd_ctx *c, u64 t, u64 n_pos, u64 n_cap, Rec **out, Rec *borrowed = 0, int fmt = 0);
+/* engine_pass.cpp: records [0, n_rec) of d_rec (times = t0 + position, all within [batch_lo, batch_hi)) -> table.  A create pass takes YK_FMT_POS alone */
+int consume_records(yakamd_ctx *c, const void *d_rec, RecFmt fmt, int64_t n_rec, u64 t0, u64 batch_lo, u64 batch_hi, const u64 *d_bstart = 0);
+/* engine_slice.cpp: the exclusive-ownership path of a create pass.  fast_admit: *out = the admitted batch's own buffer (0 when the records are `borrowed`) */
+int fast_admit(yakamd_ctx *c, RecFmt fmt, u64 t, u64 n_pos, u64 n_cap, void **out, const void *borrowed = 0);
 int fast_keep(yakamd_ctx *c, u64 n_rec);
 int fast_abandon(yakamd_ctx *c);
 int fast_finish(yakamd_ctx *c, bool last = false);

@@ -145,7 +145,7 @@ static size_t count_lds_bytes(yakamd_ctx *c)
 /* count-existing pass, records = 8-byte hashes grouped by prefix (d_bstart), tables beyond the LDS
  * kernel: level-2 partition by home-slot range (k_hpart2) + one workgroup per range (k_img_count_rng).
  * Returns 0 done, -1 error, 1 not applicable (caller falls back to the device-atomics kernel). */
-static int count_by_ranges(yakamd_ctx *c, const Rec *d_rec, int64_t n_rec, const u64 *d_bstart)
+static int count_by_ranges(yakamd_ctx *c, const void *d_hash, int64_t n_rec, const u64 *d_bstart)
 {
 	const int P = c->P;
 	u32 bmax = 0;
@@ -157,7 +157,7 @@ static int count_by_ranges(yakamd_ctx *c, const Rec *d_rec, int64_t n_rec, const
 	HIPCK(hipMemcpyAsync(bst.data(), d_bstart, (NB + 1) * 8, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
 	ChunkTable t;
-	chunk_runs(t, d_rec, 8, bst.data(), P, (u64)yk_hpart2_chunk());
+	chunk_runs(t, d_hash, yk_rec_bytes(YK_FMT_HASH), bst.data(), P, (u64)yk_hpart2_chunk());
 	std::vector<u64> bbase(P + 1, 0);
 	for (int p = 0; p < P; ++p) bbase[p + 1] = bbase[p] + (bst[p + 1] - bst[p]);
 	DevBuf<u64> d_bbase, d_sbstart, d_h2, d_list; DevBuf<u32> d_rows2, d_ln;
@@ -212,12 +212,13 @@ static int count_own_plan(yakamd_ctx *c, int *rng_log_out, int *rb_out, u32 *kma
 	return 0;
 }
 
-/* ytag: the records are k_xpart_wcs<false>'s with the top bits of the home-slot product in place of the sub-table's own bits */
-static int count_own(yakamd_ctx *c, const Rec *d_rec, const u64 *d_bstart, int hash_only, int ytag)
+/* records that only k_img_count_own reads: the range-tagged hashes the extraction made for it, the tagged level-1 records of the pass before */
+static bool own_count_only(RecFmt fmt) { return fmt == YK_FMT_HASH_RNG || fmt == YK_FMT_TAGGED; }
+static int count_own(yakamd_ctx *c, const void *d_rec, RecFmt fmt, const u64 *d_bstart)
 {
 	int rng_log, rb; u32 kmax;
 	const int pl = count_own_plan(c, &rng_log, &rb, &kmax);
-	if (pl) return ytag ? fail("the table changed between the extraction and the count of a pass") : 1;
+	if (pl) return own_count_only(fmt) ? fail("the table changed between the extraction and the count of a pass") : 1;
 	if (rb < 0) return 0;
 	DevBuf<u32> d_ln; DevBuf<u64> d_list;
 	const u32 list_cap = (u32)std::min<int64_t>(env_i64("YAKAMD_XLIST_CAP", 1 << 22), 1 << 22);   /* the knob is for tests */
@@ -226,12 +227,12 @@ static int count_own(yakamd_ctx *c, const Rec *d_rec, const u64 *d_bstart, int h
 	const ImgView img = img_view(c);
 	const size_t lds = yk_count_own_lds(1u << rng_log, kmax);
 	if (hipMemsetAsync(d_ln, 0, 8, c->st) != hipSuccess) r = fail("memset");
-	if (!r && yk_launch_img_count_own(d_rec, hash_only, 0, ytag, d_bstart, img, c->plo, c->phi, rb, rng_log, kmax, lds, d_list, d_ln, list_cap, c->st)) r = fail("key-owning count kernel could not be configured");
+	if (!r && yk_launch_img_count_own(d_rec, fmt, 0, d_bstart, img, c->plo, c->phi, rb, rng_log, kmax, lds, d_list, d_ln, list_cap, c->st)) r = fail("key-owning count kernel could not be configured");
 	u32 xn[2] = { 0, 0 };
 	if (!r && (hipMemcpyAsync(xn, d_ln, 8, hipMemcpyDeviceToHost, c->st) != hipSuccess || hipStreamSynchronize(c->st) != hipSuccess)) r = fail("key-owning count kernel failed: %s", hipGetErrorString(hipGetLastError()));
 	if (!r) {
 		if (xn[1]) yk_event(YKE_OWN_SWEEPS);
-		if (xn[1]) yk_launch_img_count_own(d_rec, hash_only, 1, ytag, d_bstart, img, c->plo, c->phi, rb, rng_log, kmax, lds, d_list, d_ln, list_cap, c->st);   /* list too small: second sweep */
+		if (xn[1]) yk_launch_img_count_own(d_rec, fmt, 1, d_bstart, img, c->plo, c->phi, rb, rng_log, kmax, lds, d_list, d_ln, list_cap, c->st);   /* list too small: second sweep */
 		else if (xn[0]) yk_launch_img_count_h(d_list, (int64_t)xn[0], img, c->st);
 		if (env_i64("YAKAMD_VERBOSE", 0)) fprintf(stderr, "[yak_amd] key-owning count: 2^%d slots per range (up to 2^%d ranges per sub-table), %u keys of LDS room, %zu B of LDS, %u boundary-crossing instances%s\n",
 		                                          rng_log, rb, kmax, lds, xn[0], xn[1] ? " (list overflow: second sweep)" : "");
@@ -240,7 +241,7 @@ static int count_own(yakamd_ctx *c, const Rec *d_rec, const u64 *d_bstart, int h
 	return r;
 }
 
-int consume_records(yakamd_ctx *c, const Rec *d_rec, int64_t n_rec, u64 t0, u64 batch_lo, u64 batch_hi, const u64 *d_bstart, int hash_only, int ytag)
+int consume_records(yakamd_ctx *c, const void *d_rec, RecFmt fmt, int64_t n_rec, u64 t0, u64 batch_lo, u64 batch_hi, const u64 *d_bstart)
 {
 	if (n_rec <= 0) return 0;
 	ImgView img = img_view(c);
@@ -253,14 +254,14 @@ int consume_records(yakamd_ctx *c, const Rec *d_rec, int64_t n_rec, u64 t0, u64 
 		/* records grouped by sub-table and every sub-table small enough for LDS rank counters:
 		 * exclusive-ownership counting, no global atomics */
 		if (d_bstart) {
-			const int r = count_own(c, d_rec, d_bstart, hash_only, ytag);
-			if (r <= 0 || ytag) {
+			const int r = count_own(c, d_rec, fmt, d_bstart);
+			if (r <= 0 || own_count_only(fmt)) {
 				insert_ms(c, tm);
 				return r;
 			}
 		}
 		const size_t lds = d_bstart ? count_lds_bytes(c) : 0;
-		if (!lds && d_bstart && hash_only && c->nb_bits == c->pre && env_i64("YAKAMD_COUNT_RNG", 1) != 0) {
+		if (!lds && d_bstart && fmt == YK_FMT_HASH && c->nb_bits == c->pre && env_i64("YAKAMD_COUNT_RNG", 1) != 0) {
 			/* sub-tables too large for one workgroup's LDS: split each one's hashes by home-slot range first */
 			const int r = count_by_ranges(c, d_rec, n_rec, d_bstart);
 			if (r <= 0) {                                        /* done (0) or failed (-1); 1 = not applicable */
@@ -273,15 +274,16 @@ int consume_records(yakamd_ctx *c, const Rec *d_rec, int64_t n_rec, u64 t0, u64 
 			for (int p = c->plo; p < c->phi; ++p) ck_stride = std::max(ck_stride, c->h_count[p]);
 			if (d_ck.alloc((size_t)(c->phi - c->plo) * ck_stride)) return -1;
 		}
-		const bool lds_done = lds && yk_launch_img_count_lds(d_rec, hash_only, d_bstart, img, c->plo, c->phi, lds, d_ck, ck_stride, c->st) == 0;
+		const bool lds_done = lds && yk_launch_img_count_lds(d_rec, fmt, d_bstart, img, c->plo, c->phi, lds, d_ck, ck_stride, c->st) == 0;
 		if (d_ck) { HIPCK(hipStreamSynchronize(c->st)); d_ck.reset(); }
 		if (!lds_done) {
-			if (hash_only) yk_launch_img_count_h((const u64*)d_rec, n_rec, img, c->st);
-			else yk_launch_img_count(d_rec, n_rec, img, c->st);
+			if (fmt == YK_FMT_HASH) yk_launch_img_count_h((const u64*)d_rec, n_rec, img, c->st);
+			else yk_launch_img_count((const Rec*)d_rec, n_rec, img, c->st);
 		}
 		insert_ms(c, tm);
 		return 0;
 	}
+	const Rec *rec = (const Rec*)d_rec;                        /* a create pass: {hash, position} records */
 	const int img_nonempty = c->img_keys_total > 0;
 	if (img_nonempty) { if (delta_ensure(c)) return -1; c->delta_dirty = true; img = img_view(c); }   /* the view above was taken before the delta array existed: k_acc_insert adds to img.delta */
 	if (c->bloom_mode && bloom_materialise(c)) return -1;
@@ -289,7 +291,7 @@ int consume_records(yakamd_ctx *c, const Rec *d_rec, int64_t n_rec, u64 t0, u64 
 	u64 h_cnt[YKC_N];
 	{
 		EvTimer tm(c->st);
-		yk_launch_acc_insert(d_rec, n_rec, t0, c->pass.acc, img, img_nonempty, c->bloom_mode,
+		yk_launch_acc_insert(rec, n_rec, t0, c->pass.acc, img, img_nonempty, c->bloom_mode,
 		                     c->bloom_mode ? c->pass.newlist : 0, c->d_counters, c->st);
 		insert_ms(c, tm);
 	}
@@ -299,7 +301,7 @@ int consume_records(yakamd_ctx *c, const Rec *d_rec, int64_t n_rec, u64 t0, u64 
 	c->pass.acc_count += n_new;
 	HIPCK(hipMemsetAsync(c->d_counters + YKC_NEW, 0, 8, c->st));
 	if (c->bloom_mode && bloom_phases(c, n_new)) return -1;
-	return lastput_phase(c, d_rec, n_rec, t0, batch_lo, batch_hi, img_nonempty);
+	return lastput_phase(c, rec, n_rec, t0, batch_lo, batch_hi, img_nonempty);
 }
 
 /* a base image on the device (ASCII, or packed with d_valid) into the open pass, a batch at a time */
@@ -322,33 +324,33 @@ static int feed_image(yak_ch_t *h, const void *d_bases, const u32 *d_valid, int6
 	}
 	int64_t batch = env_i64("YAKAMD_BATCH", (int64_t)1 << 31);
 	batch = std::min<int64_t>((int64_t)1 << 31, std::max<int64_t>(4096, batch & ~(int64_t)4095));   /* run starts are 31-bit (tagged records: bit 31 is the toggle) */
-	int hash_only = !c->create_new;                        /* counting existing keys needs no stream positions */
-	int ytag = 0;
-	if (hash_only && c->k < 32 && c->nb_bits <= 10 && env_i64("YAKAMD_YTAG", 1) != 0) {   /* the key-owning count will run: its range test is prepared by the extraction */
+	RecFmt consumed = c->create_new ? YK_FMT_POS : YK_FMT_HASH;   /* of a batch that is consumed at once: counting existing keys needs no stream positions */
+	if (!c->create_new && c->k < 32 && c->nb_bits <= 10 && env_i64("YAKAMD_YTAG", 1) != 0) {   /* the key-owning count will run: its range test is prepared by the extraction */
 		int rl, rb; u32 km;
-		if (count_own_plan(c, &rl, &rb, &km) == 0 && rb >= 0) { ytag = 1; hash_only = 3; }
+		if (count_own_plan(c, &rl, &rb, &km) == 0 && rb >= 0) consumed = YK_FMT_HASH_RNG;
 	}
+	/* a kept batch: tagged 8-byte records (half the partition traffic) when the hash leaves room for the tag, (hash >> pre) < 2^52 */
+	const RecFmt kept = yk_tagged_fits(c->k, c->pre) && c->nb_bits == c->pre && !c->or_mode ? YK_FMT_TAGGED : YK_FMT_POS;
 	const int64_t bmax = std::min(batch, (n_bytes + 4095) & ~(int64_t)4095);
 	if ((!c->fast && c->pass.rec.reserve((size_t)bmax)) || part_reserve(c, yk_xpart_blocks(bmax))) return -1;   /* the fast path keeps every batch in a buffer of its own */
 	for (int64_t pos = 0; pos < n_bytes; pos += batch) {
 		const int64_t end = std::min(n_bytes, pos + batch);
 		u64 n_rec = 0;
-		Rec *out = c->pass.rec;
+		void *out = c->pass.rec.get();
 		if (c->fast) {                                   /* the batch stays resident until pass_end */
-			/* tagged 8-byte records (half the partition traffic) when the hash leaves room for the tag: (hash >> pre) < 2^52 */
-			const int fmt = c->k < 32 && 2 * c->k - c->pre <= 64 - YK_R8_TAG_BITS && c->nb_bits == c->pre && c->nb_bits <= 10 && !c->or_mode && env_i64("YAKAMD_REC8", 1) != 0;
-			if (fast_admit(c, t0 + (u64)pos, (u64)(end - pos), (u64)(end - pos), &out, 0, fmt)) return -1;
-			if (!c->fast) { if (c->pass.rec.reserve((size_t)bmax)) return -1; out = c->pass.rec; }   /* the pass has just left the fast path */
+			if (fast_admit(c, kept, t0 + (u64)pos, (u64)(end - pos), (u64)(end - pos), &out)) return -1;
+			if (!c->fast) { if (c->pass.rec.reserve((size_t)bmax)) return -1; out = c->pass.rec.get(); }   /* the pass has just left the fast path */
 		}
+		const RecFmt fmt = c->fast ? kept : consumed;
 		{
 			EvTimer tm(c->st);
 			yk_launch_xpart((const uint8_t*)d_bases, pos, end, pos, c->k, c->pre, c->plo, c->phi, c->nb_bits,
-			                c->rows, c->d_partial, c->d_bstart, out, (c->fast && c->pass.kept.back().fmt) ? 2 : hash_only, c->st, d_valid);
+			                c->rows, c->d_partial, c->d_bstart, out, fmt, c->st, d_valid);
 			HIPCK(hipMemcpyAsync(&n_rec, c->d_bstart + ((size_t)1 << c->nb_bits), 8, hipMemcpyDeviceToHost, c->st));
 			c->st_cur.ms_extract += tm.stop();
 		}
 		if (c->fast) { if (fast_keep(c, n_rec)) return -1; if (t0 + (u64)end > c->t_end) c->t_end = t0 + (u64)end; continue; }
-		if (consume_records(c, out, (int64_t)n_rec, t0 + (u64)pos, t0 + (u64)pos, t0 + (u64)end, c->d_bstart, hash_only ? 1 : 0, ytag)) return -1;
+		if (consume_records(c, out, fmt, (int64_t)n_rec, t0 + (u64)pos, t0 + (u64)pos, t0 + (u64)end, c->d_bstart)) return -1;
 	}
 	return 0;
 }
@@ -430,17 +432,17 @@ extern "C" int yakamd_feed_hashed_dev(yak_ch_t *h, const void *d_hash, const voi
 	if (n <= 0) return 0;
 	if (c->pass.rec.reserve((size_t)n) || part_reserve(c, yk_rpart_blocks(n))) return -1;
 	u64 n_rec = 0;
-	Rec *out = c->pass.rec;
-	if (c->fast && fast_admit(c, t0, t_span, (u64)n, &out)) return -1;
+	void *out = c->pass.rec.get();
+	if (c->fast && fast_admit(c, YK_FMT_POS, t0, t_span, (u64)n, &out)) return -1;
 	yk_launch_rpart((const u64*)d_hash, (const u32*)d_t, n, c->pre, c->plo, c->phi, c->nb_bits,
-	                c->rows, c->d_partial, c->d_bstart, out, c->st);
+	                c->rows, c->d_partial, c->d_bstart, (Rec*)out, c->st);
 	HIPCK(hipMemcpyAsync(&n_rec, c->d_bstart + ((size_t)1 << c->nb_bits), 8, hipMemcpyDeviceToHost, c->st));
 	HIPCK(hipStreamSynchronize(c->st));
 	if (c->fast) { if (t0 + t_span > c->t_end) c->t_end = t0 + t_span; return fast_keep(c, n_rec); }
-	return consume_records(c, out, (int64_t)n_rec, t0, t0, t0 + t_span, c->d_bstart);
+	return consume_records(c, out, YK_FMT_POS, (int64_t)n_rec, t0, t0, t0 + t_span, c->d_bstart);
 }
 
-static int64_t partition_dev(int k, int pre, const void *d_bases, int64_t n_bytes, void *d_out, uint64_t *h_bstart, int hash_only)
+static int64_t partition_dev(int k, int pre, const void *d_bases, int64_t n_bytes, void *d_out, RecFmt fmt, uint64_t *h_bstart)
 {
 	if (k < 1 || k > 63 || pre < 3 || pre > 13) { fail("partition: unsupported k / pre"); return -1; }
 	if (((uintptr_t)d_bases & 15) != 0 || n_bytes >= ((int64_t)1 << 32)) { fail("partition: base image must be 16-byte aligned and < 4 GiB"); return -1; }
@@ -454,7 +456,7 @@ static int64_t partition_dev(int k, int pre, const void *d_bases, int64_t n_byte
 	int dev = 0;
 	(void)hipGetDevice(&dev);
 	hipStream_t ps = yk_stream_get(dev);
-	yk_launch_xpart((const uint8_t*)d_bases, 0, n_bytes, 0, k, pre, 0, 1 << pre, pre, d_rows, d_partial, d_bstart, (Rec*)d_out, hash_only, ps);
+	yk_launch_xpart((const uint8_t*)d_bases, 0, n_bytes, 0, k, pre, 0, 1 << pre, pre, d_rows, d_partial, d_bstart, d_out, fmt, ps);
 	hipError_t e = hipMemcpyAsync(h_bstart, d_bstart, (NB + 1) * 8, hipMemcpyDeviceToHost, ps);
 	if (e == hipSuccess) e = hipStreamSynchronize(ps);
 	yk_stream_put(dev, ps);
@@ -464,25 +466,25 @@ static int64_t partition_dev(int k, int pre, const void *d_bases, int64_t n_byte
 
 extern "C" int64_t yakamd_partition_dev(int k, int pre, const void *d_bases, int64_t n_bytes, void *d_rec_out, uint64_t *h_bstart)
 {
-	return partition_dev(k, pre, d_bases, n_bytes, d_rec_out, h_bstart, 0);
+	return partition_dev(k, pre, d_bases, n_bytes, d_rec_out, YK_FMT_POS, h_bstart);
 }
 
 /* the same partition as 8-byte tagged records (yk_device.h YK_R8_*: half the exchange payload of a sharded pass); for
  * yakamd_feed_partitioned_tagged_dev on the owner.  yakamd_tagged_ok says whether k / pre allow the format */
-extern "C" int yakamd_tagged_ok(int k, int pre) { return k >= 1 && k < 32 && 2 * k - pre <= 64 - YK_R8_TAG_BITS && pre >= 3 && pre <= 10 && env_i64("YAKAMD_REC8", 1) != 0; }
+extern "C" int yakamd_tagged_ok(int k, int pre) { return k >= 1 && pre >= 3 && yk_tagged_fits(k, pre); }   /* (k and pre as partition_dev takes them) */
 extern "C" int64_t yakamd_partition_tagged_dev(int k, int pre, const void *d_bases, int64_t n_bytes, void *d_rec8_out, uint64_t *h_bstart)
 {
 	if (!yakamd_tagged_ok(k, pre)) { fail("partition: tagged records need k < 32, 2k - pre <= 52, pre <= 10"); return -1; }
 	if (n_bytes > ((int64_t)1 << 31)) { fail("partition: at most 2^31 stream positions per call with tagged records (31-bit run starts)"); return -1; }
-	return partition_dev(k, pre, d_bases, n_bytes, d_rec8_out, h_bstart, 2);
+	return partition_dev(k, pre, d_bases, n_bytes, d_rec8_out, YK_FMT_TAGGED, h_bstart);
 }
 
 extern "C" int64_t yakamd_partition_hashes_dev(int k, int pre, const void *d_bases, int64_t n_bytes, void *d_hash_out, uint64_t *h_bstart)
 {
-	return partition_dev(k, pre, d_bases, n_bytes, d_hash_out, h_bstart, 1);
+	return partition_dev(k, pre, d_bases, n_bytes, d_hash_out, YK_FMT_HASH, h_bstart);
 }
 
-static int feed_partitioned(yak_ch_t *h, const void *d_rec, int64_t n, const uint64_t *h_bstart, uint64_t t0, uint64_t t_span, bool borrow, int fmt = 0)
+static int feed_partitioned(yak_ch_t *h, const void *d_rec, RecFmt fmt, int64_t n, const uint64_t *h_bstart, uint64_t t0, uint64_t t_span, bool borrow)
 {
 	yakamd_ctx *c = ctx_of(h);
 	if (!c || !c->in_pass) return fail("feed outside a pass");
@@ -491,11 +493,11 @@ static int feed_partitioned(yak_ch_t *h, const void *d_rec, int64_t n, const uin
 	if (n <= 0) return 0;
 	const size_t NB = (size_t)1 << c->nb_bits;
 	if (c->fast) {
-		Rec *out = 0;
-		if (fmt && !(yakamd_tagged_ok(c->k, c->pre) && !c->or_mode)) return fail("tagged records do not fit this table (k, pre)");
-		if (fast_admit(c, t0, t_span, (u64)n, &out, borrow ? (Rec*)d_rec : 0, fmt)) return -1;
+		void *out = 0;
+		if (fmt == YK_FMT_TAGGED && !(yakamd_tagged_ok(c->k, c->pre) && !c->or_mode)) return fail("tagged records do not fit this table (k, pre)");
+		if (fast_admit(c, fmt, t0, t_span, (u64)n, &out, borrow ? d_rec : 0)) return -1;
 		if (c->fast) {                                       /* admitted: already grouped by prefix; keep a private copy unless lent */
-			if (!borrow) HIPCK(hipMemcpyAsync(out, d_rec, (size_t)n * (fmt ? 8 : sizeof(Rec)), hipMemcpyDeviceToDevice, c->st));
+			if (!borrow) HIPCK(hipMemcpyAsync(out, d_rec, (size_t)n * yk_rec_bytes(fmt), hipMemcpyDeviceToDevice, c->st));
 			Kept &k = c->pass.kept.back();
 			k.bstart.assign(h_bstart, h_bstart + NB + 1);
 			k.n = (u64)n;
@@ -504,18 +506,18 @@ static int feed_partitioned(yak_ch_t *h, const void *d_rec, int64_t n, const uin
 			return 0;
 		}
 	}
-	if (fmt) return fail("tagged records need the exclusive-ownership path (the pass left it: input beyond the device budget, or YAKAMD_FAST=0)");
-	return consume_records(c, (const Rec*)d_rec, n, t0, t0, t0 + t_span);   /* general path / pass 2: consume in place */
+	if (fmt == YK_FMT_TAGGED) return fail("tagged records need the exclusive-ownership path (the pass left it: input beyond the device budget, or YAKAMD_FAST=0)");
+	return consume_records(c, d_rec, fmt, n, t0, t0, t0 + t_span);   /* general path / pass 2: consume in place */
 }
 
 extern "C" int yakamd_feed_partitioned_dev(yak_ch_t *h, const void *d_rec, int64_t n, const uint64_t *h_bstart, uint64_t t0, uint64_t t_span)
 {
-	return feed_partitioned(h, d_rec, n, h_bstart, t0, t_span, false);
+	return feed_partitioned(h, d_rec, YK_FMT_POS, n, h_bstart, t0, t_span, false);
 }
 
 extern "C" int yakamd_feed_partitioned_lent_dev(yak_ch_t *h, const void *d_rec, int64_t n, const uint64_t *h_bstart, uint64_t t0, uint64_t t_span)
 {
-	return feed_partitioned(h, d_rec, n, h_bstart, t0, t_span, true);
+	return feed_partitioned(h, d_rec, YK_FMT_POS, n, h_bstart, t0, t_span, true);
 }
 
 /* 1 while the open pass of h runs on the exclusive-ownership path (the only one that takes tagged records) */
@@ -523,7 +525,7 @@ extern "C" int yakamd_pass_fast(yak_ch_t *h) { yakamd_ctx *c = ctx_of(h); return
 
 extern "C" int yakamd_feed_partitioned_tagged_dev(yak_ch_t *h, const void *d_rec8, int64_t n, const uint64_t *h_bstart, uint64_t t0, uint64_t t_span, int lent)
 {
-	return feed_partitioned(h, d_rec8, n, h_bstart, t0, t_span, lent != 0, 1);
+	return feed_partitioned(h, d_rec8, YK_FMT_TAGGED, n, h_bstart, t0, t_span, lent != 0);
 }
 
 extern "C" int yakamd_count_partitioned_dev(yak_ch_t *h, const void *d_hash_u64, int64_t n, const uint64_t *h_bstart)
@@ -536,7 +538,7 @@ extern "C" int yakamd_count_partitioned_dev(yak_ch_t *h, const void *d_hash_u64,
 	const size_t NB = (size_t)1 << c->nb_bits;
 	if (part_reserve(c, 1)) return -1;
 	HIPCK(hipMemcpyAsync(c->d_bstart, h_bstart, (NB + 1) * 8, hipMemcpyHostToDevice, c->st));
-	const int r = consume_records(c, (const Rec*)d_hash_u64, n, 0, 0, 0, c->d_bstart, 1);
+	const int r = consume_records(c, d_hash_u64, YK_FMT_HASH, n, 0, 0, 0, c->d_bstart);
 	HIPCK(hipStreamSynchronize(c->st));                       /* h_bstart may be a temporary of the caller */
 	return r;
 }
@@ -637,7 +639,7 @@ extern "C" int yakamd_count_retained(yak_ch_t *h)
 	for (auto &b : c->ret.l1) {
 		if (r) break;
 		if (hipMemcpyAsync(c->d_bstart, b.bstart.data(), (NB + 1) * 8, hipMemcpyHostToDevice, c->st) != hipSuccess) { r = fail("memcpy"); break; }
-		r = consume_records(c, b.rec, (int64_t)b.n, 0, 0, 0, c->d_bstart, 1, 2);
+		r = consume_records(c, b.rec.get(), YK_FMT_TAGGED, (int64_t)b.n, 0, 0, 0, c->d_bstart);
 		if (!r && hipStreamSynchronize(c->st) != hipSuccess) r = fail("count of the retained records failed");
 	}
 	retained_drop(c);

@@ -28,10 +28,11 @@ void chunk_runs(ChunkTable &t, const void *base, size_t stride, const u64 *start
 struct Slice {
 	FastParams fp;
 	u64 n_total = 0, sort_tmax = 0, budget = 0;
-	int fmt_in = 0, s2 = 0, s2a = 0, s2b = 0;
+	RecFmt fmt_in = YK_FMT_POS; int s2 = 0, s2a = 0, s2b = 0;   /* fmt_in: of every kept batch, YK_FMT_POS or YK_FMT_TAGGED */
 	bool three = false, nowb_plan = false, keep2 = false;
 	size_t n_sb = 0;
 	DevBuf<u64> sbstart; DevBuf<u32> segcur, ovf2; DevBuf<Rec> r2;   /* the level-2 partition: the sub-buckets' starts and records */
+	int r2_alloc() { return r2.alloc(fp.rec8_out ? (n_total + 1) / 2 : n_total); }   /* (level 2's own 8-byte records: FastParams.rec8_out) */
 	DevBuf<u64> lo_kc, lo_T; DevBuf<u32> lo_nsel, lo_lp, lo_nd; DevBuf<unsigned short> lo_c2;   /* k_lc2's output (LcOut) */
 	DevBuf<u32> ndist;
 	std::vector<u32> m; std::vector<u64> ro; u64 n_sel = 0;        /* the gather: keys per sub-table (m), their offsets (ro) */
@@ -61,7 +62,7 @@ static int slice_plan(yakamd_ctx *c, Slice &s, bool last)
 {
 	const int P = c->P;
 	for (auto &k : c->pass.kept) s.n_total += k.n;
-	s.fmt_in = c->pass.kept.empty() ? 0 : c->pass.kept.front().fmt;
+	s.fmt_in = c->pass.kept.empty() ? YK_FMT_POS : c->pass.kept.front().fmt;
 	s.sort_tmax = c->t_end;
 	FastParams &fp = s.fp;
 	fp.pre = c->pre; fp.k = c->k; fp.bloom_mode = c->bloom_mode; fp.nb = c->nb; fp.n_hash = c->n_hash;
@@ -86,8 +87,8 @@ static int slice_plan(yakamd_ctx *c, Slice &s, bool last)
 	size_t fr = 0, tot = 0;
 	s.budget = cap_gb >= 0 ? (u64)cap_gb << 30 : hipMemGetInfo(&fr, &tot) == hipSuccess ? tot / 8 : 0;
 	bool &nowb_plan = s.nowb_plan;
-	nowb_plan = c->bloom_mode && c->bf_virgin && last && c->n_slices == 0 && c->img_keys_total == 0 && c->retain_on && !c->retain_broken && s.fmt_in == 1 &&
-	            !c->or_mode && c->ret.l1.empty() && c->ret.l1_bytes + n_total * 8 <= s.budget && c->n_hash <= 32 &&
+	nowb_plan = c->bloom_mode && c->bf_virgin && last && c->n_slices == 0 && c->img_keys_total == 0 && c->retain_on && !c->retain_broken && s.fmt_in == YK_FMT_TAGGED &&
+	            !c->or_mode && c->ret.l1.empty() && c->ret.l1_bytes + n_total * yk_rec_bytes(YK_FMT_TAGGED) <= s.budget && c->n_hash <= 32 &&
 	            env_i64("YAKAMD_RETAIN2", 1) != 0 && env_i64("YAKAMD_BF_DEFER", 1) != 0 && env_i64("YAKAMD_LC2", 1) != 0 && env_i64("YAKAMD_LC2_NOSTAGE", 1) != 0;
 	for (auto &k : c->pass.kept) nowb_plan = nowb_plan && k.own;
 	/* one sweep of the level-2 scatter takes up to 2^11 sub-buckets (2^13 in sweeps over the chunk); beyond that -- the share of an N-GPU job's rank:
@@ -120,7 +121,7 @@ static int slice_plan(yakamd_ctx *c, Slice &s, bool last)
 	fp.s2_bits = s2; fp.s2_tot = s2;
 	fp.sw = c->bloom_mode ? c->nb - 9 : s2; fp.ssh = fp.sw - s2;
 	fp.bf_virgin = 0;
-	fp.rec8_in = s.fmt_in; fp.tb = YK_R8_TAG_BITS + s2;
+	fp.rec8_in = s.fmt_in == YK_FMT_TAGGED; fp.tb = YK_R8_TAG_BITS + s2;
 	fp.rec8_out = 0;                                         /* set below, once the largest sub-table stream is known */
 	if (c->bloom_mode) {
 		FastParams probe = fp;                                    /* will k_lc2 run (yk_lc2_ok, asked again by slice_count)?  The tier behind it works on the filter in memory and needs real zeros */
@@ -130,7 +131,7 @@ static int slice_plan(yakamd_ctx *c, Slice &s, bool last)
 		c->bf_virgin = false;
 	}
 	s.n_sb = (size_t)P << s2;
-	if (s.fmt_in) {
+	if (s.fmt_in == YK_FMT_TAGGED) {
 		if (np_max >= (1ull << 32)) return fail("more than 2^32 k-mer instances of one sub-table in one slice");
 		fp.rec8_out = np_max < (1ull << fp.tb) && env_i64("YAKAMD_REC8_OUT", 1) != 0;   /* the rank must fit below the hash bits; else 16-byte records {hash, rank} */
 		fp.t_pass0 = 0;                                       /* times are ranks inside the sub-table's stream of this slice */
@@ -143,14 +144,14 @@ static int slice_plan(yakamd_ctx *c, Slice &s, bool last)
  * records, or none.  The kept batches are released or handed to c->ret.l1 */
 static void slice_retain(yakamd_ctx *c, Slice &s, bool last)
 {
-	bool keep = c->retain_on && !c->retain_broken && s.fmt_in == 1 && c->bloom_mode && !c->or_mode && c->ret.l1_bytes + s.n_total * 8 <= s.budget;
+	bool keep = c->retain_on && !c->retain_broken && s.fmt_in == YK_FMT_TAGGED && c->bloom_mode && !c->or_mode && c->ret.l1_bytes + s.n_total * yk_rec_bytes(YK_FMT_TAGGED) <= s.budget;
 	for (auto &k : c->pass.kept) keep = keep && k.own;
 	/* the whole pass in this one slice, into an empty table: the level-2 records and the sub-buckets' key lists serve the count pass better (k_cnt2) */
 	s.keep2 = keep && last && c->n_slices == 0 && c->img_keys_total == 0 && s.fp.rec8_out && c->ret.l1.empty() && env_i64("YAKAMD_RETAIN2", 1) != 0;
 	if (s.keep2) keep = false;
 	if (c->retain_on && !keep && !s.keep2 && !c->pass.kept.empty()) { c->retain_broken = true; retained_drop(c); }
 	for (auto &k : c->pass.kept)
-		if (keep && k.n) { Retained r; r.rec = std::move(k.own); r.n = k.n; r.bstart.swap(k.bstart); c->ret.l1.push_back(std::move(r)); c->ret.l1_bytes += k.n * 8; }
+		if (keep && k.n) { Retained r; r.rec = std::move(k.own); r.n = k.n; r.bstart.swap(k.bstart); c->ret.l1.push_back(std::move(r)); c->ret.l1_bytes += k.n * yk_rec_bytes(YK_FMT_TAGGED); }
 	c->pass.kept.clear(); c->pass.kept_bytes = 0;
 }
 
@@ -172,9 +173,9 @@ static int slice_partition(yakamd_ctx *c, Slice &s, bool last)
 			const u64 a = k.bstart[p], b = k.bstart[p + 1];
 			for (u64 o = a; o < b; o += ch2) {
 				Chunk2 ch;
-				ch.rec = s.fmt_in ? (const Rec*)((const u64*)k.d_rec + o) : k.d_rec + o; ch.spare = 0;
+				ch.rec = (const Rec*)((const char*)k.d_rec + o * yk_rec_bytes(s.fmt_in)); ch.spare = 0;
 				ch.n = (u32)std::min<u64>(ch2, b - o); ch.bucket = (u32)p;
-				ch.tbase = s.fmt_in ? (u32)np : (u32)(k.t0 - c->t_pass0); ch.pad = (u32)s.fmt_in;   /* tagged: ranks continue from the earlier batches of this sub-table */
+				ch.tbase = s.fmt_in == YK_FMT_TAGGED ? (u32)np : (u32)(k.t0 - c->t_pass0); ch.fmt = (u32)s.fmt_in;   /* tagged: ranks continue from the earlier batches of this sub-table */
 				ch.before = (u32)(o - a); ch.after = (u32)(b - (o + ch.n));
 				t.h.push_back(ch);
 			}
@@ -186,7 +187,7 @@ static int slice_partition(yakamd_ctx *c, Slice &s, bool last)
 	t.first[P] = (u32)t.h.size();
 	DevBuf<u64> d_bbase, d_sba; DevBuf<u32> d_rows2; DevBuf<Rec> d_ra;
 	if (t.upload(c->st) || d_bbase.alloc(P + 1) || d_rows2.alloc(t.h.size() << s2_first) || s.sbstart.alloc(s.n_sb + 1) || s.segcur.alloc(P) || s.ovf2.alloc(s.n_sb)) return -1;
-	if (s.three ? (d_ra.alloc(s.n_total) || d_sba.alloc(((size_t)P << s.s2a) + 1)) : s.r2.alloc(fp.rec8_out ? (s.n_total + 1) / 2 : s.n_total)) return -1;
+	if (s.three ? (d_ra.alloc(s.n_total) || d_sba.alloc(((size_t)P << s.s2a) + 1)) : s.r2_alloc()) return -1;
 	HIPCK(hipMemcpyAsync(d_bbase, bbase.data(), (P + 1) * 8, hipMemcpyHostToDevice, c->st));
 	HIPCK(hipMemsetAsync(c->d_counters + YKC_NOVF2, 0, 8, c->st));
 	std::vector<u64> h_sba;
@@ -215,7 +216,7 @@ static int slice_partition(yakamd_ctx *c, Slice &s, bool last)
 		chunk_runs(t, d_ra, sizeof(Rec), h_sba.data(), PB, std::max<u64>((u64)env_i64("YAKAMD_CH2", YK_CH2), (u64)32 << s.s2b));
 		FastParams fb = fp;
 		fb.s2_bits = s.s2b; fb.rec8_in = 0;                          /* routes by the low s2b bits, packs with all of them (s2_tot) */
-		if (t.upload(c->st) || d_rows2.alloc(t.h.size() * S2B) || s.r2.alloc(fp.rec8_out ? (s.n_total + 1) / 2 : s.n_total)) return -1;
+		if (t.upload(c->st) || d_rows2.alloc(t.h.size() * S2B) || s.r2_alloc()) return -1;
 		EvTimer tm(c->st);
 		yk_launch_part2(t.d, (int)t.h.size(), t.d_first, d_sba, fb, (int)PB, d_rows2, s.sbstart, s.r2, c->st);
 		const double ms = tm.stop();                                /* (the host vectors above outlive the copies) */
@@ -487,13 +488,13 @@ int fast_finish(yakamd_ctx *c, bool last)
 /* leave the fast path: push every kept batch through the accumulator path, in stream order */
 int fast_abandon(yakamd_ctx *c)
 {
-	for (auto &k : c->pass.kept) if (k.fmt) return fail("a batch was fed out of stream order after tagged 8-byte batches were kept: feed in order, or set YAKAMD_REC8=0");
+	for (auto &k : c->pass.kept) if (k.fmt != YK_FMT_POS) return fail("a batch was fed out of stream order after tagged 8-byte batches were kept: feed in order, or set YAKAMD_REC8=0");
 	c->fast = false;
 	yk_event(YKE_FAST_ABANDONED);
 	c->retain_broken = true; retained_drop(c);                 /* the pass leaves the path whose records can be kept */
 	int r = 0;
 	for (auto &k : c->pass.kept) {
-		if (!r) r = consume_records(c, k.d_rec, (int64_t)k.n, k.t0, k.t0, k.t0 + k.span);
+		if (!r) r = consume_records(c, k.d_rec, k.fmt, (int64_t)k.n, k.t0, k.t0, k.t0 + k.span);
 		k.own.reset();
 	}
 	c->pass.kept.clear(); c->pass.kept_bytes = 0;
@@ -512,17 +513,19 @@ static int fast_flush_slice(yakamd_ctx *c)
 
 /* may this batch (n_pos stream positions starting at time t) stay on the fast path?  If so,
  * allocate its level-1 output buffers */
-int fast_admit(yakamd_ctx *c, u64 t, u64 n_pos, u64 n_cap, Rec **out, Rec *borrowed, int fmt)
+int fast_admit(yakamd_ctx *c, RecFmt fmt, u64 t, u64 n_pos, u64 n_cap, void **out, const void *borrowed)
 {
 	if (!c->t_pass0_set) { c->t_pass0 = t; c->t_pass0_set = true; }
 	/* what a kept record costs against the budget (a quarter of the free memory): its 16 bytes, or for an 8-byte tagged record 12 -- the count of
 	 * the slice holds 24-32 bytes per record at its peak (level-2 records, 8 or 16 bytes when the ranks outgrow their field, + 16 of key / time
 	 * output), so that a slice admitted by records x 12 <= free / 4 peaks at two thirds of the free memory.  (Tagged slices used to be cut by the
 	 * 2^32-position limit long before memory mattered; a rank of an 8-GPU job feeds 9 G records.)  A borrowed buffer is the caller's memory */
-	const u64 cost = borrowed ? 0 : n_cap * (fmt ? 12 : 16);
+	const u64 tagged_peak_share = 4;                            /* what a tagged record is charged beyond its own bytes, for its part in that peak */
+	const bool tagged = fmt == YK_FMT_TAGGED;
+	const u64 cost = borrowed ? 0 : n_cap * (yk_rec_bytes(fmt) + (tagged ? tagged_peak_share : 0));
 	/* {hash, position} records hold 32-bit positions relative to the slice; tagged records hold no position at all (their times are ranks inside a
 	 * sub-table's stream, checked when the slice is counted), so a slice of them may span more than 2^32 stream positions */
-	const bool span_ok = fmt != 0 || t + n_pos - c->t_pass0 < 0xfffffff0ull;
+	const bool span_ok = tagged || t + n_pos - c->t_pass0 < 0xfffffff0ull;
 	bool fits = t >= c->t_pass0 && span_ok && c->pass.kept_bytes + cost <= c->fast_budget;
 	if (fits && !c->pass.kept.empty()) {
 		/* the count of a slice cuts a sub-table into at most 2^13 sub-buckets, each meant to hold what one workgroup's LDS table takes (fast_finish):
@@ -536,7 +539,7 @@ int fast_admit(yakamd_ctx *c, u64 t, u64 n_pos, u64 n_cap, Rec **out, Rec *borro
 	if (!c->pass.kept.empty() && c->pass.kept.back().fmt != fmt) fits = false;   /* tagged records carry ranks, Rec records stream positions: never in one slice */
 	/* (a chunk that continues a sequence cut by the caller starts k - 1 positions before the end of the previous one, yak_multi.cpp take_piece:
 	 * its first k - 1 positions complete no k-mer, so it is still "behind" everything kept) */
-	if (!fits && !c->pass.kept.empty() && t + (u64)(c->k - 1) >= c->t_end && (fmt != 0 || n_pos < 0xfffffff0ull) && cost <= c->fast_budget && !c->pass.acc.s) {
+	if (!fits && !c->pass.kept.empty() && t + (u64)(c->k - 1) >= c->t_end && (tagged || n_pos < 0xfffffff0ull) && cost <= c->fast_budget && !c->pass.acc.s) {
 		/* the kept batches are a complete prefix of the stream: count them now, exactly as if the pass
 		 * ended here (table, filter and counts carry over; the next slice meets them as existing state --
 		 * what the reference does chunk after chunk), and start a new slice with times relative to t */
@@ -547,8 +550,8 @@ int fast_admit(yakamd_ctx *c, u64 t, u64 n_pos, u64 n_cap, Rec **out, Rec *borro
 	if (!fits) { if (fast_abandon(c)) return -1; return 0; }
 	Kept k;
 	k.t0 = t; k.span = n_pos; k.fmt = fmt;
-	if (!borrowed && k.own.alloc((size_t)(fmt ? (n_cap + 1) / 2 : n_cap))) return -1;
-	*out = k.d_rec = borrowed ? borrowed : k.own.get();
+	if (!borrowed && k.own.alloc(yk_rec_units(fmt, (size_t)n_cap))) return -1;
+	*out = k.own.get(); k.d_rec = borrowed ? borrowed : k.own.get();
 	c->pass.kept_bytes += cost;
 	c->pass.kept.push_back(std::move(k));
 	return 0;

@@ -37,7 +37,7 @@ __device__ __forceinline__ u32 r8_rank(const u64 *src_, int64_t i, u32 before, u
 template <bool NEED_T>
 __device__ __forceinline__ void p2_load(const Chunk2 &c, u32 i, const FastParams &fp, u64 *h, u32 *t)
 {
-	if (c.pad == 1) {
+	if (c.fmt == 1) {
 		const u64 *src = (const u64*)c.rec;
 		*h = (yk_global(u64, src)[i] >> YK_R8_TAG_BITS) << fp.pre | c.bucket;
 		if (NEED_T) *t = c.tbase + r8_rank(src, (int64_t)i, c.before, c.n, c.after);

@@ -1,13 +1,17 @@
 /* kern_launch.inc -- part of kernels.hip (one translation unit, included in this order): launch wrappers (extern "C", declared in yk_device.h) */
 #include <atomic>
-/* "set on the current device": the dynamic-LDS limit of a kernel (hipFuncSetAttribute) belongs to the device that was current when it was set, so a
- * process that drives several GPUs sets it once on each -- `static DevOnce attr; if (!attr) { ...; attr = true; }` */
-struct DevOnce {
-	std::atomic<unsigned> m{0};
-	static unsigned bit() { int d = 0; (void)hipGetDevice(&d); return 1u << (d & 31); }
-	bool operator!() const { return !(m.load(std::memory_order_acquire) & bit()); }
-	DevOnce &operator=(bool) { m.fetch_or(bit(), std::memory_order_release); return *this; }
-};
+/* The dynamic-LDS limit of kernel K (hipFuncSetAttribute) belongs to the device that was current when it was set, so a process that drives several
+ * GPUs sets it once on each: lds_limit<K>(bytes), before a launch of K that asks for more than 64 KiB, sets it once per kernel and device.  false: the
+ * runtime refused (the error stays for the caller to clear or to find; the next call asks again) -- what that means is the caller's to say */
+template <auto K> static bool lds_limit(int bytes)
+{
+	static std::atomic<unsigned> done{0};                             /* bit d: set on device d */
+	int d = 0; (void)hipGetDevice(&d);
+	if (done.load(std::memory_order_acquire) >> (d & 31) & 1) return true;
+	if (hipFuncSetAttribute((const void*)K, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+	done.fetch_or(1u << (d & 31), std::memory_order_release);
+	return true;
+}
 extern "C" {
 
 /* k-mers ENDING at positions [pos0, n) of `bases` (bytes before pos0 are read as left context);
@@ -39,61 +43,63 @@ void yk_launch_pack(const uint8_t *a, int64_t n, u32 *codes, u32 *valid, hipStre
 	if (n > 0) YK_LAUNCH(k_pack, dim3((unsigned)((n + 32 * 256 - 1) / (32 * 256))), dim3(256), 0, st, a, n, codes, valid);
 }
 
-/* partitioning extraction: returns through bstart[1 << nb_bits] (device) the record count */
+/* partitioning extraction: a histogram sweep, the scan of its rows, the scatter of the records of format `fmt`; bstart[1 << nb_bits] (device) = the record count */
 void yk_launch_xpart(const uint8_t *bases, int64_t pos0, int64_t n, int64_t t_sub, int k, int pre, int plo, int phi,
-                     int nb_bits, u32 *rows, u64 *partial, u64 *bstart, Rec *out, int hash_only, hipStream_t st, const u32 *valid)
+                     int nb_bits, u32 *rows, u64 *partial, u64 *bstart, void *out, RecFmt fmt, hipStream_t st, const u32 *valid)
 {
 	if (n <= pos0) return;
-	const int n_blk = (int)(((u64)(n - pos0) + (u64)XP_T * XT_TILE - 1) / ((u64)XP_T * XT_TILE));
+	const int n_blk = yk_xpart_blocks(n - pos0);
 	const size_t lds = sizeof(u32) << nb_bits;
-	if (hash_only == 2) {                                             /* tagged 8-byte records: needs nb_bits <= 10, k < 32 (the caller checks) */
-		static DevOnce attr3;
-		if (!attr3) { hipFuncSetAttribute((const void*)k_xpart_wcs<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096); attr3 = true; }
+	const int lds_max = 160 * 1024 - 4096;
+	auto histogram = [&]() {                                          /* (the tagged records' own sweep also counts the rounds that reach a bucket) */
+		YK_LAUNCH(k_xpart<0>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, (Rec*)out, valid);
+		launch_part_scan(rows, n_blk, nb_bits, partial, bstart, st);
+	};
+	switch (fmt) {
+	case YK_FMT_TAGGED: {                                             /* needs nb_bits <= 10, k < 32 (the caller checks) */
+		const size_t wlds = wc_lds_bytes<8, XW_CAP_S, false>(1 << nb_bits, 1024);
+		lds_limit<k_xpart_wcs<true>>(lds_max);
 		static bool said = false;
 		if (!said && getenv("YAKAMD_VERBOSE") && atoi(getenv("YAKAMD_VERBOSE")) > 1) {
 			int nb = 0; said = true;
-			hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_xpart_wcs<true>, 1024, wc_lds_bytes<8, XW_CAP_S, false>(1 << nb_bits, 1024));
-			fprintf(stderr, "[yak_amd] k_xpart_wcs: %zu B of dynamic LDS, %d workgroups per CU\n", wc_lds_bytes<8, XW_CAP_S, false>(1 << nb_bits, 1024), nb);
+			hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void*)k_xpart_wcs<true>, 1024, wlds);
+			fprintf(stderr, "[yak_amd] k_xpart_wcs: %zu B of dynamic LDS, %d workgroups per CU\n", wlds, nb);
 		}
-		const size_t wlds = wc_lds_bytes<8, XW_CAP_S, false>(1 << nb_bits, 1024);
-		if (k == 31) {                                                /* yak's default k: the variants with the constant folded in */
-			static DevOnce attr31;
-			if (!attr31) { hipFuncSetAttribute((const void*)k_xpart_wcs<true, 31>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096); attr31 = true; }
-			YK_LAUNCH((k_xpart<3, 31>), dim3(n_blk), dim3(XT_THREADS), 3 * lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
-			launch_part_scan(rows, n_blk, nb_bits, partial, bstart, st, true);
-			YK_LAUNCH((k_xpart_wcs<true, 31>), dim3(n_blk), dim3(1024), wlds, st, bases, pos0, n, k, pre, plo, phi, nb_bits, (const u32*)rows, (u64*)out, 0, valid);
-			return;
-		}
-		YK_LAUNCH(k_xpart<3>, dim3(n_blk), dim3(XT_THREADS), 3 * lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
+		const bool k31 = k == 31;                                     /* yak's default k: the variants with the constant folded in */
+		if (k31) YK_LAUNCH((k_xpart<3, 31>), dim3(n_blk), dim3(XT_THREADS), 3 * lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, (Rec*)out, valid);
+		else YK_LAUNCH(k_xpart<3>, dim3(n_blk), dim3(XT_THREADS), 3 * lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, (Rec*)out, valid);
 		launch_part_scan(rows, n_blk, nb_bits, partial, bstart, st, true);
-		YK_LAUNCH(k_xpart_wcs<true>, dim3(n_blk), dim3(1024), wlds, st,
-		                   bases, pos0, n, k, pre, plo, phi, nb_bits, (const u32*)rows, (u64*)out, 0, valid);
+		if (k31) {
+			lds_limit<k_xpart_wcs<true, 31>>(lds_max);
+			YK_LAUNCH((k_xpart_wcs<true, 31>), dim3(n_blk), dim3(1024), wlds, st, bases, pos0, n, k, pre, plo, phi, nb_bits, (const u32*)rows, (u64*)out, 0, valid);
+		}
+		else YK_LAUNCH(k_xpart_wcs<true>, dim3(n_blk), dim3(1024), wlds, st, bases, pos0, n, k, pre, plo, phi, nb_bits, (const u32*)rows, (u64*)out, 0, valid);
 		return;
 	}
-	YK_LAUNCH(k_xpart<0>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
-	launch_part_scan(rows, n_blk, nb_bits, partial, bstart, st);
-	const int wc = 3;                                             /* write-combining scatters for both record kinds (the plain ones serve prefixes beyond 10 bits) */
-	static DevOnce attr;
-	if (!attr) {
-		hipFuncSetAttribute((const void*)k_xpart_wc<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-		hipFuncSetAttribute((const void*)k_xpart_wc<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096);
-		attr = true;
-	}
-	if (nb_bits <= 10 && ((wc >> (hash_only ? 1 : 0) & 1) || hash_only == 3)) {
-		const int wcs2 = 1;
-		if (hash_only && (wcs2 || hash_only == 3) && k < 32) {   /* hash_only == 3: bare hashes with the range tag (the caller checked k and nb_bits) */                         /* the round-stable variant needs 7 slots per stack only: two workgroups per CU */
-			static DevOnce attr4;
-			if (!attr4) { hipFuncSetAttribute((const void*)k_xpart_wcs<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4096); attr4 = true; }
-			YK_LAUNCH(k_xpart_wcs<false>, dim3(n_blk), dim3(1024), (wc_lds_bytes<8, XW_CAP_S, false>(1 << nb_bits, 1024)), st,
-			                   bases, pos0, n, k, pre, plo, phi, nb_bits, (const u32*)rows, (u64*)out, hash_only == 3, valid);
+	case YK_FMT_POS:                                                  /* the write-combining scatter; the plain one serves prefixes beyond 10 bits */
+		histogram();
+		if (nb_bits <= 10) {
+			lds_limit<k_xpart_wc<1>>(lds_max);
+			YK_LAUNCH(k_xpart_wc<1>, dim3(n_blk), dim3(XW_NT), (wc_lds_bytes<4, XW_CAP_T, true>(1 << nb_bits, XW_NT)), st,
+			          bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, (const u32*)rows, (const u64*)bstart, out, valid);
 		}
-		else if (hash_only) YK_LAUNCH(k_xpart_wc<2>, dim3(n_blk), dim3(XW_NT), (wc_lds_bytes<8, XW_CAP_H, false>(1 << nb_bits, XW_NT)), st,
-		                                  bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, (const u32*)rows, (const u64*)bstart, (void*)out, valid);
-		else YK_LAUNCH(k_xpart_wc<1>, dim3(n_blk), dim3(XW_NT), (wc_lds_bytes<4, XW_CAP_T, true>(1 << nb_bits, XW_NT)), st,
-		                        bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, (const u32*)rows, (const u64*)bstart, (void*)out, valid);
+		else YK_LAUNCH(k_xpart<1>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, (Rec*)out, valid);
+		return;
+	case YK_FMT_HASH:
+	case YK_FMT_HASH_RNG:                                             /* the range tag is the round-stable scatter's alone (the caller checked k and nb_bits) */
+		histogram();
+		if (nb_bits <= 10 && k < 32) {                                /* round-stable: 7 slots per stack, two workgroups per CU */
+			lds_limit<k_xpart_wcs<false>>(lds_max);
+			YK_LAUNCH(k_xpart_wcs<false>, dim3(n_blk), dim3(1024), (wc_lds_bytes<8, XW_CAP_S, false>(1 << nb_bits, 1024)), st,
+			          bases, pos0, n, k, pre, plo, phi, nb_bits, (const u32*)rows, (u64*)out, fmt == YK_FMT_HASH_RNG, valid);
+		} else if (nb_bits <= 10) {
+			lds_limit<k_xpart_wc<2>>(lds_max);
+			YK_LAUNCH(k_xpart_wc<2>, dim3(n_blk), dim3(XW_NT), (wc_lds_bytes<8, XW_CAP_H, false>(1 << nb_bits, XW_NT)), st,
+			          bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, (const u32*)rows, (const u64*)bstart, out, valid);
+		}
+		else YK_LAUNCH(k_xpart<2>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, (Rec*)out, valid);
+		return;
 	}
-	else if (hash_only) YK_LAUNCH(k_xpart<2>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
-	else YK_LAUNCH(k_xpart<1>, dim3(n_blk), dim3(XT_THREADS), lds, st, bases, pos0, n, t_sub, k, pre, plo, phi, nb_bits, rows, out, valid);
 }
 
 int yk_part_groups(void) { return PS_G; }
@@ -153,15 +159,11 @@ void yk_launch_img_count(const Rec *rec, int64_t n, ImgView img, hipStream_t st)
 /* LDS needed by k_img_count_lds for a sub-table of `cap` slots holding `count` keys */
 size_t yk_img_count_lds_bytes(u32 cap, u32 count) { return (size_t)((cap + 31) / 32) * 8 + (size_t)(count + 1) / 2 * 4 + 16; }
 
-int yk_launch_img_count_lds(const void *rec, int hash_only, const u64 *bstart, ImgView img, int plo, int phi, size_t lds, u64 *compact, u32 stride, hipStream_t st)
+/* YK_FMT_POS or YK_FMT_HASH records, grouped by sub-table (bstart) */
+int yk_launch_img_count_lds(const void *rec, RecFmt fmt, const u64 *bstart, ImgView img, int plo, int phi, size_t lds, u64 *compact, u32 stride, hipStream_t st)
 {
-	static DevOnce attr;
-	if (!attr) {
-		if (hipFuncSetAttribute((const void*)k_img_count_lds<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess ||
-		    hipFuncSetAttribute((const void*)k_img_count_lds<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess) { (void)hipGetLastError(); return -1; }
-		attr = true;
-	}
-	if (hash_only) YK_LAUNCH(k_img_count_lds<1>, dim3(phi - plo), dim3(1024), lds, st, (const u64*)rec, bstart, img, plo, compact, stride);
+	if (!lds_limit<k_img_count_lds<1>>(160 * 1024 - 256) || !lds_limit<k_img_count_lds<2>>(160 * 1024 - 256)) { (void)hipGetLastError(); return -1; }
+	if (fmt != YK_FMT_POS) YK_LAUNCH(k_img_count_lds<1>, dim3(phi - plo), dim3(1024), lds, st, (const u64*)rec, bstart, img, plo, compact, stride);
 	else YK_LAUNCH(k_img_count_lds<2>, dim3(phi - plo), dim3(1024), lds, st, (const u64*)rec, bstart, img, plo, compact, stride);
 	return 0;
 }
@@ -259,8 +261,7 @@ void yk_launch_replay(const ReplayTask *tasks, int n_tasks, int n_threads, const
                       const u64 *rec_kc, const u64 *rec_t, const u64 *lastput,
                       u32 *out_bits, u32 *out_count, u32 lds_words, hipStream_t st)
 {
-	static DevOnce attr;
-	if (!attr) { hipFuncSetAttribute((const void*)k_replay, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 1024); attr = true; }
+	lds_limit<k_replay>(160 * 1024 - 1024);
 	if (lds_words < 2 * RP_LDS_WORDS) lds_words = 2 * RP_LDS_WORDS;
 	YK_LAUNCH(k_replay, dim3(n_tasks), dim3(n_threads), (size_t)lds_words * 4, st, tasks, old_keys, old_used, new_keys, new_used,
 	                   scr_used, scr_owner, scr_par, rec_kc, rec_t, lastput, out_bits, out_count, lds_words);
@@ -309,9 +310,8 @@ void yk_launch_part2_ts(const Chunk2 *chunks, int n_chunks, const u32 *chunk_fir
                         u32 *rows2, u64 *sbstart, Rec *out, hipStream_t st)
 {
 	const size_t lds = sizeof(u32) << fp.s2_bits;
-	static DevOnce attr;
-	if (!attr) { hipFuncSetAttribute((const void*)k_part2<1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256);
-	             hipFuncSetAttribute((const void*)k_part2_wc<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); attr = true; }
+	lds_limit<k_part2<1, true>>(160 * 1024 - 256);
+	lds_limit<k_part2_wc<true>>(160 * 1024 - 256);
 	if (n_chunks) YK_LAUNCH((k_part2<0, true>), dim3(n_chunks), dim3(256), lds, st, chunks, fp, rows2, bbase, out);
 	YK_LAUNCH(k_part2_scan, dim3(P), dim3(256), 0, st, chunk_first, bbase, fp.s2_bits, rows2, sbstart, P, 1);
 	if (n_chunks && fp.s2_bits <= 13 && fp.s2_bits >= 4) {
@@ -331,8 +331,7 @@ int yk_launch_ts_rank(const u64 *binstart, const Rec *in, int w, int j, u32 bin_
 {
 	u32 cap = 0;
 	const size_t lds = yk_ts_rank_lds(w + j, &cap);
-	static DevOnce attr;
-	if (!attr) { if (hipFuncSetAttribute((const void*)k_ts_rank, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024) != hipSuccess) { (void)hipGetLastError(); return -1; } attr = true; }
+	if (!lds_limit<k_ts_rank>(100 * 1024)) { (void)hipGetLastError(); return -1; }
 	if (lds > 100 * 1024 || (n_bins & ((1u << j) - 1))) return -1;
 	const u32 n_super = n_bins >> j;
 	const u32 grid = std::min<u32>(n_super, 256 * 4 * 16);        /* a few steps per workgroup, handed out as slots free up */
@@ -350,35 +349,29 @@ void yk_launch_part2(const Chunk2 *chunks, int n_chunks, const u32 *chunk_first,
 {
 	const size_t lds = sizeof(u32) << fp.s2_bits;
 	const int nt = 1024;
-	static DevOnce attr;
-	if (!attr) { hipFuncSetAttribute((const void*)k_part2<1, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); attr = true; }
+	lds_limit<k_part2<1, false>>(160 * 1024 - 256);
 	if (n_chunks) YK_LAUNCH((k_part2<0>), dim3(n_chunks), dim3(256), lds, st, chunks, fp, rows2, bbase, out);
 	YK_LAUNCH(k_part2_scan, dim3(P), dim3(256), 0, st, chunk_first, bbase, fp.s2_bits, rows2, sbstart, P, 1);
 	const int wc = (int)yk_knob("YAKAMD_P2_WC", 1);
 	if (n_chunks && wc && fp.rec8_out && fp.s2_bits <= 13 && fp.s2_bits >= 4) {
-		static DevOnce attr8;                                  /* the kernel has 6.5 KB of static LDS besides */
-		if (!attr8) { if (hipFuncSetAttribute((const void*)k_part2_wc8<false>, hipFuncAttributeMaxDynamicSharedMemorySize, WC_SEG * WC8_CAP * 8 + WC_SEG * 8 + WC_NT * 4 + 16) != hipSuccess) (void)hipGetLastError(); attr8 = true; }
+		if (!lds_limit<k_part2_wc8<false>>(WC_SEG * WC8_CAP * 8 + WC_SEG * 8 + WC_NT * 4 + 16)) (void)hipGetLastError();   /* the kernel has 6.5 KB of static LDS besides */
 		const size_t seg = fp.s2_bits < 11 ? (size_t)1 << fp.s2_bits : WC_SEG;
 		if (fp.rec8_in && seg <= 1024 && yk_knob("YAKAMD_P2_CAP7", 1) != 0) {   /* <= 76 KB with the ring: two workgroups per CU */
-			static DevOnce attr7;
-			if (!attr7) { if (hipFuncSetAttribute((const void*)k_part2_wc8<false, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, 1024 * 7 * 8 + 1024 * 8 + WC_NT * 4 + 16) != hipSuccess) (void)hipGetLastError(); attr7 = true; }
+			if (!lds_limit<k_part2_wc8<false, 7>>(1024 * 7 * 8 + 1024 * 8 + WC_NT * 4 + 16)) (void)hipGetLastError();
 			YK_LAUNCH((k_part2_wc8<false, 7>), dim3(n_chunks), dim3(WC_NT), seg * 7 * 8 + seg * 8 + WC_NT * 4 + 16, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, (u64*)out);
 		}
 		else if (fp.rec8_in) YK_LAUNCH((k_part2_wc8<false>), dim3(n_chunks), dim3(WC_NT), seg * WC8_CAP * 8 + seg * 8 + WC_NT * 4 + 16, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, (u64*)out);
 		else {                                                      /* the second sweep of a two-sweep partition: {hash, rank} records in */
-			static DevOnce attr8r;
-			if (!attr8r) { if (hipFuncSetAttribute((const void*)k_part2_wc8r, hipFuncAttributeMaxDynamicSharedMemorySize, WC_SEG * WC8_CAP * 8 + WC_SEG * 8 + WC_NT * 4 + 16) != hipSuccess) (void)hipGetLastError(); attr8r = true; }
+			if (!lds_limit<k_part2_wc8r>(WC_SEG * WC8_CAP * 8 + WC_SEG * 8 + WC_NT * 4 + 16)) (void)hipGetLastError();
 			YK_LAUNCH(k_part2_wc8r, dim3(n_chunks), dim3(WC_NT), seg * WC8_CAP * 8 + seg * 8 + WC_NT * 4 + 16, st, chunks, fp, (const u32*)rows2, bbase, (u64*)out);
 		}
 	} else if (n_chunks && wc && fp.rec8_in && fp.s2_bits <= 13 && fp.s2_bits >= 4) {
 		/* tagged records in, {hash, rank} records out (the first sweep of a two-sweep partition; ranks beyond their field): the ring kernel with 16-byte stacks */
-		static DevOnce attr16;
-		if (!attr16) { if (hipFuncSetAttribute((const void*)k_part2_wc8<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 8192) != hipSuccess) (void)hipGetLastError(); attr16 = true; }
+		if (!lds_limit<k_part2_wc8<true>>(160 * 1024 - 8192)) (void)hipGetLastError();
 		const size_t l2 = wc_lds_bytes<4, WC_CAP, true>(fp.s2_bits < 11 ? 1 << fp.s2_bits : WC_SEG, WC_NT);
 		YK_LAUNCH((k_part2_wc8<true>), dim3(n_chunks), dim3(WC_NT), l2, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, (u64*)out);
 	} else if (n_chunks && wc && fp.s2_bits <= 13 && fp.s2_bits >= 4) {
-		static DevOnce attr2;
-		if (!attr2) { hipFuncSetAttribute((const void*)k_part2_wc<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); attr2 = true; }
+		lds_limit<k_part2_wc<false>>(160 * 1024 - 256);
 		const size_t l2 = wc_lds_bytes<4, WC_CAP, true>(fp.s2_bits < 11 ? 1 << fp.s2_bits : WC_SEG, WC_NT);
 		YK_LAUNCH((k_part2_wc<false>), dim3(n_chunks), dim3(WC_NT), l2, st, chunks, fp, (const u32*)rows2, (const u64*)sbstart, bbase, out);
 	} else if (n_chunks) YK_LAUNCH((k_part2<1>), dim3(n_chunks), dim3(nt), lds, st, chunks, fp, rows2, bbase, out);
@@ -395,8 +388,7 @@ void yk_launch_hpart2(const Chunk2 *chunks, int n_chunks, const u32 *chunk_first
                       u32 *rows2, u64 *sbstart, u64 *out, hipStream_t st)
 {
 	const int S2 = 1 << rb;
-	static DevOnce attr;
-	if (!attr) { hipFuncSetAttribute((const void*)k_hpart2<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256); attr = true; }
+	lds_limit<k_hpart2<1>>(160 * 1024 - 256);
 	if (n_chunks) YK_LAUNCH(k_hpart2<0>, dim3(n_chunks), dim3(WC_NT), sizeof(u32) * S2, st, chunks, img, rb, yk_rng_log(), rows2, (const u64*)sbstart, out);
 	YK_LAUNCH(k_part2_scan, dim3(P), dim3(256), 0, st, chunk_first, bbase, rb, rows2, sbstart, P, 0);
 	if (n_chunks) YK_LAUNCH(k_hpart2<1>, dim3(n_chunks), dim3(WC_NT), (wc_lds_bytes<8, XW_CAP_H, false>(S2, WC_NT)), st,
@@ -406,12 +398,7 @@ void yk_launch_hpart2(const Chunk2 *chunks, int n_chunks, const u32 *chunk_first
 int yk_launch_img_count_rng(const u64 *rec, int cross, const u64 *sbstart, ImgView img, int plo, int phi, int rb, u32 max_len,
                             u64 *list, u32 *list_n, u32 list_cap, hipStream_t st)
 {
-	static DevOnce attr;
-	if (!attr) {
-		if (hipFuncSetAttribute((const void*)k_img_count_rng<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess ||
-		    hipFuncSetAttribute((const void*)k_img_count_rng<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess) { (void)hipGetLastError(); return -1; }
-		attr = true;
-	}
+	if (!lds_limit<k_img_count_rng<0>>(160 * 1024 - 256) || !lds_limit<k_img_count_rng<1>>(160 * 1024 - 256)) { (void)hipGetLastError(); return -1; }
 	const size_t lds = (size_t)((max_len + 31) / 32) * 4 + (size_t)(max_len + 1) / 2 * 4 + 16;
 	const dim3 grid((unsigned)(phi - plo) << rb), blk(1024);
 	if (cross) YK_LAUNCH(k_img_count_rng<1>, grid, blk, lds, st, rec, sbstart, img, plo, rb, yk_rng_log(), list, list_n, list_cap);
@@ -429,19 +416,19 @@ void yk_launch_lds_count_ovf(FastParams fp, const u64 *sbstart, const Rec *rec,
 
 size_t yk_count_own_lds(u32 range_len, u32 kmax) { const u32 nw = (range_len + 31) / 32; return (size_t)2 * ((nw + 1) & ~1u) * 4 + (size_t)kmax * 8 + (size_t)((kmax + 1) / 2 + 1 & ~1u) * 4 + 16 * 128 * 8 + 16; }   /* bitmap, ranks, keys, counters, 16 wave queues */
 
-int yk_launch_img_count_own(const void *rec, int hash_only, int cross, int ytag, const u64 *bstart, ImgView img, int plo, int phi, int rb, int rng_log, u32 kmax,
+/* records of any RecFmt, grouped by sub-table (bstart).  The format gives the kernel its two arguments: W, the record's stride in words, and ytag, how the
+ * record's one word is read -- 0 the hash, 1 the range-tagged hash, 2 the tagged level-1 record */
+int yk_launch_img_count_own(const void *rec, RecFmt fmt, int cross, const u64 *bstart, ImgView img, int plo, int phi, int rb, int rng_log, u32 kmax,
                             size_t lds, u64 *list, u32 *list_n, u32 list_cap, hipStream_t st)
 {
-	static DevOnce attr;
-	if (!attr) {
-		const void *fn[4] = { (const void*)k_img_count_own<1, 0>, (const void*)k_img_count_own<1, 1>, (const void*)k_img_count_own<2, 0>, (const void*)k_img_count_own<2, 1> };
-		for (int i = 0; i < 4; ++i) if (hipFuncSetAttribute(fn[i], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256) != hipSuccess) { (void)hipGetLastError(); return -1; }
-		attr = true;
-	}
+	const int lds_max = 160 * 1024 - 256;
+	if (!lds_limit<k_img_count_own<1, 0>>(lds_max) || !lds_limit<k_img_count_own<1, 1>>(lds_max) || !lds_limit<k_img_count_own<2, 0>>(lds_max) ||
+	    !lds_limit<k_img_count_own<2, 1>>(lds_max)) { (void)hipGetLastError(); return -1; }
+	const int ytag = fmt == YK_FMT_HASH_RNG ? 1 : fmt == YK_FMT_TAGGED ? 2 : 0;
 	const int n_p = phi - plo;
 	const dim3 grid((unsigned)((n_p + 7) / 8 * 8) << rb), blk(1024);
 #define YK_OWN(Wv, Cv) YK_LAUNCH((k_img_count_own<Wv, Cv>), grid, blk, lds, st, (const u64*)rec, bstart, img, plo, n_p, rb, rng_log, kmax, list, list_n, list_cap, ytag)
-	if (hash_only) { if (cross) YK_OWN(1, 1); else YK_OWN(1, 0); }
+	if (fmt != YK_FMT_POS) { if (cross) YK_OWN(1, 1); else YK_OWN(1, 0); }
 	else { if (cross) YK_OWN(2, 1); else YK_OWN(2, 0); }
 #undef YK_OWN
 	return 0;
@@ -499,8 +486,7 @@ int yk_r2_head(void) { const u32 seg = 1u << yk_r2_seg_log(); return (int)(seg /
 void yk_r2_place(const R2Tab *tabs, const R2Act *acts, int P, int p0, int np, u32 bmax, u64 *K0, u64 *K1, const u64 *kc, u64 *pk, u32 *pr, u32 *seg_start,
                  u32 *head, u64 *spill, u32 *spill_n, u32 spill_cap, u32 *fail, u32 *img_u, const u32 *USED, u32 *pcnt, int G, hipStream_t st)
 {
-	static DevOnce attr;
-	if (!attr) { hipFuncSetAttribute((const void*)k_r2_place, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024 + 8192 + 256); attr = true; }
+	lds_limit<k_r2_place>(64 * 1024 + 8192 + 256);
 	const u32 SL = (u32)yk_r2_seg_log(), HD = (u32)yk_r2_head();
 	const u32 nseg = bmax > SL ? 1u << (bmax - SL) : 1, L = bmax > SL ? 1u << SL : 1u << bmax;
 	hipMemsetAsync(spill_n, 0, 4, st);
@@ -670,12 +656,9 @@ int yk_launch_inspect(const u64 *keys, const u64 *off, u64 n, int n_sub, int sub
 	const u64 steps = (n + IN_THREADS * IN_U - 1) / (IN_THREADS * IN_U);
 	const u64 grid = std::max<u64>(std::min<u64>((u64)n_cu * per_cu, steps), (n >> 31) + 1);
 	const bool lng = img.k >= 32;
-	static DevOnce attr;
-	if (!attr) {
-		for (const void *f : { (const void*)k_inspect<false, false>, (const void*)k_inspect<true, false>, (const void*)k_inspect<true, true> })
-			hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-		attr = true;
-	}
+	lds_limit<k_inspect<false, false>>(160 * 1024);
+	lds_limit<k_inspect<true, false>>(160 * 1024);
+	lds_limit<k_inspect<true, true>>(160 * 1024);
 	if (!has_b) YK_LAUNCH((k_inspect<false, false>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
 	else if (lng) YK_LAUNCH((k_inspect<true, true>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
 	else YK_LAUNCH((k_inspect<true, false>), dim3((unsigned)grid), dim3(IN_THREADS), lds, st, a, img);
@@ -724,14 +707,9 @@ int yk_launch_hetmer(int mode, const u64 *keys, const u64 *off, u64 n, int n_sub
 	const int n_cu = cu_count();
 	const u64 per_cu = std::max<u64>(1, std::min<u64>(4, (u64)(160 * 1024) / (lds + (mode == 0 ? 0 : HM_CORNER_BYTES))));
 	const u64 grid = std::max<u64>(std::min<u64>((u64)n_cu * per_cu, yk_hetmer_tiles(n)), (n >> 31) + 1);
-	static DevOnce attr;
-	if (!attr) {
-		/* 128 KiB is the most a launch asks for (the corner, 32 KiB of directory at pre 12, 32 KiB of offsets); COUNT and WRITE hold 32 bytes of static
-		 * LDS besides, so the whole 160 KiB cannot be asked for as dynamic */
-		for (const void *f : { (const void*)k_hetmer<HM_TALLY>, (const void*)k_hetmer<HM_COUNT>, (const void*)k_hetmer<HM_WRITE> })
-			if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) return -1;
-		attr = true;
-	}
+	/* 128 KiB is the most a launch asks for (the corner, 32 KiB of directory at pre 12, 32 KiB of offsets); COUNT and WRITE hold 32 bytes of static
+	 * LDS besides, so the whole 160 KiB cannot be asked for as dynamic */
+	if (!lds_limit<k_hetmer<HM_TALLY>>(128 * 1024) || !lds_limit<k_hetmer<HM_COUNT>>(128 * 1024) || !lds_limit<k_hetmer<HM_WRITE>>(128 * 1024)) return -1;
 	if (mode == 0) YK_LAUNCH((k_hetmer<HM_TALLY>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
 	else if (mode == 1) YK_LAUNCH((k_hetmer<HM_COUNT>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);
 	else YK_LAUNCH((k_hetmer<HM_WRITE>), dim3((unsigned)grid), dim3(HM_THREADS), lds, st, a, img);

@@ -220,7 +220,8 @@ int multi_gpus(const yak_copt_t *opt, std::vector<int> *dev, const char *fn)
 	return N;
 }
 
-static bool multi_open(MultiJob *J, int N, int P, const std::vector<int> &dev, int64_t chunk_dev = 0, bool tagged_only = false)   /* chunk_dev > 0: the chunks are the caller's device buffers of at most that many bytes */
+static int rec_words(RecFmt f) { return (int)(yk_rec_bytes(f) / 8); }   /* the buffers and the exchange count 8-byte words */
+static bool multi_open(MultiJob *J, int N, int P, const std::vector<int> &dev, int64_t chunk_dev = 0, RecFmt widest = YK_FMT_POS)   /* chunk_dev > 0: the chunks are the caller's device buffers of at most that many bytes; widest: the largest records a round will send */
 {
 	J->N = N; J->P = P; J->dev = dev;
 	J->sdev.clear(); J->slot_of.assign(N, 0);
@@ -242,7 +243,7 @@ static bool multi_open(MultiJob *J, int N, int P, const std::vector<int> &dev, i
 	if (chunk_dev > 0) J->chunk = chunk_dev;
 	J->chunk = (J->chunk + 4095) & ~(int64_t)4095;
 	J->ext_base = chunk_dev > 0;
-	J->send_words = (tagged_only ? 1 : 2) * J->chunk;          /* one 16-byte record per position at most (8-byte tagged records use half of it) */
+	J->send_words = rec_words(widest) * J->chunk;               /* one record per position at most */
 	/* a slot receives, for the ranks it hosts, their share of the S - 1 other chunks: (ranks here / N) each on average; refused beyond 1.5 x that */
 	int most = 0;
 	for (int s = 0; s < S; ++s) { int n_here = 0; for (int r = 0; r < N; ++r) n_here += J->slot_of[r] == s; most = std::max(most, n_here); }
@@ -306,7 +307,7 @@ static void multi_close(MultiJob *J)
  * may run one after the other (multi_round) or overlapped round against round (yakamd_count_multi_dev: the partition of round b + 1 runs while round b
  * is on the wire and fed; the two buffer sets make that safe: set x is not touched again before the feed of the round that used it has returned). */
 struct RoundPlan {
-	bool tagged; int W;                                         /* 8-byte tagged records; words per record */
+	RecFmt fmt;                                                 /* of the round's records: YK_FMT_TAGGED or YK_FMT_POS in a create pass (round_fmt), YK_FMT_HASH in a count pass */
 	std::vector<int64_t> fill; std::vector<uint64_t> t0;
 	ExchangePlan X;                                             /* round_plan.h: X.bst is the partition's to fill, the rest round_exchange builds from it */
 	std::string why; std::mutex why_mu;
@@ -314,19 +315,19 @@ struct RoundPlan {
 };
 
 /* 8-byte tagged records: half the exchange; every owner must still be on the exclusive-ownership path */
-static bool round_tagged(MultiJob *J, yak_ch_ext *e, int k, int pre, int create_new)
+static RecFmt round_fmt(MultiJob *J, yak_ch_ext *e, int k, int pre, int create_new)
 {
-	bool tagged = create_new && yakamd_tagged_ok(k, pre) && !yk_knob("YAKAMD_MGPU_REC16", 0);
+	if (!create_new) return YK_FMT_HASH;
+	bool tagged = yakamd_tagged_ok(k, pre) && !yk_knob("YAKAMD_MGPU_REC16", 0);
 	for (int r = 0; r < J->N && tagged; ++r) tagged = e->sub[r] && yakamd_pass_fast(e->sub[r]);
-	return tagged;
+	return tagged ? YK_FMT_TAGGED : YK_FMT_POS;
 }
 
 /* every slot groups the k-mers of its chunk by prefix (its own stream: nothing here waits for, or holds up, the owners' streams) */
-static bool round_partition(MultiJob *J, int x, int k, int pre, int create_new, RoundPlan *R)
+static bool round_partition(MultiJob *J, int x, int k, int pre, RoundPlan *R)
 {
 	const int P = J->P, S = J->S;
-	R->W = create_new && !R->tagged ? 2 : 1;                    /* {hash, position}, or one word (tagged record / bare hash) */
-	for (int s = 0; s < S; ++s) if (R->fill[s] * R->W > J->send_words) { fprintf(stderr, "[E::yak_count] a chunk of %lld positions does not fit the send buffer (%lld words): 16-byte records were not planned for\n", (long long)R->fill[s], (long long)J->send_words); return false; }
+	for (int s = 0; s < S; ++s) if (R->fill[s] * rec_words(R->fmt) > J->send_words) { fprintf(stderr, "[E::yak_count] a chunk of %lld positions does not fit the send buffer (%lld words): 16-byte records were not planned for\n", (long long)R->fill[s], (long long)J->send_words); return false; }
 	R->X.bst.assign(S, std::vector<uint64_t>(P + 1, 0));
 	std::vector<char> ok(S, 1);
 	std::vector<std::thread> th;
@@ -341,9 +342,9 @@ static bool round_partition(MultiJob *J, int x, int k, int pre, int create_new, 
 			if (nb < 0) { if (!J->d_hpc[s]) yk_set_error("out of device memory for the compacted chunk"); ok[s] = 0; R->note(); return; }
 			base = J->d_hpc[s];
 		}
-		const int64_t n = R->tagged ? yakamd_partition_tagged_dev(k, pre, base, nb, J->d_send[x][s], R->X.bst[s].data())
-		                : create_new ? yakamd_partition_dev(k, pre, base, nb, J->d_send[x][s], R->X.bst[s].data())
-		                             : yakamd_partition_hashes_dev(k, pre, base, nb, J->d_send[x][s], R->X.bst[s].data());
+		const int64_t n = R->fmt == YK_FMT_TAGGED ? yakamd_partition_tagged_dev(k, pre, base, nb, J->d_send[x][s], R->X.bst[s].data())
+		                : R->fmt == YK_FMT_POS ? yakamd_partition_dev(k, pre, base, nb, J->d_send[x][s], R->X.bst[s].data())
+		                                       : yakamd_partition_hashes_dev(k, pre, base, nb, J->d_send[x][s], R->X.bst[s].data());
 		if (n < 0) { ok[s] = 0; R->note(); }
 	});
 	for (auto &t : th) t.join();
@@ -356,8 +357,8 @@ static bool round_exchange(MultiJob *J, int x, RoundPlan *R)
 {
 	const int S = J->S;
 	ExchangePlan &X = R->X;
-	X.build(J->N, J->P, S, J->slot_of, R->W);
-	for (int s = 0; s < S; ++s) if ((int64_t)(X.recv[s] * R->W) > J->recv_words) { fprintf(stderr, "[E::yak_count] device %d would receive %llu records in one round: prefixes too unevenly filled for YAKAMD_MGPU_CHUNK\n", J->sdev[s], (unsigned long long)X.recv[s]); return false; }
+	X.build(J->N, J->P, S, J->slot_of, rec_words(R->fmt));
+	for (int s = 0; s < S; ++s) if ((int64_t)(X.recv[s] * rec_words(R->fmt)) > J->recv_words) { fprintf(stderr, "[E::yak_count] device %d would receive %llu records in one round: prefixes too unevenly filled for YAKAMD_MGPU_CHUNK\n", J->sdev[s], (unsigned long long)X.recv[s]); return false; }
 	if (S <= 1) return true;
 	bool ok = true;
 	auto peer_copies = [&]() {
@@ -399,7 +400,7 @@ static bool round_exchange(MultiJob *J, int x, RoundPlan *R)
 }
 
 /* every owner takes its slices, in chunk order = stream order; owners that share a slot take turns (a feed may count a whole slice of the pass) */
-static bool round_feed(MultiJob *J, int x, yak_ch_ext *e, int create_new, RoundPlan *R)
+static bool round_feed(MultiJob *J, int x, yak_ch_ext *e, RoundPlan *R)
 {
 	const int N = J->N, S = J->S;
 	std::vector<char> ok(N, 1);
@@ -409,9 +410,9 @@ static bool round_feed(MultiJob *J, int x, yak_ch_ext *e, int create_new, RoundP
 		for (const RoundSlice &f : R->X.feed[d]) {
 			const int s = f.slot;
 			const uint64_t *rec = (f.own ? J->d_send[x][sd] : J->d_recv[x][sd]) + f.off;
-			const int rc = R->tagged ? yakamd_feed_partitioned_tagged_dev(e->sub[d], rec, (int64_t)f.cnt, f.ob.data(), R->t0[s], (uint64_t)R->fill[s], 0)
-			             : create_new ? yakamd_feed_partitioned_dev(e->sub[d], rec, (int64_t)f.cnt, f.ob.data(), R->t0[s], (uint64_t)R->fill[s])
-			                          : yakamd_count_partitioned_dev(e->sub[d], rec, (int64_t)f.cnt, f.ob.data());
+			const int rc = R->fmt == YK_FMT_TAGGED ? yakamd_feed_partitioned_tagged_dev(e->sub[d], rec, (int64_t)f.cnt, f.ob.data(), R->t0[s], (uint64_t)R->fill[s], 0)
+			             : R->fmt == YK_FMT_POS ? yakamd_feed_partitioned_dev(e->sub[d], rec, (int64_t)f.cnt, f.ob.data(), R->t0[s], (uint64_t)R->fill[s])
+			                                    : yakamd_count_partitioned_dev(e->sub[d], rec, (int64_t)f.cnt, f.ob.data());
 			if (rc != 0) { ok[d] = 0; R->note(); }
 		}
 		if (hipStreamSynchronize(yk_ctx_stream(((yak_ch_ext*)e->sub[d])->ctx)) != hipSuccess) ok[d] = 0;   /* the copies out of this set's buffers are done before the set is filled again */
@@ -425,8 +426,8 @@ static bool multi_round(MultiJob *J, int x, yak_ch_ext *e, int k, int pre, int c
 {
 	RoundPlan R;
 	R.fill = fill; R.t0 = t0;
-	R.tagged = round_tagged(J, e, k, pre, create_new);
-	const bool ok = round_partition(J, x, k, pre, create_new, &R) && round_exchange(J, x, &R) && round_feed(J, x, e, create_new, &R);
+	R.fmt = round_fmt(J, e, k, pre, create_new);
+	const bool ok = round_partition(J, x, k, pre, &R) && round_exchange(J, x, &R) && round_feed(J, x, e, &R);
 	if (!ok && why && why->empty()) *why = R.why;
 	return ok;
 }
@@ -643,8 +644,8 @@ extern "C" yak_ch_t *yakamd_count_multi_dev(const yak_copt_t *opt, yak_ch_t *h0,
 		for (int i = 0; i < n_rounds * (int)sd.size(); ++i) cmax = std::max<int64_t>(cmax, n_bytes[i]);
 	}
 	if (cmax > ((int64_t)1 << 31) - 4096) { fprintf(stderr, "[E::yakamd_count_multi_dev] a chunk holds at most 2^31 - 4096 stream positions\n"); if (!h0) yak_ch_destroy(h); return 0; }
-	const bool tagged_only = create_new && yakamd_tagged_ok(opt->k, opt->pre) && !yk_knob("YAKAMD_MGPU_REC16", 0) && env_fast_default();
-	bool ok = multi_open(&J, N, P, dev, cmax, tagged_only || !create_new);
+	const RecFmt widest = !create_new ? YK_FMT_HASH : yakamd_tagged_ok(opt->k, opt->pre) && !yk_knob("YAKAMD_MGPU_REC16", 0) && env_fast_default() ? YK_FMT_TAGGED : YK_FMT_POS;
+	bool ok = multi_open(&J, N, P, dev, cmax, widest);
 	const int S = J.S;
 	yk_realtime();
 	ok = ok && begin_passes(e, N, create_new);
@@ -664,12 +665,12 @@ extern "C" yak_ch_t *yakamd_count_multi_dev(const yak_copt_t *opt, yak_ch_t *h0,
 			r.t0[s] = t_stream; t_stream += (uint64_t)r.fill[s];
 			J.d_base[b & 1][s] = (uint8_t*)d_chunk[(size_t)b * S + s];
 		}
-		r.tagged = round_tagged(&J, e, opt->k, opt->pre, create_new);
+		r.fmt = round_fmt(&J, e, opt->k, opt->pre, create_new);
 	};
 	std::thread part;
 	bool part_ok = true;
 	double t_part = 0, t_wait = 0, t_exch = 0, t_feed = 0;        /* YAKAMD_VERBOSE: the partition thread's time; this thread's wait for it, exchange, feed */
-	auto start_partition = [&](int b) { part = std::thread([&, b]() { const double t0 = yk_realtime(); part_ok = round_partition(&J, b & 1, opt->k, opt->pre, create_new, &R[b & 1]); t_part += yk_realtime() - t0; }); };
+	auto start_partition = [&](int b) { part = std::thread([&, b]() { const double t0 = yk_realtime(); part_ok = round_partition(&J, b & 1, opt->k, opt->pre, &R[b & 1]); t_part += yk_realtime() - t0; }); };
 	const double t_rounds0 = yk_realtime();
 	if (ok && n_rounds > 0) { prepare(0); start_partition(0); }
 	for (int b = 0; b < n_rounds && ok; ++b) {
@@ -680,7 +681,7 @@ extern "C" yak_ch_t *yakamd_count_multi_dev(const yak_copt_t *opt, yak_ch_t *h0,
 		t_wait += yk_realtime() - t0; t0 = yk_realtime();
 		ok = ok && round_exchange(&J, b & 1, &R[b & 1]);
 		t_exch += yk_realtime() - t0; t0 = yk_realtime();
-		ok = ok && round_feed(&J, b & 1, e, create_new, &R[b & 1]);
+		ok = ok && round_feed(&J, b & 1, e, &R[b & 1]);
 		t_feed += yk_realtime() - t0;
 		if (!ok && why.empty()) why = !R[b & 1].why.empty() ? R[b & 1].why : R[(b + 1) & 1].why;
 	}

@@ -15,6 +15,28 @@ typedef ulonglong2 Rec;                  /* one k-mer instance: .x = yak_hash64 
 #define YK_TINF    0xFFFFFFFFFFFFFFFFull     /* "never" */
 #define YK_FLAG_FP 1u                        /* first occurrence passed the bloom gate */
 
+/* Tagged 8-byte level-1 record (k < 32, 2k - pre <= 52): (hash >> pre) << 12 | toggle << 10 | position inside the 1024-position
+ * round of the partitioning workgroup.  Inside a bucket the records of one round are contiguous and the rounds follow each other in
+ * stream order (the write combining is stable at round granularity); the toggle bit flips between consecutive rounds that
+ * contributed to the bucket, across workgroups too (the histogram sweep counts them), so the level-2 partition recovers every
+ * record's rank in the sub-table's stream: the "time" that orders put-calls.  Stream positions are not stored at all. */
+#define YK_R8_TAG_BITS 12
+#define YK_R8_TOGGLE   (1u << 10)
+
+/* What a buffer of level-1 records holds; it travels as `const void *` beside its RecFmt.  A Chunk2 holds the first two,
+ * and the level-2 kernels compare Chunk2::fmt with these values */
+enum RecFmt {
+	YK_FMT_POS = 0,                      /* Rec {hash, position}, 16 bytes */
+	YK_FMT_TAGGED = 1,                   /* the tagged record above, 8 bytes */
+	YK_FMT_HASH = 2,                     /* the bare hash, 8 bytes */
+	YK_FMT_HASH_RNG = 3                  /* the hash with the sub-table's own bits (the bucket says them) replaced by the top bits of its home-slot product: k_img_count_own's range test, 8 bytes */
+};
+static inline size_t yk_rec_bytes(RecFmt f) { return f == YK_FMT_POS ? sizeof(Rec) : 8; }
+static inline size_t yk_rec_units(RecFmt f, size_t n) { return (n * yk_rec_bytes(f) + sizeof(Rec) - 1) / sizeof(Rec); }   /* elements of a DevBuf<Rec> that hold n records */
+extern "C" int64_t yk_knob(const char *name, int64_t dflt);   /* pool.cpp: a run-time setting -- the test hook's value (yakamd_test_set), else (public names only) the environment's, else dflt */
+/* tagged records fit this k and prefix: a one-word hash whose bits above `pre` leave the tag its room, and no more buckets than k_xpart_wcs takes */
+static inline bool yk_tagged_fits(int k, int pre) { return k < 32 && 2 * k - pre <= 64 - YK_R8_TAG_BITS && pre <= 10 && yk_knob("YAKAMD_REC8", 1) != 0; }
+
 /* the inverse of yak_hash64 (reference yak-priv.h:41-68): one definition for the host (yak_ch_getseq) and the device (kern_print.inc) */
 __host__ __device__ static inline u64 yk_hash64_inv(u64 x, u64 m)
 {
@@ -72,8 +94,10 @@ extern "C" {
 void yk_launch_extract(const uint8_t *bases, int64_t pos0, int64_t n, int64_t t_sub, int k, int pre, int plo, int phi,
                        u64 *out_hash, u32 *out_t, u64 *cursor, hipStream_t st);
 void yk_launch_pack(const uint8_t *a, int64_t n, u32 *codes, u32 *valid, hipStream_t st);
+/* the level-1 partition of the k-mers ending at [pos0, n): records of any RecFmt to `out`, grouped by their nb_bits-bit prefix; bucket starts and record count to
+ * bstart[0 .. 1 << nb_bits].  YK_FMT_TAGGED and YK_FMT_HASH_RNG need k < 32, nb_bits <= 10 (the caller checks).  valid != 0: `bases` is the packed 2-bit image */
 void yk_launch_xpart(const uint8_t *bases, int64_t pos0, int64_t n, int64_t t_sub, int k, int pre, int plo, int phi,
-                     int nb_bits, u32 *rows, u64 *partial, u64 *bstart, Rec *out, int hash_only, hipStream_t st, const u32 *valid = 0);   /* valid != 0: `bases` is the packed 2-bit image (yakamd_feed_packed_dev) */   /* hash_only: 0 = Rec, 1 = bare hashes, 2 = tagged 8-byte records */
+                     int nb_bits, u32 *rows, u64 *partial, u64 *bstart, void *out, RecFmt fmt, hipStream_t st, const u32 *valid = 0);
 void yk_launch_rpart(const u64 *in_hash, const u32 *in_t, int64_t n, int pre, int plo, int phi,
                      int nb_bits, u32 *rows, u64 *partial, u64 *bstart, Rec *out, hipStream_t st);
 int yk_xpart_blocks(int64_t n_pos);
@@ -161,7 +185,7 @@ int64_t yk_hpc_tiles(int packed, int64_t n);
 void yk_launch_hpc_count(const void *in, const u32 *valid, int64_t n, u32 *tcnt, hipStream_t st);
 void yk_launch_hpc_scatter(const void *in, const u32 *valid, int64_t n, const u64 *toff, uint8_t *out, hipStream_t st);
 void yk_launch_hpc_remap(const uint8_t *a, int64_t n, const u64 *toff, const u64 *off, const u32 *len, int64_t n_seq, u64 *off_out, u32 *len_out, hipStream_t st);
-int yk_launch_img_count_lds(const void *rec, int hash_only, const u64 *bstart, ImgView img, int plo, int phi, size_t lds, u64 *compact, u32 stride, hipStream_t st);
+int yk_launch_img_count_lds(const void *rec, RecFmt fmt, const u64 *bstart, ImgView img, int plo, int phi, size_t lds, u64 *compact, u32 stride, hipStream_t st);
 void yk_launch_img_count_h(const u64 *hash, int64_t n, ImgView img, hipStream_t st);
 void yk_launch_img_inc(ImgView img, u64 hash, u64 *out2, hipStream_t st);
 void yk_launch_img_fold(ImgView img, u64 n_slots, hipStream_t st);
@@ -198,7 +222,6 @@ struct ResizeTask { u32 old_bits, new_bits, rehash, pad; u64 old_off, new_off; }
 void yk_launch_resize(const ResizeTask *tasks, int P, const u64 *old_keys, const u32 *old_used, u64 *new_keys, u32 *new_used, u32 *scr_used, hipStream_t st);
 void yk_launch_keys_to_hashes(const u64 *kc, const u64 *seg_off, int P, int pre, u64 *hash, u32 *t, hipStream_t st, unsigned short *cnt = 0);   /* cnt != 0: the keys' counts as well */
 void yk_launch_img_add_counts(const u64 *hash, const unsigned short *cnt, u64 n, ImgView img, int plo, int phi, u32 *missing, hipStream_t st);
-int64_t yk_knob(const char *name, int64_t dflt);             /* pool.cpp: a run-time setting -- the test hook's value (yakamd_test_set), else (public names only) the environment's, else dflt */
 void yk_launch_put_u64(const u64 *pos, const u64 *val, u32 n, u64 *out, hipStream_t st);
 
 #ifdef __cplusplus
@@ -218,17 +241,9 @@ struct Chunk2 {                     /* one level-2 partition work item: a run of
 	u64 spare;
 	u32 n, bucket;
 	u32 tbase;                      /* added to tlo: time relative to the start of the pass */
-	u32 pad;                        /* record format of the chunk: 0 = Rec {hash, position}; 1 = tagged 8-byte records (YK_R8_*), tbase = records of this bucket in earlier batches */
-	u32 before, after;              /* format 1: records of the same bucket of the same batch lying before / behind the chunk in memory */
+	u32 fmt;                        /* RecFmt of the chunk: YK_FMT_POS, or YK_FMT_TAGGED (tbase = records of this bucket in earlier batches) */
+	u32 before, after;              /* YK_FMT_TAGGED: records of the same bucket of the same batch lying before / behind the chunk in memory */
 };
-
-/* Tagged 8-byte level-1 record (k < 32, 2k - pre <= 52): (hash >> pre) << 12 | toggle << 10 | position inside the 1024-position
- * round of the partitioning workgroup.  Inside a bucket the records of one round are contiguous and the rounds follow each other in
- * stream order (the write combining is stable at round granularity); the toggle bit flips between consecutive rounds that
- * contributed to the bucket, across workgroups too (the histogram sweep counts them), so the level-2 partition recovers every
- * record's rank in the sub-table's stream: the "time" that orders put-calls.  Stream positions are not stored at all. */
-#define YK_R8_TAG_BITS 12
-#define YK_R8_TOGGLE   (1u << 10)
 
 struct FastParams {
 	int pre, k, s2_bits;            /* sub-buckets per sub-table = 1 << s2_bits */
@@ -281,7 +296,7 @@ int yk_r2_small_f(void);
 int yk_r2_seg_log(void);
 int yk_r2_head(void);
 size_t yk_count_own_lds(u32 range_len, u32 kmax);
-int yk_launch_img_count_own(const void *rec, int hash_only, int cross, int ytag, const u64 *bstart, ImgView img, int plo, int phi, int rb, int rng_log, u32 kmax,
+int yk_launch_img_count_own(const void *rec, RecFmt fmt, int cross, const u64 *bstart, ImgView img, int plo, int phi, int rb, int rng_log, u32 kmax,
                             size_t lds, u64 *list, u32 *list_n, u32 list_cap, hipStream_t st);
 int yk_lc2_ok(FastParams fp);
 int yk_lc2_per_sb(int bloom_mode);
