@@ -17,11 +17,12 @@
  *     recount  the counts of a table's k-mers in other sequences, reference main.c:66-88 (restore, tighten, yak_recount)
  *     subtract, isec   the k-mers of the first table absent from / present in the others, reference main.c:217-284
  *     version  the library's YAKS_VERSION
- * and six beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table), hetmers
+ * and seven beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table), hetmers
  * (yakamd_hetmers: the pairs of k-mers of a count table that differ in the middle base alone), cover (yakamd_cover: the bases of every sequence
  * that lie inside k-mers a table holds, lacks or holds too often -- as a table, as intervals or as a masked FASTA), unitigs (yakamd_unitigs: the
- * de Bruijn graph the k-mers of a count table span, as its unitigs in FASTA or as its tallies) and paths (yakamd_paths: the sequences of a file as
- * paths through those unitigs, as GAF or as tallies per sequence).  `count -c` and `qv -c` work in homopolymer-compressed
+ * de Bruijn graph the k-mers of a count table span, as its unitigs in FASTA or as its tallies), paths (yakamd_paths: the sequences of a file as
+ * paths through those unitigs, as GAF or as tallies per sequence) and bubbles (yakamd_bubbles: the forks of that graph whose two arms join again,
+ * with their types and alleles).  `count -c` and `qv -c` work in homopolymer-compressed
  * space (yakamd_count_hpc; yakamd_ch_set_hpc on the restored table): every run of one base is one base before k-mers are taken.
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
@@ -34,6 +35,7 @@
 #include "yak_amd_walk.h"  /* yakamd_unitigs_dev (unitigs -g) */
 #include "yak_amd_gfa.h"   /* yakamd_unitigs_gfa (unitigs -G) */
 #include "yak_amd_path.h"  /* yakamd_paths (paths) */
+#include "yak_amd_bubble.h" /* yakamd_bubbles (bubbles) */
 #include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_cover, yakamd_unitigs, yakamd_count_hpc and yakamd_ch_set_hpc */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
@@ -613,6 +615,37 @@ static int cmd_paths(int argc, char **argv)
 	return rc;
 }
 
+/* ---- bubbles (not in the reference) ---- */
+/* the simple bubbles of the unitig graph of a count table -- a fork whose two arms are one unitig each and join again --, a line per bubble with
+ * its type (SNP, equal length, indel) and its two alleles, or with -s the tallies of `unitigs -G -s` and a B line (yakamd_bubbles of
+ * libyak_amd_bubble.so) */
+static int cmd_bubbles(int argc, char **argv)
+{
+	yakamd_ugopt_t o;
+	const char *out = 0;
+	int stats = 0, min_cnt = 1;
+	yakamd_ugopt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'c', ARG_I32, &min_cnt, "a k-mer with a count below this is absent, 1 .. 1023 [1]" },
+		{ 's', ARG_FLAG, &stats, "the tallies of the graph, its unitigs and links, and of the bubbles, forks and tips, not the bubbles" },
+		{ 'o', ARG_TEXT, &out, "write the output here; stdout without it" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first >= argc) { arg_help("bubbles [options] <table.yak>", defs, nd); return 1; }
+	uint32_t k = 0, pre = 0;
+	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd bubbles: %s is not a readable .yak file\n", argv[first]); return 2; }
+	if (!(k & 1)) { fprintf(stderr, "yak-amd bubbles: %s has k = %u: the graph is defined for an odd k only\n", argv[first], k); return 2; }
+	if (k >= 32) { fprintf(stderr, "yak-amd bubbles: %s has k = %u: k must be below 32\n", argv[first], k); return 2; }
+	if (min_cnt < 1 || min_cnt > 1023) { fprintf(stderr, "yak-amd bubbles: -c must be in [1, 1023]\n"); return 1; }
+	o.min_cnt = min_cnt; o.stats_only = stats;
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd bubbles: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	const int rc = yakamd_bubbles(&o, tab, out) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 /* ---- hetmers (not in the reference) ---- */
 /* the pairs of k-mers of a count table that differ in the middle base alone, as a histogram of their two counts (yakamd_hetmers) */
 static int cmd_hetmers(int argc, char **argv)
@@ -685,6 +718,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && strcmp(argv[1], "cover") == 0) return cmd_cover(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "unitigs") == 0) return cmd_unitigs(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "paths") == 0) return cmd_paths(argc - 1, argv + 1);
+	if (argc >= 2 && strcmp(argv[1], "bubbles") == 0) return cmd_bubbles(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
 	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-8s %s\n", cmds[i].name, cmds[i].what);
 	fprintf(stderr, "  beyond the reference:\n      yak-amd %-8s %s\n", "sum", "add the counts of two or more .yak tables together");
@@ -693,5 +727,6 @@ int main(int argc, char **argv)
 	fprintf(stderr, "      yak-amd %-8s %s\n", "cover", "the bases of each sequence that lie inside k-mers a .yak table holds, lacks or holds too often");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "unitigs", "the unitigs of the de Bruijn graph that the k-mers of a .yak table span");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "paths", "sequences as paths through the unitigs of that graph (GAF)");
+	fprintf(stderr, "      yak-amd %-8s %s\n", "bubbles", "the simple bubbles of that graph: forks whose two arms join again, with their alleles");
 	return 1;
 }
