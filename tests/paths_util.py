@@ -93,7 +93,7 @@ R2_SEGMENTED = ["k_r2_place", "k_r2_spill", "k_r2_headfill", "k_r2_publish"]   #
 # (up to 9) with -b28 only; without a switch s2 = 1 / 1 / 2 / 1, below the write-combining scatters' 4 bits (k_part2<1>).  Tagged 8-byte records in
 # and out (k < 32, np_max < 2^(12 + s2)).
 EVERY_INSERT_PATH = {
-    # engine_pass.cpp pass_begin: c->fast = ... YAKAMD_FAST != 0 -> consume_records' create_new branch; pass_end_body's accumulator branch
+    # engine_pass.cpp pass_begin: c->fast = ... YAKAMD_FAST != 0 -> acc_records per batch; acc_finish at the end of the pass (engine_acc.cpp)
     "general_path": E(["k_acc_init", "k_bf_check", "k_bf_mapfill", "k_bf_resolve", "k_acc_insert", "k_select_count", "k_select_scatter", SORT256, "k_bf_test", "k_bf_set", "k_lastput", "k_xpart_wc<1>"], FAST_ONLY, slices="==0", fast_abandoned="==0"),
     # slice_plan: s2 = 0; with a filter nb - 9 - s2 > 7, so yk_lc2_ok refuses and slice_count sends every sub-bucket on (h_cnt[YKC_NOVF2] = n_all)
     "lds_overflow_to_global": E(["k_lds_count_ovf", P2_PLAIN], [WC8_7, WC8_8], lc2_passed_on=">0", ovf_groups=">0", ovf_more_groups="==0"),   # -b28: nb - 9 - 0 = 9 > 7
@@ -101,7 +101,7 @@ EVERY_INSERT_PATH = {
     "budget_exceeded_midpass": E(["k_acc_insert", "k_select_scatter", SORT256], FAST_ONLY, fast_abandoned=">0", slices="==0"),
     # yk_launch_part2: fp.s2_bits >= 4 fails -> k_part2<1>
     "s2_3_multibatch": E([P2_PLAIN, "k_xpart_wcs<true,31>", "k_xpart_wcs<true>"], [WC8_7, WC8_8, WC8_T, P2_WC16], slices=">0", early_slices="==0", fast_abandoned="==0"),
-    # pass_begin: nb_bits = 6 != pre -> c->fast = false; count pass: count_own_plan / count_lds_bytes / count_by_ranges all want nb_bits == pre -> k_img_count_h
+    # pass_begin: nb_bits = 6 != pre -> c->fast = false; count pass: count_plan: key-owning ranges, LDS ranks and home-slot ranges all want nb_bits == pre -> k_img_count_h
     "part6_general": E(["k_acc_insert", "k_xpart_wc<1>", "k_img_count_h"], FAST_ONLY + ["k_img_count_own*", "k_img_count_lds*", "k_img_count_rng*"], slices="==0"),
     # yk_launch_part2: rec8_out, rec8_in, seg = 64 <= 1024, YAKAMD_P2_CAP7 != 0
     "write_combined_level2": E([WC8_7], [WC8_8, WC8_T, WC8_R, P2_WC16]),
@@ -110,20 +110,20 @@ EVERY_INSERT_PATH = {
     "write_combined_level2_segments": E([WC8_8], [WC8_T, WC8_R, P2_WC16]),
     # yk_launch_part2: wc = YAKAMD_P2_WC = 0 -> the last branch
     "plain_scatters": E([P2_PLAIN], [WC8_7, WC8_8, WC8_T, WC8_R, P2_WC16]),
-    # consume_records (count pass): count_own returns 1, count_lds_bytes 0 -> count_by_ranges
+    # count_records: count_plan finds neither key-owning ranges nor LDS ranks -> YK_COUNT_RANGES, count_by_ranges
     "range_count_whole_table": E(["k_hpart2<0>", "k_hpart2<1>", RNG], [RNGX, "k_img_count_own*", "k_img_count_lds*"], rng_sweeps="==0"),
     "range_count_split": E(["k_hpart2<1>", RNG, "k_img_count_h"], [RNGX, "k_img_count_own*", "k_img_count_lds*"], rng_sweeps="==0"),   # xn[0] boundary-crossing instances -> k_img_count_h
-    # count_by_ranges: xn[1] (list too small) -> the cross sweep
+    # count_by_ranges (XList::run): xn[1] (list too small) -> the cross sweep
     "range_count_cross_sweep": E([RNG, RNGX], ["k_img_count_own*"], rng_sweeps=">0"),
     "range_count_short_list": E([RNG, RNGX], ["k_img_count_own*"], rng_sweeps=">0"),
-    # consume_records: all three refuse -> !lds_done, YK_FMT_HASH
+    # count_plan: all three refused -> YK_COUNT_ATOMICS, YK_FMT_HASH
     "count_with_device_atomics": E(["k_img_count_h"], ["k_img_count_own*", "k_img_count_lds*", "k_img_count_rng*", "k_hpart2*"]),
-    # count_lds_bytes > 0 -> yk_launch_img_count_lds, YK_FMT_HASH
+    # count_plan: YK_COUNT_LDS -> yk_launch_img_count_lds, YK_FMT_HASH
     "count_lds_rank_kernel": E(["k_img_count_lds<1>"], ["k_img_count_own*", "k_img_count_rng*", "k_img_count_h", "k_img_count_lds<2>"]),
-    # count_own_plan: the LDS budget leaves 32-slot ranges (THIN_INPUT: sub-tables of 1024 / 2048 slots; a whole table of up to ~250 keys is cheaper
-    # than any range of it, e + e / 8 + 192 keys of room); the list holds every boundary-crossing instance -> count_own's k_img_count_h over it
+    # count_plan, key-owning ranges: the LDS budget leaves 32-slot ranges (THIN_INPUT: sub-tables of 1024 / 2048 slots; a whole table of up to ~250 keys is cheaper
+    # than any range of it, e + e / 8 + 192 keys of room); the list holds every boundary-crossing instance -> XList::run's k_img_count_h over it
     "key_owning_count_32_slot_ranges": E([OWN_H, "k_xpart_wcs<false>", "k_img_count_h"], [OWN_HX, "k_img_count_rng*", "k_img_count_lds*"], own_sweeps="==0"),
-    # count_own: xn[1] -> the cross sweep
+    # count_own (XList::run): xn[1] -> the cross sweep
     "key_owning_count_cross_sweep": E([OWN_H, OWN_HX], ["k_img_count_rng*"], own_sweeps=">0"),
     "key_owning_count_short_list": E([OWN_H, OWN_HX], ["k_img_count_rng*"], own_sweeps=">0"),
     # yk_lc2_ok: YAKAMD_LC2 = 0 -> slice_count's !lc2 branch
@@ -210,7 +210,7 @@ EVERY_INSERT_PATH = {
 }
 # cases of test_every_insert_path_is_exact whose path needs larger sub-tables than synth(20000, g=90000) gives (~540 keys, 1024 slots, without a
 # filter; ~100 keys with one): the same reads over a 2 Mb genome, 1.5 x -- ~2 300 keys per sub-table (4096 slots: several segments of 1024 or 2048
-# slots for the streaming replay) without a filter, 500-1 400 with one (enough for count_own_plan to cut ranges)
+# slots for the streaming replay) without a filter, 500-1 400 with one (enough for count_plan to cut ranges)
 THIN_INPUT = {"streaming_replay_1k_slot_segments", "streaming_replay_2k_slot_segments", "streaming_replay_keys_grouped_by_3_workgroups",
               "streaming_replay_keys_grouped_by_16_workgroups_6_wave_doubling",
               "key_owning_count_32_slot_ranges", "key_owning_count_cross_sweep", "key_owning_count_short_list", "pass2_plain_hashes_cross_sweep"}
@@ -222,7 +222,7 @@ REPLAY_VARIANTS = {
     "lds_ranks": K_REPLAY, "global_ranks": K_REPLAY, "lds_16bit_ranks": K_REPLAY,
     # kern_layout.inc: the parallel doubling is skipped under YAKAMD_PAR_REPLAY = 0 (no scratch for it: sp == 0)
     "serial_doubling": E(["k_replay"], [], par_ok="==0", par_fail="==0"),
-    # count_by_ranges: bmax = 12 > RNG_LOG = 10 -> rb = 2
+    # count_plan: bmax = 12 > RNG_LOG = 10 -> rb = 2
     "pass2_by_slot_ranges": E(["k_hpart2<0>", "k_hpart2<1>", RNG], ["k_img_count_own*", "k_img_count_lds*"], rng_sweeps="==0"),
     "pass2_ranges_list_overflow": E([RNG, RNGX], ["k_img_count_own*"], rng_sweeps=">0"),
     "streaming_replay_2k_slot_segments": E(["k_r2_ppart"] + R2_SEGMENTED, ["k_r2_ppart_cnt"], r2_used=">0", r2_refused="==0"),
@@ -270,7 +270,7 @@ SECOND_PASS_RETAINED = {
     "prefix_records_many_batches": E([LC2_FILTER, OWN_H], ["k_cnt2*", LC2_NOSTAGE_W6], pass2_prefix=">0", pass2_none="==0"),
     # slice_plan: budget 0 -> nothing kept; yakamd_count_retained returns 1 and the test feeds the input
     "budget_refuses": E([LC2_FILTER, OWN_H], ["k_cnt2*"], pass2_none=">0", pass2_fused="==0", pass2_prefix="==0"),
-    # count_own_plan returns 1 -> 1; the feed then counts with k_img_count_lds
+    # count_plan refuses tagged records -> 1; the feed then counts with k_img_count_lds
     "count_kernel_not_applicable": E(["k_img_count_lds<1>"], ["k_cnt2*", "k_img_count_own*"], pass2_none=">0", pass2_prefix="==0"),
     # small_max = -1 -> the 2048-slot table
     "subbucket_records_big_lds_table": E(["k_cnt2<2048,1280>"], ["k_cnt2<512,320>"], pass2_recount=">0", pass2_fused="==0"),
@@ -308,9 +308,9 @@ SUB_BUCKETS_PASSED_ON = {"": E([LC2_NOSTAGE_W6, "k_lds_count_ovf", "k_cnt2_apply
 # ::test_seg_sort_pass_of_long_segments (test_gpu_parity.py): slice_sort's sort_big = n_sel / (phi - plo) >= 30000
 LONG_SEGMENTS = {"": E([SORT1024], [SORT256, "k_ts_rank"], rank_refused="==0")}
 
-# ---- test_gpu_parity.py::test_count_pass_over_hashed_records ----  consume_records with YK_FMT_POS: the W = 2 / MODE 2 instances
+# ---- test_gpu_parity.py::test_count_pass_over_hashed_records ----  count_records with YK_FMT_POS: the W = 2 / MODE 2 instances
 HASHED_RECORDS = {
-    # count_own and count_lds_bytes refuse, count_by_ranges wants hashes alone -> !lds_done, YK_FMT_POS
+    # count_plan: key-owning ranges and LDS ranks refused, the home-slot ranges want hashes alone -> YK_COUNT_ATOMICS, YK_FMT_POS
     "device_atomics": E(["k_rpart<0>", "k_rpart<1>", "k_img_count"], ["k_img_count_own*", "k_img_count_lds*", "k_img_count_rng*", "k_img_count_h"]),
     "lds_rank_kernel": E(["k_img_count_lds<2>"], ["k_img_count_own*", "k_img_count_lds<1>", "k_img_count", "k_img_count_h"]),
     # yk_launch_img_count_own: YK_FMT_POS -> W = 2; the crossing instances of the 32-slot ranges go through the list (k_img_count_h)
@@ -405,7 +405,7 @@ ADVERSARIAL_B22 = {
 }
 # pass 2 on the clustered tables, keyed by the row; every case of test_gpu_adversarial.PASS2_CASES runs under each, with -b22 (k = 31) and -b20 (k = 21), in one tally.
 # `retained`: both passes on one device image with yakamd_retain_input (the protocol of test_second_pass_counts_the_records_the_first_pass_retained);
-# else count_protocol_host, whose count pass feeds the input again (feed_image -> consume_records -> count_own / count_by_ranges / k_img_count_h)
+# else count_protocol_host, whose count pass feeds the input again (feed_image -> consume_records -> count_records: count_own / count_by_ranges / k_img_count_h)
 ADVERSARIAL_PASS2_ROWS = {
     "fused": dict(retained=1), "cnt2_unfused": dict(retained=1, YAKAMD_CNT2_FUSED="0"), "retain2_off": dict(retained=1, YAKAMD_RETAIN2="0"),
     "count_atomics": dict(YAKAMD_COUNT_OWN="0", YAKAMD_COUNT_LDS="0", YAKAMD_COUNT_RNG="0"),
@@ -417,11 +417,11 @@ ADVERSARIAL_PASS2 = {
     "fused": E(["k_cnt2_apply"], ["k_cnt2<*"], pass2_fused=">0", pass2_none="==0"),
     "cnt2_unfused": E(["k_cnt2_apply"], [], pass2_recount=">0", pass2_fused="==0"),                    # YAKAMD_CNT2_FUSED = 0: k_cnt2 counts again
     "retain2_off": E([OWN_H], ["k_cnt2*"], pass2_prefix=">0", pass2_none="==0"),                       # slice_retain: the level-1 records; consume_records
-    # consume_records: count_own, count_lds_bytes and count_by_ranges all refuse -> every instance walks its chain with device atomics
+    # count_plan: key-owning ranges, LDS ranks and home-slot ranges all refused -> every instance walks its chain with device atomics
     "count_atomics": E(["k_img_count_h"], ["k_img_count_own*", "k_img_count_lds*", "k_img_count_rng*", "k_hpart2*"]),
     # count_by_ranges: ranges of 32 slots; a chain that leaves its range is an exception, and a list of no entries sends them all to the cross sweep
     "ranges_32_slots_no_list": E([RNG, RNGX], ["k_img_count_own*"], rng_sweeps=">0"),
-    # count_own_plan: 18700 B leave room for ~228 keys (yk_count_own_lds): ranges of 64 slots and fewer; the instances whose key sits beyond their
+    # count_plan: 18700 B leave room for ~228 keys (yk_count_own_lds): ranges of 64 slots and fewer; the instances whose key sits beyond their
     # home slot's range -- all but a few of a cluster's -- go through the list (k_img_count_h), or with no list through the cross sweep
     "own_lds": E([OWN_H, "k_img_count_h"], [OWN_HX, "k_img_count_rng*", "k_img_count_lds*"], own_sweeps="==0"),
     "own_lds_no_list": E([OWN_H, OWN_HX], ["k_img_count_rng*"], own_sweeps=">0"),

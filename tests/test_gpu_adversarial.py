@@ -78,7 +78,7 @@ def test_one_block_at_the_staged_table_bound(name, ya, inputs):
     paths_util.hold(ran, paths_util.ADVERSARIAL_B22[name], paths_util.names(ya.lib()), name)
 
 
-# fewer than 2^12 records per sub-table: their level-2 records can be kept; and tables of 32 slots or more with either k: count_own_plan has no range
+# fewer than 2^12 records per sub-table: their level-2 records can be kept; and tables of 32 slots or more with either k: count_plan has no key-owning range
 # for a smaller one (hot_block_probes_600 has 4 keys at k = 21) and hands it to k_img_count_lds, which test_gpu_parity's count_kernel_not_applicable covers
 PASS2_CASES = ("hot_block_769", "one_home_last_1544", "one_home_mid_392", "segment_mid_12_513")
 

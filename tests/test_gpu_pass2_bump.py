@@ -1,6 +1,6 @@
 """yak_ch_clear is deferred (engine_table.cpp yk_ctx_clear: k_img_clear runs when the image is next read or written), and the count pass over the
 input of the pass before takes a pending clear over: one sweep raises every count by one and k_cnt2_apply probes only the keys whose count is
-something else (engine_pass.cpp yakamd_count_retained; the rule itself: tests/test_pass2_bump.py).  Against the oracle, byte for byte: the
+something else (engine_count.cpp yakamd_count_retained; the rule itself: tests/test_pass2_bump.py).  Against the oracle, byte for byte: the
 protocol with that branch on and off (YAKAMD_PASS2_BUMP), everything that can look at a table between a clear and the next pass, the retained sets
 that must not take the branch, and a count pass without a clear in front."""
 import contextlib

@@ -1,4 +1,4 @@
-"""The invariant behind the count pass that raises every count in one sweep (engine_pass.cpp yakamd_count_retained), stated
+"""The invariant behind the count pass that raises every count in one sweep (engine_count.cpp yakamd_count_retained), stated
 against the oracle alone, no GPU: in the filtered two-pass protocol (reference main.c:53-57, htab.c:62-74) the first pass counts every occurrence of
 a k-mer but the first, which the filter takes, and the second pass counts every occurrence.  So after "pass 1, clear, pass 2 on the same reads" a
 key's count c2 is min(c1 + 1, 1023), c1 its count after pass 1 -- except for the keys whose first occurrence the filter let through at once (a

@@ -1,7 +1,7 @@
 /*
  * engine_ctx.cpp -- the context of a table in the MI355X counting engine behind yak.h: error text, device count, the stream and event cache,
  * context create and destroy, shard and HPC settings, the host mirror, the scratch buffer and the one-line accessors.  The passes are in
- * engine_pass.cpp, the count of a slice in engine_slice.cpp, whole-table operations in engine_table.cpp.
+ * engine_pass.cpp (with engine_acc.cpp and engine_count.cpp), the count of a slice in engine_slice.cpp, whole-table operations in engine_table.cpp.
  *
  * State model.  The authoritative copy of a counting table lives in HBM as an exact image of the
  * reference's 1<<pre khashl sets (one arena of 64-bit slots + one "used" bitmap, reference

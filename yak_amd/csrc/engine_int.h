@@ -1,5 +1,5 @@
-/* engine_int.h -- what the engine's own translation units (engine_ctx.cpp: the context; engine_pass.cpp: passes and feeds; engine_slice.cpp: the
- * count of a slice; engine_table.cpp: whole-table operations; layout.cpp: exact slot layout; table_read.cpp: the staged ranges, owner cut and
+/* engine_int.h -- what the engine's own translation units (engine_ctx.cpp: the context; engine_pass.cpp: passes and feeds; engine_acc.cpp: the
+ * accumulator path of a create pass; engine_count.cpp: counting into existing keys, by the plan of count_plan.h; engine_slice.cpp: the count of a slice; engine_table.cpp: whole-table operations; layout.cpp: exact slot layout; table_read.cpp: the staged ranges, owner cut and
  * refusals of the commands that read a table's stored keys; lookup_dev.cpp: the device-level exports of the lookup commands; yak_hetmer.cpp and
  * yak_graph.cpp: hetmers and unitigs) share and nobody else sees: the context of a table with the buffers it owns (dev_buf.h), the error macro, and the few functions that
  * cross between those files. */
@@ -223,8 +223,16 @@ int bloom_materialise(yakamd_ctx *c);                       /* give a never-writ
 int delta_ensure(yakamd_ctx *c);                            /* the per-slot pending increments exist from here to the end of the pass */
 void retained_drop(yakamd_ctx *c);
 void pass_free(yakamd_ctx *c);
-/* engine_pass.cpp: records [0, n_rec) of d_rec (times = t0 + position, all within [batch_lo, batch_hi)) -> table.  A create pass takes YK_FMT_POS alone */
+/* engine_pass.cpp: records [0, n_rec) of d_rec (times = t0 + position, all within [batch_lo, batch_hi)) -> table.  A create pass takes YK_FMT_POS alone.
+ * d_bstart: the records are grouped by level-1 bucket, and these are the buckets' starts */
 int consume_records(yakamd_ctx *c, const void *d_rec, RecFmt fmt, int64_t n_rec, u64 t0, u64 batch_lo, u64 batch_hi, const u64 *d_bstart = 0);
+int part_reserve(yakamd_ctx *c, int n_blk);                 /* the level-1 partition's scratch (rows, d_partial, d_bstart): room for a launch of n_blk blocks */
+/* engine_acc.cpp: the accumulator path of a create pass -- a batch into the accumulator; at the end of the pass its new keys into the image (*n_ins of them) */
+int acc_records(yakamd_ctx *c, const Rec *rec, int64_t n_rec, u64 t0, u64 batch_lo, u64 batch_hi);
+int acc_finish(yakamd_ctx *c, int64_t *n_ins);
+/* engine_count.cpp: a batch counted into the keys the table holds, by the plan of count_plan.h; the format that plan wants a count pass's extraction to write */
+int count_records(yakamd_ctx *c, const void *d_rec, RecFmt fmt, int64_t n_rec, const u64 *d_bstart);
+RecFmt count_pass_fmt(const yakamd_ctx *c);
 /* engine_slice.cpp: the exclusive-ownership path of a create pass.  fast_admit: *out = the admitted batch's own buffer (0 when the records are `borrowed`) */
 int fast_admit(yakamd_ctx *c, RecFmt fmt, u64 t, u64 n_pos, u64 n_cap, void **out, const void *borrowed = 0);
 int fast_keep(yakamd_ctx *c, u64 n_rec);

@@ -1,6 +1,6 @@
 /* engine_slice.cpp -- the exclusive-ownership path of a create pass: the batches of a pass are kept (fast_admit, fast_keep) and counted together
  * as a slice (fast_finish: its stages below, handing each other a Slice) at the end of the pass, or earlier when the budget says so
- * (fast_flush_slice); a pass that cannot stay on the path hands what it kept to the accumulator path of engine_pass.cpp (fast_abandon). */
+ * (fast_flush_slice); a pass that cannot stay on the path hands what it kept to the accumulator path of engine_acc.cpp (fast_abandon). */
 #include "engine_int.h"
 #include "seg_sort_tile.h"
 

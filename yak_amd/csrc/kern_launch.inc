@@ -1,5 +1,6 @@
 /* kern_launch.inc -- part of kernels.hip (one translation unit, included in this order): launch wrappers (extern "C", declared in yk_device.h) */
 #include <atomic>
+#include "count_plan.h"                  /* the two LDS size formulas of the count-existing kernels */
 /* The dynamic-LDS limit of kernel K (hipFuncSetAttribute) belongs to the device that was current when it was set, so a process that drives several
  * GPUs sets it once on each: lds_limit<K>(bytes), before a launch of K that asks for more than 64 KiB, sets it once per kernel and device.  false: the
  * runtime refused (the error stays for the caller to clear or to find; the next call asks again) -- what that means is the caller's to say */
@@ -157,7 +158,7 @@ void yk_launch_img_count(const Rec *rec, int64_t n, ImgView img, hipStream_t st)
 }
 
 /* LDS needed by k_img_count_lds for a sub-table of `cap` slots holding `count` keys */
-size_t yk_img_count_lds_bytes(u32 cap, u32 count) { return (size_t)((cap + 31) / 32) * 8 + (size_t)(count + 1) / 2 * 4 + 16; }
+size_t yk_img_count_lds_bytes(u32 cap, u32 count) { return yk_plan_img_count_lds_bytes(cap, count); }
 
 /* YK_FMT_POS or YK_FMT_HASH records, grouped by sub-table (bstart) */
 int yk_launch_img_count_lds(const void *rec, RecFmt fmt, const u64 *bstart, ImgView img, int plo, int phi, size_t lds, u64 *compact, u32 stride, hipStream_t st)
@@ -414,7 +415,7 @@ void yk_launch_lds_count_ovf(FastParams fp, const u64 *sbstart, const Rec *rec,
 	                              O, ovf_list, scr_off, scr);
 }
 
-size_t yk_count_own_lds(u32 range_len, u32 kmax) { const u32 nw = (range_len + 31) / 32; return (size_t)2 * ((nw + 1) & ~1u) * 4 + (size_t)kmax * 8 + (size_t)((kmax + 1) / 2 + 1 & ~1u) * 4 + 16 * 128 * 8 + 16; }   /* bitmap, ranks, keys, counters, 16 wave queues */
+size_t yk_count_own_lds(u32 range_len, u32 kmax) { return yk_plan_count_own_lds(range_len, kmax); }   /* (count_plan.h) */
 
 /* records of any RecFmt, grouped by sub-table (bstart).  The format gives the kernel its two arguments: W, the record's stride in words, and ytag, how the
  * record's one word is read -- 0 the hash, 1 the range-tagged hash, 2 the tagged level-1 record */

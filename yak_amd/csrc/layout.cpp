@@ -1,7 +1,7 @@
 /*
  * layout.cpp -- the exact-layout stage of a pass: the streaming replay of large sub-tables (kern_replay2.inc) as a sequence of stages over the host
  * plan of replay_plan.h (capacities after the new keys, khashl.h:197-221; the doubling / placement schedule; the arenas), and the one-workgroup-per-table
- * replay of small tables (k_replay).  Cut out of the engine's passes (now engine_pass.cpp, engine_slice.cpp) in round 6.
+ * replay of small tables (k_replay).  Cut out of the engine's passes (now engine_pass.cpp, engine_acc.cpp, engine_slice.cpp) in round 6.
  */
 #include "engine_int.h"
 

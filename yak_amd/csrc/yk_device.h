@@ -23,14 +23,7 @@ typedef ulonglong2 Rec;                  /* one k-mer instance: .x = yak_hash64 
 #define YK_R8_TAG_BITS 12
 #define YK_R8_TOGGLE   (1u << 10)
 
-/* What a buffer of level-1 records holds; it travels as `const void *` beside its RecFmt.  A Chunk2 holds the first two,
- * and the level-2 kernels compare Chunk2::fmt with these values */
-enum RecFmt {
-	YK_FMT_POS = 0,                      /* Rec {hash, position}, 16 bytes */
-	YK_FMT_TAGGED = 1,                   /* the tagged record above, 8 bytes */
-	YK_FMT_HASH = 2,                     /* the bare hash, 8 bytes */
-	YK_FMT_HASH_RNG = 3                  /* the hash with the sub-table's own bits (the bucket says them) replaced by the top bits of its home-slot product: k_img_count_own's range test, 8 bytes */
-};
+#include "rec_fmt.h"                     /* RecFmt: what a buffer of level-1 records holds -- Rec, the tagged record above, the hash, the range-tagged hash */
 static inline size_t yk_rec_bytes(RecFmt f) { return f == YK_FMT_POS ? sizeof(Rec) : 8; }
 static inline size_t yk_rec_units(RecFmt f, size_t n) { return (n * yk_rec_bytes(f) + sizeof(Rec) - 1) / sizeof(Rec); }   /* elements of a DevBuf<Rec> that hold n records */
 extern "C" int64_t yk_knob(const char *name, int64_t dflt);   /* pool.cpp: a run-time setting -- the test hook's value (yakamd_test_set), else (public names only) the environment's, else dflt */
