@@ -24,11 +24,11 @@ yak_amd/kernels.o: $(CSRC)/kernels.hip $(wildcard $(CSRC)/kern_*.inc) $(CSRC)/yk
 yak_amd/tally.o: $(CSRC)/tally.cpp $(CSRC)/tally.h include/yak_amd.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 # every other object of the library: one header list for all of them (a header too many costs a rebuild, one too few a stale object)
-ENGDEPS = $(CSRC)/engine_int.h $(CSRC)/dev_buf.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/table_ranges.h $(CSRC)/yk_device.h $(CSRC)/rec_fmt.h $(CSRC)/replay_plan.h $(CSRC)/count_plan.h $(CSRC)/seg_sort_tile.h \
+ENGDEPS = $(CSRC)/engine_int.h $(CSRC)/dev_buf.h $(CSRC)/tally.h $(CSRC)/engine.h $(CSRC)/table_ranges.h $(CSRC)/yak_file.h $(CSRC)/yk_device.h $(CSRC)/rec_fmt.h $(CSRC)/replay_plan.h $(CSRC)/count_plan.h $(CSRC)/seg_sort_tile.h \
           $(CSRC)/hpc_host.h $(CSRC)/unitig_walk.h $(CSRC)/yak_host.h $(CSRC)/pgz.h $(CSRC)/round_plan.h include/yak.h include/yak_amd.h
 yak_amd/%.o: $(CSRC)/%.cpp $(ENGDEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/tally.o yak_amd/pool.o yak_amd/engine_ctx.o yak_amd/engine_pass.o yak_amd/engine_acc.o yak_amd/engine_count.o yak_amd/engine_slice.o yak_amd/engine_table.o yak_amd/layout.o yak_amd/table_read.o yak_amd/lookup_dev.o yak_amd/yak_hetmer.o yak_amd/yak_graph.o yak_amd/yak_hpc.o yak_amd/yak_api.o yak_amd/yak_count.o yak_amd/yak_qv_solve.o yak_amd/yak_reader.o yak_amd/yak_multi.o yak_amd/yak_lookup.o yak_amd/yak_inspect.o yak_amd/yak_print.o $(CSRC)/libyak_amd.map
+yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/tally.o yak_amd/pool.o yak_amd/engine_ctx.o yak_amd/engine_pass.o yak_amd/engine_acc.o yak_amd/engine_count.o yak_amd/engine_slice.o yak_amd/engine_table.o yak_amd/layout.o yak_amd/table_read.o yak_amd/lookup_dev.o yak_amd/yak_hetmer.o yak_amd/yak_graph.o yak_amd/yak_hpc.o yak_amd/yak_api.o yak_amd/yak_table_ops.o yak_amd/yak_file.o yak_amd/yak_count.o yak_amd/yak_qv_solve.o yak_amd/yak_reader.o yak_amd/yak_multi.o yak_amd/yak_lookup.o yak_amd/yak_inspect.o yak_amd/yak_print.o $(CSRC)/libyak_amd.map
 	$(HIPCC) --offload-arch=$(ARCH) -shared -Wl,-Bsymbolic -Wl,--version-script=$(CSRC)/libyak_amd.map -o $@ $(filter %.o,$^) -lz
 
 # The four layers above libyak_amd.so (DESIGN.md sections 21 to 24 and 26): each its own kernels, public calls of the libraries below it only, the shared

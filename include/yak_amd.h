@@ -536,6 +536,9 @@ int64_t yakamd_dump_mem(yak_ch_t *h, uint8_t **out);
 /* the bytes of sub-tables [lo, hi) alone ({u32 capacity, u32 size, keys in slot order} each, htab.c:385-389; no header): one rank's share of the
  * .yak file of a prefix-sharded job; malloc'ed, returns the size or -1 */
 int64_t yakamd_dump_range_mem(yak_ch_t *h, int lo, int hi, uint8_t **out);
+/* k and pre of a .yak file's header: what a command compares between its tables before it loads any.  0, or -1 after a message (yakamd_last_error()):
+ * the file cannot be opened, it is shorter than a header, it does not start with the magic.  No device call */
+int yakamd_yak_header(const char *fn, int *k, int *pre);
 
 /* sub-table shape, for tests: capacity and size of sub-table i (device-authoritative) */
 int yakamd_subtable(yak_ch_t *h, int i, uint32_t *capacity, uint32_t *size);

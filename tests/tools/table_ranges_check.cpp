@@ -151,6 +151,31 @@ static void one_case(int P, const std::vector<uint32_t> &size, int64_t budget)
 	}
 }
 
+/* ---- the shards of a table: yk_shard_owner and yk_shard_span against the two expressions yak_api.cpp had, (x & pm) * n_sub >> pre in insert_list,
+ * get, inc and getseq, (r << pre) / n_sub in dump_through, for every n_sub that divides 1 << pre ---- */
+static void shards()
+{
+	for (int pre = 10; pre <= 14; ++pre)
+		for (int n_sub = 1; n_sub <= 1 << pre; n_sub <<= 1) {
+			g_case = -(pre * 100000 + n_sub);
+			const uint64_t pm = (1ULL << pre) - 1;
+			int next = 0;
+			for (int r = 0; r < n_sub; ++r) {
+				const ShardSpan s = yk_shard_span(pre, n_sub, r);
+				CHECK(s.lo == next && s.hi > s.lo);                   /* the spans tile [0, 1 << pre) in order */
+				CHECK(s.lo == (int)(((int64_t)r << pre) / n_sub) && s.hi == (int)(((int64_t)(r + 1) << pre) / n_sub));
+				for (int p = s.lo; p < s.hi; ++p) CHECK(yk_shard_owner(pre, n_sub, (uint64_t)p) == r);   /* owner(p) == r exactly on span(r): the spans are disjoint */
+				next = s.hi;
+			}
+			CHECK(next == 1 << pre);
+			for (int p = 0; p < 1 << pre; ++p) {
+				const uint64_t x = rnd() << pre | (uint64_t)p;         /* a hash with prefix p */
+				CHECK(yk_shard_owner(pre, n_sub, x & pm) == (int)((x & ((1ULL << pre) - 1)) * n_sub >> pre));
+				CHECK(yk_shard_owner(pre, n_sub, (uint64_t)p) == (int)((uint64_t)p * n_sub >> pre));   /* getseq's */
+			}
+		}
+}
+
 int main()
 {
 	int n_vec = 0;
@@ -178,6 +203,7 @@ int main()
 	for (int P = 1; P <= 64; P += 9) { one_case(P, std::vector<uint32_t>(P, 0), 0); one_case(P, std::vector<uint32_t>(P, 0), 7); ++n_vec; }
 	/* no sub-table at all: no range */
 	CHECK(table_ranges(3, 3, [](int) { return (u64)1; }, 5, true).empty());
+	shards();
 	if (g_bad) { fprintf(stderr, "%d checks failed over %d size vectors\n", g_bad, n_vec); return 1; }
 	printf("ok\n");
 	return 0;

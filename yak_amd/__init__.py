@@ -40,7 +40,7 @@ YAK_AMD_H_SYMBOLS = [
     "yakamd_chkerr_lookup_dev", "yakamd_chkerr_streaks_dev", "yakamd_ceopt_init", "yakamd_chkerr",
     "yakamd_sexchr_reduce_dev", "yakamd_scopt_init", "yakamd_sexchr",
     "yakamd_kmers_dev", "yakamd_print_dev", "yakamd_propt_init", "yakamd_print", "yakamd_host_syncs",
-    "yakamd_ch_sum",
+    "yakamd_ch_sum", "yakamd_yak_header",
     "yakamd_depth_reduce_dev", "yakamd_dpopt_init", "yakamd_depth",
     "yakamd_cover_dev", "yakamd_cvopt_init", "yakamd_cover",
     "yakamd_hetmers_dev", "yakamd_hetmer_pairs_dev", "yakamd_hmopt_init", "yakamd_hetmers",
@@ -213,6 +213,7 @@ def lib():
     L.yakamd_dump_mem.argtypes = [P(ChT), P(P(C.c_uint8))]
     L.yakamd_dump_range_mem.restype = C.c_int64
     L.yakamd_dump_range_mem.argtypes = [P(ChT), C.c_int, C.c_int, P(P(C.c_uint8))]
+    L.yakamd_yak_header.restype = C.c_int; L.yakamd_yak_header.argtypes = [C.c_char_p, P(C.c_int), P(C.c_int)]
     L.yakamd_peak_bytes.restype = C.c_int64; L.yakamd_peak_bytes.argtypes = [C.c_int, C.c_int]
     L.yakamd_last_sweeps.restype = C.c_int; L.yakamd_last_sweeps.argtypes = []
     L.yakamd_pool_report.restype = None; L.yakamd_pool_report.argtypes = [C.c_char_p]
@@ -768,13 +769,13 @@ def cover(table_yak, seq, lo=1, hi=1023, intervals=False, mask=None, min_frac=0.
 
 
 def yak_header(fn):
-    """(k, pre) of a .yak file's header"""
-    import struct
-    with open(fn, "rb") as f:
-        b = f.read(16)
-    if len(b) < 16 or b[:4] != b"YAK\x02":
+    """(k, pre) of a .yak file's header (yakamd_yak_header); a file that cannot be opened raises as open() does"""
+    with open(fn, "rb"):
+        pass
+    k, pre = C.c_int(), C.c_int()
+    if lib().yakamd_yak_header(os.fsencode(fn), C.byref(k), C.byref(pre)) != 0:
         raise ValueError("%s: not a .yak file" % fn)
-    return struct.unpack("<3I", b[4:])[:2]
+    return k.value, pre.value
 
 
 def sexchr_table(y, x, par):

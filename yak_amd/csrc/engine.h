@@ -1,5 +1,5 @@
 /* engine.h -- internal interface between pool.cpp, the engine (engine_ctx.cpp, engine_pass.cpp, engine_acc.cpp, engine_count.cpp, engine_slice.cpp, engine_table.cpp), table_read.cpp,
- * lookup_dev.cpp and the yak.h surface (yak_api.cpp, yak_count.cpp, yak_reader.cpp, yak_multi.cpp, yak_inspect.cpp, yak_print.cpp) */
+ * lookup_dev.cpp and the yak.h surface (yak_api.cpp, yak_table_ops.cpp, yak_file.cpp, yak_count.cpp, yak_reader.cpp, yak_multi.cpp, yak_inspect.cpp, yak_print.cpp) */
 #ifndef YK_ENGINE_H
 #define YK_ENGINE_H
 #include <vector>

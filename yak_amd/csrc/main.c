@@ -282,13 +282,10 @@ static int cmd_chkerr(int argc, char **argv)
 /* k and pre of a .yak file's header (htab.c:381-384); 0 if it cannot be read */
 static int yak_header(const char *fn, uint32_t *k, uint32_t *pre)
 {
-	FILE *fp = fopen(fn, "rb");
-	char magic[4];
-	uint32_t t[3];
-	int ok = fp && fread(magic, 1, 4, fp) == 4 && memcmp(magic, YAK_MAGIC, 4) == 0 && fread(t, 4, 3, fp) == 3;
-	if (fp) fclose(fp);
-	if (ok) { *k = t[0]; *pre = t[1]; }
-	return ok;
+	int k_ = 0, pre_ = 0;
+	if (yakamd_yak_header(fn, &k_, &pre_) != 0) return 0;
+	*k = (uint32_t)k_; *pre = (uint32_t)pre_;
+	return 1;
 }
 
 static int cmd_sexchr(int argc, char **argv)

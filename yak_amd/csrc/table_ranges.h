@@ -26,4 +26,11 @@ template <class Size> std::vector<TableRange> table_ranges(int lo, int hi, Size 
 	if (lo < hi) close(hi);
 	return out;
 }
+
+/* A table sharded over n_sub owners: owner r holds the prefixes [r P / n_sub, (r + 1) P / n_sub), P = 1 << pre.  Precondition: n_sub divides P
+ * (so it is a power of two; yak_multi.cpp deals the prefixes out so and refuses any other number) -- the span's bounds are then exact and the owner
+ * of a prefix is the one whose span holds it; with another n_sub the two would round differently */
+static inline int yk_shard_owner(int pre, int n_sub, uint64_t prefix) { return (int)(prefix * (uint64_t)n_sub >> pre); }
+struct ShardSpan { int lo, hi; };
+static inline ShardSpan yk_shard_span(int pre, int n_sub, int r) { return ShardSpan{ (int)(((int64_t)r << pre) / n_sub), (int)(((int64_t)(r + 1) << pre) / n_sub) }; }
 #endif

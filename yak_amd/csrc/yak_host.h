@@ -1,6 +1,6 @@
 /*
- * yak_host.h -- internal: what the host translation units of the library share (yak_api.cpp: the yak.h life cycle, merge / sum, dump / restore;
- * yak_count.cpp: yak_count() on one device; yak_reader.cpp: the FASTA / FASTQ reader, its parallel parser and packer, the input front end (SeqInput),
+ * yak_host.h -- internal: what the host translation units of the library share (yak_api.cpp: the yak.h life cycle and the per-key calls;
+ * yak_table_ops.cpp: subtract / isec, merge / sum; yak_file.cpp: dump / restore; yak_count.cpp: yak_count() on one device; yak_reader.cpp: the FASTA / FASTQ reader, its parallel parser and packer, the input front end (SeqInput),
  * the reader's and the gzip hooks; yak_multi.cpp: several GPUs behind yak_count(); yak_lookup.cpp: the lookup-only commands, qv and triobin first).
  */
 #ifndef YAK_HOST_H
@@ -38,6 +38,16 @@ struct yak_ch_ext { yak_ch_t pub; yakamd_ctx *ctx; uint32_t magic; int n_sub; ya
 #define EXT_MAGIC 0x59414b41u
 #define YK_MULTI(e) ((e)->n_sub > 1)
 static inline void multi_tot(yak_ch_t *h) { yak_ch_ext *e = (yak_ch_ext*)h; uint64_t t = 0; for (int r = 0; r < e->n_sub; ++r) t += e->sub[r]->tot; h->tot = t; }
+/* the tables that hold the sub-tables of `h`, each with a context of its own: its shards in prefix order, or `h` itself */
+static inline std::vector<yak_ch_t*> shards_of(const yak_ch_t *h)
+{
+	const yak_ch_ext *e = (const yak_ch_ext*)h;
+	return YK_MULTI(e) ? std::vector<yak_ch_t*>(e->sub, e->sub + e->n_sub) : std::vector<yak_ch_t*>(1, (yak_ch_t*)h);
+}
+static inline yakamd_ctx *shard_ctx(yak_ch_t *s) { return ((yak_ch_ext*)s)->ctx; }
+static inline void set_tot(yak_ch_t *h) { if (YK_MULTI((yak_ch_ext*)h)) multi_tot(h); }
+/* a context's lock for a scope: what shares its stream and its counters takes turns */
+struct CtxLock { yakamd_ctx *c; CtxLock(yakamd_ctx *c_) : c(c_) { yk_ctx_lock(c); } ~CtxLock() { yk_ctx_unlock(c); } CtxLock(const CtxLock&) = delete; CtxLock &operator=(const CtxLock&) = delete; };
 
 double yk_realtime(void);
 double yk_cputime(void);

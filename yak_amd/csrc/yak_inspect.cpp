@@ -5,75 +5,33 @@
  */
 #include "yak_host.h"
 #include "yak_amd.h"
+#include "yak_file.h"
 
 namespace {
 
 const int NC = YAK_N_COUNTS;
 
-struct YakHead { int k, pre; };
-
-/* the 16-byte header of a .yak file (htab.c:378-380); false after a message */
-bool read_head(FILE *fp, const char *fn, YakHead *h)
+/* the header of a .yak file within inspect's limits: k in [1, 63], and pre up to 30 -- no table of in1 is built, its sub-tables are streamed; false after a message */
+bool read_head(YakSrc &src, const char *fn, YakHeader *h)
 {
-	char magic[4];
-	uint32_t t[3];
-	if (fread(magic, 1, 4, fp) != 4 || fread(t, 4, 3, fp) != 3) { yk_set_error("inspect: '%s': truncated header", fn); return false; }
-	if (memcmp(magic, YAK_MAGIC, 4) != 0) { yk_set_error("inspect: '%s': wrong file magic", fn); return false; }
-	if (t[2] != YAK_COUNTER_BITS) { yk_set_error("inspect: '%s': saved counter bits %u, not %d", fn, t[2], YAK_COUNTER_BITS); return false; }
-	if (t[0] < 1 || t[0] > 63 || t[1] < YAK_COUNTER_BITS || t[1] > 30) { yk_set_error("inspect: '%s': k %u / pre %u out of range", fn, t[0], t[1]); return false; }
-	h->k = (int)t[0]; h->pre = (int)t[1];
+	const YakStatus st = yak_read_header(src, h);
+	if (st == YAK_SHORT_HEADER) { yk_set_error("inspect: '%s': truncated header", fn); return false; }
+	if (st == YAK_BAD_MAGIC) { yk_set_error("inspect: '%s': wrong file magic", fn); return false; }
+	if (st == YAK_BAD_BITS) { yk_set_error("inspect: '%s': saved counter bits %u, not %d", fn, h->bits, YAK_COUNTER_BITS); return false; }
+	if (h->k < 1 || h->k > 63 || h->pre < YAK_COUNTER_BITS || h->pre > 30) { yk_set_error("inspect: '%s': k %u / pre %u out of range", fn, h->k, h->pre); return false; }
 	return true;
 }
 
-/* one batch of in1: the keys of sub-tables [lo, lo + off.size() - 1) in file order, off[j] = keys before sub-table lo + j.  A sub-table larger
- * than the room left is split: the batch ends with its first part and the next one starts with the rest, under the same index */
-struct Batch {
-	std::vector<uint64_t> keys, off;
-	int lo = 0;
-	void clear() { keys.clear(); off.clear(); }
-	int n_sub() const { return (int)off.size() - 1; }
-};
-
-/* the body of a .yak file, read sub-table by sub-table (inspect.c:47-62) */
-struct BodyReader {
-	FILE *fp = 0;
-	const char *fn = 0;
-	int P = 0, cur = 0;                  /* next sub-table */
-	uint64_t rest = 0;                   /* keys of sub-table cur still to read */
-	bool in_sub = false;                 /* its header was read */
-	bool bad = false;
-	bool done() const { return cur >= P; }
-	/* the next batch of about `cap` keys; false on a short read (after a message) */
-	bool next(int64_t cap, Batch *b)
-	{
-		b->clear();
-		b->lo = cur;
-		b->off.push_back(0);
-		while (cur < P) {
-			if (!in_sub) {
-				uint32_t t[2];
-				if (fread(t, 4, 2, fp) != 2) return fail();
-				rest = t[1]; in_sub = true;
-			}
-			const uint64_t room = (uint64_t)cap - b->keys.size(), take = rest < room ? rest : room;
-			if (take) {
-				const size_t at = b->keys.size();
-				b->keys.resize(at + take);
-				if (fread(b->keys.data() + at, 8, take, fp) != take) return fail();
-				rest -= take;
-			}
-			b->off.push_back(b->keys.size());
-			if (rest) break;                                      /* split: the rest of sub-table cur opens the next batch */
-			in_sub = false; ++cur;
-			if ((int64_t)b->keys.size() >= cap) break;
-		}
-		return true;
-	}
-	bool fail() { yk_set_error("inspect: '%s': truncated at sub-table %d", fn, cur); bad = true; return false; }
-};
+/* the next batch of in1's body; false on a short read, after a message */
+bool next_batch(YakBody &rd, const char *fn, int64_t cap, YakBatch *b)
+{
+	if (rd.next(cap, b) == YAK_OK) return true;
+	yk_set_error("inspect: '%s': truncated at sub-table %d", fn, rd.cur);
+	return false;
+}
 
 /* one batch on the device and joined into d_joint */
-bool join_batch(const Batch &b, yak_ch_t *ch, int k, int pre, int ref_probe, GrowBuf &d_keys, GrowBuf &d_off, uint64_t *d_joint)
+bool join_batch(const YakBatch &b, yak_ch_t *ch, int k, int pre, int ref_probe, GrowBuf &d_keys, GrowBuf &d_off, uint64_t *d_joint)
 {
 	if (b.keys.empty()) return true;
 	const size_t nk = b.keys.size(), no = b.off.size();
@@ -148,17 +106,19 @@ int yakamd_inspect(const yakamd_inopt_t *opt, const char *fn1, const char *fn2, 
 	if (!fp) { yk_set_error("inspect: cannot open '%s'", fn1); return -1; }
 	struct Closer { FILE *f; ~Closer() { fclose(f); } } fp_close{ fp };
 	setvbuf(fp, fbuf.data(), _IOFBF, fbuf.size());
-	YakHead h1, h2;
-	if (!read_head(fp, fn1, &h1)) return -1;
+	YakSrc src = YakSrc::file(fp);
+	YakHeader h1, h2;
+	if (!read_head(src, fn1, &h1)) return -1;
 	if (fn2) {
 		FILE *f2 = fopen(fn2, "rb");
 		if (!f2) { yk_set_error("inspect: cannot open '%s'", fn2); return -1; }
-		const bool ok = read_head(f2, fn2, &h2);
+		YakSrc src2 = YakSrc::file(f2);
+		const bool ok = read_head(src2, fn2, &h2);
 		fclose(f2);
 		if (!ok) return -1;
-		if (h1.k != h2.k) { yk_set_error("inspect: the tables have different k (%d and %d)", h1.k, h2.k); return -1; }
+		if (h1.k != h2.k) { yk_set_error("inspect: the tables have different k (%d and %d)", (int)h1.k, (int)h2.k); return -1; }
 		if (!opt->ref_probe && h1.k >= 32 && h1.pre != h2.pre) {
-			yk_set_error("inspect: at k >= 32 a stored key holds hash bits [pre, pre + 54): the tables must have the same pre (%d and %d; -R probes as the reference does)", h1.pre, h2.pre);
+			yk_set_error("inspect: at k >= 32 a stored key holds hash bits [pre, pre + 54): the tables must have the same pre (%d and %d; -R probes as the reference does)", (int)h1.pre, (int)h2.pre);
 			return -1;
 		}
 	}
@@ -176,15 +136,14 @@ int yakamd_inspect(const yakamd_inopt_t *opt, const char *fn1, const char *fn2, 
 	uint64_t *d_joint = (uint64_t*)yakamd_dev_alloc((size_t)NC * NC * 8);
 	std::vector<int64_t> J((size_t)NC * NC, 0);
 	bool ok = d_joint && yakamd_memcpy_h2d(d_joint, J.data(), J.size() * 8) == 0;
-	BodyReader rd;
-	rd.fp = fp; rd.fn = fn1; rd.P = 1 << h1.pre;
+	YakBody rd(&src, (int)h1.pre);
 	const int64_t cap = opt->batch_keys > 0 ? opt->batch_keys : 1;
-	Batch cur, nxt;
+	YakBatch cur, nxt;
 	GrowBuf d_keys, d_off;
 	double t_read = 0, t_join = 0;
 	{
 		const double a = yk_realtime();
-		ok = ok && rd.next(cap, &cur);
+		ok = ok && next_batch(rd, fn1, cap, &cur);
 		t_read += yk_realtime() - a;
 	}
 	while (ok) {
@@ -192,7 +151,7 @@ int yakamd_inspect(const yakamd_inopt_t *opt, const char *fn1, const char *fn2, 
 		bool rok = true;
 		double t_rd = 0;
 		std::thread reader;
-		if (more) reader = std::thread([&]() { const double a = yk_realtime(); rok = rd.next(cap, &nxt); t_rd = yk_realtime() - a; });
+		if (more) reader = std::thread([&]() { const double a = yk_realtime(); rok = next_batch(rd, fn1, cap, &nxt); t_rd = yk_realtime() - a; });
 		const double a = yk_realtime();
 		ok = join_batch(cur, ch, h1.k, h1.pre, opt->ref_probe, d_keys, d_off, d_joint);
 		t_join += yk_realtime() - a;
