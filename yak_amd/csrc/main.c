@@ -17,12 +17,12 @@
  *     recount  the counts of a table's k-mers in other sequences, reference main.c:66-88 (restore, tighten, yak_recount)
  *     subtract, isec   the k-mers of the first table absent from / present in the others, reference main.c:217-284
  *     version  the library's YAKS_VERSION
- * and seven beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table), hetmers
+ * and eight beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table), hetmers
  * (yakamd_hetmers: the pairs of k-mers of a count table that differ in the middle base alone), cover (yakamd_cover: the bases of every sequence
  * that lie inside k-mers a table holds, lacks or holds too often -- as a table, as intervals or as a masked FASTA), unitigs (yakamd_unitigs: the
  * de Bruijn graph the k-mers of a count table span, as its unitigs in FASTA or as its tallies), paths (yakamd_paths: the sequences of a file as
- * paths through those unitigs, as GAF or as tallies per sequence) and bubbles (yakamd_bubbles: the forks of that graph whose two arms join again,
- * with their types and alleles).  `count -c` and `qv -c` work in homopolymer-compressed
+ * paths through those unitigs, as GAF or as tallies per sequence), bubbles (yakamd_bubbles: the forks of that graph whose two arms join again,
+ * with their types and alleles) and clean (yakamd_clean: the table without the k-mers of that graph's tips and weaker bubble arms).  `count -c` and `qv -c` work in homopolymer-compressed
  * space (yakamd_count_hpc; yakamd_ch_set_hpc on the restored table): every run of one base is one base before k-mers are taken.
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
@@ -36,6 +36,7 @@
 #include "yak_amd_gfa.h"   /* yakamd_unitigs_gfa (unitigs -G) */
 #include "yak_amd_path.h"  /* yakamd_paths (paths) */
 #include "yak_amd_bubble.h" /* yakamd_bubbles (bubbles) */
+#include "yak_amd_clean.h" /* yakamd_clean (clean) */
 #include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_cover, yakamd_unitigs, yakamd_count_hpc and yakamd_ch_set_hpc */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
@@ -643,6 +644,43 @@ static int cmd_bubbles(int argc, char **argv)
 	return rc;
 }
 
+/* ---- clean (not in the reference) ---- */
+/* the unitig graph of a count table cleaned round by round -- tips clipped, the weaker arm of every simple bubble popped -- by taking the k-mers of
+ * the removed unitigs out of the table: the cleaned table goes to a .yak file that every command reads (yakamd_clean of libyak_amd_clean.so) */
+static int cmd_clean(int argc, char **argv)
+{
+	yakamd_cleanopt_t o;
+	const char *report = 0;
+	int list = 0;
+	yakamd_cleanopt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'c', ARG_I32, &o.min_cnt, "a k-mer with a count below this is absent and is dropped, 1 .. 1023 [1]" },
+		{ 't', ARG_I32, &o.tip_nodes, "clip tips of fewer nodes than this, 0 .. 1048576, 0: none [k]" },
+		{ 'b', ARG_I32, &o.pop_pct, "pop the weaker arm of a bubble when its coverage is at most this per cent of the other's, 0 .. 100, 0: none [100]" },
+		{ 'r', ARG_I32, &o.max_rounds, "rounds at the most, 1 .. 64 [8]" },
+		{ 'l', ARG_FLAG, &list, "list every removed unitig in the report (T and P lines)" },
+		{ 'o', ARG_TEXT, &report, "write the report here; stdout without it" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 1 >= argc) { arg_help("clean [options] <in.yak> <out.yak>", defs, nd); return 1; }
+	uint32_t k = 0, pre = 0;
+	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd clean: %s is not a readable .yak file\n", argv[first]); return 2; }
+	if (!(k & 1)) { fprintf(stderr, "yak-amd clean: %s has k = %u: the graph is defined for an odd k only\n", argv[first], k); return 2; }
+	if (k >= 32) { fprintf(stderr, "yak-amd clean: %s has k = %u: k must be below 32\n", argv[first], k); return 2; }
+	if (o.min_cnt < 1 || o.min_cnt > 1023) { fprintf(stderr, "yak-amd clean: -c must be in [1, 1023]\n"); return 1; }
+	if (o.tip_nodes < -1 || o.tip_nodes > YAKAMD_CLEAN_MAX_TIP_NODES || o.pop_pct < 0 || o.pop_pct > 100 || o.max_rounds < 1 || o.max_rounds > 64) {
+		fprintf(stderr, "yak-amd clean: -t must be in [0, %d], -b in [0, 100] and -r in [1, 64]\n", YAKAMD_CLEAN_MAX_TIP_NODES);
+		return 1;
+	}
+	o.list = list;
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd clean: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	const int rc = yakamd_clean(&o, tab, argv[first + 1], report ? report : "-") == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 /* ---- hetmers (not in the reference) ---- */
 /* the pairs of k-mers of a count table that differ in the middle base alone, as a histogram of their two counts (yakamd_hetmers) */
 static int cmd_hetmers(int argc, char **argv)
@@ -716,6 +754,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && strcmp(argv[1], "unitigs") == 0) return cmd_unitigs(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "paths") == 0) return cmd_paths(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "bubbles") == 0) return cmd_bubbles(argc - 1, argv + 1);
+	if (argc >= 2 && strcmp(argv[1], "clean") == 0) return cmd_clean(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
 	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-8s %s\n", cmds[i].name, cmds[i].what);
 	fprintf(stderr, "  beyond the reference:\n      yak-amd %-8s %s\n", "sum", "add the counts of two or more .yak tables together");
@@ -725,5 +764,6 @@ int main(int argc, char **argv)
 	fprintf(stderr, "      yak-amd %-8s %s\n", "unitigs", "the unitigs of the de Bruijn graph that the k-mers of a .yak table span");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "paths", "sequences as paths through the unitigs of that graph (GAF)");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "bubbles", "the simple bubbles of that graph: forks whose two arms join again, with their alleles");
+	fprintf(stderr, "      yak-amd %-8s %s\n", "clean", "that graph with its tips clipped and its bubbles popped, as a .yak table of the k-mers that stay");
 	return 1;
 }
