@@ -22,7 +22,7 @@
  * that lie inside k-mers a table holds, lacks or holds too often -- as a table, as intervals or as a masked FASTA), unitigs (yakamd_unitigs: the
  * de Bruijn graph the k-mers of a count table span, as its unitigs in FASTA or as its tallies), paths (yakamd_paths: the sequences of a file as
  * paths through those unitigs, as GAF or as tallies per sequence), bubbles (yakamd_bubbles: the forks of that graph whose two arms join again,
- * with their types and alleles) and clean (yakamd_clean: the table without the k-mers of that graph's tips and weaker bubble arms).  `count -c` and `qv -c` work in homopolymer-compressed
+ * with their types and alleles) and clean (yakamd_clean: the table without the k-mers of that graph's tips and weaker bubble arms), and correct (yakamd_correct: reads with their single substitution errors repaired against a table).  `count -c` and `qv -c` work in homopolymer-compressed
  * space (yakamd_count_hpc; yakamd_ch_set_hpc on the restored table): every run of one base is one base before k-mers are taken.
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
@@ -37,6 +37,7 @@
 #include "yak_amd_path.h"  /* yakamd_paths (paths) */
 #include "yak_amd_bubble.h" /* yakamd_bubbles (bubbles) */
 #include "yak_amd_clean.h" /* yakamd_clean (clean) */
+#include "yak_amd_correct.h" /* yakamd_correct (correct) */
 #include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_cover, yakamd_unitigs, yakamd_count_hpc and yakamd_ch_set_hpc */
 
 /* ---- a table-driven option scanner: "-x", "-xVALUE" and "-x VALUE"; stops at the first non-option ---- */
@@ -681,6 +682,40 @@ static int cmd_clean(int argc, char **argv)
 	return rc;
 }
 
+/* ---- correct (not in the reference) ---- */
+/* the reads with their single substitution errors repaired against a count table: a run of weak k-mers whose length names the base, the three
+ * other bases tried with the table's own lookup, the base replaced where exactly one of them makes the run solid (yakamd_correct of
+ * libyak_amd_correct.so) */
+static int cmd_correct(int argc, char **argv)
+{
+	yakamd_cropt_t o;
+	const char *out = 0, *report = 0;
+	yakamd_cropt_init(&o);
+	const struct arg_def defs[] = {
+		{ 'c', ARG_I32, &o.min_cnt, "a k-mer with a count below this is weak, 1 .. 1023 [3]" },
+		{ 'e', ARG_I32, &o.min_run, "the shortest run of weak k-mers that is tried, 1 .. k [1]" },
+		{ 'l', ARG_FLAG, &o.list, "list every fixed base in the report (X lines)" },
+		{ 's', ARG_FLAG, &o.stats_only, "the report alone: no reads are written (the report goes to stdout without -r)" },
+		{ 'K', ARG_I64SIZE, &o.chunk_size, "bases per chunk" },
+		{ 'o', ARG_TEXT, &out, "write the corrected reads here; stdout without it" },
+		{ 'r', ARG_TEXT, &report, "write the report here; none without it" },
+	};
+	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
+	const int first = arg_scan(argc, argv, defs, nd);
+	if (first < 0 || first + 1 >= argc) { arg_help("correct [options] <kmer.yak> <reads.fq>", defs, nd); return 1; }
+	uint32_t k = 0, pre = 0;
+	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd correct: %s is not a readable .yak file\n", argv[first]); return 2; }
+	if (k >= 32) { fprintf(stderr, "yak-amd correct: %s has k = %u: the per-position lookup serves k below 32 only\n", argv[first], k); return 2; }
+	if (o.min_cnt < 1 || o.min_cnt > 1023) { fprintf(stderr, "yak-amd correct: -c must be in [1, 1023]\n"); return 1; }
+	if (o.min_run < 1 || o.min_run > (int)k) { fprintf(stderr, "yak-amd correct: -e must be in [1, %u], the table's k\n", k); return 1; }
+	if (o.chunk_size < 1) { fprintf(stderr, "yak-amd correct: -K must be in [1, 2^63)\n"); return 1; }
+	yak_ch_t *tab = yak_ch_restore(argv[first]);
+	if (!tab) { fprintf(stderr, "yak-amd correct: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	const int rc = yakamd_correct(&o, tab, argv[first + 1], out, report ? report : o.stats_only ? "-" : 0) == 0 ? 0 : 3;
+	yak_ch_destroy(tab);
+	return rc;
+}
+
 /* ---- hetmers (not in the reference) ---- */
 /* the pairs of k-mers of a count table that differ in the middle base alone, as a histogram of their two counts (yakamd_hetmers) */
 static int cmd_hetmers(int argc, char **argv)
@@ -755,6 +790,7 @@ int main(int argc, char **argv)
 	if (argc >= 2 && strcmp(argv[1], "paths") == 0) return cmd_paths(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "bubbles") == 0) return cmd_bubbles(argc - 1, argv + 1);
 	if (argc >= 2 && strcmp(argv[1], "clean") == 0) return cmd_clean(argc - 1, argv + 1);
+	if (argc >= 2 && strcmp(argv[1], "correct") == 0) return cmd_correct(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
 	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-8s %s\n", cmds[i].name, cmds[i].what);
 	fprintf(stderr, "  beyond the reference:\n      yak-amd %-8s %s\n", "sum", "add the counts of two or more .yak tables together");
@@ -765,5 +801,6 @@ int main(int argc, char **argv)
 	fprintf(stderr, "      yak-amd %-8s %s\n", "paths", "sequences as paths through the unitigs of that graph (GAF)");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "bubbles", "the simple bubbles of that graph: forks whose two arms join again, with their alleles");
 	fprintf(stderr, "      yak-amd %-8s %s\n", "clean", "that graph with its tips clipped and its bubbles popped, as a .yak table of the k-mers that stay");
+	fprintf(stderr, "      yak-amd %-8s %s\n", "correct", "reads with their single substitution errors repaired against a .yak table");
 	return 1;
 }
