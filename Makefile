@@ -39,7 +39,7 @@ yak_amd/libyak_amd.so: yak_amd/kernels.o yak_amd/tally.o yak_amd/pool.o yak_amd/
 # headers of yak_amd/layer/, and tally.o linked in once more: its table is per library behind the version script.
 #   $(1) the name and its directory under yak_amd/, $(2) its further headers, $(3) the libraries below it in link order, $(4) further link flags
 LAYER     = yak_amd/layer
-LAYERDEPS = $(LAYER)/layer_host.h $(LAYER)/layer_dev.h $(CSRC)/tally.h include/yak.h include/yak_amd.h include/yak_amd_walk.h
+LAYERDEPS = $(LAYER)/layer_host.h $(LAYER)/layer_dev.h $(LAYER)/layer_seqs.h $(LAYER)/seq_reader.h $(CSRC)/tally.h include/yak.h include/yak_amd.h include/yak_amd_walk.h
 define LAYER_LIB
 yak_amd/$(1).o: yak_amd/$(1)/$(1).hip $(2) $$(LAYERDEPS)
 	$$(HIPCC) $$(HIPFLAGS) -c $$< -o $$@
@@ -52,13 +52,13 @@ $(eval $(call LAYER_LIB,walk,$(WALK)/uwalk_step.h $(WALK)/uwalk_host.h,yak_amd/l
 # the links between unitigs of `yak-amd unitigs -G`
 $(eval $(call LAYER_LIB,gfa,$(GFA)/gfa_step.h $(GFA)/gfa_text.h include/yak_amd_gfa.h,yak_amd/libyak_amd_walk.so yak_amd/libyak_amd.so))
 # sequences as paths on the unitig graph, `yak-amd paths`; gfa_step.h is a header and makes no link dependency
-$(eval $(call LAYER_LIB,path,$(PATHD)/path_step.h $(PATHD)/path_text.h $(PATHD)/path_reader.h $(GFA)/gfa_step.h include/yak_amd_path.h,yak_amd/libyak_amd_walk.so yak_amd/libyak_amd.so,-lz))
+$(eval $(call LAYER_LIB,path,$(PATHD)/path_step.h $(PATHD)/path_text.h $(GFA)/gfa_step.h include/yak_amd_path.h,yak_amd/libyak_amd_walk.so yak_amd/libyak_amd.so,-lz))
 # the simple bubbles of the unitig graph, `yak-amd bubbles`; gfa_text.h and gfa_step.h come in as headers for the -s text
 $(eval $(call LAYER_LIB,bubble,$(BUBBLE)/bubble_step.h $(BUBBLE)/bubble_text.h $(GFA)/gfa_step.h $(GFA)/gfa_text.h include/yak_amd_gfa.h include/yak_amd_bubble.h,yak_amd/libyak_amd_gfa.so yak_amd/libyak_amd_walk.so yak_amd/libyak_amd.so))
 # tips clipped and bubbles popped, `yak-amd clean`; the steps and texts of the bubbles and the links come in as headers
 $(eval $(call LAYER_LIB,clean,$(CLEAN)/clean_step.h $(CLEAN)/clean_text.h $(BUBBLE)/bubble_step.h $(BUBBLE)/bubble_text.h $(GFA)/gfa_step.h $(GFA)/gfa_text.h include/yak_amd_gfa.h include/yak_amd_bubble.h include/yak_amd_clean.h,yak_amd/libyak_amd_bubble.so yak_amd/libyak_amd_gfa.so yak_amd/libyak_amd_walk.so yak_amd/libyak_amd.so))
 # substitution errors of reads repaired, `yak-amd correct`: above libyak_amd.so alone
-$(eval $(call LAYER_LIB,correct,$(CORRECT)/correct_step.h $(CORRECT)/correct_text.h $(CORRECT)/correct_reader.h include/yak_amd_correct.h,yak_amd/libyak_amd.so,-lz))
+$(eval $(call LAYER_LIB,correct,$(CORRECT)/correct_step.h $(CORRECT)/correct_text.h include/yak_amd_correct.h,yak_amd/libyak_amd.so,-lz))
 
 yak_amd/yak-amd: $(CSRC)/main.c include/yak.h include/yak_amd.h include/yak_amd_walk.h include/yak_amd_gfa.h include/yak_amd_path.h include/yak_amd_bubble.h include/yak_amd_clean.h include/yak_amd_correct.h yak_amd/libyak_amd.so yak_amd/libyak_amd_walk.so yak_amd/libyak_amd_gfa.so yak_amd/libyak_amd_path.so yak_amd/libyak_amd_bubble.so yak_amd/libyak_amd_clean.so yak_amd/libyak_amd_correct.so
 	gcc -O2 -Wall -Iinclude $(CSRC)/main.c -o $@ -Lyak_amd -lyak_amd_correct -lyak_amd_clean -lyak_amd_bubble -lyak_amd_path -lyak_amd_gfa -lyak_amd_walk -lyak_amd -Wl,-rpath,'$$ORIGIN' -lz

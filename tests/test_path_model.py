@@ -1,9 +1,10 @@
 """The sequential model of the path kernels (tests/tools/path_model_check.cpp: the staging, the claims of every node in the index, the hits, the count
 per tile, the scan of the tile array, the emit and the tallies with the very functions of yak_amd/path/path_step.h, the texts of path_text.h, the
-reader of path_reader.h; built with the host compiler under the address and undefined-behaviour sanitizers and run as a program of its own, nothing
+reader of yak_amd/layer/seq_reader.h; built with the host compiler under the address and undefined-behaviour sanitizers and run as a program of its own, nothing
 of it is loaded into Python) against the restatement of tests/path_util.py, byte for byte: the hits, the records, the GAF and the -s text -- on the
 hand-derived cases of tests/test_path.py, on tiny random tables, with tiles of 8 and of 1024 positions, at a capacity of the index equal to the
-number of its keys, where the probe walks are longest; its refusals; and its reader against the engine's on the golden inputs."""
+number of its keys, where the probe walks are longest; its refusals; and its reader against the engine's on the golden inputs, and in its two
+modes -- the quality kept or only counted -- on awkward files."""
 import glob
 import gzip
 import os
@@ -147,7 +148,7 @@ def test_model_refuses(programs, tmp_path):
 
 
 def test_reader_against_the_engines(programs, tmp_path):
-    """what PxReader gives, sequence after sequence, is the image the engine's reader makes of the same file: the golden inputs, plain and gzip, a FASTQ
+    """what SeqReader gives, sequence after sequence, is the image the engine's reader makes of the same file: the golden inputs, plain and gzip, a FASTQ
     with '@' and '+' at the start of quality lines, and line ends of \\r\\n"""
     import yak_amd
     fq = tmp_path / "tricky.fq"
@@ -166,3 +167,52 @@ def test_reader_against_the_engines(programs, tmp_path):
         assert b"".join(s + b"\n" for s in seqs) == img, f
     got = run(programs[1024], "-", str(fq), "reader")
     assert got == b"a\tACGTACGTNN\nb\tTTGCA\nc\tACGT\nd\t\ne\tA\n"
+
+
+AWKWARD = [   # what the file holds, and the record it is: name, comment, sequence, quality
+    (b"@r1 first comment\r\nACGT\r\nAC\r\n+\r\nIIII\r\nJJ\r\n", (b"r1", b"first comment", b"ACGTAC", b"IIIIJJ")),      # \r\n; sequence and quality over two lines
+    (b"\n\n>r2\tc\tx\n\nAC\n\nGT\n", (b"r2", b"c\tx", b"ACGT", b"")),                                                  # empty lines in front and inside
+    (b">\nAAA\n", (b"", b"", b"AAA", b"")),                                                                            # an empty name
+    (b"> only a comment\nCC\n", (b"", b"only a comment", b"CC", b"")),
+    (b">e\n", (b"e", b"", b"", b"")),                                                                                  # an empty sequence
+    (b"@q\nAC\nGT\n+q\n@+\n>@\n", (b"q", b"", b"ACGT", b"@+>@")),                                                      # quality lines that start like headers
+    (b"@z\n+\n", (b"z", b"", b"", b"")),
+    (b">last trailing \nACGT", (b"last", b"trailing ", b"ACGT", b"")),                                                 # no newline at the end
+]
+
+
+def kept_records(out):
+    """the records of the mode records-kept: four times `<length>:<bytes>`, then a newline"""
+    recs, at = [], 0
+    while at < len(out):
+        rec = []
+        for _ in range(4):
+            colon = out.index(b":", at)
+            n = int(out[at:colon])
+            rec.append(out[colon + 1:colon + 1 + n])
+            at = colon + 1 + n
+        assert out[at:at + 1] == b"\n"
+        at += 1
+        recs.append(tuple(rec))
+    return recs
+
+
+def test_reader_keeps_or_counts_the_quality(programs, tmp_path):
+    """SeqReader in its two modes on one set of awkward files, plain and gzip: \\r\\n, a sequence and a quality over several lines, empty lines, no
+    newline at the end, an empty name, a comment, an empty sequence -- and behind them a record whose quality is one character short, which ends the
+    file in front of that record, whether more follows it or not.  With the quality kept the four parts of every record are what was written; with
+    it counted the names, the sequences and the number of records are the same"""
+    want = [rec for _, rec in AWKWARD]
+    whole = b"".join(text for text, _ in AWKWARD)
+    files = {"whole.fq": whole, "short.fq": whole + b"\n@bad\nACGT\n+\nIII\n>after\nAC\n", "short_at_end.fq": whole + b"\n@bad\nACGT\n+\nIII"}
+    for name, text in sorted(files.items()):
+        assert len(text) < 400
+        plain, gz = tmp_path / name, tmp_path / (name + ".gz")
+        plain.write_bytes(text)
+        with gzip.open(gz, "wb") as o:
+            o.write(text)
+        for f in (str(plain), str(gz)):
+            kept = kept_records(run(programs[1024], "-", f, "records-kept"))
+            assert kept == want, f
+            counted = run(programs[1024], "-", f, "reader")
+            assert counted == b"".join(r[0] + b"\t" + r[2] + b"\n" for r in kept), f

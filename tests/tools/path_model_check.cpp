@@ -1,18 +1,19 @@
-/* path_model_check.cpp -- `yak-amd paths` (yak_amd/path/path_step.h, path_text.h, path_reader.h) as a sequential program of its own, for the host
- * compiler and its sanitizers: path_model_check <model file> <sequences> hits|records|gaf|stats|reader reads the file tests/path_util.py model_file()
- * writes (64-bit words: k, min_cnt, the capacity of the index or 0, min_len, the numbers of unitigs and of bases, the descriptors; then the bases)
- * and the sequences through PxReader, and does what the kernels of yak_amd/path/path.hip do, tile by tile and thread by thread, with the very
+/* path_model_check.cpp -- `yak-amd paths` (yak_amd/path/path_step.h, path_text.h, yak_amd/layer/seq_reader.h) as a sequential program of its own,
+ * for the host compiler and its sanitizers: path_model_check <model file> <sequences> hits|records|gaf|stats|reader|records-kept reads the file
+ * tests/path_util.py model_file() writes (64-bit words: k, min_cnt, the capacity of the index or 0, min_len, the numbers of unitigs and of bases, the descriptors; then the bases)
+ * and the sequences through SeqReader, and does what the kernels of yak_amd/path/path.hip do, tile by tile and thread by thread, with the very
  * functions they call: the staging, the claims of every node, the hits, the count per tile, the scan of the tile array in slices, the emit on top of
  * it, the tallies lane by lane.  Built with -DPX_THREADS_N=2 its tiles have 8 positions.  It prints the hits one a line, or the records (`P seq qs
  * qe ps step_off n_step`, `S step`, `Y n_kmer n_hit n_path n_step`, a last line `T table_slots keys max_probe`), or one of the two texts, or what
- * the reader gives (`name<tab>sequence`).  Exit 1 after a message when a file cannot be read, the capacity is below the number of keys, a claim
- * meets no free slot or a key a second time, or the descriptors do not fit the bases. */
+ * the reader gives (`name<tab>sequence` with the quality counted; with it kept, for records-kept, name, comment, sequence and quality, each as
+ * its length, a colon and its bytes, and a newline behind the four).  Exit 1 after a message when a file cannot be read, the capacity is below
+ * the number of keys, a claim meets no free slot or a key a second time, or the descriptors do not fit the bases. */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <vector>
 #include "../../yak_amd/path/path_text.h"
-#include "../../yak_amd/path/path_reader.h"
+#include "../../yak_amd/layer/seq_reader.h"
 
 static int fail(const char *what) { fprintf(stderr, "path: %s\n", what); return 1; }
 
@@ -35,13 +36,18 @@ static void load_hits(const std::vector<uint64_t> &hit, int64_t n, int64_t i0, u
 
 int main(int argc, char **argv)
 {
-	if (argc != 4) { fprintf(stderr, "usage: path_model_check <model file> <sequences> hits|records|gaf|stats|reader\n"); return 2; }
+	if (argc != 4) { fprintf(stderr, "usage: path_model_check <model file> <sequences> hits|records|gaf|stats|reader|records-kept\n"); return 2; }
 	const char *mode = argv[3];
-	if (strcmp(mode, "reader") == 0) {
-		PxReader rd;
-		std::string name, seq;
+	if (strcmp(mode, "reader") == 0 || strcmp(mode, "records-kept") == 0) {
+		const bool kept = strcmp(mode, "records-kept") == 0;
+		SeqReader rd(kept);
+		seq_record_t r;
 		if (!rd.open(argv[2])) return fail("cannot read the sequences");
-		while (rd.next(name, seq)) printf("%s\t%s\n", name.c_str(), seq.c_str());
+		while (rd.next(r)) {
+			if (!kept) { printf("%s\t%s\n", r.name.c_str(), r.seq.c_str()); continue; }
+			for (const std::string *s : { &r.name, &r.comment, &r.seq, &r.qual }) { printf("%zu:", s->size()); fwrite(s->data(), 1, s->size(), stdout); }
+			putchar('\n');
+		}
 		return rd.failed() ? fail("the sequences are damaged") : 0;
 	}
 	FILE *fp = fopen(argv[1], "rb");
@@ -90,17 +96,18 @@ int main(int argc, char **argv)
 	if (n_key != n_node) return fail("the index does not hold every node");
 
 	/* the sequences: one chunk */
-	std::vector<pxt_seq_t> seqs;
+	std::vector<std::string> seqs;
 	std::vector<unsigned char> img;
 	std::vector<uint64_t> off;
 	std::vector<uint32_t> len;
 	{
-		PxReader rd;
-		std::string name, seq;
+		SeqReader rd(false);
+		seq_record_t r;
 		if (!rd.open(argv[2])) return fail("cannot read the sequences");
-		while (rd.next(name, seq)) {
+		while (rd.next(r)) {
+			const std::string &seq = r.seq;
 			off.push_back(img.size()); len.push_back((uint32_t)seq.size());
-			seqs.push_back(pxt_seq_t{ name, seq.size() });
+			seqs.push_back(r.name);
 			img.insert(img.end(), seq.begin(), seq.end());
 			img.push_back('\n');
 		}
@@ -206,11 +213,11 @@ int main(int argc, char **argv)
 		return 0;
 	}
 	if (strcmp(mode, "gaf") == 0) {
-		if (!pxt_gaf(text, seqs, paths.data(), n_path, steps.data(), n_step, nodes_of.data(), n_u, k, min_len)) return fail("a record does not fit its chunk");
+		if (!pxt_gaf(text, seqs, len.data(), paths.data(), n_path, steps.data(), n_step, nodes_of.data(), n_u, k, min_len)) return fail("a record does not fit its chunk");
 	} else if (strcmp(mode, "stats") == 0) {
 		pxt_total_t tot = { 0, 0, 0, 0, 0, 0 };
 		pxt_stats_head(text, k, min_cnt);
-		pxt_stats(text, seqs, tally.data(), &tot);
+		pxt_stats(text, seqs, len.data(), tally.data(), &tot);
 		pxt_stats_tail(text, tot);
 	} else return fail("the mode is none of hits, records, gaf, stats, reader");
 	fwrite(text.data(), 1, text.size(), stdout);

@@ -1,6 +1,6 @@
 /* correct_model_check.cpp -- the sequential model of the correction kernels (yak_amd/correct/correct.hip): the find, the trial
  * image and the decisions with the very functions of yak_amd/correct/correct_step.h, a position or a record at a time in image order, the texts of
- * correct_text.h and the reader of correct_reader.h.  Host compiler only, built with the address and undefined-behaviour sanitizers
+ * correct_text.h and the reader of yak_amd/layer/seq_reader.h.  Host compiler only, built with the address and undefined-behaviour sanitizers
  * (tools/Makefile) and run as a program of its own by tests/test_correct_model.py.  The lookups are served from the stored keys of a .yak dump:
  *
  *   correct_model_check <table> <reads> <mode> [chunk_size]
@@ -18,7 +18,7 @@
 #include <vector>
 #include "../yak_amd/correct/correct_step.h"
 #include "../yak_amd/correct/correct_text.h"
-#include "../yak_amd/correct/correct_reader.h"
+#include "../yak_amd/layer/seq_reader.h"
 
 namespace {
 
@@ -85,7 +85,7 @@ struct Image {
 	std::vector<uint8_t> img;
 	std::vector<uint64_t> off;
 	std::vector<uint32_t> len;
-	std::vector<cr_record_t> recs;
+	std::vector<seq_record_t> recs;
 	void clear() { img.clear(); off.clear(); len.clear(); recs.clear(); }
 };
 
@@ -175,12 +175,12 @@ bool run_image(const Table &t, Image *im, std::string *report, std::string *read
 	for (size_t j = 0; j < im->recs.size(); ++j) {
 		crt_seq(*report, im->recs[j].name, im->len[j], tally[j], tot);
 		for (; f < fix.size() && fix[f].seq <= j; ++f) if (fix[f].seq == j && fix[f].why == CR_DONE) crt_fix(*report, im->recs[j].name, fix[f]);
-		crt_read(*reads, im->recs[j], (const char*)im->img.data() + im->off[j], im->len[j]);
+		crt_read(*reads, im->recs[j].name, im->recs[j].comment, im->recs[j].qual, (const char*)im->img.data() + im->off[j], im->len[j]);
 	}
 	return true;
 }
 
-void add(Image *im, cr_record_t &r)
+void add(Image *im, seq_record_t &r)
 {
 	im->off.push_back(im->img.size());
 	im->len.push_back((uint32_t)r.seq.size());
@@ -202,10 +202,10 @@ int main(int argc, char **argv)
 	if (t.min_cnt < 1 || t.min_cnt > 1023 || t.min_run < 1 || t.min_run > t.k) return die("min_cnt or min_run out of range");
 	const uint64_t chunk = argc > 4 ? strtoull(argv[4], 0, 10) : (uint64_t)1 << 28;
 	if (chunk < 1) return die("chunk_size out of range");
-	CrReader rd;
+	SeqReader rd(true);
 	if (!rd.open(argv[2])) return die("the reads cannot be opened");
 	Image im;
-	cr_record_t r;
+	seq_record_t r;
 	if (mode == "report" || mode == "reads") {
 		std::string report, reads;
 		crt_total_t tot;

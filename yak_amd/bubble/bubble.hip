@@ -285,14 +285,7 @@ extern "C" int yakamd_bubble_stats(yakamd_bubble_set_t *b, yakamd_bubstat_t *st)
 
 extern "C" int64_t yakamd_bubble_records_dev(yakamd_bubble_set_t *b, void *d, int64_t cap)
 {
-	if (!b) return fail("bubble records: no bubbles");
-	const u64 n = b->st.n_bubble;
-	if (!d || cap < (int64_t)n) return (int64_t)n;
-	if (((uintptr_t)d & 15) != 0) return fail("bubble records: the entries must be 16-byte aligned");
-	if (n == 0) return 0;
-	OnDevice dev(b->dev);
-	HIPCK(hipMemcpy(d, b->rec.p, n * sizeof(bb_rec_t), hipMemcpyDeviceToDevice));
-	return (int64_t)n;
+	return copy_out(b != 0, b ? b->dev : 0, b ? b->rec.p : 0, b ? b->st.n_bubble : 0, sizeof(bb_rec_t), d, cap, "bubble records", "bubbles", "the entries");
 }
 
 /* the command: the walk, the links, the bubbles, then the text from the tallies or from the records, the descriptors and the bases */
@@ -300,18 +293,18 @@ extern "C" int yakamd_bubbles(const yakamd_ugopt_t *opt, yak_ch_t *ch, const cha
 {
 	if (!opt) return fail("yakamd_bubbles: no options");
 	WalkGuard W{ yakamd_uwalk_open(ch, opt->min_cnt) };
-	if (!W.w) return fail_below(yakamd_walk_last_error());
-	struct Gfa { yakamd_gfa_t *g; ~Gfa() { yakamd_gfa_close(g); } } G{ yakamd_gfa_open(W.w, ch->k) };
-	if (!G.g) return fail_below(yakamd_gfa_last_error());
-	struct Bub { yakamd_bubble_set_t *b; ~Bub() { yakamd_bubble_close(b); } } B{ bubble_open(W.w, G.g, ch->k, !opt->stats_only) };
-	yakamd_bubble_set_t *b = B.b;
+	if (!W.p) return fail_below(yakamd_walk_last_error());
+	Guard<yakamd_gfa_t, yakamd_gfa_close> G{ yakamd_gfa_open(W.p, ch->k) };
+	if (!G.p) return fail_below(yakamd_gfa_last_error());
+	Guard<yakamd_bubble_set_t, yakamd_bubble_close> B{ bubble_open(W.p, G.p, ch->k, !opt->stats_only) };
+	yakamd_bubble_set_t *b = B.p;
 	if (!b) return -1;
 	const double t0 = now_ms();
 	yakamd_gstat_t gs;
 	yakamd_uwstat_t us;
 	yakamd_gfastat_t fs;
-	if (yakamd_uwalk_gstat(W.w, &gs) != 0 || yakamd_uwalk_stats(W.w, &us) != 0) return fail_below(yakamd_walk_last_error());
-	if (yakamd_gfa_stats(G.g, &fs) != 0) return fail_below(yakamd_gfa_last_error());
+	if (yakamd_uwalk_gstat(W.p, &gs) != 0 || yakamd_uwalk_stats(W.p, &us) != 0) return fail_below(yakamd_walk_last_error());
+	if (yakamd_gfa_stats(G.p, &fs) != 0) return fail_below(yakamd_gfa_last_error());
 	std::string bases;
 	std::vector<bb_desc_t> desc;
 	std::vector<bb_rec_t> rec;
@@ -328,14 +321,9 @@ extern "C" int yakamd_bubbles(const yakamd_ugopt_t *opt, yak_ch_t *ch, const cha
 	bool ok = true;
 	try {
 		if (opt->stats_only) {
-			gft_tallies_t t;
-			t.k = b->k; t.min_cnt = opt->min_cnt;
-			t.n_key = gs.n_key; t.n_node = gs.n_node; t.n_arc = gs.n_arc; t.n_linked_side = gs.n_linked_side;
-			for (int l = 0; l < 5; ++l) for (int r = 0; r < 5; ++r) t.deg[l][r] = gs.deg[l][r];
-			t.n_open = us.n_open; t.n_cycle = us.n_cycle; t.sum_len = us.sum_len; t.max_len = us.max_len; t.n50 = us.n50;
 			bbt_stats_t s;
 			memcpy(&s, &b->st, sizeof s);
-			ok = out.write(gft_stats(t, fs.n_link, fs.end_deg) + bbt_stats_line(s));
+			ok = out.write(gft_stats(gft_tallies(b->k, opt->min_cnt, gs, us), fs.n_link, fs.end_deg) + bbt_stats_line(s));
 		} else
 			ok = bbt_bubbles(rec.data(), rec.size(), desc.data(), b->n_unitig, bases.data(), b->n_bases, b->k, opt->min_cnt,
 			                 [&out](const std::string &t) { return out.write(t); });

@@ -308,9 +308,6 @@ yakamd_clean_set_t *clean_open(yakamd_uwalk_t *w, yakamd_gfa_t *g, yakamd_bubble
 	return c;
 }
 
-struct GfaGuard { yakamd_gfa_t *g; ~GfaGuard() { close(); } void close() { yakamd_gfa_close(g); g = 0; } };
-struct BubGuard { yakamd_bubble_set_t *b; ~BubGuard() { close(); } void close() { yakamd_bubble_close(b); b = 0; } };
-struct CleanGuard { yakamd_clean_set_t *c; ~CleanGuard() { yakamd_clean_close(c); } };
 struct TableGuard { yak_ch_t *h; ~TableGuard() { if (h) yak_ch_destroy(h); } };
 
 /* the options of a round or a command, tip_nodes resolved against the table's k */
@@ -332,38 +329,38 @@ int64_t round_run(yak_ch_t *h, int min_cnt, int tip_nodes, int pop_pct, yakamd_c
 	memset(st, 0, sizeof *st);
 	double t0 = now_ms();
 	WalkGuard W{ yakamd_uwalk_open(h, min_cnt) };
-	if (!W.w) return fail_below(yakamd_walk_last_error());
+	if (!W.p) return fail_below(yakamd_walk_last_error());
 	g_ms[MS_WALK] += now_ms() - t0; t0 = now_ms();
-	GfaGuard G{ yakamd_gfa_open(W.w, h->k) };
-	if (!G.g) return fail_below(yakamd_gfa_last_error());
+	Guard<yakamd_gfa_t, yakamd_gfa_close> G{ yakamd_gfa_open(W.p, h->k) };
+	if (!G.p) return fail_below(yakamd_gfa_last_error());
 	g_ms[MS_LINKS] += now_ms() - t0; t0 = now_ms();
-	BubGuard B{ yakamd_bubble_open(W.w, G.g, h->k) };
-	if (!B.b) return fail_below(yakamd_bubble_last_error());
+	Guard<yakamd_bubble_set_t, yakamd_bubble_close> B{ yakamd_bubble_open(W.p, G.p, h->k) };
+	if (!B.p) return fail_below(yakamd_bubble_last_error());
 	g_ms[MS_BUBBLES] += now_ms() - t0;
 	yakamd_uwstat_t us;
 	yakamd_gfastat_t gs;
 	yakamd_bubstat_t bs;
-	CleanGuard C{ clean_open(W.w, G.g, B.b, h->k, tip_nodes, pop_pct, &us, &gs, &bs) };
-	if (!C.c) return -1;
+	Guard<yakamd_clean_set_t, yakamd_clean_close> C{ clean_open(W.p, G.p, B.p, h->k, tip_nodes, pop_pct, &us, &gs, &bs) };
+	if (!C.p) return -1;
 	B.close(); G.close(); W.close();                               /* their device memory is free for D */
-	const yakamd_cleanstat_t &cs = C.c->st;
+	const yakamd_cleanstat_t &cs = C.p->st;
 	st->n_key = us.n_key; st->n_unitig = gs.n_unitig; st->n_link = gs.n_link; st->n_bubble = bs.n_bubble;
 	st->n_tip = cs.n_tip; st->tip_nodes = cs.tip_nodes; st->n_pop = cs.n_pop; st->pop_nodes = cs.pop_nodes;
 	if (cs.n_rec == 0) return 0;                                   /* nothing goes: the table stays as it is, no D */
 	t0 = now_ms();
 	const u64 nodes = cs.tip_nodes + cs.pop_nodes;
-	OnDevice dev(C.c->dev);
+	OnDevice dev(C.p->dev);
 	if (list) {
 		try { list->resize((size_t)cs.n_rec); } catch (const std::bad_alloc&) { return fail("clean: %llu records do not fit the host's memory", (u64)cs.n_rec); }
-		HIPCK(hipMemcpy(list->data(), C.c->rec.p, (size_t)cs.n_rec * sizeof(cl_rec_t), hipMemcpyDeviceToHost));
+		HIPCK(hipMemcpy(list->data(), C.p->rec.p, (size_t)cs.n_rec * sizeof(cl_rec_t), hipMemcpyDeviceToHost));
 	}
 	TableGuard D{ yak_ch_init(h->k, h->pre, 0, 0) };
 	if (!D.h) return fail_below(yakamd_last_error());
 	int d_dev = -1;
 	HIPCK(hipGetDevice(&d_dev));
-	if (d_dev != C.c->dev) return fail("clean: the table lives on device %d and a new table opens on device %d: set YAKAMD_DEVICE to %d", C.c->dev, d_dev, C.c->dev);
+	if (d_dev != C.p->dev) return fail("clean: the table lives on device %d and a new table opens on device %d: set YAKAMD_DEVICE to %d", C.p->dev, d_dev, C.p->dev);
 	if (yakamd_pass_begin(D.h, 1) != 0) return fail_below(yakamd_last_error());
-	const int fed = yakamd_feed_bases_dev(D.h, C.c->img.p, (int64_t)cs.img_bytes, 0);
+	const int fed = yakamd_feed_bases_dev(D.h, C.p->img.p, (int64_t)cs.img_bytes, 0);
 	const int64_t n_new = yakamd_pass_end(D.h);                    /* closes the pass whatever the feed did */
 	if (fed != 0 || n_new < 0) return fail_below(yakamd_last_error());
 	D.h->tot += (uint64_t)n_new;
@@ -408,26 +405,12 @@ extern "C" int yakamd_clean_stats(yakamd_clean_set_t *c, yakamd_cleanstat_t *st)
 
 extern "C" int64_t yakamd_clean_records_dev(yakamd_clean_set_t *c, void *d, int64_t cap)
 {
-	if (!c) return fail("clean records: no decisions");
-	const u64 n = c->st.n_rec;
-	if (!d || cap < (int64_t)n) return (int64_t)n;
-	if (((uintptr_t)d & 15) != 0) return fail("clean records: the entries must be 16-byte aligned");
-	if (n == 0) return 0;
-	OnDevice dev(c->dev);
-	HIPCK(hipMemcpy(d, c->rec.p, n * sizeof(cl_rec_t), hipMemcpyDeviceToDevice));
-	return (int64_t)n;
+	return copy_out(c != 0, c ? c->dev : 0, c ? c->rec.p : 0, c ? c->st.n_rec : 0, sizeof(cl_rec_t), d, cap, "clean records", "decisions", "the entries");
 }
 
 extern "C" int64_t yakamd_clean_image_dev(yakamd_clean_set_t *c, void *d, int64_t cap)
 {
-	if (!c) return fail("clean image: no decisions");
-	const u64 n = c->st.img_bytes;
-	if (!d || cap < (int64_t)n) return (int64_t)n;
-	if (((uintptr_t)d & 15) != 0) return fail("clean image: the image must be 16-byte aligned");
-	if (n == 0) return 0;
-	OnDevice dev(c->dev);
-	HIPCK(hipMemcpy(d, c->img.p, n, hipMemcpyDeviceToDevice));
-	return (int64_t)n;
+	return copy_out(c != 0, c ? c->dev : 0, c ? c->img.p : 0, c ? c->st.img_bytes : 0, 1, d, cap, "clean image", "decisions", "the image");
 }
 
 extern "C" int64_t yakamd_clean_round(yak_ch_t *h, const yakamd_cleanopt_t *o, yakamd_cleanround_t *st)
@@ -449,7 +432,7 @@ extern "C" int yakamd_clean(const yakamd_cleanopt_t *o, yak_ch_t *ch, const char
 	{
 		WalkGuard probe{ yakamd_uwalk_open(ch, o->min_cnt) };          /* everything the walk refuses, before the table is touched */
 		yakamd_uwstat_t us;
-		if (!probe.w || yakamd_uwalk_stats(probe.w, &us) != 0) return fail_below(yakamd_walk_last_error());
+		if (!probe.p || yakamd_uwalk_stats(probe.p, &us) != 0) return fail_below(yakamd_walk_last_error());
 		n_in = us.n_key;                                               /* a restored table does not say in `tot` how many keys it holds */
 	}
 	std::string text = clt_head(ch->k, o->min_cnt, tip_nodes, o->pop_pct);

@@ -2,7 +2,7 @@
  * correct.hip -- libyak_amd_correct.so: single substitution errors of reads repaired on the GPU against a count table (include/yak_amd_correct.h;
  * DESIGN.md section 30).  A layer above libyak_amd.so alone: it calls yakamd_lookup_dev for every probe of the table, yakamd_ch_hpc and
  * seq_nt4_table, nothing else, and owns its device memory (hipMalloc / hipFree).  The per-thread steps are those of correct_step.h, the texts those
- * of correct_text.h, the reader that of correct_reader.h; every launch goes through the launch macro of ../csrc/tally.h into this library's own
+ * of correct_text.h, the reader and the chunk loop those of ../layer/layer_seqs.h; every launch goes through the launch macro of ../csrc/tally.h into this library's own
  * tally (yakamd_correct_tally_*).  The host scaffolding and the scan are those of ../layer/layer_host.h and ../layer/layer_dev.h.
  *
  *   k_cor_find<COUNT>  a workgroup per group of eight tiles of 1024 positions of the count array, a tile at a time staged in LDS with one entry in front and k + 1 behind (16-byte
@@ -24,10 +24,10 @@
 #include "yak_amd_correct.h"
 #define LAYER_NAME "correct"
 #include "../layer/layer_host.h"
+#include "../layer/layer_seqs.h"
 #include "../layer/layer_dev.h"
 #include "correct_step.h"
 #include "correct_text.h"
-#include "correct_reader.h"
 
 static_assert(sizeof(yakamd_fix_t) == 32 && sizeof(cr_fix_t) == 32 && sizeof(yakamd_ctally_t) == 32 && sizeof(cr_tally_t) == 32 && sizeof(yakamd_cropt_t) == 24,
               "the records as declared");
@@ -261,7 +261,6 @@ void k_cor_decide(const uint16_t *__restrict__ tc, cr_fix_t *__restrict__ rec, u
 thread_local double g_ms[6];                                       /* of this thread's last call */
 enum { MS_LOOKUP1 = 0, MS_FIND = 1, MS_TRIALS = 2, MS_LOOKUP2 = 3, MS_DECIDE = 4, MS_TEXT = 5 };
 
-inline u64 up16(u64 n) { return (n + 15) / 16 * 16; }
 
 /* device memory kept from one image to the next */
 struct Work {
@@ -465,55 +464,37 @@ extern "C" int64_t yakamd_correct_image_dev(yak_ch_t *h, int min_cnt, int min_ru
 /* ---- the command ---- */
 namespace {
 
-struct Chunk {
-	std::vector<cr_record_t> recs;
-	std::vector<char> img;
-	std::vector<uint64_t> off;
-	std::vector<uint32_t> len;
-	void clear() { recs.clear(); img.clear(); off.clear(); len.clear(); }
-};
-struct ChunkDev { DevBuf img, off, len, tally; };
-
-/* a text goes to its output, if it has one, in pieces of 4 MiB; *ok = false once a piece could not be written */
-void flush(std::string &text, OutFile *out, bool all, bool *ok)
-{
-	if (!all && text.size() < (size_t)1 << 22) return;
-	if (out && !text.empty()) *ok = out->write(text) && *ok;
-	text.clear();
-}
+struct ChunkDev { SeqChunkDev seqs; DevBuf tally; };
 
 /* one chunk through the device; its lines behind `report`, its reads behind `reads` */
-int run_chunk(Work &w, yak_ch_t *h, const yakamd_cropt_t &o, Chunk &c, ChunkDev &d, std::string &report, std::string &reads, crt_total_t *tot, OutFile *report_out,
+int run_chunk(Work &w, yak_ch_t *h, const yakamd_cropt_t &o, SeqChunk &c, ChunkDev &d, std::string &report, std::string &reads, crt_total_t *tot, OutFile *report_out,
               OutFile *reads_out, bool *ok)
 {
-	const size_t n = c.img.size(), n_seq = c.recs.size();
+	const size_t n_seq = c.name.size();
+	size_t n = 0;
 	if (n_seq == 0) return 0;
 	double t0 = now_ms();
-	c.img.resize((size_t)up16(n), '\n');
-	if (!d.img.need(c.img.size()) || !d.off.need(n_seq * 8) || !d.len.need(n_seq * 4) || !d.tally.need(n_seq * sizeof(cr_tally_t)))
-		return fail("yakamd_correct: no device memory for a chunk of %zu bytes", n);
-	HIPCK(hipMemcpy(d.img.p, c.img.data(), c.img.size(), hipMemcpyHostToDevice));
-	HIPCK(hipMemcpy(d.off.p, c.off.data(), n_seq * 8, hipMemcpyHostToDevice));
-	HIPCK(hipMemcpy(d.len.p, c.len.data(), n_seq * 4, hipMemcpyHostToDevice));
+	if (!d.tally.need(n_seq * sizeof(cr_tally_t))) return fail("yakamd_correct: no device memory for a chunk of %zu bytes", c.img.size());
+	if (d.seqs.upload("yakamd_correct", c, &n, 0) != 0) return -1;
 	g_ms[MS_TEXT] += now_ms() - t0;
 	yakamd_fix_t *d_fix = 0;
-	const int64_t n_fix = image_run(w, h, o.min_cnt, o.min_run, d.img.p, (int64_t)n, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)n_seq, 0, 0,
+	const int64_t n_fix = image_run(w, h, o.min_cnt, o.min_run, d.seqs.img.p, (int64_t)n, (const uint64_t*)d.seqs.off.p, (const uint32_t*)d.seqs.len.p, (int64_t)n_seq, 0, 0,
 	                                (yakamd_ctally_t*)d.tally.p, &d_fix);
 	if (n_fix < 0) return -1;
 	t0 = now_ms();
 	std::vector<cr_tally_t> tally(n_seq);
 	std::vector<cr_fix_t> fix;
 	HIPCK(hipMemcpy(tally.data(), d.tally.p, n_seq * sizeof(cr_tally_t), hipMemcpyDeviceToHost));
-	if (n_fix > 0 && !o.stats_only) HIPCK(hipMemcpy(c.img.data(), d.img.p, n, hipMemcpyDeviceToHost));
+	if (n_fix > 0 && !o.stats_only) HIPCK(hipMemcpy(c.img.data(), d.seqs.img.p, n, hipMemcpyDeviceToHost));
 	if (n_fix > 0 && o.list) {
 		fix.resize((size_t)n_fix);
 		HIPCK(hipMemcpy(fix.data(), d_fix, (size_t)n_fix * sizeof(cr_fix_t), hipMemcpyDeviceToHost));
 	}
 	size_t f = 0;
 	for (size_t j = 0; j < n_seq; ++j) {
-		crt_seq(report, c.recs[j].name, c.len[j], tally[j], tot);
-		for (; f < fix.size() && fix[f].seq <= j; ++f) if (fix[f].seq == j && fix[f].why == CR_DONE) crt_fix(report, c.recs[j].name, fix[f]);
-		if (!o.stats_only) crt_read(reads, c.recs[j], c.img.data() + c.off[j], c.len[j]);
+		crt_seq(report, c.name[j], c.len[j], tally[j], tot);
+		for (; f < fix.size() && fix[f].seq <= j; ++f) if (fix[f].seq == j && fix[f].why == CR_DONE) crt_fix(report, c.name[j], fix[f]);
+		if (!o.stats_only) crt_read(reads, c.name[j], c.comment[j], c.qual[j], c.img.data() + c.off[j], c.len[j]);
 		flush(reads, reads_out, false, ok);
 		flush(report, report_out, false, ok);
 	}
@@ -530,7 +511,7 @@ extern "C" int yakamd_correct(const yakamd_cropt_t *o, yak_ch_t *ch, const char 
 	if (o->chunk_size < 1) return fail("yakamd_correct: chunk_size %lld", (long long)o->chunk_size);
 	if (table_check("yakamd_correct", ch, o->min_cnt, o->min_run) != 0) return -1;
 	if (!fn) return fail("yakamd_correct: no reads");
-	CrReader rd;
+	SeqReader rd(true);                                            /* the qualities are written out again */
 	if (!rd.open(fn)) return fail("yakamd_correct: cannot read '%s'", fn);
 	struct Out {                                                   /* an output that may be absent */
 		OutFile *f;
@@ -540,43 +521,21 @@ extern "C" int yakamd_correct(const yakamd_cropt_t *o, yak_ch_t *ch, const char 
 	if (!o->stats_only && (!reads_out.f || !reads_out.f->f)) return fail("yakamd_correct: cannot write '%s'", out_fn ? out_fn : "-");
 	if (report_fn && (!report_out.f || !report_out.f->f)) return fail("yakamd_correct: cannot write '%s'", report_fn);
 	bool ok = true;
-	try {
-		Work w;
-		Chunk c;
-		ChunkDev d;
-		std::string report, reads;
-		crt_total_t tot;
-		memset(&tot, 0, sizeof tot);
-		crt_head(report, ch->k, o->min_cnt, o->min_run);
-		uint64_t bases = 0;
-		bool more = true;
-		while (more) {
-			double t0 = now_ms();
-			cr_record_t r;
-			more = rd.next(r);
-			if (more) {
-				if (r.seq.size() >= 0xffffffffull) return fail("yakamd_correct: sequence '%s' has %zu bases: a length is a 32-bit number", r.name.c_str(), r.seq.size());
-				c.off.push_back(c.img.size());
-				c.len.push_back((uint32_t)r.seq.size());
-				c.img.insert(c.img.end(), r.seq.begin(), r.seq.end());
-				c.img.push_back('\n');
-				bases += r.seq.size();
-				r.seq.clear();                                             /* the image holds it */
-				c.recs.push_back(std::move(r));
-			}
-			g_ms[MS_TEXT] += now_ms() - t0;
-			if ((!more || bases >= (uint64_t)o->chunk_size) && !c.recs.empty()) {
-				if (run_chunk(w, ch, *o, c, d, report, reads, &tot, report_out.f, reads_out.f, &ok) != 0) return -1;
-				c.clear(); bases = 0;
-			}
-			t0 = now_ms();
-			if (!more) crt_last(report, tot);
-			flush(reads, reads_out.f, !more, &ok);
-			flush(report, report_out.f, !more, &ok);
-			g_ms[MS_TEXT] += now_ms() - t0;
-		}
-		if (rd.failed()) return fail("yakamd_correct: '%s' is damaged: the inflater gave up", fn);
-	} catch (const std::bad_alloc&) { return fail("yakamd_correct: no host memory for a chunk"); }
+	Work w;
+	ChunkDev d;
+	std::string report, reads;
+	crt_total_t tot;
+	memset(&tot, 0, sizeof tot);
+	crt_head(report, ch->k, o->min_cnt, o->min_run);
+	if (seq_chunks("yakamd_correct", rd, fn, o->chunk_size, &g_ms[MS_TEXT], [&](SeqChunk &c, bool last) {
+		if (run_chunk(w, ch, *o, c, d, report, reads, &tot, report_out.f, reads_out.f, &ok) != 0) return -1;
+		const double t0 = now_ms();
+		if (last) crt_last(report, tot);
+		flush(reads, reads_out.f, last, &ok);
+		flush(report, report_out.f, last, &ok);
+		g_ms[MS_TEXT] += now_ms() - t0;
+		return 0;
+	}) != 0) return -1;
 	if (reads_out.f && !(reads_out.f->finish() && ok)) return fail("yakamd_correct: cannot write '%s'", reads_out.f->name);
 	if (report_out.f && !(report_out.f->finish() && ok)) return fail("yakamd_correct: cannot write '%s'", report_out.f->name);
 	if (getenv("YAKAMD_VERBOSE"))

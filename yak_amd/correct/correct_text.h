@@ -5,7 +5,6 @@
 #define YK_CORRECT_TEXT_H
 #include <stdio.h>
 #include <string>
-#include "correct_reader.h"
 #include "correct_step.h"
 
 struct crt_total_t { uint64_t n_seq, sum_len, v[7]; };
@@ -57,14 +56,14 @@ static inline void crt_last(std::string &text, const crt_total_t &tot)
 }
 
 /* a record in its normal form with `seq` (len bytes) for its sequence: `>name[ comment]\nSEQ\n`, or `@name[ comment]\nSEQ\n+\nQUAL\n` with a quality */
-static inline void crt_read(std::string &text, const cr_record_t &r, const char *seq, size_t len)
+static inline void crt_read(std::string &text, const std::string &name, const std::string &comment, const std::string &qual, const char *seq, size_t len)
 {
-	text += r.qual.empty() ? '>' : '@';
-	text += r.name;
-	if (!r.comment.empty()) { text += ' '; text += r.comment; }
+	text += qual.empty() ? '>' : '@';
+	text += name;
+	if (!comment.empty()) { text += ' '; text += comment; }
 	text += '\n';
 	text.append(seq, len);
 	text += '\n';
-	if (!r.qual.empty()) { text += "+\n"; text += r.qual; text += '\n'; }
+	if (!qual.empty()) { text += "+\n"; text += qual; text += '\n'; }
 }
 #endif

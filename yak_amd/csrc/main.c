@@ -17,12 +17,13 @@
  *     recount  the counts of a table's k-mers in other sequences, reference main.c:66-88 (restore, tighten, yak_recount)
  *     subtract, isec   the k-mers of the first table absent from / present in the others, reference main.c:217-284
  *     version  the library's YAKS_VERSION
- * and eight beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table), hetmers
+ * and nine beyond the reference: sum (yakamd_ch_sum), depth (yakamd_depth: the depth of every sequence or window in a count table), hetmers
  * (yakamd_hetmers: the pairs of k-mers of a count table that differ in the middle base alone), cover (yakamd_cover: the bases of every sequence
  * that lie inside k-mers a table holds, lacks or holds too often -- as a table, as intervals or as a masked FASTA), unitigs (yakamd_unitigs: the
  * de Bruijn graph the k-mers of a count table span, as its unitigs in FASTA or as its tallies), paths (yakamd_paths: the sequences of a file as
  * paths through those unitigs, as GAF or as tallies per sequence), bubbles (yakamd_bubbles: the forks of that graph whose two arms join again,
- * with their types and alleles) and clean (yakamd_clean: the table without the k-mers of that graph's tips and weaker bubble arms), and correct (yakamd_correct: reads with their single substitution errors repaired against a table).  `count -c` and `qv -c` work in homopolymer-compressed
+ * with their types and alleles), clean (yakamd_clean: the table without the k-mers of that graph's tips and weaker bubble arms) and correct
+ * (yakamd_correct: reads with their single substitution errors repaired against a table).  `count -c` and `qv -c` work in homopolymer-compressed
  * space (yakamd_count_hpc; yakamd_ch_set_hpc on the restored table): every run of one base is one base before k-mers are taken.
  * Option letters follow the reference so that test command lines can be shared; the parser, the
  * sub-command table and the usage texts are this file's own.
@@ -96,6 +97,50 @@ static void arg_help(const char *synopsis, const struct arg_def *defs, int n_def
 	for (int j = 0; j < n_defs; ++j) fprintf(stderr, "    -%c%s  %s\n", defs[j].letter, defs[j].kind == ARG_FLAG ? "     " : " VAL ", defs[j].what);
 }
 
+/* ---- the table of a command ---- */
+/* k and pre of a .yak file's header (htab.c:381-384); 0 if it cannot be read */
+static int yak_header(const char *fn, uint32_t *k, uint32_t *pre)
+{
+	int k_ = 0, pre_ = 0;
+	if (yakamd_yak_header(fn, &k_, &pre_) != 0) return 0;
+	*k = (uint32_t)k_; *pre = (uint32_t)pre_;
+	return 1;
+}
+
+/* why a command takes no table of an even k, or of a k from 32 on */
+#define K_ODD_GRAPH "the graph is defined for an odd k only"
+#define K_ODD_MIDDLE "a k-mer of even length has no middle base"
+#define K_32_LOOKUP "the per-position lookup serves k below 32 only"
+#define K_32_GRAPH "k must be below 32"
+#define K_32_HASH "a k-mer can be rebuilt from its hash for k below 32 only"
+
+/* the k of the table in fn, read from its header before anything is loaded; -1 after the message if the file is no .yak file, if k is even and
+ * `odd_why` says why that will not do, or if k is 32 or more and `why_32` says the same: the caller returns 2 */
+static int table_k(const char *cmd, const char *fn, const char *odd_why, const char *why_32)
+{
+	uint32_t k = 0, pre = 0;
+	if (!yak_header(fn, &k, &pre)) { fprintf(stderr, "yak-amd %s: %s is not a readable .yak file\n", cmd, fn); return -1; }
+	if (odd_why && !(k & 1)) { fprintf(stderr, "yak-amd %s: %s has k = %u: %s\n", cmd, fn, k, odd_why); return -1; }
+	if (why_32 && k >= 32) { fprintf(stderr, "yak-amd %s: %s has k = %u: %s\n", cmd, fn, k, why_32); return -1; }
+	return (int)k;
+}
+
+/* -c of the commands that take a k-mer below it for absent or weak; 0 after the message: the caller returns 1 */
+static int min_cnt_ok(const char *cmd, int min_cnt)
+{
+	if (min_cnt >= 1 && min_cnt <= 1023) return 1;
+	fprintf(stderr, "yak-amd %s: -c must be in [1, 1023]\n", cmd);
+	return 0;
+}
+
+/* the table of fn on the device; 0 after the message: the caller returns 2 */
+static yak_ch_t *table_load(const char *cmd, const char *fn)
+{
+	yak_ch_t *tab = yak_ch_restore(fn);
+	if (!tab) fprintf(stderr, "yak-amd %s: cannot load %s (or no MI355X)\n", cmd, fn);
+	return tab;
+}
+
 /* ---- count ---- */
 static int cmd_count(int argc, char **argv)
 {
@@ -162,8 +207,8 @@ static int cmd_qv(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 1 >= argc) { arg_help("qv [options] <table.yak> <sequences.fa>", defs, nd); return 1; }
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd qv: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("qv", argv[first]);
+	if (!tab) return 2;
 	if (hpc && yakamd_ch_set_hpc(tab, 1) != 0) { yak_ch_destroy(tab); return 2; }
 	static int64_t in_table[YAK_N_COUNTS], in_seqs[YAK_N_COUNTS];
 	static yak_qstat_t st;
@@ -273,23 +318,14 @@ static int cmd_chkerr(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 1 >= argc) { arg_help("chkerr [options] <count.yak> <seq.fa>", defs, nd); return 1; }
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd chkerr: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("chkerr", argv[first]);
+	if (!tab) return 2;
 	const int rc = yakamd_chkerr(&o, tab, argv[first + 1], 0) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
 }
 
 /* ---- sexchr ---- */
-/* k and pre of a .yak file's header (htab.c:381-384); 0 if it cannot be read */
-static int yak_header(const char *fn, uint32_t *k, uint32_t *pre)
-{
-	int k_ = 0, pre_ = 0;
-	if (yakamd_yak_header(fn, &k_, &pre_) != 0) return 0;
-	*k = (uint32_t)k_; *pre = (uint32_t)pre_;
-	return 1;
-}
-
 static int cmd_sexchr(int argc, char **argv)
 {
 	yakamd_scopt_t o;
@@ -333,12 +369,10 @@ static int cmd_print(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first >= argc) { arg_help("print [options] <in.yak>", defs, nd); return 1; }
-	uint32_t k = 0, pre = 0;
-	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd print: %s is not a readable .yak file\n", argv[first]); return 2; }
-	if (k >= 32) { fprintf(stderr, "yak-amd print: %s has k = %u: a k-mer can be rebuilt from its hash for k below 32 only\n", argv[first], k); return 2; }
+	if (table_k("print", argv[first], 0, K_32_HASH) < 0) return 2;
 	o.with_counts = with_counts;
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd print: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("print", argv[first]);
+	if (!tab) return 2;
 	yak_ch_tighten(tab);
 	const int rc = yakamd_print(&o, tab, 0) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
@@ -401,8 +435,8 @@ static int cmd_recount(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 1 >= argc) { arg_help("recount [options] <in.yak> <seq.fa>", defs, nd); return 1; }
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd recount: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("recount", argv[first]);
+	if (!tab) return 2;
 	yak_ch_tighten(tab);
 	int rc = 0;
 	yak_recount(argv[first + 1], tab);
@@ -424,8 +458,8 @@ static int keep_cmd(int argc, char **argv, int isec)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 1 >= argc) { arg_help(isec ? "isec [options] <a.yak> <b.yak> [c.yak ...]" : "subtract [options] <a.yak> <b.yak>", defs, nd); return 1; }
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd %s: cannot load %s (or no MI355X)\n", cmd, argv[first]); return 2; }
+	yak_ch_t *tab = table_load(cmd, argv[first]);
+	if (!tab) return 2;
 	const int last = isec ? argc : first + 2;
 	for (int i = first + 1; i < last; ++i) {
 		yak_ch_t *other = yak_ch_restore(argv[i]);
@@ -456,8 +490,8 @@ static int cmd_sum(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 1 >= argc) { arg_help("sum [options] <a.yak> <b.yak> [c.yak ...]", defs, nd); return 1; }
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd sum: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("sum", argv[first]);
+	if (!tab) return 2;
 	for (int i = first + 1; i < argc; ++i) {
 		yak_ch_t *other = yak_ch_restore(argv[i]);
 		if (!other) { fprintf(stderr, "yak-amd sum: cannot load %s\n", argv[i]); yak_ch_destroy(tab); return 2; }
@@ -488,12 +522,10 @@ static int cmd_depth(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 1 >= argc) { arg_help("depth [options] <table.yak> <seq.fa>", defs, nd); return 1; }
-	uint32_t k = 0, pre = 0;
-	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd depth: %s is not a readable .yak file\n", argv[first]); return 2; }
-	if (k >= 32) { fprintf(stderr, "yak-amd depth: %s has k = %u: the per-position lookup serves k below 32 only\n", argv[first], k); return 2; }
+	if (table_k("depth", argv[first], 0, K_32_LOOKUP) < 0) return 2;
 	if (o.window < 0) { fprintf(stderr, "yak-amd depth: -w must not be negative\n"); return 1; }
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd depth: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("depth", argv[first]);
+	if (!tab) return 2;
 	const int rc = yakamd_depth(&o, tab, argv[first + 1], out) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
@@ -534,11 +566,9 @@ static int cmd_cover(int argc, char **argv)
 		if (o.mask < 0) { fprintf(stderr, "yak-amd cover: -m takes none, soft or hard\n"); return 1; }
 	}
 	if (!(o.min_frac >= 0.0 && o.min_frac <= 1.0) || o.min_hit < 0) { fprintf(stderr, "yak-amd cover: -f must be in [0, 1] and -n must not be negative\n"); return 1; }
-	uint32_t k = 0, pre = 0;
-	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd cover: %s is not a readable .yak file\n", argv[first]); return 2; }
-	if (k >= 32) { fprintf(stderr, "yak-amd cover: %s has k = %u: the per-position lookup serves k below 32 only\n", argv[first], k); return 2; }
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd cover: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	if (table_k("cover", argv[first], 0, K_32_LOOKUP) < 0) return 2;
+	yak_ch_t *tab = table_load("cover", argv[first]);
+	if (!tab) return 2;
 	const int rc = yakamd_cover(&o, tab, argv[first + 1], out) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
@@ -566,15 +596,12 @@ static int cmd_unitigs(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first >= argc) { arg_help("unitigs [options] <table.yak>", defs, nd); return 1; }
-	uint32_t k = 0, pre = 0;
-	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd unitigs: %s is not a readable .yak file\n", argv[first]); return 2; }
-	if (!(k & 1)) { fprintf(stderr, "yak-amd unitigs: %s has k = %u: the graph is defined for an odd k only\n", argv[first], k); return 2; }
-	if (k >= 32) { fprintf(stderr, "yak-amd unitigs: %s has k = %u: k must be below 32\n", argv[first], k); return 2; }
-	if (min_cnt < 1 || min_cnt > 1023) { fprintf(stderr, "yak-amd unitigs: -c must be in [1, 1023]\n"); return 1; }
+	if (table_k("unitigs", argv[first], K_ODD_GRAPH, K_32_GRAPH) < 0) return 2;
+	if (!min_cnt_ok("unitigs", min_cnt)) return 1;
 	if (n_threads < 1) { fprintf(stderr, "yak-amd unitigs: -t must be at least 1\n"); return 1; }
 	o.min_cnt = min_cnt; o.stats_only = stats; o.n_threads = n_threads;
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd unitigs: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("unitigs", argv[first]);
+	if (!tab) return 2;
 	const int rc = (gfa ? yakamd_unitigs_gfa(&o, tab, out) : on_gpu ? yakamd_unitigs_dev(&o, tab, out) : yakamd_unitigs(&o, tab, out)) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
@@ -600,15 +627,12 @@ static int cmd_paths(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 1 >= argc) { arg_help("paths [options] <table.yak> <seqs.fa|fq[.gz]>", defs, nd); return 1; }
-	uint32_t k = 0, pre = 0;
-	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd paths: %s is not a readable .yak file\n", argv[first]); return 2; }
-	if (!(k & 1)) { fprintf(stderr, "yak-amd paths: %s has k = %u: the graph is defined for an odd k only\n", argv[first], k); return 2; }
-	if (k >= 32) { fprintf(stderr, "yak-amd paths: %s has k = %u: k must be below 32\n", argv[first], k); return 2; }
-	if (min_cnt < 1 || min_cnt > 1023) { fprintf(stderr, "yak-amd paths: -c must be in [1, 1023]\n"); return 1; }
+	if (table_k("paths", argv[first], K_ODD_GRAPH, K_32_GRAPH) < 0) return 2;
+	if (!min_cnt_ok("paths", min_cnt)) return 1;
 	if (min_len < 0 || o.chunk_size < 1) { fprintf(stderr, "yak-amd paths: -l must not be negative and -K must be at least 1\n"); return 1; }
 	o.min_cnt = min_cnt; o.min_len = min_len; o.stats_only = stats;
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd paths: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("paths", argv[first]);
+	if (!tab) return 2;
 	const int rc = yakamd_paths(&o, tab, argv[first + 1], out) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
@@ -632,14 +656,11 @@ static int cmd_bubbles(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first >= argc) { arg_help("bubbles [options] <table.yak>", defs, nd); return 1; }
-	uint32_t k = 0, pre = 0;
-	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd bubbles: %s is not a readable .yak file\n", argv[first]); return 2; }
-	if (!(k & 1)) { fprintf(stderr, "yak-amd bubbles: %s has k = %u: the graph is defined for an odd k only\n", argv[first], k); return 2; }
-	if (k >= 32) { fprintf(stderr, "yak-amd bubbles: %s has k = %u: k must be below 32\n", argv[first], k); return 2; }
-	if (min_cnt < 1 || min_cnt > 1023) { fprintf(stderr, "yak-amd bubbles: -c must be in [1, 1023]\n"); return 1; }
+	if (table_k("bubbles", argv[first], K_ODD_GRAPH, K_32_GRAPH) < 0) return 2;
+	if (!min_cnt_ok("bubbles", min_cnt)) return 1;
 	o.min_cnt = min_cnt; o.stats_only = stats;
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd bubbles: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("bubbles", argv[first]);
+	if (!tab) return 2;
 	const int rc = yakamd_bubbles(&o, tab, out) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
@@ -665,18 +686,15 @@ static int cmd_clean(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 1 >= argc) { arg_help("clean [options] <in.yak> <out.yak>", defs, nd); return 1; }
-	uint32_t k = 0, pre = 0;
-	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd clean: %s is not a readable .yak file\n", argv[first]); return 2; }
-	if (!(k & 1)) { fprintf(stderr, "yak-amd clean: %s has k = %u: the graph is defined for an odd k only\n", argv[first], k); return 2; }
-	if (k >= 32) { fprintf(stderr, "yak-amd clean: %s has k = %u: k must be below 32\n", argv[first], k); return 2; }
-	if (o.min_cnt < 1 || o.min_cnt > 1023) { fprintf(stderr, "yak-amd clean: -c must be in [1, 1023]\n"); return 1; }
+	if (table_k("clean", argv[first], K_ODD_GRAPH, K_32_GRAPH) < 0) return 2;
+	if (!min_cnt_ok("clean", o.min_cnt)) return 1;
 	if (o.tip_nodes < -1 || o.tip_nodes > YAKAMD_CLEAN_MAX_TIP_NODES || o.pop_pct < 0 || o.pop_pct > 100 || o.max_rounds < 1 || o.max_rounds > 64) {
 		fprintf(stderr, "yak-amd clean: -t must be in [0, %d], -b in [0, 100] and -r in [1, 64]\n", YAKAMD_CLEAN_MAX_TIP_NODES);
 		return 1;
 	}
 	o.list = list;
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd clean: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("clean", argv[first]);
+	if (!tab) return 2;
 	const int rc = yakamd_clean(&o, tab, argv[first + 1], report ? report : "-") == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
@@ -703,14 +721,13 @@ static int cmd_correct(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first + 1 >= argc) { arg_help("correct [options] <kmer.yak> <reads.fq>", defs, nd); return 1; }
-	uint32_t k = 0, pre = 0;
-	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd correct: %s is not a readable .yak file\n", argv[first]); return 2; }
-	if (k >= 32) { fprintf(stderr, "yak-amd correct: %s has k = %u: the per-position lookup serves k below 32 only\n", argv[first], k); return 2; }
-	if (o.min_cnt < 1 || o.min_cnt > 1023) { fprintf(stderr, "yak-amd correct: -c must be in [1, 1023]\n"); return 1; }
-	if (o.min_run < 1 || o.min_run > (int)k) { fprintf(stderr, "yak-amd correct: -e must be in [1, %u], the table's k\n", k); return 1; }
+	const int k = table_k("correct", argv[first], 0, K_32_LOOKUP);
+	if (k < 0) return 2;
+	if (!min_cnt_ok("correct", o.min_cnt)) return 1;
+	if (o.min_run < 1 || o.min_run > k) { fprintf(stderr, "yak-amd correct: -e must be in [1, %d], the table's k\n", k); return 1; }
 	if (o.chunk_size < 1) { fprintf(stderr, "yak-amd correct: -K must be in [1, 2^63)\n"); return 1; }
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd correct: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("correct", argv[first]);
+	if (!tab) return 2;
 	const int rc = yakamd_correct(&o, tab, argv[first + 1], out, report ? report : o.stats_only ? "-" : 0) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
@@ -732,14 +749,11 @@ static int cmd_hetmers(int argc, char **argv)
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first >= argc) { arg_help("hetmers [options] <table.yak>", defs, nd); return 1; }
-	uint32_t k = 0, pre = 0;
-	if (!yak_header(argv[first], &k, &pre)) { fprintf(stderr, "yak-amd hetmers: %s is not a readable .yak file\n", argv[first]); return 2; }
-	if (!(k & 1)) { fprintf(stderr, "yak-amd hetmers: %s has k = %u: a k-mer of even length has no middle base\n", argv[first], k); return 2; }
-	if (k >= 32) { fprintf(stderr, "yak-amd hetmers: %s has k = %u: k must be below 32\n", argv[first], k); return 2; }
-	if (min_cnt < 1 || min_cnt > 1023) { fprintf(stderr, "yak-amd hetmers: -c must be in [1, 1023]\n"); return 1; }
+	if (table_k("hetmers", argv[first], K_ODD_MIDDLE, K_32_GRAPH) < 0) return 2;
+	if (!min_cnt_ok("hetmers", min_cnt)) return 1;
 	o.min_cnt = min_cnt; o.print_pairs = pairs;
-	yak_ch_t *tab = yak_ch_restore(argv[first]);
-	if (!tab) { fprintf(stderr, "yak-amd hetmers: cannot load %s (or no MI355X)\n", argv[first]); return 2; }
+	yak_ch_t *tab = table_load("hetmers", argv[first]);
+	if (!tab) return 2;
 	const int rc = yakamd_hetmers(&o, tab, out) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
@@ -755,21 +769,31 @@ static int cmd_version(int argc, char **argv)
 
 int main(int argc, char **argv)
 {
-	static const struct { const char *name; int (*run)(int, char**); const char *what; } cmds[] = {
-		{ "count", cmd_count, "count k-mers on the GPU, write a .yak table" },
-		{ "qv", cmd_qv, "look the k-mers of sequences up in a .yak table" },
-		{ "triobin", cmd_triobin, "bin reads by the k-mers of the two parents' .yak tables" },
-		{ "trioeval", cmd_trioeval, "evaluate the phasing of an assembly by the k-mers of the two parents' .yak tables" },
-		{ "inspect", cmd_inspect, "the k-mer histogram of a .yak table, or the joint spectrum of two" },
-		{ "chkerr", cmd_chkerr, "report the streaks of low k-mers of sequences against a .yak table" },
-		{ "sexchr", cmd_sexchr, "count the sex-chromosome k-mers of two haplotype assemblies" },
-		{ "print", cmd_print, "list the k-mers of a .yak table as text" },
-		{ "cntasm", cmd_cntasm, "count in how many assemblies each k-mer occurs, write a .yak table" },
-		{ "recount", cmd_recount, "count the k-mers of a .yak table in other sequences" },
-		{ "subtract", cmd_subtract, "the k-mers of a .yak table that are absent from a second one" },
-		{ "isec", cmd_isec, "the k-mers of a .yak table that are present in every further one" },
-		{ "version", cmd_version, "print the version" },
+	static const struct { const char *name; int (*run)(int, char**); int beyond; const char *what; } cmds[] = {   /* beyond: not in the reference */
+		{ "count", cmd_count, 0, "count k-mers on the GPU, write a .yak table" },
+		{ "qv", cmd_qv, 0, "look the k-mers of sequences up in a .yak table" },
+		{ "triobin", cmd_triobin, 0, "bin reads by the k-mers of the two parents' .yak tables" },
+		{ "trioeval", cmd_trioeval, 0, "evaluate the phasing of an assembly by the k-mers of the two parents' .yak tables" },
+		{ "inspect", cmd_inspect, 0, "the k-mer histogram of a .yak table, or the joint spectrum of two" },
+		{ "chkerr", cmd_chkerr, 0, "report the streaks of low k-mers of sequences against a .yak table" },
+		{ "sexchr", cmd_sexchr, 0, "count the sex-chromosome k-mers of two haplotype assemblies" },
+		{ "print", cmd_print, 0, "list the k-mers of a .yak table as text" },
+		{ "cntasm", cmd_cntasm, 0, "count in how many assemblies each k-mer occurs, write a .yak table" },
+		{ "recount", cmd_recount, 0, "count the k-mers of a .yak table in other sequences" },
+		{ "subtract", cmd_subtract, 0, "the k-mers of a .yak table that are absent from a second one" },
+		{ "isec", cmd_isec, 0, "the k-mers of a .yak table that are present in every further one" },
+		{ "version", cmd_version, 0, "print the version" },
+		{ "sum", cmd_sum, 1, "add the counts of two or more .yak tables together" },
+		{ "depth", cmd_depth, 1, "the depth of the k-mers of each sequence, or window, in a .yak table" },
+		{ "hetmers", cmd_hetmers, 1, "the pairs of k-mers of a .yak table that differ in the middle base, by their two counts" },
+		{ "cover", cmd_cover, 1, "the bases of each sequence that lie inside k-mers a .yak table holds, lacks or holds too often" },
+		{ "unitigs", cmd_unitigs, 1, "the unitigs of the de Bruijn graph that the k-mers of a .yak table span" },
+		{ "paths", cmd_paths, 1, "sequences as paths through the unitigs of that graph (GAF)" },
+		{ "bubbles", cmd_bubbles, 1, "the simple bubbles of that graph: forks whose two arms join again, with their alleles" },
+		{ "clean", cmd_clean, 1, "that graph with its tips clipped and its bubbles popped, as a .yak table of the k-mers that stay" },
+		{ "correct", cmd_correct, 1, "reads with their single substitution errors repaired against a .yak table" },
 	};
+	const size_t n_cmds = sizeof(cmds) / sizeof(cmds[0]);
 	/* -X name=value (anywhere on the line, any number of times): a test switch of the library (yakamd_test_set) -- tests force code paths with it */
 	for (int i = 1; i + 1 < argc; ) {
 		char *eq = strcmp(argv[i], "-X") == 0 ? strchr(argv[i + 1], '=') : 0;
@@ -780,27 +804,12 @@ int main(int argc, char **argv)
 		argc -= 2;
 	}
 	if (argc >= 2)
-		for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i)
+		for (size_t i = 0; i < n_cmds; ++i)
 			if (strcmp(argv[1], cmds[i].name) == 0) return cmds[i].run(argc - 1, argv + 1);
-	if (argc >= 2 && strcmp(argv[1], "sum") == 0) return cmd_sum(argc - 1, argv + 1);
-	if (argc >= 2 && strcmp(argv[1], "depth") == 0) return cmd_depth(argc - 1, argv + 1);
-	if (argc >= 2 && strcmp(argv[1], "hetmers") == 0) return cmd_hetmers(argc - 1, argv + 1);
-	if (argc >= 2 && strcmp(argv[1], "cover") == 0) return cmd_cover(argc - 1, argv + 1);
-	if (argc >= 2 && strcmp(argv[1], "unitigs") == 0) return cmd_unitigs(argc - 1, argv + 1);
-	if (argc >= 2 && strcmp(argv[1], "paths") == 0) return cmd_paths(argc - 1, argv + 1);
-	if (argc >= 2 && strcmp(argv[1], "bubbles") == 0) return cmd_bubbles(argc - 1, argv + 1);
-	if (argc >= 2 && strcmp(argv[1], "clean") == 0) return cmd_clean(argc - 1, argv + 1);
-	if (argc >= 2 && strcmp(argv[1], "correct") == 0) return cmd_correct(argc - 1, argv + 1);
 	fprintf(stderr, "yak-amd: driver of libyak_amd.so (lh3/yak's C API on MI355X)\n");
-	for (size_t i = 0; i < sizeof(cmds) / sizeof(cmds[0]); ++i) fprintf(stderr, "    yak-amd %-8s %s\n", cmds[i].name, cmds[i].what);
-	fprintf(stderr, "  beyond the reference:\n      yak-amd %-8s %s\n", "sum", "add the counts of two or more .yak tables together");
-	fprintf(stderr, "      yak-amd %-8s %s\n", "depth", "the depth of the k-mers of each sequence, or window, in a .yak table");
-	fprintf(stderr, "      yak-amd %-8s %s\n", "hetmers", "the pairs of k-mers of a .yak table that differ in the middle base, by their two counts");
-	fprintf(stderr, "      yak-amd %-8s %s\n", "cover", "the bases of each sequence that lie inside k-mers a .yak table holds, lacks or holds too often");
-	fprintf(stderr, "      yak-amd %-8s %s\n", "unitigs", "the unitigs of the de Bruijn graph that the k-mers of a .yak table span");
-	fprintf(stderr, "      yak-amd %-8s %s\n", "paths", "sequences as paths through the unitigs of that graph (GAF)");
-	fprintf(stderr, "      yak-amd %-8s %s\n", "bubbles", "the simple bubbles of that graph: forks whose two arms join again, with their alleles");
-	fprintf(stderr, "      yak-amd %-8s %s\n", "clean", "that graph with its tips clipped and its bubbles popped, as a .yak table of the k-mers that stay");
-	fprintf(stderr, "      yak-amd %-8s %s\n", "correct", "reads with their single substitution errors repaired against a .yak table");
+	for (size_t i = 0; i < n_cmds; ++i) {
+		if (cmds[i].beyond && !cmds[i - 1].beyond) fprintf(stderr, "  beyond the reference:\n");
+		fprintf(stderr, "%s    yak-amd %-8s %s\n", cmds[i].beyond ? "  " : "", cmds[i].name, cmds[i].what);
+	}
 	return 1;
 }

@@ -249,14 +249,7 @@ extern "C" int yakamd_gfa_stats(yakamd_gfa_t *g, yakamd_gfastat_t *st)
 
 extern "C" int64_t yakamd_gfa_links_dev(yakamd_gfa_t *g, void *d, int64_t cap)
 {
-	if (!g) return fail("gfa links: no links");
-	const u64 n = g->st.n_link;
-	if (!d || cap < (int64_t)n) return (int64_t)n;
-	if (((uintptr_t)d & 15) != 0) return fail("gfa links: the entries must be 16-byte aligned");
-	if (n == 0) return 0;
-	OnDevice dev(g->dev);
-	HIPCK(hipMemcpy(d, g->links.p, n * 16, hipMemcpyDeviceToDevice));
-	return (int64_t)n;
+	return copy_out(g != 0, g ? g->dev : 0, g ? g->links.p : 0, g ? g->st.n_link : 0, 16, d, cap, "gfa links", "links", "the entries");
 }
 
 /* the command: the walk, the links, then the text from the tallies or from the descriptors, the bases and the links */
@@ -264,14 +257,14 @@ extern "C" int yakamd_unitigs_gfa(const yakamd_ugopt_t *opt, yak_ch_t *ch, const
 {
 	if (!opt) return fail("yakamd_unitigs_gfa: no options");
 	WalkGuard W{ yakamd_uwalk_open(ch, opt->min_cnt) };
-	if (!W.w) return fail_below(yakamd_walk_last_error());
-	struct Gfa { yakamd_gfa_t *g; ~Gfa() { yakamd_gfa_close(g); } } G{ gfa_open(W.w, ch->k, !opt->stats_only) };
-	yakamd_gfa_t *g = G.g;
+	if (!W.p) return fail_below(yakamd_walk_last_error());
+	Guard<yakamd_gfa_t, yakamd_gfa_close> G{ gfa_open(W.p, ch->k, !opt->stats_only) };
+	yakamd_gfa_t *g = G.p;
 	if (!g) return -1;
 	const double t0 = now_ms();
 	yakamd_gstat_t gs;
 	yakamd_uwstat_t us;
-	if (yakamd_uwalk_gstat(W.w, &gs) != 0 || yakamd_uwalk_stats(W.w, &us) != 0) return fail_below(yakamd_walk_last_error());
+	if (yakamd_uwalk_gstat(W.p, &gs) != 0 || yakamd_uwalk_stats(W.p, &us) != 0) return fail_below(yakamd_walk_last_error());
 	std::string bases;
 	std::vector<gf_link_t> links;
 	if (!opt->stats_only) {
@@ -285,14 +278,9 @@ extern "C" int yakamd_unitigs_gfa(const yakamd_ugopt_t *opt, yak_ch_t *ch, const
 	if (!out.f) return fail("yakamd_unitigs_gfa: cannot write '%s'", out.name);
 	bool ok = true;
 	try {
-		if (opt->stats_only) {
-			gft_tallies_t t;
-			t.k = g->k; t.min_cnt = opt->min_cnt;
-			t.n_key = gs.n_key; t.n_node = gs.n_node; t.n_arc = gs.n_arc; t.n_linked_side = gs.n_linked_side;
-			for (int l = 0; l < 5; ++l) for (int r = 0; r < 5; ++r) t.deg[l][r] = gs.deg[l][r];
-			t.n_open = us.n_open; t.n_cycle = us.n_cycle; t.sum_len = us.sum_len; t.max_len = us.max_len; t.n50 = us.n50;
-			ok = out.write(gft_stats(t, g->st.n_link, g->st.end_deg));
-		} else
+		if (opt->stats_only)
+			ok = out.write(gft_stats(gft_tallies(g->k, opt->min_cnt, gs, us), g->st.n_link, g->st.end_deg));
+		else
 			ok = gft_gfa(g->h_desc.data(), g->h_desc.size(), bases.data(), g->n_bases, links.data(), links.size(), g->k,
 			             [&out](const std::string &t) { return out.write(t); });
 	} catch (const std::bad_alloc&) { return fail("yakamd_unitigs_gfa: no host memory for the text"); }

@@ -8,6 +8,17 @@
 
 /* what the -s text states: the options, the graph's tallies (yakamd_gstat_t) and the walk's (yakamd_uwstat_t) */
 struct gft_tallies_t { int k, min_cnt; uint64_t n_key, n_node, n_arc, n_linked_side, deg[5][5], n_open, n_cycle, sum_len, max_len, n50; };
+/* filled from the two; templates, so that this header needs neither declaration */
+template<class Graph, class Walk>
+static inline gft_tallies_t gft_tallies(int k, int min_cnt, const Graph &gs, const Walk &us)
+{
+	gft_tallies_t t;
+	t.k = k; t.min_cnt = min_cnt;
+	t.n_key = gs.n_key; t.n_node = gs.n_node; t.n_arc = gs.n_arc; t.n_linked_side = gs.n_linked_side;
+	for (int l = 0; l < 5; ++l) for (int r = 0; r < 5; ++r) t.deg[l][r] = gs.deg[l][r];
+	t.n_open = us.n_open; t.n_cycle = us.n_cycle; t.sum_len = us.sum_len; t.max_len = us.max_len; t.n50 = us.n50;
+	return t;
+}
 
 /* the text of `unitigs -s` restated line by line, then `G n_link end_deg[0] .. end_deg[4]` */
 static inline std::string gft_stats(const gft_tallies_t &t, uint64_t n_link, const uint64_t end_deg[5])

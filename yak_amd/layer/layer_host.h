@@ -1,7 +1,8 @@
-/* layer_host.h -- the host scaffolding that walk.hip, gfa.hip and path.hip share: the error state, the clock, the device
- * guard, device memory that frees itself, the output file of a command, the guard of a walk, the copy of a walk's results and the exports of the
- * launch tally.  The including file defines LAYER_NAME ("walk", "gfa", "path") first.  Everything here has internal linkage: each library gets code
- * and state of its own, and nothing in here is shared between two of them. */
+/* layer_host.h -- the host scaffolding that the layer libraries share: the error state, the clock, the device guard, device
+ * memory that frees itself, the output file of a command and the flush of a text into it, the guard of a handle, the copy of a result list to the
+ * caller's device memory, the copy of a walk's results and the exports of the launch tally.  The including file defines LAYER_NAME ("walk", "gfa",
+ * "path", ...) first.  Everything here has internal linkage: each library gets code and state of its own, and nothing in here is shared between two
+ * of them.  The sequence front end of paths and correct, which needs zlib, is layer_seqs.h. */
 #ifndef YAKAMD_LAYER_HOST_H
 #define YAKAMD_LAYER_HOST_H
 #ifndef LAYER_NAME
@@ -83,12 +84,35 @@ struct OutFile {
 	}
 };
 
-/* a walk for the length of a command */
-struct WalkGuard {
-	yakamd_uwalk_t *w;
-	~WalkGuard() { close(); }
-	void close() { yakamd_uwalk_close(w); w = 0; }
+/* a text goes to its output, if it has one, in pieces of 4 MiB; *ok = false once a piece could not be written */
+inline void flush(std::string &text, const OutFile *out, bool all, bool *ok)
+{
+	if (!all && text.size() < (size_t)1 << 22) return;
+	if (out && !text.empty()) *ok = out->write(text) && *ok;
+	text.clear();
+}
+
+/* a handle with a close function that takes none as well, for the length of a command or until close() */
+template<class T, void (*Close)(T*)>
+struct Guard {
+	T *p;
+	~Guard() { close(); }
+	void close() { Close(p); p = 0; }
 };
+typedef Guard<yakamd_uwalk_t, yakamd_uwalk_close> WalkGuard;
+
+/* n entries of `each` bytes of a handle's result list into the caller's device memory d of cap entries: n, also where d is none or too small and
+ * nothing is copied; -1 with the message.  `none` is what a null handle lacks, `aligned` what must be 16-byte aligned (0: nothing) */
+inline int64_t copy_out(bool present, int dev, const void *src, u64 n, u64 each, void *d, int64_t cap, const char *what, const char *none, const char *aligned)
+{
+	if (!present) return fail("%s: no %s", what, none);
+	if (!d || cap < (int64_t)n) return (int64_t)n;
+	if (aligned && ((uintptr_t)d & 15) != 0) return fail("%s: %s must be 16-byte aligned", what, aligned);
+	if (n == 0) return 0;
+	OnDevice on(dev);
+	HIPCK(hipMemcpy(d, src, n * each, hipMemcpyDeviceToDevice));
+	return (int64_t)n;
+}
 
 /* *cap = the power of two at or above what the environment variable asks for, if it is set.  false: it asks for less than n_key slots, none, or
  * more than 2^40; *want is what it asks for */

@@ -1,21 +1,23 @@
-/* correct_reader.h -- the records of a FASTA or FASTQ file for `yak-amd correct`, host only: a short reader of kseq's
- * grammar through gzread (plain, gzip, `-` for stdin), as ../path/path_reader.h is, that keeps all four parts of a record because the command
- * writes the records out again.  A header starts with '>' or '@'; its name runs to the first white space and its comment from behind that one
+/* seq_reader.h -- the records of a FASTA or FASTQ file for the layers above libyak_amd.so, host only and HIP-free: a short
+ * reader of kseq's grammar through gzread (plain, gzip, `-` or no name for stdin), because the engine's reader (../csrc/yak_host.h) cannot be
+ * included from a layer above it.  A header starts with '>' or '@'; its name runs to the first white space and its comment from behind that one
  * character to the end of the line.  The sequence is every line up to one that starts with '>', '@' or '+'; behind '+' the quality runs until it
- * covers the sequence's length, and a quality of another length ends the file in front of its record, as it does in kseq.  Line ends may be "\n"
- * or "\r\n".  correct.hip and tools/correct_model_check.cpp share it. */
-#ifndef YK_CORRECT_READER_H
-#define YK_CORRECT_READER_H
+ * covers the sequence's length, and a quality of another length ends the file in front of its record, as it does in kseq.  Empty lines are skipped;
+ * line ends may be "\n" or "\r\n".  A reader that keeps the quality gives its text (`yak-amd correct` writes the records out again); one that does
+ * not leaves `qual` empty and only counts its length (`yak-amd paths`).  path.hip, correct.hip and the two model programs
+ * (tests/tools/path_model_check.cpp, tools/correct_model_check.cpp) share it. */
+#ifndef YAKAMD_SEQ_READER_H
+#define YAKAMD_SEQ_READER_H
 #include <string.h>
 #include <zlib.h>
 #include <string>
 
-struct cr_record_t { std::string name, comment, seq, qual; };
+struct seq_record_t { std::string name, comment, seq, qual; };
 
-class CrReader {
+class SeqReader {
 public:
-	CrReader() : fp_(0), at_(0), end_(0), eof_(false), pending_(false), bad_(false) {}
-	~CrReader() { close(); }
+	explicit SeqReader(bool keep_qual) : fp_(0), at_(0), end_(0), keep_qual_(keep_qual), eof_(false), pending_(false), bad_(false) {}
+	~SeqReader() { close(); }
 	bool open(const char *fn)
 	{
 		close();
@@ -26,8 +28,9 @@ public:
 	}
 	void close() { if (fp_) gzclose(fp_); fp_ = 0; }
 	bool failed() const { return bad_; }                          /* the inflater reported an error */
+	bool keeps_qual() const { return keep_qual_; }
 	/* the next record; false at the end */
-	bool next(cr_record_t &r)
+	bool next(seq_record_t &r)
 	{
 		if (!pending_) {
 			while (line()) if (!line_.empty() && (line_[0] == '>' || line_[0] == '@')) { pending_ = true; break; }
@@ -44,8 +47,9 @@ public:
 			const char c = line_[0];
 			if (c == '>' || c == '@') { pending_ = true; return true; }
 			if (c == '+') {
-				while (r.qual.size() < r.seq.size() && line()) r.qual += line_;
-				if (r.qual.size() != r.seq.size()) { eof_ = true; at_ = end_ = 0; return false; }      /* as kseq: a quality of another length ends the file */
+				size_t q = 0;
+				while (q < r.seq.size() && line()) { q += line_.size(); if (keep_qual_) r.qual += line_; }
+				if (q != r.seq.size()) { eof_ = true; at_ = end_ = 0; return false; }      /* as kseq: a quality of another length ends the file */
 				return true;
 			}
 			r.seq += line_;
@@ -83,6 +87,7 @@ private:
 	gzFile fp_;
 	char buf_[1 << 16];
 	size_t at_, end_;
+	const bool keep_qual_;
 	bool eof_, pending_, bad_;
 	std::string line_;
 };

@@ -2,9 +2,9 @@
  * path.hip -- libyak_amd_path.so: sequences laid onto the unitig graph of a count table as paths, on the GPU (include/yak_amd_path.h; DESIGN.md
  * section 23).  A layer above libyak_amd_walk.so and libyak_amd.so: it calls their public functions only (yakamd_uwalk_open / _stats / _desc_dev /
  * _bases_dev / _close, yakamd_walk_last_error, yakamd_ch_hpc, seq_nt4_table) and owns its device memory (hipMalloc / hipFree).  The per-thread steps
- * are those of path_step.h (with ../gfa/gfa_step.h's k-mers and table), the texts those of path_text.h, the reader that of path_reader.h; every
+ * are those of path_step.h (with ../gfa/gfa_step.h's k-mers and table), the texts those of path_text.h, the reader and the chunk loop those of ../layer/layer_seqs.h; every
  * launch goes through YK_LAUNCH of ../csrc/tally.h into this library's own tally (yakamd_path_tally_*).  The host scaffolding and the workgroup scan
- * are those of ../layer/layer_host.h and ../layer/layer_dev.h, which the three layers share.
+ * are those of ../layer/layer_host.h and ../layer/layer_dev.h, which the layers share.
  *
  * A workgroup of 256 threads serves a tile of 1024 positions, a thread 4 consecutive ones.
  *   k_path_index      over the positions of the walk's bases: the tile and k - 1 bytes behind it staged in LDS by 16-byte loads; a thread finds its
@@ -24,10 +24,10 @@
 #include "yak_amd_path.h"
 #define LAYER_NAME "path"
 #include "../layer/layer_host.h"
+#include "../layer/layer_seqs.h"
 #include "../layer/layer_dev.h"
 #include "path_step.h"
 #include "path_text.h"
-#include "path_reader.h"
 
 static_assert(sizeof(yakamd_udesc_t) == sizeof(gf_desc_t) && sizeof(yakamd_upath_t) == sizeof(px_path_t) && sizeof(px_path_t) == 32 &&
               sizeof(yakamd_ptally_t) == sizeof(px_tally_t) && sizeof(gf_slot_t) == 16, "the records as declared");
@@ -194,7 +194,6 @@ thread_local double g_ms[6];
 
 const u64 MAX_TILES = 0x7fffffffull;                              /* a grid's first dimension */
 u64 tiles_of(u64 n) { return (n + PX_TILE - 1) / PX_TILE; }
-u64 up16(u64 n) { return (n + 15) & ~(u64)15; }
 
 }   // namespace
 
@@ -393,50 +392,39 @@ extern "C" int yakamd_path_chain_dev(yakamd_path_t *px, const uint64_t *d_hit, i
 /* ---- the command ---- */
 namespace {
 
-struct Chunk {
-	std::vector<pxt_seq_t> seqs;
-	std::vector<char> img;
-	std::vector<uint64_t> off;
-	std::vector<uint32_t> len;
-	void clear() { seqs.clear(); img.clear(); off.clear(); len.clear(); }
-};
-struct ChunkDev { DevBuf img, hit, off, len, tally, paths, steps; };
+struct ChunkDev { SeqChunkDev seqs; DevBuf hit, tally, paths, steps; };
 
 /* one chunk through the device; its text behind `text` */
-int run_chunk(yakamd_path *px, const yakamd_ppopt_t &o, Chunk &c, ChunkDev &d, std::string &text, pxt_total_t *tot)
+int run_chunk(yakamd_path *px, const yakamd_ppopt_t &o, SeqChunk &c, ChunkDev &d, std::string &text, pxt_total_t *tot)
 {
-	const size_t n = c.img.size(), n_seq = c.seqs.size();
+	const size_t n_seq = c.name.size();
+	size_t n = 0;
 	if (n_seq == 0) return 0;
-	c.img.resize((size_t)up16(n), '\n');
-	if (!d.img.need(c.img.size()) || !d.hit.need(c.img.size() * 8) || !d.off.need(n_seq * 8) || !d.len.need(n_seq * 4) || !d.tally.need(n_seq * 16))
-		return fail("yakamd_paths: no device memory for a chunk of %zu bytes", n);
-	double t0 = now_ms();
-	HIPCK(hipMemcpy(d.img.p, c.img.data(), c.img.size(), hipMemcpyHostToDevice));
-	HIPCK(hipMemcpy(d.off.p, c.off.data(), n_seq * 8, hipMemcpyHostToDevice));
-	HIPCK(hipMemcpy(d.len.p, c.len.data(), n_seq * 4, hipMemcpyHostToDevice));
-	g_ms[4] += now_ms() - t0;
-	if (yakamd_path_hits_dev(px, d.img.p, (int64_t)n, (uint64_t*)d.hit.p) != 0) return -1;
+	if (!d.hit.need((size_t)up16(c.img.size()) * 8) || !d.tally.need(n_seq * 16)) return fail("yakamd_paths: no device memory for a chunk of %zu bytes", c.img.size());
+	if (d.seqs.upload("yakamd_paths", c, &n, &g_ms[4]) != 0) return -1;
+	const uint64_t *d_off = (const uint64_t*)d.seqs.off.p;
+	const uint32_t *d_len = (const uint32_t*)d.seqs.len.p;
+	if (yakamd_path_hits_dev(px, d.seqs.img.p, (int64_t)n, (uint64_t*)d.hit.p) != 0) return -1;
 	int64_t n_out[2];
-	int rc = yakamd_path_chain_dev(px, (const uint64_t*)d.hit.p, (int64_t)n, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)n_seq, 0, 0, 0, 0,
-	                               (yakamd_ptally_t*)d.tally.p, n_out);
+	int rc = yakamd_path_chain_dev(px, (const uint64_t*)d.hit.p, (int64_t)n, d_off, d_len, (int64_t)n_seq, 0, 0, 0, 0, (yakamd_ptally_t*)d.tally.p, n_out);
 	if (rc < 0) return -1;
 	std::vector<px_path_t> paths;
 	std::vector<uint64_t> steps;
 	std::vector<px_tally_t> tally;
+	double t0;
 	if (o.stats_only) {
 		tally.resize(n_seq);
 		t0 = now_ms();
 		HIPCK(hipMemcpy(tally.data(), d.tally.p, n_seq * 16, hipMemcpyDeviceToHost));
 		g_ms[4] += now_ms() - t0; t0 = now_ms();
-		pxt_stats(text, c.seqs, tally.data(), tot);
+		pxt_stats(text, c.name, c.len.data(), tally.data(), tot);
 		g_ms[5] += now_ms() - t0;
 		return 0;
 	}
 	if (n_out[0] == 0) return 0;
 	if (!d.paths.need((size_t)n_out[0] * 32) || !d.steps.need((size_t)n_out[1] * 8)) return fail("yakamd_paths: no device memory for %lld paths of %lld steps", (long long)n_out[0], (long long)n_out[1]);
 	int64_t again[2];
-	rc = yakamd_path_chain_dev(px, (const uint64_t*)d.hit.p, (int64_t)n, (const uint64_t*)d.off.p, (const uint32_t*)d.len.p, (int64_t)n_seq, (yakamd_upath_t*)d.paths.p, n_out[0],
-	                           (uint64_t*)d.steps.p, n_out[1], 0, again);
+	rc = yakamd_path_chain_dev(px, (const uint64_t*)d.hit.p, (int64_t)n, d_off, d_len, (int64_t)n_seq, (yakamd_upath_t*)d.paths.p, n_out[0], (uint64_t*)d.steps.p, n_out[1], 0, again);
 	if (rc != 0) return rc < 0 ? -1 : fail("yakamd_paths: the writing call counted %lld paths of %lld steps, the counting call %lld of %lld", (long long)again[0], (long long)again[1],
 	                                        (long long)n_out[0], (long long)n_out[1]);
 	paths.resize((size_t)n_out[0]); steps.resize((size_t)n_out[1]);
@@ -444,7 +432,7 @@ int run_chunk(yakamd_path *px, const yakamd_ppopt_t &o, Chunk &c, ChunkDev &d, s
 	HIPCK(hipMemcpy(paths.data(), d.paths.p, paths.size() * 32, hipMemcpyDeviceToHost));
 	HIPCK(hipMemcpy(steps.data(), d.steps.p, steps.size() * 8, hipMemcpyDeviceToHost));
 	g_ms[4] += now_ms() - t0; t0 = now_ms();
-	if (!pxt_gaf(text, c.seqs, paths.data(), paths.size(), steps.data(), steps.size(), px->n_node.data(), px->n_node.size(), px->k, o.min_len))
+	if (!pxt_gaf(text, c.name, c.len.data(), paths.data(), paths.size(), steps.data(), steps.size(), px->n_node.data(), px->n_node.size(), px->k, o.min_len))
 		return fail("yakamd_paths: a path record does not fit its chunk");
 	g_ms[5] += now_ms() - t0;
 	return 0;
@@ -459,48 +447,27 @@ extern "C" int yakamd_paths(const yakamd_ppopt_t *opt, yak_ch_t *ch, const char 
 	if (opt->chunk_size < 1) return fail("yakamd_paths: chunk_size %lld", (long long)opt->chunk_size);
 	if (!fn) return fail("yakamd_paths: no sequences");
 	if (ch && yakamd_ch_hpc(ch)) return fail("yakamd_paths: the table is marked homopolymer-compressed: its unitigs are no sequences to lay others onto");
-	PxReader rd;
+	SeqReader rd(false);                                           /* of a quality its length alone */
 	if (ch && !rd.open(fn)) return fail("yakamd_paths: cannot read '%s'", fn);
 	WalkGuard W{ yakamd_uwalk_open(ch, opt->min_cnt) };
-	if (!W.w) return fail_below(yakamd_walk_last_error());
-	struct Px { yakamd_path_t *p; ~Px() { yakamd_path_close(p); } } P{ yakamd_path_open(W.w, ch->k) };
+	if (!W.p) return fail_below(yakamd_walk_last_error());
+	Guard<yakamd_path_t, yakamd_path_close> P{ yakamd_path_open(W.p, ch->k) };
 	yakamd_path_t *px = P.p;
 	if (!px) return -1;
 	W.close();
 	OutFile out(out_fn);
 	if (!out.f) return fail("yakamd_paths: cannot write '%s'", out.name);
 	bool ok = true;
-	try {
-		Chunk c;
-		ChunkDev d;
-		std::string text, name, seq;
-		pxt_total_t tot = { 0, 0, 0, 0, 0, 0 };
-		if (opt->stats_only) pxt_stats_head(text, px->k, opt->min_cnt);
-		uint64_t bases = 0;
-		bool more = true;
-		while (more) {
-			more = rd.next(name, seq);
-			if (more) {
-				if (seq.size() >= 0xffffffffull) return fail("yakamd_paths: sequence '%s' has %zu bases: a length is a 32-bit number", name.c_str(), seq.size());
-				c.off.push_back(c.img.size());
-				c.len.push_back((uint32_t)seq.size());
-				c.seqs.push_back(pxt_seq_t{ name, seq.size() });
-				c.img.insert(c.img.end(), seq.begin(), seq.end());
-				c.img.push_back('\n');
-				bases += seq.size();
-			}
-			if ((!more || bases >= (uint64_t)opt->chunk_size) && !c.seqs.empty()) {
-				if (run_chunk(px, *opt, c, d, text, &tot) != 0) return -1;
-				c.clear(); bases = 0;
-			}
-			if (text.size() >= (size_t)1 << 22 || !more) {
-				if (!more && opt->stats_only) pxt_stats_tail(text, tot);
-				ok = out.write(text) && ok;
-				text.clear();
-			}
-		}
-		if (rd.failed()) return fail("yakamd_paths: '%s' is damaged: the inflater gave up", fn);
-	} catch (const std::bad_alloc&) { return fail("yakamd_paths: no host memory for a chunk"); }
+	ChunkDev d;
+	std::string text;
+	pxt_total_t tot = { 0, 0, 0, 0, 0, 0 };
+	if (opt->stats_only) pxt_stats_head(text, px->k, opt->min_cnt);
+	if (seq_chunks("yakamd_paths", rd, fn, opt->chunk_size, 0, [&](SeqChunk &c, bool last) {
+		if (run_chunk(px, *opt, c, d, text, &tot) != 0) return -1;
+		if (last && opt->stats_only) pxt_stats_tail(text, tot);
+		flush(text, &out, last, &ok);
+		return 0;
+	}) != 0) return -1;
 	if (!(out.finish() && ok)) return fail("yakamd_paths: cannot write '%s'", out.name);
 	if (getenv("YAKAMD_VERBOSE"))
 		fprintf(stderr, "[yak_amd] paths: index %.1f ms, hits %.1f ms, count and scan %.1f ms, emit %.1f ms, copies %.1f ms, text %.1f ms (longest probe %llu)\n", g_ms[0], g_ms[1],

@@ -1,5 +1,6 @@
 /* path_text.h -- the two texts of `yak-amd paths` (include/yak_amd_path.h) made on the host, HIP-free like path_step.h: the GAF
- * lines from a chunk's path records and steps, and the -s form from its tallies.  path.hip and tests/tools/path_model_check.cpp share it. */
+ * lines from a chunk's path records and steps, and the -s form from its tallies; a chunk's sequences are their names and, beside them, their
+ * lengths.  path.hip and tests/tools/path_model_check.cpp share it. */
 #ifndef YK_PATH_TEXT_H
 #define YK_PATH_TEXT_H
 #include <stdio.h>
@@ -7,7 +8,6 @@
 #include <vector>
 #include "path_step.h"
 
-struct pxt_seq_t { std::string name; uint64_t len; };
 struct pxt_total_t { uint64_t n_seq, len, kmer, hit, path, step; };
 
 static inline void pxt_decimal(std::string &text, uint64_t v)
@@ -20,16 +20,15 @@ static inline void pxt_decimal(std::string &text, uint64_t v)
 
 /* one GAF line per path of the chunk with qe - qs >= min_len, appended to text: name len qs qe + <path> plen ps pe nm nm 255.  n_node[j] = the nodes
  * of unitig j.  false for a record that names no sequence of the chunk, no step of the list or no unitig */
-static inline bool pxt_gaf(std::string &text, const std::vector<pxt_seq_t> &seqs, const px_path_t *paths, uint64_t n_path, const uint64_t *steps, uint64_t n_step,
+static inline bool pxt_gaf(std::string &text, const std::vector<std::string> &name, const uint32_t *len, const px_path_t *paths, uint64_t n_path, const uint64_t *steps, uint64_t n_step,
                            const uint32_t *n_node, uint64_t n_unitig, int k, int min_len)
 {
 	for (uint64_t r = 0; r < n_path; ++r) {
 		const px_path_t &p = paths[r];
-		if (p.seq >= seqs.size() || p.qe < p.qs || p.step_off > n_step || p.n_step > n_step - p.step_off || p.n_step < 1) return false;
+		if (p.seq >= name.size() || p.qe < p.qs || p.step_off > n_step || p.n_step > n_step - p.step_off || p.n_step < 1) return false;
 		const uint64_t span = p.qe - p.qs;
 		if (span < (uint64_t)(min_len > 0 ? min_len : 0)) continue;
-		const pxt_seq_t &s = seqs[p.seq];
-		text += s.name; text += '\t'; pxt_decimal(text, s.len);
+		text += name[p.seq]; text += '\t'; pxt_decimal(text, len[p.seq]);
 		text += '\t'; pxt_decimal(text, p.qs);
 		text += '\t'; pxt_decimal(text, p.qe);
 		text += "\t+\t";
@@ -57,18 +56,18 @@ static inline void pxt_stats_head(std::string &text, int k, int min_cnt)
 	text.append(line, (size_t)snprintf(line, sizeof line, "#paths\tk=%d\tmin_cnt=%d\n", k, min_cnt));
 }
 /* an S line per sequence of the chunk, added to the totals */
-static inline void pxt_stats(std::string &text, const std::vector<pxt_seq_t> &seqs, const px_tally_t *tally, pxt_total_t *tot)
+static inline void pxt_stats(std::string &text, const std::vector<std::string> &name, const uint32_t *len, const px_tally_t *tally, pxt_total_t *tot)
 {
-	for (size_t s = 0; s < seqs.size(); ++s) {
+	for (size_t s = 0; s < name.size(); ++s) {
 		const px_tally_t &t = tally[s];
-		text += "S\t"; text += seqs[s].name;
-		text += '\t'; pxt_decimal(text, seqs[s].len);
+		text += "S\t"; text += name[s];
+		text += '\t'; pxt_decimal(text, len[s]);
 		text += '\t'; pxt_decimal(text, t.n_kmer);
 		text += '\t'; pxt_decimal(text, t.n_hit);
 		text += '\t'; pxt_decimal(text, t.n_path);
 		text += '\t'; pxt_decimal(text, t.n_step);
 		text += '\n';
-		++tot->n_seq; tot->len += seqs[s].len; tot->kmer += t.n_kmer; tot->hit += t.n_hit; tot->path += t.n_path; tot->step += t.n_step;
+		++tot->n_seq; tot->len += len[s]; tot->kmer += t.n_kmer; tot->hit += t.n_hit; tot->path += t.n_path; tot->step += t.n_step;
 	}
 }
 static inline void pxt_stats_tail(std::string &text, const pxt_total_t &t)

@@ -324,17 +324,6 @@ int walk_run(yakamd_uwalk *w, yakamd_graph_t **gp, yak_ch_t *h, int min_cnt)
 	return 0;
 }
 
-int64_t copy_out(yakamd_uwalk_t *w, const void *src, u64 n, u64 each, void *d, int64_t cap, const char *what)
-{
-	if (!w) return fail("%s: no walk", what);
-	if (!d || cap < (int64_t)n) return (int64_t)n;
-	if (each > 1 && ((uintptr_t)d & 15) != 0) return fail("%s: the entries must be 16-byte aligned", what);
-	if (n == 0) return 0;
-	OnDevice dev(w->dev);
-	HIPCK(hipMemcpy(d, src, n * each, hipMemcpyDeviceToDevice));
-	return (int64_t)n;
-}
-
 }   // namespace
 
 extern "C" const char *yakamd_walk_last_error(void) { return g_err; }
@@ -378,16 +367,21 @@ extern "C" int yakamd_uwalk_gstat(yakamd_uwalk_t *w, yakamd_gstat_t *st)
 	return 0;
 }
 
-extern "C" int64_t yakamd_uwalk_map_dev(yakamd_uwalk_t *w, void *d, int64_t cap) { return copy_out(w, w ? w->map.p : 0, w ? w->st.n_key : 0, 16, d, cap, "walk map"); }
-extern "C" int64_t yakamd_uwalk_desc_dev(yakamd_uwalk_t *w, void *d, int64_t cap) { return copy_out(w, w ? w->desc.p : 0, w ? w->st.n_open + w->st.n_cycle : 0, 32, d, cap, "walk desc"); }
-extern "C" int64_t yakamd_uwalk_bases_dev(yakamd_uwalk_t *w, void *d, int64_t cap) { return copy_out(w, w ? w->bases.p : 0, w ? w->st.sum_len : 0, 1, d, cap, "walk bases"); }
+/* entries of 16 and 32 bytes must be aligned, single bases need not be */
+static int64_t w_out(yakamd_uwalk_t *w, const void *src, u64 n, u64 each, void *d, int64_t cap, const char *what)
+{
+	return copy_out(w != 0, w ? w->dev : 0, src, n, each, d, cap, what, "walk", each > 1 ? "the entries" : 0);
+}
+extern "C" int64_t yakamd_uwalk_map_dev(yakamd_uwalk_t *w, void *d, int64_t cap) { return w_out(w, w ? w->map.p : 0, w ? w->st.n_key : 0, 16, d, cap, "walk map"); }
+extern "C" int64_t yakamd_uwalk_desc_dev(yakamd_uwalk_t *w, void *d, int64_t cap) { return w_out(w, w ? w->desc.p : 0, w ? w->st.n_open + w->st.n_cycle : 0, 32, d, cap, "walk desc"); }
+extern "C" int64_t yakamd_uwalk_bases_dev(yakamd_uwalk_t *w, void *d, int64_t cap) { return w_out(w, w ? w->bases.p : 0, w ? w->st.sum_len : 0, 1, d, cap, "walk bases"); }
 
 /* the command: the walk, then the text from the descriptors and, for the FASTA, the bases */
 extern "C" int yakamd_unitigs_dev(const yakamd_ugopt_t *opt, yak_ch_t *ch, const char *out_fn)
 {
 	if (!opt) return fail("yakamd_unitigs_dev: no options");
 	WalkGuard W{ yakamd_uwalk_open(ch, opt->min_cnt) };
-	yakamd_uwalk_t *w = W.w;
+	yakamd_uwalk_t *w = W.p;
 	if (!w) return -1;
 	const yakamd_uwstat_t &u = w->st;
 	double t0 = now_ms();
