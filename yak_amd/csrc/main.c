@@ -22,7 +22,7 @@
  * that lie inside k-mers a table holds, lacks or holds too often -- as a table, as intervals or as a masked FASTA), unitigs (yakamd_unitigs: the
  * de Bruijn graph the k-mers of a count table span, as its unitigs in FASTA or as its tallies), paths (yakamd_paths: the sequences of a file as
  * paths through those unitigs, as GAF or as tallies per sequence), bubbles (yakamd_bubbles: the forks of that graph whose two arms join again,
- * with their types and alleles), clean (yakamd_clean: the table without the k-mers of that graph's tips and weaker bubble arms) and correct
+ * with their types and alleles; with -r yakamd_alleles: the reads of a file that pass each allele, a call per bubble and the alleles per read), clean (yakamd_clean: the table without the k-mers of that graph's tips and weaker bubble arms) and correct
  * (yakamd_correct: reads with their single substitution errors repaired against a table).  `count -c` and `qv -c` work in homopolymer-compressed
  * space (yakamd_count_hpc; yakamd_ch_set_hpc on the restored table): every run of one base is one base before k-mers are taken.
  * Option letters follow the reference so that test command lines can be shared; the parser, the
@@ -37,6 +37,7 @@
 #include "yak_amd_gfa.h"   /* yakamd_unitigs_gfa (unitigs -G) */
 #include "yak_amd_path.h"  /* yakamd_paths (paths) */
 #include "yak_amd_bubble.h" /* yakamd_bubbles (bubbles) */
+#include "yak_amd_allele.h" /* yakamd_alleles (bubbles -r) */
 #include "yak_amd_clean.h" /* yakamd_clean (clean) */
 #include "yak_amd_correct.h" /* yakamd_correct (correct) */
 #include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_cover, yakamd_unitigs, yakamd_count_hpc and yakamd_ch_set_hpc */
@@ -641,27 +642,44 @@ static int cmd_paths(int argc, char **argv)
 /* ---- bubbles (not in the reference) ---- */
 /* the simple bubbles of the unitig graph of a count table -- a fork whose two arms are one unitig each and join again --, a line per bubble with
  * its type (SNP, equal length, indel) and its two alleles, or with -s the tallies of `unitigs -G -s` and a B line (yakamd_bubbles of
- * libyak_amd_bubble.so) */
+ * libyak_amd_bubble.so).  With -r the reads of a file are laid onto the graph and every bubble gets the reads that pass its two alleles: the
+ * support and a call per bubble, with -f the alleles every read passes (yakamd_alleles of libyak_amd_allele.so) */
 static int cmd_bubbles(int argc, char **argv)
 {
 	yakamd_ugopt_t o;
-	const char *out = 0;
-	int stats = 0, min_cnt = 1;
+	yakamd_alopt_t a;
+	const char *out = 0, *reads = 0;
+	int stats = 0, min_cnt = 1, frags = 0;
+	int32_t min_sup = INT32_MIN, min_frag = INT32_MIN;           /* not given */
 	yakamd_ugopt_init(&o);
+	yakamd_alopt_init(&a);
 	const struct arg_def defs[] = {
 		{ 'c', ARG_I32, &min_cnt, "a k-mer with a count below this is absent, 1 .. 1023 [1]" },
 		{ 's', ARG_FLAG, &stats, "the tallies of the graph, its unitigs and links, and of the bubbles, forks and tips, not the bubbles" },
 		{ 'o', ARG_TEXT, &out, "write the output here; stdout without it" },
+		{ 'r', ARG_TEXT, &reads, "reads (fa|fq[.gz]): per bubble the reads that pass each allele and a call, not the bubbles; -s: their tallies" },
+		{ 'm', ARG_I32, &min_sup, "with -r: an allele is supported by this many reads that span it [2]" },
+		{ 'n', ARG_I32, &min_frag, "with -r -f: list the reads that span this many alleles or more [1]" },
+		{ 'f', ARG_FLAG, &frags, "with -r: an F line per read with the alleles it spans" },
 	};
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first >= argc) { arg_help("bubbles [options] <table.yak>", defs, nd); return 1; }
+	if (!reads && (min_sup != INT32_MIN || min_frag != INT32_MIN || frags)) { fprintf(stderr, "yak-amd bubbles: -m, -n and -f need the reads of -r\n"); return 1; }
 	if (table_k("bubbles", argv[first], K_ODD_GRAPH, K_32_GRAPH) < 0) return 2;
 	if (!min_cnt_ok("bubbles", min_cnt)) return 1;
+	if (min_sup == INT32_MIN) min_sup = a.min_sup;
+	if (min_frag == INT32_MIN) min_frag = a.min_frag;
+	if (min_sup < 1 || min_frag < 1) { fprintf(stderr, "yak-amd bubbles: -m and -n must be at least 1\n"); return 1; }
 	o.min_cnt = min_cnt; o.stats_only = stats;
 	yak_ch_t *tab = table_load("bubbles", argv[first]);
 	if (!tab) return 2;
-	const int rc = yakamd_bubbles(&o, tab, out) == 0 ? 0 : 3;
+	int rc;
+	if (reads) {
+		a.min_cnt = min_cnt; a.min_sup = min_sup; a.min_frag = min_frag; a.fragments = frags; a.stats_only = stats;
+		rc = yakamd_alleles(&a, tab, reads, out) == 0 ? 0 : 3;
+	} else
+		rc = yakamd_bubbles(&o, tab, out) == 0 ? 0 : 3;
 	yak_ch_destroy(tab);
 	return rc;
 }
