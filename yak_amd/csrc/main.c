@@ -38,6 +38,7 @@
 #include "yak_amd_path.h"  /* yakamd_paths (paths) */
 #include "yak_amd_bubble.h" /* yakamd_bubbles (bubbles) */
 #include "yak_amd_allele.h" /* yakamd_alleles (bubbles -r) */
+#include "yak_amd_phase.h" /* yakamd_phase (bubbles -r -p) */
 #include "yak_amd_clean.h" /* yakamd_clean (clean) */
 #include "yak_amd_correct.h" /* yakamd_correct (correct) */
 #include "yak_amd.h"       /* beyond yak.h: yakamd_test_set (-X), yakamd_triobin, yakamd_trioeval, yakamd_inspect, yakamd_chkerr, yakamd_sexchr, yakamd_print, yakamd_ch_sum, yakamd_depth, yakamd_hetmers, yakamd_cover, yakamd_unitigs, yakamd_count_hpc and yakamd_ch_set_hpc */
@@ -643,16 +644,19 @@ static int cmd_paths(int argc, char **argv)
 /* the simple bubbles of the unitig graph of a count table -- a fork whose two arms are one unitig each and join again --, a line per bubble with
  * its type (SNP, equal length, indel) and its two alleles, or with -s the tallies of `unitigs -G -s` and a B line (yakamd_bubbles of
  * libyak_amd_bubble.so).  With -r the reads of a file are laid onto the graph and every bubble gets the reads that pass its two alleles: the
- * support and a call per bubble, with -f the alleles every read passes (yakamd_alleles of libyak_amd_allele.so) */
+ * support and a call per bubble, with -f the alleles every read passes (yakamd_alleles of libyak_amd_allele.so); with -p as well the alleles
+ * are phased from the reads that span two bubbles: a haplotype per het bubble and the blocks (yakamd_phase of libyak_amd_phase.so) */
 static int cmd_bubbles(int argc, char **argv)
 {
 	yakamd_ugopt_t o;
 	yakamd_alopt_t a;
+	yakamd_phopt_t p;
 	const char *out = 0, *reads = 0;
-	int stats = 0, min_cnt = 1, frags = 0;
-	int32_t min_sup = INT32_MIN, min_frag = INT32_MIN;           /* not given */
+	int stats = 0, min_cnt = 1, frags = 0, phase = 0, edges = 0;
+	int32_t min_sup = INT32_MIN, min_frag = INT32_MIN, min_link = INT32_MIN;           /* not given */
 	yakamd_ugopt_init(&o);
 	yakamd_alopt_init(&a);
+	yakamd_phopt_init(&p);
 	const struct arg_def defs[] = {
 		{ 'c', ARG_I32, &min_cnt, "a k-mer with a count below this is absent, 1 .. 1023 [1]" },
 		{ 's', ARG_FLAG, &stats, "the tallies of the graph, its unitigs and links, and of the bubbles, forks and tips, not the bubbles" },
@@ -661,21 +665,32 @@ static int cmd_bubbles(int argc, char **argv)
 		{ 'm', ARG_I32, &min_sup, "with -r: an allele is supported by this many reads that span it [2]" },
 		{ 'n', ARG_I32, &min_frag, "with -r -f: list the reads that span this many alleles or more [1]" },
 		{ 'f', ARG_FLAG, &frags, "with -r: an F line per read with the alleles it spans" },
+		{ 'p', ARG_FLAG, &phase, "with -r: phase the alleles from the reads that span two bubbles: a haplotype per het bubble, and the blocks" },
+		{ 'w', ARG_I32, &min_link, "with -r -p: two bubbles are linked from this many votes more one way than the other [2]" },
+		{ 'e', ARG_FLAG, &edges, "with -r -p: an E line per link with its votes" },
 	};
 	const int nd = (int)(sizeof(defs) / sizeof(defs[0]));
 	const int first = arg_scan(argc, argv, defs, nd);
 	if (first < 0 || first >= argc) { arg_help("bubbles [options] <table.yak>", defs, nd); return 1; }
 	if (!reads && (min_sup != INT32_MIN || min_frag != INT32_MIN || frags)) { fprintf(stderr, "yak-amd bubbles: -m, -n and -f need the reads of -r\n"); return 1; }
+	if (!reads && (phase || min_link != INT32_MIN || edges)) { fprintf(stderr, "yak-amd bubbles: -p, -w and -e need the reads of -r\n"); return 1; }
+	if (!phase && (min_link != INT32_MIN || edges)) { fprintf(stderr, "yak-amd bubbles: -w and -e need the phasing of -p\n"); return 1; }
+	if (phase && (frags || min_frag != INT32_MIN)) { fprintf(stderr, "yak-amd bubbles: -f and -n do not go with -p, which keeps the fragments on the device\n"); return 1; }
 	if (table_k("bubbles", argv[first], K_ODD_GRAPH, K_32_GRAPH) < 0) return 2;
 	if (!min_cnt_ok("bubbles", min_cnt)) return 1;
 	if (min_sup == INT32_MIN) min_sup = a.min_sup;
 	if (min_frag == INT32_MIN) min_frag = a.min_frag;
+	if (min_link == INT32_MIN) min_link = p.min_link;
 	if (min_sup < 1 || min_frag < 1) { fprintf(stderr, "yak-amd bubbles: -m and -n must be at least 1\n"); return 1; }
+	if (min_link < 1) { fprintf(stderr, "yak-amd bubbles: -w must be at least 1\n"); return 1; }
 	o.min_cnt = min_cnt; o.stats_only = stats;
 	yak_ch_t *tab = table_load("bubbles", argv[first]);
 	if (!tab) return 2;
 	int rc;
-	if (reads) {
+	if (reads && phase) {
+		p.min_cnt = min_cnt; p.min_sup = min_sup; p.min_link = min_link; p.edges = edges; p.stats_only = stats;
+		rc = yakamd_phase(&p, tab, reads, out) == 0 ? 0 : 3;
+	} else if (reads) {
 		a.min_cnt = min_cnt; a.min_sup = min_sup; a.min_frag = min_frag; a.fragments = frags; a.stats_only = stats;
 		rc = yakamd_alleles(&a, tab, reads, out) == 0 ? 0 : 3;
 	} else
